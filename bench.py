@@ -8,7 +8,15 @@ update (trace -> shade -> irradiance/visibility/border/offset update) of every
 probe; with N GPUs the grid is split in Z-slabs (strong scaling: fixed total
 work) and the atlases are all-gathered over RCCL after each update.
 
-Besides `value`, rank 0 at N = 1 reports: the reference's own windows (K = 4096,
+A plain run sets up, warms up, times exactly `--steps` steps and prints the headline
+line (`value`, `ms_per_step` = wall milliseconds per timed step, the workload's
+`config`). `--dump-outputs DIR` then also writes what the last timed step left in the
+context as DIR/<name>.npy (dump_outputs(); the inputs are seeded, so two runs with the
+same arguments are comparable array for array). Everything below is measured only with
+`--full`: a counter-instrumented update and three per-kernel timed updates before the
+timed region (`per_ray`, `kernels_ms`, `update_ms`, `roofline`), and the side lines.
+
+With `--full`, besides `value`, rank 0 at N = 1 reports: the reference's own windows (K = 4096,
 the node's cap, DDGINode.h:23; K = 2048, its default, DDGINode.h:31) with per-kernel
 times; config C2 (Cornell 8^3 x 64) on the GPU; the CPU baseline (the oracle on the
 box's host cores, one warm-up then the median of >= 5 frames, C4 and C2); the C1 AO
@@ -20,7 +28,7 @@ it, `frac_hip_event`: over this run's HIP-event launch time); the SURVEY
 node fetches hit L2 / Infinity Cache), with the VALU issue fractions and the
 whole-update figures (roofline()).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE starts the N ranks itself
@@ -97,6 +105,13 @@ def parse(argv=None):
                     help="rendezvous port of the ranks bench.py starts itself (--gpus N > 1 without WORLD_SIZE)")
     ap.add_argument("--dry-run", action="store_true",
                     help="print the launch decision (run in this process / start N ranks / refuse) as JSON and exit; no GPU call")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the counter-instrumented and per-kernel timed updates, the roofline, "
+                         "and at N = 1 the reference windows, C2 / C5 / C3, the CPU baseline, the C1 AO bake and the consumers "
+                         "(each with its own --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step left in the context (irradiance and visibility "
+                         "atlases, probe offsets, surfels) as DIR/<name>.npy, float32 (dump_outputs())")
     return ap.parse_args(argv)
 
 
@@ -231,21 +246,22 @@ def main(argv=None):
         step()
     torch.cuda.synchronize(device)
 
-    # --- counter-instrumented update (separate kernel variant; not timed) -----
-    ctx.set_counting(True)
-    step()
-    torch.cuda.synchronize(device)
-    cnt = ctx.counters()
-    ctx.set_counting(False)
-
-    # --- per-kernel device time from HIP events on the update stream ----------
-    ctx.set_timing(True)
-    ktimes = []
-    for _ in range(3):
+    cnt, ktimes = None, []
+    if args.full:
+        # --- counter-instrumented update (separate kernel variant; not timed) -----
+        ctx.set_counting(True)
         step()
-        ktimes.append(ctx.last_timings())
-    ctx.set_timing(False)
-    torch.cuda.synchronize(device)
+        torch.cuda.synchronize(device)
+        cnt = ctx.counters()
+        ctx.set_counting(False)
+
+        # --- per-kernel device time from HIP events on the update stream ----------
+        ctx.set_timing(True)
+        for _ in range(3):
+            step()
+            ktimes.append(ctx.last_timings())
+        ctx.set_timing(False)
+        torch.cuda.synchronize(device)
 
     # --- timed region: exactly `steps` steps -----------------------------------
     if world > 1:
@@ -268,18 +284,14 @@ def main(argv=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
 
+    if args.dump_outputs and rank == 0:
+        dump_outputs(ctx, args.dump_outputs)
+
     total_rays = args.steps * K * R
     total_probes = args.steps * K
     mrays = total_rays / dt / 1e6
     lib_sha = library_sha16()
-
-    # roofline of the dominant kernel (per launch, this rank's share)
-    avg = [sum(k[i] for k in ktimes) / len(ktimes) for i in range(5)]
-    kernel_bytes = algorithmic_bytes(cnt, R)
-    kernel_ms = {"k_trace": avg[1], "k_shade": avg[2], "k_shadow": avg[4], "k_probe_update": avg[3]}
-    dom = max(kernel_ms, key=kernel_ms.get)
     ms_per_step = dt / args.steps * 1e3
-    roof = roofline(args, dom, kernel_bytes, kernel_ms, ms_per_step, lib_sha, G)
 
     result = {
         "metric": "Mrays/s + probes-updated/s, DDGI 32^3 grid x 256 rays, at 1/2/4/8 MI355X",
@@ -309,27 +321,35 @@ def main(argv=None):
             "setup_s": round(setup_s, 2),
             "lib_sha16": lib_sha,
         },
-        "roofline": roof,
-        "kernels_ms": {k: round(v, 4) for k, v in kernel_ms.items()},
-        "update_ms": round(avg[0], 4),
-        "per_ray": per_ray(cnt),
     }
 
-    if rank == 0 and world == 1 and not args.no_windows:
+    if args.full:
+        # roofline of the dominant kernel (per launch, this rank's share)
+        avg = [sum(k[i] for k in ktimes) / len(ktimes) for i in range(5)]
+        kernel_bytes = algorithmic_bytes(cnt, R)
+        kernel_ms = {"k_trace": avg[1], "k_shade": avg[2], "k_shadow": avg[4], "k_probe_update": avg[3]}
+        dom = max(kernel_ms, key=kernel_ms.get)
+        result["roofline"] = roofline(args, dom, kernel_bytes, kernel_ms, ms_per_step, lib_sha, G)
+        result["kernels_ms"] = {k: round(v, 4) for k, v in kernel_ms.items()}
+        result["update_ms"] = round(avg[0], 4)
+        result["per_ray"] = per_ray(cnt)
+
+    side_lines = args.full and rank == 0 and world == 1
+    if side_lines and not args.no_windows:
         result["reference_windows"] = reference_windows(node, ctx, torch, device, sptr, frame)
         result["c2"] = c2_line(args, torch, device)
 
-    if rank == 0 and world == 1 and not args.no_configs:
+    if side_lines and not args.no_configs:
         for name in ("c5", "c3"):
             result[name] = config_line(name, torch, device)
 
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if side_lines and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baseline(scene, grid, R, args, exposure)
 
-    if rank == 0 and world == 1 and not args.no_ao_bake:
+    if side_lines and not args.no_ao_bake:
         result["ao_bake"] = ao_bake_c1(args, torch, device)
 
-    if rank == 0 and world == 1 and not args.no_compose:
+    if side_lines and not args.no_compose:
         result["lighting_compose"] = lighting_compose_line(args, torch, node.ctx)
         result["rt_reflections"] = rt_reflections_line(args, torch, node.ctx)
 
@@ -359,6 +379,55 @@ def _host_staged(band):
             _host_gather(full, mine)
 
     return exchange
+
+
+DUMP_RESOURCES = (("irradiance", "ARK_DDGI_ATLAS_IRRADIANCE"), ("visibility", "ARK_DDGI_ATLAS_VISIBILITY"),
+                  ("probe_offsets", "ARK_DDGI_PROBE_OFFSETS"), ("surfels", "ARK_DDGI_SURFELS"))
+DUMP_BUDGET_BYTES = 64_000_000  # all files of one dump together
+# per array: an equal share of the budget, less 4 KiB for the .npy header, in float32 elements
+DUMP_MAX_ELEMENTS = (DUMP_BUDGET_BYTES // len(DUMP_RESOURCES) - 4096) // 4
+DUMP_SEED = 0xA2C05E00
+DUMP_NAN = -98304.0  # finite codes of the fp16 resources' non-finite values (dump_outputs())
+DUMP_INF = 131072.0
+
+
+def dump_outputs(ctx, directory):
+    """--dump-outputs: the resources a host reads back from the context after the last
+    timed step (ark_ddgi_read: the irradiance and visibility atlases, the probe offsets,
+    the last update's surfels) as <directory>/<name>.npy, float32 (the fp16 resources
+    widened exactly). An array of more than DUMP_MAX_ELEMENTS elements is written as a
+    fixed sample: the elements at DUMP_MAX_ELEMENTS distinct, sorted indices drawn from
+    numpy's default_rng(DUMP_SEED), the same for every run of the same shapes. With every
+    array sampled the files stay within DUMP_BUDGET_BYTES.
+
+    The fp16 resources hold non-finite values by design (the visibility clear's zFar^2
+    overflows to +inf and blends to NaN). So that two dumps compare
+    element for element under any comparison, NaN with NaN included, they are written as
+    finite codes outside the fp16 range (|x| <= 65504): NaN as DUMP_NAN, +inf / -inf as
+    +/- DUMP_INF."""
+    from arkoserenderer_amd import abi
+
+    os.makedirs(directory, exist_ok=True)
+    for name, which in DUMP_RESOURCES:
+        dump_array(os.path.join(directory, f"{name}.npy"), ctx.read(getattr(abi, which)))
+
+
+def dump_array(path, a):
+    """One resource of dump_outputs(): `a` as ark_ddgi_read returns it (uint16 = fp16
+    bits, or float32), sampled above DUMP_MAX_ELEMENTS, as a float32 .npy file."""
+    import numpy as np
+
+    half = a.dtype == np.uint16
+    if half:
+        a = a.view(np.float16)
+    if a.size > DUMP_MAX_ELEMENTS:
+        idx = np.random.default_rng(DUMP_SEED).choice(a.size, DUMP_MAX_ELEMENTS, replace=False, shuffle=False)
+        idx.sort()
+        a = a[idx]
+    a = a.astype(np.float32)
+    if half:
+        a = np.nan_to_num(a, nan=DUMP_NAN, posinf=DUMP_INF, neginf=-DUMP_INF)
+    np.save(path, a)
 
 
 def library_sha16() -> str:

@@ -44,6 +44,46 @@ def test_n_gpus_spawns_torchrun_child_with_same_arguments():
     assert cmd[script + 1:] == argv  # each rank sees WORLD_SIZE = 4 = --gpus: ("run", 4)
 
 
+def test_plain_run_is_the_default():
+    a = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = bench.parse(["--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+
+
+def test_dump_of_oversized_resources_stays_within_64_mb(tmp_path):
+    """--dump-outputs at the real cap with every resource above it (a grid of more than
+    1 M probes): the files together are at most 64 MB; a sample is distinct, ordered
+    elements, the same on every call; fp16 NaN / inf become the finite codes."""
+    import numpy as np
+
+    assert bench.DUMP_BUDGET_BYTES == 64_000_000 and len(bench.DUMP_RESOURCES) == 4
+    n = bench.DUMP_MAX_ELEMENTS + 100_001
+    ramp = np.arange(n, dtype=np.float32)  # exact: n < 2^24
+    bits = np.zeros(n, np.uint16)
+    bits[0::3], bits[1::3], bits[2::3] = 0x3C00, 0x7E00, 0xFC00  # 1, NaN, -inf
+    for name, _ in bench.DUMP_RESOURCES:
+        bench.dump_array(str(tmp_path / f"{name}.npy"), ramp if name == "probe_offsets" else bits)
+    assert sum(os.path.getsize(tmp_path / f"{name}.npy") for name, _ in bench.DUMP_RESOURCES) <= 64_000_000
+    a = np.load(tmp_path / "probe_offsets.npy")
+    assert a.dtype == np.float32 and a.size == bench.DUMP_MAX_ELEMENTS
+    assert np.all(np.diff(a) > 0) and a[-1] < n  # distinct elements of the input, in order
+    bench.dump_array(str(tmp_path / "again.npy"), ramp)
+    assert np.array_equal(np.load(tmp_path / "again.npy"), a)
+    h = np.load(tmp_path / "surfels.npy")
+    assert h.dtype == np.float32 and set(np.unique(h)) == {1.0, bench.DUMP_NAN, -bench.DUMP_INF}
+    want = np.array([1.0, bench.DUMP_NAN, -bench.DUMP_INF], np.float32)[a.astype(np.int64) % 3]
+    assert np.array_equal(h, want)  # the same indices for the same length
+
+
+def test_dump_keeps_small_resources_whole(tmp_path):
+    import numpy as np
+
+    x = np.array([0x0000, 0x3C00, 0x7C00, 0x7E00, 0xC000], np.uint16)  # 0, 1, +inf, NaN, -2
+    bench.dump_array(str(tmp_path / "x.npy"), x)
+    assert np.array_equal(np.load(tmp_path / "x.npy"), np.array([0.0, 1.0, bench.DUMP_INF, bench.DUMP_NAN, -2.0], np.float32))
+
+
 def _dry(*args, env=None):
     e = dict(os.environ)
     e.pop("WORLD_SIZE", None)

@@ -13,7 +13,7 @@ for setting in "$@"; do
   envs=""
   [[ "$setting" != "-" ]] && envs="$setting"
   env $envs timeout -k 10 240 python -u tools/shard_proxy.py --shards 1 4 8 --steps 60 > $OUT/proxy$i.log 2>&1 || { echo "proxy failed ($setting) rc=$?"; tail -20 $OUT/proxy$i.log; exit 1; }
-  env $envs timeout -k 10 240 python -u bench.py --steps 10 --warmup 2 --no-cpu-baseline --no-ao-bake --no-compose > $OUT/bench$i.log 2>&1 || { echo "bench failed ($setting) rc=$?"; tail -20 $OUT/bench$i.log; exit 1; }
+  env $envs timeout -k 10 240 python -u bench.py --full --steps 10 --warmup 2 --no-cpu-baseline --no-ao-bake --no-compose > $OUT/bench$i.log 2>&1 || { echo "bench failed ($setting) rc=$?"; tail -20 $OUT/bench$i.log; exit 1; }
   python - "$OUT/proxy$i.log" "$OUT/bench$i.log" "$setting" <<'PY'
 import json, sys
 p = [json.loads(l) for l in open(sys.argv[1]) if l.startswith("{")]

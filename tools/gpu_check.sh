@@ -20,6 +20,6 @@ if [[ " $* " != *" --no-prof "* ]]; then
   python3 tools/sq_summary.py $OUT/prof $TAG --json --latest > profiles/${TAG}_sq.txt 2>&1 || { echo "sq summary failed"; exit 1; }
   cp profiles/${TAG}_* profiles/latest_pmc.json profiles/latest_sq.json $OUT/profiles/
 fi
-timeout -k 10 400 python -u bench.py > $OUT/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -20 $OUT/bench.log; exit 1; }
+timeout -k 10 400 python -u bench.py --full > $OUT/bench.log 2>&1 || { echo "bench failed rc=$?"; tail -20 $OUT/bench.log; exit 1; }
 tail -1 $OUT/bench.log
 echo "gpu_check done"

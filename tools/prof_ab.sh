@@ -11,7 +11,7 @@ if [[ "$1" == "--pmc" ]]; then PMC=1; shift; fi
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd - > /dev/null
-BENCH="bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-windows --no-ao-bake --no-compose --no-configs --serial-frames"
+BENCH="bench.py --full --steps 4 --warmup 1 --no-cpu-baseline --no-windows --no-ao-bake --no-compose --no-configs --serial-frames"
 i=0
 for setting in "$@"; do
   i=$((i+1))
