@@ -38,13 +38,17 @@ constexpr int kPipeTracePerCu = 3; // traversal workgroups per CU of such a wind
 // Idle traversal lanes are refilled in batches of >= kRefillMin (the refill then stalls
 // a wave once per 16 finished rays, and the rays it starts descend from the root
 // together: C4 2.98 vs 3.30 ms at 1 in round 1; with the fetches outside branches 16
-// is the best: step 3.53 -> 3.46 ms against 4, 24 and 32, profiles/r03_as, r03_at). The
+// is the best: step 3.53 -> 3.46 ms against 4, 24 and 32, profiles/r03_as, r03_at; with
+// k_trace's refills reading staged records from LDS, measured again: C4 2,566 / 2,580 /
+// 2,589 / 2,565 Mrays/s at 8 / 12 / 16 / 24, means of three interleaved runs,
+// EXPERIMENTS.md "LDS ray pool"). The
 // sun's any-hit rays in the light-space BVH are short: 32 (profiles/r05_q: C4 shadow
 // phase 0.648 -> 0.630 ms, K = 2048 0.327 -> 0.320 ms; the world BVHs' shadow rays keep
 // 16: 32 there made C5's shadow phase 1.92 -> 2.07 ms). kGrabChunk: rays per
 // partition-head grab, 64 = a probe quarter of direction-clustered rays per wave pool
 // (16 and 8 measured slower on 1/8 slabs).
 constexpr uint32_t kRefillMin = 16, kSunRefillMin = 32, kGrabChunk = 64;
+static_assert(kGrabChunk <= 64, "a wave stages one ray of a chunk per lane (k_trace's pool, the shadow traversal's refill)");
 
 // roctx range over a scope (host-side enqueue markers, named after the reference's
 // ScopedDebugZone labels, DDGINode.cpp:152-247); end() closes it early.

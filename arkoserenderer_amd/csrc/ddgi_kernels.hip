@@ -9,7 +9,8 @@
 //                       software 8-wide quantized BVH (80 B nodes) with a per-lane
 //                       LDS ring stack of node groups (spilling to HBM only beyond
 //                       kStackLds entries) and wave64 ballot refill of finished
-//                       lanes (raygen.rgen:35-92).
+//                       lanes from a wave-private LDS pool of staged ray records
+//                       (raygen.rgen:35-92).
 //   3. k_shadow_gen     lit lights of every front hit -> shadow-ray list
 //      k_trace_shadow   persistent any-hit traversal of that list (opaque.rchit:35-54).
 //   4. k_shade          closest-hit shading (opaque.rchit:105-176) with the shadow
@@ -895,36 +896,104 @@ __device__ __forceinline__ void grabRays(const FrameArgs& f, uint32_t* heads, ui
     }
 }
 
+// The same two grabs called by every lane of a wave with wave-uniform arguments
+// (k_trace): the partition arithmetic stays on the scalar unit, lane 0 alone adds to
+// the head counter and its answer is broadcast. The one-lane forms above run that
+// arithmetic as vector instructions with one lane enabled.
+__device__ __forceinline__ uint32_t waveAtomicAdd(uint32_t* p, uint32_t v, uint32_t lane)
+{
+    uint32_t off = 0;
+    if (lane == 0) off = atomicAdd(p, v);
+    return __builtin_amdgcn_readfirstlane(off);
+}
+
+__device__ __forceinline__ void grabItemsWave(uint32_t* heads, uint32_t total, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t CHUNK)
+{
+    b = e = 0;
+    for (; tried < kRayParts; ++tried) {
+        const uint32_t p = (home + tried) & (kRayParts - 1);
+        const uint32_t pb = static_cast<uint32_t>(static_cast<uint64_t>(total) * p / kRayParts);
+        const uint32_t pe = static_cast<uint32_t>(static_cast<uint64_t>(total) * (p + 1) / kRayParts);
+        if (pb >= pe) continue;
+        const uint32_t off = waveAtomicAdd(heads + p * kRayCounterStride, CHUNK, lane);
+        if (off < pe - pb) {
+            b = pb + off;
+            e = min(b + CHUNK, pe);
+            return;
+        }
+    }
+}
+
+__device__ __forceinline__ void grabRaysWave(const FrameArgs& f, uint32_t* heads, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t CHUNK)
+{
+    b = e = 0;
+    for (; tried < kRayParts; ++tried) {
+        const uint32_t p = (home + tried) & (kRayParts - 1);
+        const uint32_t pb = partRayBegin(f, p), pe = partRayBegin(f, p + 1);
+        if (pb >= pe) continue;
+        const uint32_t off = waveAtomicAdd(heads + p * kRayCounterStride, CHUNK, lane);
+        if (off < pe - pb) {
+            b = pb + off;
+            e = min(b + CHUNK, pe);
+            return;
+        }
+    }
+}
+
 // ---------------------------------------------------------------------------
 // 2b. k_trace: probe-ray traversal (persistent, per-lane wave64 ballot refill)
 // ---------------------------------------------------------------------------
 // Every lane owns one probe ray at a time (pass 0 opaque, 1 masked). One outer
 // iteration visits one BVH8 node or one leaf triangle per active lane; lanes whose
 // ray finished are refilled at the top of the next iteration from a wave-private
-// pool of consecutive ray indices (ballot + mbcnt rank, one atomic per 64 rays), so
-// the SIMD stays full until the global ray counter runs out.
+// pool of consecutive rays (ballot + mbcnt rank, one atomic per 64 rays), so the SIMD
+// stays full until the global ray counter runs out.
+//
+// The pool holds ray records, not just indices: when a wave grabs a chunk of at most
+// 64 consecutive rays, lane i sets up ray i of the chunk with every lane enabled
+// (Src::stage: the slot, origin and direction lookups, the rotation) and parks the
+// record in slot i of the wave's LDS region. A refill, which runs with a quarter of
+// the lanes, then only reads a record: no global load stands between a refill and
+// the new rays' first node fetch. The setup used to run in every refill, about four
+// times per chunk at quarter occupancy, behind two dependent global loads.
+
+// Ray record of the pool: origin, direction, one word of the source's own (28 B in a
+// 32-B slot, read and written as two 16-B halves).
+struct PoolRec {
+    V3 o, d;
+    uint32_t a;
+};
 
 // Ray sources of the closest-hit traversal. ProbeRays: the window's probe rays from
 // the slot table (raygen.rgen:35-92: opaque pass then masked pass, tmin 1e-4, tmax
 // zFar), partitions of whole probes. ListRays: a ray list of {origin, tmax},
 // {direction, id} (rt-reflections/raygen.rgen:111-119: RayFlags_Opaque, cullMask
 // 0x01, tmin 0.01), f.list_count entries, the hit record at the list index.
+// grab: the next chunk, called by every lane of the wave; stage(r): the record of ray
+// r (every lane, once per chunk); take(r, a): what a lane starting ray r needs
+// besides o and d (hit record index, tmax), from the record's own word.
 struct ProbeRays {
     static constexpr bool kMaskedPass = true;
     static constexpr float kTmin = 0.0001f;
-    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t& tried, uint32_t& b, uint32_t& e)
+    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
     {
-        grabRays(f, f.ray_counter, home, tried, b, e, f.grab_chunk);
+        grabRaysWave(f, f.ray_counter, home, lane, tried, b, e, chunk);
     }
-    __device__ static void load(const FrameArgs& f, uint32_t r, uint32_t& ray, V3& o, V3& d, float& tmax)
+    __device__ static PoolRec stage(const FrameArgs& f, uint32_t r)
     {
         const uint32_t qp = r / f.R;
         const uint32_t slot = slotAt(f, qp);
         const float4 fv = f.fib_order[r - qp * f.R]; // (direction, sample index)
         const GpuProbeSlot ps = f.slots[slot];
-        ray = slot * f.R + __float_as_uint(fv.w); // hit record index
-        o = { ps.pos[0], ps.pos[1], ps.pos[2] };
-        d = rotate(v3(fv.x, fv.y, fv.z), v3(ps.axis[0], ps.axis[1], ps.axis[2]), ps.angle_sin, ps.angle_cos);
+        PoolRec rec;
+        rec.o = { ps.pos[0], ps.pos[1], ps.pos[2] };
+        rec.d = rotate(v3(fv.x, fv.y, fv.z), v3(ps.axis[0], ps.axis[1], ps.axis[2]), ps.angle_sin, ps.angle_cos);
+        rec.a = slot * f.R + __float_as_uint(fv.w); // hit record index
+        return rec;
+    }
+    __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t recA, uint32_t& ray, float& tmax)
+    {
+        ray = recA;
         tmax = f.z_far;
     }
 };
@@ -932,36 +1001,53 @@ struct ProbeRays {
 struct ListRays {
     static constexpr bool kMaskedPass = false;
     static constexpr float kTmin = 0.01f;
-    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t& tried, uint32_t& b, uint32_t& e)
+    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
     {
-        grabItems(f.ray_counter, *f.list_count, home, tried, b, e, f.grab_chunk);
+        grabItemsWave(f.ray_counter, *f.list_count, home, lane, tried, b, e, chunk);
     }
-    __device__ static void load(const FrameArgs& f, uint32_t r, uint32_t& ray, V3& o, V3& d, float& tmax)
+    __device__ static PoolRec stage(const FrameArgs& f, uint32_t r)
     {
         const float4 a = f.ray_list[2u * r], b = f.ray_list[2u * r + 1u];
+        PoolRec rec;
+        rec.o = { a.x, a.y, a.z };
+        rec.d = { b.x, b.y, b.z };
+        rec.a = __float_as_uint(a.w); // tmax
+        return rec;
+    }
+    __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t recA, uint32_t& ray, float& tmax)
+    {
         ray = r;
-        o = { a.x, a.y, a.z };
-        tmax = a.w;
-        d = { b.x, b.y, b.z };
+        tmax = __uint_as_float(recA);
     }
 };
 
-template<bool COUNT, int WPE, class Src = ProbeRays>
+// SLOTS: records per wave pool. A chunk never exceeds it (the grab size is clamped to
+// it below). 64 for the whole-grid launches; the half-occupancy windows, which grab 32
+// rays at a time, run the 32-slot instance: their three workgroups per CU share the CU
+// with the previous frame's shadow traversal and shading, and 4 KB of LDS per workgroup
+// that no chunk would ever fill are taken from those (launch_trace).
+template<bool COUNT, int WPE, class Src = ProbeRays, int SLOTS = 64>
 __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace(SceneArgs sc, FrameArgs f)
 {
     if (frameAborted(f.abort_word)) return;
     __shared__ uint32_t ldsStack[kStackLds * 2 * kTraceBlock];
     // nodes from global memory only (GF dual steps): no LDS node cache, the octant table
     __shared__ uint4 ldsNodes[5];
+    // the waves' ray pools: SLOTS records each, as two 16-B halves [wave][half][slot]
+    static_assert(SLOTS == 32 || SLOTS == 64, "a wave stages at most one record per lane");
+    __shared__ uint4 ldsPool[2 * SLOTS * (kTraceBlock / 64)];
     const NodeCache nc = loadNodeCache<kTraceBlock, 0>(sc, ldsNodes);
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
     const uint32_t nthreads = gridDim.x * kTraceBlock;
     Stack<kTraceBlock> st { ldsStack + threadIdx.x, f.spill + gtid, nthreads, 0 };
     const uint32_t lane = threadIdx.x & 63u;
+    uint4* const pool = ldsPool + 2u * SLOTS * (threadIdx.x >> 6);
+    const uint32_t chunk = min(f.grab_chunk, static_cast<uint32_t>(SLOTS)); // a chunk fits the pool
     const float tmin = Src::kTmin;
     uint32_t cNodes = 0, cTris = 0, cHits = 0, cIter = 0, rSteps = 0;
 
-    uint32_t poolNext = 0, poolEnd = 0;
+    uint32_t poolNext = 0, poolEnd = 0; // rays of the pool not handed out yet
+    uint32_t poolBase = 0;              // the ray whose record is in slot 0
     const uint32_t home = xccId();
     uint32_t tried = 0; // partitions found drained (wave-uniform)
     bool exhausted = false;
@@ -1012,29 +1098,52 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
             const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(need >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(need), 0u));
             const uint32_t avail = poolEnd - poolNext;
             uint32_t fb = 0, fe = 0; // fresh chunk [fb, fe)
-            if (avail < n) {
-                uint32_t b = 0, e = 0, t = tried;
-                if (lane == 0) Src::grab(f, home, t, b, e);
-                fb = __shfl(b, 0);
-                fe = __shfl(e, 0);
-                tried = __shfl(t, 0);
+            if (avail < n) Src::grab(f, home, lane, tried, fb, fe, chunk); // every lane, wave-uniform
+            // An idle lane takes ray r by its rank among the idle lanes: the pool's
+            // leftover first, then the fresh chunk. The leftover records are read
+            // before the chunk is staged over them, and the chunk is staged before its
+            // records are read. The region is the wave's own, so no workgroup barrier:
+            // what is relied on is that the compiler keeps the region's reads and
+            // writes in program order (one sequentially consistent wave-level fence
+            // on each side of the staging) and that a wave's LDS operations execute
+            // in the order issued. A record goes straight into the idle lane's own o
+            // and d.
+            uint32_t r = kNoHit, recA = 0;
+            auto readRec = [&](uint32_t slot) {
+                const uint4 lo = pool[slot], hi = pool[SLOTS + slot];
+                o = { __uint_as_float(lo.x), __uint_as_float(lo.y), __uint_as_float(lo.z) };
+                d = { __uint_as_float(lo.w), __uint_as_float(hi.x), __uint_as_float(hi.y) };
+                recA = hi.z;
+            };
+            if (!active && rank < avail) {
+                r = poolNext + rank;
+                readRec(r - poolBase);
             }
-            if (!active) {
-                uint32_t r = kNoHit;
-                if (rank < avail) r = poolNext + rank;
-                else if (fb + (rank - avail) < fe) r = fb + (rank - avail);
-                if (r != kNoHit) {
-                    float tmax;
-                    Src::load(f, r, ray, o, d, tmax);
-                    idir = safeInv(d);
-                    oct = rayOctant(idir);
-                    active = true;
-                    h = RayHit { tmax, 0.0f, 0.0f, kNoHit, 0u, 0u, false };
-                    pass = 0;
-                    st.depth = 0;
-                    nBits = 0;
-                    ts = TravState { static_cast<uint32_t>(sc.root_opaque), sc.root_opaque >= 0 ? rootGroupBits() : 0u, 0u, 0u };
+            if (fb < fe) {
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                if (lane < fe - fb) {
+                    const PoolRec s = Src::stage(f, fb + lane);
+                    pool[lane] = make_uint4(__float_as_uint(s.o.x), __float_as_uint(s.o.y), __float_as_uint(s.o.z), __float_as_uint(s.d.x));
+                    pool[SLOTS + lane] = make_uint4(__float_as_uint(s.d.y), __float_as_uint(s.d.z), s.a, 0u);
                 }
+                __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+                poolBase = __builtin_amdgcn_readfirstlane(fb);
+                if (!active && rank >= avail && rank - avail < fe - fb) {
+                    r = fb + (rank - avail);
+                    readRec(rank - avail);
+                }
+            }
+            if (r != kNoHit) {
+                float tmax;
+                Src::take(f, r, recA, ray, tmax);
+                idir = safeInv(d);
+                oct = rayOctant(idir);
+                active = true;
+                h = RayHit { tmax, 0.0f, 0.0f, kNoHit, 0u, 0u, false };
+                pass = 0;
+                st.depth = 0;
+                nBits = 0;
+                ts = TravState { static_cast<uint32_t>(sc.root_opaque), sc.root_opaque >= 0 ? rootGroupBits() : 0u, 0u, 0u };
             }
             if (avail < n) {
                 if (fb >= fe) {
@@ -2295,10 +2404,14 @@ const void* kernel_trace_ptr(bool count)
     return count ? reinterpret_cast<const void*>(&dev::k_trace<true, 1>) : reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe>);
 }
 
+// A launch whose chunks are at most 32 rays (the half-occupancy windows) runs the
+// instance with 32-slot pools: 4 KB less LDS per workgroup for the kernels beside it.
 hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s)
 {
     void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
-    return hipLaunchKernel(kernel_trace_ptr(count), dim3(blocks), dim3(kTraceBlock), args, 0, s);
+    const void* fn = kernel_trace_ptr(count);
+    if (!count && f.grab_chunk <= 32u) fn = reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::ProbeRays, 32>);
+    return hipLaunchKernel(fn, dim3(blocks), dim3(kTraceBlock), args, 0, s);
 }
 
 // Co-resident workgroups of a persistent kernel on this device (cached per kernel).
