@@ -52,6 +52,7 @@ ARK_DDGI_SUN_BVH_WORLD = 1
 ARK_DDGI_SUN_BVH_LIGHT_SPACE = 2
 ARK_DDGI_FLAG_SERIAL_FRAMES = 0x1
 ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD = 0x2
+ARK_DDGI_FLAG_GPU_REBUILD = 0x4
 
 ARK_TEX_RGBA8_UNORM = 0
 ARK_TEX_RGBA8_SRGB = 1
@@ -288,6 +289,9 @@ class ArkDdgiBvhStats(C.Structure):
         ("bvh_built_refit_version", C.c_uint32),
         ("sun_built_refit_version", C.c_uint32),
         ("bvh_rebuild_failures", C.c_uint32),
+        ("bvh_gpu_rebuilds", C.c_uint32),
+        ("bvh_gpu_fallbacks", C.c_uint32),
+        ("bvh_installed_builder", C.c_uint32),
     ]
 
 
@@ -504,6 +508,9 @@ EXPORTS = {
     "ark_ddgi_debug_sun_bvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_choice": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.POINTER(C.c_double)]),
     "ark_ddgi_debug_scene_digest": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_world_bvh_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

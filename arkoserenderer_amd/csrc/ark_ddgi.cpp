@@ -221,6 +221,10 @@ struct WorldJob {
     std::vector<uint32_t> levelOffsets;
     float ms = 0.0f;
     bool ok = false;
+    // runWorldJobGpu: the device built the result; or it handed the job to the host build
+    // (t0: the job's start, so that ms stays the whole job's wall time)
+    bool gpu = false, gpuFallback = false;
+    std::chrono::steady_clock::time_point t0 {};
     std::string error;
     ~WorldJob()
     {
@@ -330,6 +334,9 @@ struct SceneStore {
     std::unique_ptr<WorldJob> worldJob;
     uint32_t worldRebuilds = 0, refitCount = 0;
     bool worldRebuildFailed = false;
+    // ARK_DDGI_FLAG_GPU_REBUILD: the installed world BVHs are a device build (an LBVH: once
+    // the motion stops one host rebuild replaces it, worldSettleWanted)
+    bool worldGpuBuilt = false;
     // the background build started last (loosenedTurn: loosened BVHs take turns)
     enum : uint8_t { kBackgroundNone, kBackgroundWorld, kBackgroundSun };
     uint8_t lastBackground = kBackgroundNone;
@@ -1081,7 +1088,7 @@ bool checkBvh8Structure(const std::vector<GpuBvh8Node>& allNodes, const std::vec
 // bit for bit), the record order's source indices and the refit's level order.
 void runWorldJob(WorldJob* job, int device, int threads)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = job->gpuFallback ? job->t0 : std::chrono::steady_clock::now();
     bool ok = hipSetDevice(device) == hipSuccess;
     hipStream_t s = nullptr;
     ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
@@ -1188,6 +1195,258 @@ void runWorldJob(WorldJob* job, int device, int threads)
     job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     job->ok = ok;
     job->done.store(true, std::memory_order_release);
+}
+
+// The deepest BVH8 the device build installs. The traversal's spill area is sized from the
+// installed depth (ensureSpill: depth + 2 - kStackLds entries per lane, st.worldDepth),
+// and the deepest tree the host builds hand it is bounded by the BVH2 builder's depth cap
+// (BvhBuildOptions::max_depth, 60); a radix tree over coincident centroids can be
+// deeper, and such a scene is left to the host build.
+constexpr uint32_t kGpuBuildMaxDepth = 60;
+
+// Errors after which the device is not used again by the job (no host fallback)
+bool isDeviceFault(hipError_t e)
+{
+    return e == hipErrorIllegalAddress || e == hipErrorLaunchFailure || e == hipErrorLaunchTimeOut || e == hipErrorECCNotCorrectable || e == hipErrorAssert ||
+           e == hipErrorNoDevice || e == hipErrorInvalidDevice;
+}
+
+// The device build of runWorldJobGpu on `s`: hipSuccess and `why` empty when job holds the
+// result; `why` set when the host has to build this scene.
+hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
+{
+    // Scratch in two allocations (one sized from the snapshot, one from the count of
+    // triangles read back): a free waits for the device's streams, frames in flight included
+    struct Arena {
+        DeviceBuffer buf;
+        size_t used = 0;
+        static size_t pad(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
+        DeviceBuffer take(size_t n)
+        {
+            DeviceBuffer b;
+            b.ptr = static_cast<char*>(buf.ptr) + used;
+            b.bytes = n;
+            used += pad(n);
+            return b; // a view: never released
+        }
+        ~Arena() { buf.release(); }
+    } arenaA, arenaB;
+    struct {
+        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes;
+    } w;
+    hipError_t e = hipSuccess;
+#define ARK_GB(expr)                          \
+    do {                                      \
+        if ((e = (expr)) != hipSuccess) return e; \
+    } while (0)
+    if (job->snapRecords == 0 || job->snapRecords > 0x7fffffffull || job->classOf.empty()) {
+        why = "no records";
+        return hipSuccess;
+    }
+    const uint32_t records = static_cast<uint32_t>(job->snapRecords), instances = static_cast<uint32_t>(job->classOf.size());
+    const GpuTriangle* snap = job->snap.as<GpuTriangle>();
+    std::vector<uint32_t> classHost(job->classOf.begin(), job->classOf.end());
+    ARK_GB(arenaA.buf.alloc(Arena::pad(instances * 4ull) + Arena::pad(sizeof(LbvhHeader)) + Arena::pad(records * 4ull) + Arena::pad(records * 8ull)));
+    w.classOf = arenaA.take(instances * 4ull);
+    w.hdr = arenaA.take(sizeof(LbvhHeader));
+    w.idx = arenaA.take(records * 4ull);
+    w.keys = arenaA.take(records * 8ull);
+    ARK_GB(hipMemcpyAsync(w.classOf.ptr, classHost.data(), instances * 4ull, hipMemcpyHostToDevice, s));
+    ARK_GB(hipStreamWaitEvent(s, job->evSnap, 0));
+    ARK_GB(launch_lbvh_prims(snap, records, w.classOf.as<uint32_t>(), instances, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
+    LbvhHeader hdr {};
+    ARK_GB(hipMemcpyAsync(&hdr, w.hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost, s));
+    ARK_GB(hipStreamSynchronize(s));
+    if (hdr.error || hdr.prims == 0 || hdr.prims > records || hdr.classCount[0] + hdr.classCount[1] + hdr.classCount[2] != hdr.prims) {
+        why = hdr.error ? "record of an unknown instance" : "no triangles";
+        return hipSuccess;
+    }
+    const uint32_t n = hdr.prims;
+    // sort the (key, record index) pairs
+    size_t tempBytes = 0;
+    ARK_GB(launch_lbvh_sort(nullptr, tempBytes, w.keys.as<uint64_t>(), nullptr, w.idx.as<uint32_t>(), nullptr, n, s));
+    // (the collapse's bound on the nodes: below)
+    const uint32_t nodeCap = n / 2u + 8u;
+    {
+        const size_t sizes[] = { tempBytes, n * 8ull, n * 4ull, n * 4ull, nodeCap * sizeof(GpuBvh8Node), nodeCap * sizeof(lbvh::Member), nodeCap * sizeof(lbvh::Member),
+                                 n * 4ull, kLbvhCounters * 4ull, nodeCap * 8ull, instances * sizeof(RefitInstance), nodeCap * 6ull * sizeof(float) };
+        size_t total = 0;
+        for (size_t b : sizes) total += Arena::pad(b);
+        ARK_GB(arenaB.buf.alloc(total));
+        w.sortTemp = arenaB.take(sizes[0]);
+        w.keysSorted = arenaB.take(sizes[1]);
+        w.idxSorted = arenaB.take(sizes[2]);
+        w.split = arenaB.take(sizes[3]);
+        w.nodes = arenaB.take(sizes[4]);
+        w.items[0] = arenaB.take(sizes[5]);
+        w.items[1] = arenaB.take(sizes[6]);
+        w.position = arenaB.take(sizes[7]);
+        w.counters = arenaB.take(sizes[8]);
+        w.masks = arenaB.take(sizes[9]);
+        w.inst = arenaB.take(sizes[10]);
+        w.boxes = arenaB.take(sizes[11]);
+    }
+    ARK_GB(launch_lbvh_sort(w.sortTemp.ptr, tempBytes, w.keys.as<uint64_t>(), w.keysSorted.as<uint64_t>(), w.idx.as<uint32_t>(), w.idxSorted.as<uint32_t>(), n, s));
+    // the radix trees, class by class
+    uint32_t classLo[3], first = 0;
+    for (int c = 0; c < 3; ++c) {
+        classLo[c] = first;
+        first += hdr.classCount[c];
+        ARK_GB(launch_lbvh_hierarchy(w.keysSorted.as<uint64_t>(), classLo[c], classLo[c] + hdr.classCount[c], w.split.as<uint32_t>(), s));
+    }
+    // the collapse. Every BVH8 node but a class's root is a BVH2 node of at least 4
+    // triangles, and one with an internal child has 8 members. With L nodes without an
+    // internal child (4 triangles of their own each), C with one (7 members of their
+    // own) and fewer than L with more, 4 L + 7 C <= n bounds 2 L + C by n / 2: fewer than
+    // n / 2 + 3 nodes (the kernel checks, and the job falls back beyond).
+    ARK_GB(hipMemsetAsync(w.counters.ptr, 0, kLbvhCounters * 4, s));
+    float lo[3], hi[3];
+    LbvhCollapseArgs a {};
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = lbvhOrderedFloat(hdr.lo[k]);
+        hi[k] = lbvhOrderedFloat(hdr.hi[k]);
+        a.extent[k] = hi[k] - lo[k];
+    }
+    a.keys = w.keysSorted.as<uint64_t>();
+    a.split = w.split.as<uint32_t>();
+    a.nodes = w.nodes.as<GpuBvh8Node>();
+    a.position = w.position.as<uint32_t>();
+    a.counters = w.counters.as<uint32_t>();
+    a.criterion = lbvh::kDefaultCriterion;
+    std::vector<std::array<uint32_t, 3>> levels; // node counts [depth][class]
+    uint32_t nodeTotal = 0, counters[kLbvhCounters] = {};
+    for (int c = 0; c < 3; ++c) {
+        if (!hdr.classCount[c]) continue;
+        job->roots[c] = static_cast<int32_t>(nodeTotal);
+        a.items = nullptr;
+        a.root.r.first = classLo[c];
+        a.root.r.last = classLo[c] + hdr.classCount[c] - 1u;
+        a.root.node = classLo[c];
+        a.count = 1;
+        a.levelBase = nodeTotal;
+        int pong = 0;
+        for (uint32_t depth = 0; a.count; ++depth) {
+            if (depth >= kGpuBuildMaxDepth || a.levelBase + a.count > nodeCap) {
+                why = depth >= kGpuBuildMaxDepth ? "BVH8 deeper than the device build installs" : "more nodes than the device build's scratch";
+                return hipSuccess;
+            }
+            a.nextBase = a.levelBase + a.count;
+            a.nextCapacity = nodeCap - a.nextBase;
+            a.next = w.items[pong].as<lbvh::Member>();
+            ARK_GB(hipMemsetAsync(w.counters.as<uint32_t>() + kLbvhNextCount, 0, 4, s));
+            ARK_GB(launch_lbvh_collapse(a, s));
+            // the level's count, before the next level is launched
+            ARK_GB(hipMemcpyAsync(counters, w.counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, s));
+            ARK_GB(hipStreamSynchronize(s));
+            if (counters[kLbvhOverflow]) {
+                why = "more nodes than the device build's scratch";
+                return hipSuccess;
+            }
+            if (levels.size() <= depth) levels.push_back({ 0u, 0u, 0u });
+            levels[depth][c] = a.count;
+            a.items = a.next;
+            a.levelBase = a.nextBase;
+            a.count = counters[kLbvhNextCount];
+            pong ^= 1;
+        }
+        nodeTotal = a.levelBase;
+        if (c == 0) job->opaqueNodes = nodeTotal;
+    }
+    const uint32_t outRecords = counters[kLbvhRecords];
+    const size_t nb = nodeTotal * sizeof(GpuBvh8Node);
+    job->triOffset = (nb + 255) & ~static_cast<size_t>(255);
+    if (!(job->triOffset + (outRecords + 1ull) * sizeof(GpuTriangle) < (1ull << 32))) {
+        why = "nodes and records of 4 GiB or more";
+        return hipSuccess;
+    }
+    // the installed buffers, sized from the counts read back
+    ARK_GB(job->buf.alloc(job->triOffset + (outRecords + 1ull) * sizeof(GpuTriangle)));
+    ARK_GB(job->perm.alloc(std::max<size_t>(16, outRecords * 4ull)));
+    GpuBvh8Node* nodes = job->buf.as<GpuBvh8Node>();
+    GpuTriangle* tris = reinterpret_cast<GpuTriangle*>(static_cast<char*>(job->buf.ptr) + job->triOffset);
+    ARK_GB(hipMemcpyAsync(nodes, w.nodes.ptr, nb, hipMemcpyDeviceToDevice, s));
+    ARK_GB(launch_lbvh_scatter(snap, w.idxSorted.as<uint32_t>(), w.position.as<uint32_t>(), tris, job->perm.as<uint32_t>(), n, outRecords, s));
+    // the refit's level order from the level counts (bvhLevelOrder's format: deepest level
+    // first, ascending node index within a level; each class one breadth-first range)
+    std::vector<uint32_t> order;
+    order.reserve(nodeTotal);
+    job->levelOffsets.assign(1, 0u);
+    {
+        std::vector<std::array<uint32_t, 3>> base(levels.size());
+        uint32_t at[3];
+        for (int c = 0; c < 3; ++c) at[c] = job->roots[c] >= 0 ? static_cast<uint32_t>(job->roots[c]) : 0u;
+        for (size_t d = 0; d < levels.size(); ++d)
+            for (int c = 0; c < 3; ++c) {
+                base[d][c] = at[c];
+                at[c] += levels[d][c];
+            }
+        for (size_t d = levels.size(); d-- > 0;) {
+            for (int c = 0; c < 3; ++c)
+                for (uint32_t k = 0; k < levels[d][c]; ++k) order.push_back(base[d][c] + k);
+            job->levelOffsets.push_back(static_cast<uint32_t>(order.size()));
+        }
+    }
+    ARK_GB(job->order.alloc(std::max<size_t>(16, order.size() * 4)));
+    ARK_GB(hipMemcpyAsync(job->order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
+    // boxes, grids and planes: the refit over every level, deepest first, every node live
+    // (all mask bits set, no instance dirty: no record is touched), the inflation runWorldJob's
+    ARK_GB(hipMemsetAsync(w.masks.ptr, 0xff, nodeTotal * 8ull, s));
+    ARK_GB(hipMemsetAsync(w.inst.ptr, 0, instances * sizeof(RefitInstance), s));
+    RefitBoxArgs ra {};
+    ra.inflate = bvh8_inflation_box(lo, hi);
+    ra.light = 0;
+    ra.dirty = ~0ull;
+    for (size_t l = 0; l + 1 < job->levelOffsets.size(); ++l)
+        ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), job->order.as<uint32_t>() + job->levelOffsets[l], job->levelOffsets[l + 1] - job->levelOffsets[l], ra,
+                                  w.masks.as<uint64_t>(), w.inst.as<RefitInstance>(), nullptr, nullptr, s));
+    ARK_GB(hipStreamSynchronize(s));
+#undef ARK_GB
+    job->nodes = nodeTotal;
+    job->triRecords = outRecords;
+    job->triangles = n;
+    job->depth = static_cast<uint32_t>(levels.size());
+    job->maxLeaf = std::min<uint32_t>(n, static_cast<uint32_t>(kBvh8MaxLeafSize));
+    job->sah = 0.0f; // not evaluated on the device
+    return hipSuccess;
+}
+
+// The world rebuild's thread with ARK_DDGI_FLAG_GPU_REBUILD: the same inputs and outputs as
+// runWorldJob, the three BVHs built on the device (ddgi_bvh_build.hip) on a stream of the
+// lowest priority that waits for the snapshot on the device. A scene the device build
+// does not take (4 GiB, depth, an error that is not a device fault) is built by
+// runWorldJob within this job.
+void runWorldJobGpu(WorldJob* job, int device, int threads)
+{
+    job->t0 = std::chrono::steady_clock::now();
+    hipStream_t s = nullptr;
+    std::string why;
+    hipError_t e = hipSetDevice(device);
+    int least = 0, greatest = 0;
+    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
+    if (e == hipSuccess) e = buildWorldGpu(job, s, why);
+    if (s) (void)hipStreamDestroy(s);
+    if (e == hipSuccess && why.empty()) {
+        job->gpu = true;
+        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
+        job->ok = true;
+        job->done.store(true, std::memory_order_release);
+        return;
+    }
+    if (isDeviceFault(e)) {
+        job->error = std::string("device build: ") + hipGetErrorString(e);
+        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
+        job->ok = false;
+        job->done.store(true, std::memory_order_release);
+        return;
+    }
+    // the host build from the same snapshot
+    for (DeviceBuffer* b : { &job->buf, &job->perm, &job->order }) b->release();
+    job->roots[0] = job->roots[1] = job->roots[2] = -1;
+    job->opaqueNodes = 0;
+    job->levelOffsets.clear();
+    job->gpuFallback = true;
+    runWorldJob(job, device, threads);
 }
 
 // Frames in flight may read what an install replaces: a shared scene waits for the
@@ -1320,6 +1579,17 @@ bool worldStartWanted(const ArkDdgiCtx* ctx)
     return !st.worldJob && st.refitsSinceBuild != 0 && !st.worldRebuildFailed && !(ctx->desc.flags & ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD);
 }
 
+// The settle rebuild of ARK_DDGI_FLAG_GPU_REBUILD: the installed world BVHs are a device
+// build and no refit has arrived since their snapshot - the motion has stopped - so one
+// host rebuild replaces the LBVH with the SAH tree a static scene traces faster.
+bool worldSettleWanted(const ArkDdgiCtx* ctx)
+{
+    const SceneStore& st = *ctx->sceneStore;
+    const uint32_t f = ctx->desc.flags;
+    return (f & ARK_DDGI_FLAG_GPU_REBUILD) && !(f & ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD) && st.worldGpuBuilt && !st.worldJob && st.refitsSinceBuild == 0 &&
+           !st.worldRebuildFailed;
+}
+
 int sunStart(ArkDdgiCtx* ctx, hipStream_t s)
 {
     SceneStore& st = *ctx->sceneStore;
@@ -1367,6 +1637,7 @@ int worldCollect(ArkDdgiCtx* ctx, hipStream_t s)
     if (st.worldJob && st.worldJob->done.load(std::memory_order_acquire)) {
         std::unique_ptr<WorldJob> job = std::move(st.worldJob);
         job->t.join();
+        if (job->gpuFallback) st.bvhStats.bvh_gpu_fallbacks++;
         if (!job->ok) {
             // the refitted BVHs stay (results do not depend on the tree); no more
             // background rebuilds of this scene (a set_scene builds anew), reported in
@@ -1416,6 +1687,9 @@ int worldCollect(ArkDdgiCtx* ctx, hipStream_t s)
         st.bvhStats.triangle_bytes = job->triRecords * sizeof(GpuTriangle);
         st.bvhStats.bvh_rebuilds = ++st.worldRebuilds;
         st.bvhStats.bvh_rebuild_ms = job->ms;
+        st.worldGpuBuilt = job->gpu;
+        st.bvhStats.bvh_installed_builder = job->gpu ? 1u : 0u;
+        if (job->gpu) st.bvhStats.bvh_gpu_rebuilds++;
         st.refitsSinceBuild = st.refitCount - job->refitsAt; // refits since its snapshot
         st.bvhStats.bvh_built_refit_version = job->refitsAt;
         markTopologyChanged(st);
@@ -1433,7 +1707,7 @@ int worldCollect(ArkDdgiCtx* ctx, hipStream_t s)
     return ARK_DDGI_OK;
 }
 
-int worldStart(ArkDdgiCtx* ctx, hipStream_t s)
+int worldStart(ArkDdgiCtx* ctx, hipStream_t s, bool gpu)
 {
     SceneStore& st = *ctx->sceneStore;
     auto job = std::make_unique<WorldJob>();
@@ -1448,7 +1722,7 @@ int worldStart(ArkDdgiCtx* ctx, hipStream_t s)
     ARK_HIP(orderBegin(ctx, s));
     ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
     // half the host threads: the other half stays with the frames being enqueued meanwhile
-    job->t = std::thread(runWorldJob, job.get(), st.device, std::max(1, st.buildThreads / 2));
+    job->t = std::thread(gpu ? runWorldJobGpu : runWorldJob, job.get(), st.device, std::max(1, st.buildThreads / 2));
     st.worldJob = std::move(job);
     st.lastBackground = SceneStore::kBackgroundWorld;
     st.refitsSinceBuild = 0;
@@ -1466,8 +1740,10 @@ int sceneMaintenance(ArkDdgiCtx* ctx, hipStream_t s)
     if (k == kSunMissing) {
         if (const int rc = sunStart(ctx, s)) return rc;
     }
-    const bool world = worldStartWanted(ctx), sun = k == kSunLoosened;
-    if (world && loosenedTurn(*ctx->sceneStore, SceneStore::kBackgroundWorld, sun)) return worldStart(ctx, s);
+    // loosened world BVHs: the device build with ARK_DDGI_FLAG_GPU_REBUILD; settled ones it built: the host's
+    const bool loosened = worldStartWanted(ctx), world = loosened || worldSettleWanted(ctx), sun = k == kSunLoosened;
+    if (world && loosenedTurn(*ctx->sceneStore, SceneStore::kBackgroundWorld, sun))
+        return worldStart(ctx, s, loosened && (ctx->desc.flags & ARK_DDGI_FLAG_GPU_REBUILD));
     if (sun && loosenedTurn(*ctx->sceneStore, SceneStore::kBackgroundSun, world)) return sunStart(ctx, s);
     return ARK_DDGI_OK;
 }
@@ -1515,7 +1791,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     ctx->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     const int shards = desc->shard_count > 0 ? desc->shard_count : 1;
     if (ctx->Rmax > ARK_DDGI_MAX_RAYS_PER_PROBE || ctx->Z % shards != 0 || desc->shard_rank < 0 || desc->shard_rank >= shards ||
-        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD)) ||
+        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD)) ||
         desc->build_threads < 0) {
         delete ctx;
         return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -2281,6 +2557,63 @@ int ark_ddgi_debug_scene_digest(ArkDdgiCtx* ctx, uint64_t* out)
     ARK_HIP(digest(sun ? st.sunArgs.sun_tris : nullptr, st.sunTriRecords * sizeof(GpuTriangle), out[3]));
     if (!sun) out[2] = out[3] = 0;
     return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_world_bvh_check(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "world BVH check before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    const SceneStore& st = *ctx->sceneStore;
+    std::vector<GpuBvh8Node> nodes(st.bvhStats.node_count);
+    std::vector<GpuTriangle> tris(st.triRecords);
+    std::vector<uint32_t> order(nodes.size());
+    if (!nodes.empty()) ARK_HIP(hipMemcpy(nodes.data(), st.args.nodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
+    if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), st.args.tris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
+    if (!order.empty() && st.refitOrder.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.refitOrder.ptr, order.size() * 4, hipMemcpyDeviceToHost));
+    std::vector<int> classOf(st.instHost.size());
+    for (size_t i = 0; i < st.instHost.size(); ++i) {
+        const uint32_t m = st.instHost[i].hit_mask;
+        classOf[i] = (m & ARK_RT_HIT_MASK_OPAQUE) ? 0 : (m & ARK_RT_HIT_MASK_MASKED) ? 1 : 2;
+    }
+    const int32_t roots[3] = { st.args.root_opaque, st.args.root_masked, st.args.root_blend };
+    Bvh8CheckResult c = check_bvh8_full(nodes, tris, roots, 3, &classOf, nullptr);
+    std::string why;
+    if (!checkBvh8Structure(nodes, tris, roots, 3, why)) c.violations++;
+    if (c.nodes != nodes.size()) c.violations++; // a node outside the classes' ranges
+    if (st.worldGpuBuilt) c.violations += c.notBreadthFirst; // the device build's order (the host collapse's: breadth first per subtree block)
+    if (roots[0] >= 0 && st.args.opaque_nodes != static_cast<uint32_t>((roots[1] >= 0 ? roots[1] : roots[2] >= 0 ? roots[2] : static_cast<int32_t>(nodes.size())) - roots[0]))
+        c.violations++;
+    // the refit's level order (none before the first refit after set_scene) against the
+    // one recomputed from the downloaded nodes
+    std::vector<uint32_t> wantOrder, wantOffsets;
+    if (!bvhLevelOrder(nodes.data(), nodes.size(), roots, 3, wantOrder, wantOffsets)) {
+        c.violations++;
+    } else if (!st.levelOffsets.empty() && (wantOrder != order || wantOffsets != st.levelOffsets)) {
+        c.violations++;
+        why += " level order";
+    }
+    uint64_t live = 0, digest = 0;
+    for (const GpuTriangle& g : tris) {
+        if (isHoleTriangle(g)) continue;
+        ++live;
+        uint64_t h = 1469598103934665603ull;
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(&g);
+        for (size_t k = 0; k < sizeof(GpuTriangle); ++k) h = (h ^ b[k]) * 1099511628211ull;
+        digest += h;
+    }
+    if (live != c.triangles) c.violations++;
+    out[0] = nodes.size();
+    out[1] = c.leafChildren;
+    out[2] = c.maxDepth;
+    out[3] = c.violations;
+    out[4] = live;
+    out[5] = tris.size();
+    out[6] = digest;
+    out[7] = st.worldGpuBuilt ? 1u : 0u;
+    if (c.violations) ctx->lastError = "world BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
+    return c.violations ? 1 : ARK_DDGI_OK;
 }
 
 int ark_ddgi_set_instances(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count)

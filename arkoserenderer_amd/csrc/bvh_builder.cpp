@@ -569,6 +569,35 @@ void quantGrid(float L, float H, int& e, double& p)
     }
 }
 
+// The node writer: the quantization grid of a node over `box` (p, e) and the
+// outward-rounded planes of its slots' boxes (null: an unused slot, left as it is)
+void writeNodePlanes(GpuBvh8Node& nd, const Aabb& box, const Aabb* const slotBox[8])
+{
+    double step[3], p[3];
+    for (int a = 0; a < 3; ++a) {
+        int e;
+        quantGrid(box.lo[a], box.hi[a], e, p[a]);
+        step[a] = std::ldexp(1.0, e);
+        nd.p[a] = static_cast<float>(p[a]);
+        nd.e[a] = static_cast<uint8_t>(e + 127);
+    }
+    for (int s = 0; s < 8; ++s) {
+        if (!slotBox[s]) continue;
+        const Aabb& b = *slotBox[s];
+        for (int a = 0; a < 3; ++a) {
+            double ql = std::floor((static_cast<double>(b.lo[a]) - p[a]) / step[a]);
+            double qh = std::ceil((static_cast<double>(b.hi[a]) - p[a]) / step[a]);
+            ql = std::min(255.0, std::max(0.0, ql));
+            qh = std::min(255.0, std::max(0.0, qh));
+            // outward rounding, checked on the exact fp32 decode
+            while (ql > 0.0 && static_cast<double>(static_cast<float>(p[a] + ql * step[a])) > b.lo[a]) ql -= 1.0;
+            while (qh < 255.0 && static_cast<double>(static_cast<float>(p[a] + qh * step[a])) < b.hi[a]) qh += 1.0;
+            nd.qlo[a][s] = static_cast<uint8_t>(ql);
+            nd.qhi[a][s] = static_cast<uint8_t>(qh);
+        }
+    }
+}
+
 // First-fit placement of a node's leaf-triangle rows (a 24-bit pattern over
 // positions base + 0..23) into the triangle array: the lowest base, at most
 // kRowWindow below the end of the array, whose positions are all free. The search
@@ -1017,16 +1046,13 @@ void collapseQueue(const BvhBuildResult& bvh2, const CollapsePlan& plan, const B
                 childIn[sl] = leaves[i];
             }
         }
-        // quantization grid of this node
+        // quantization grid of this node, the planes of its children
         GpuBvh8Node nd;
         std::memset(&nd, 0, sizeof(nd));
-        double step[3], p[3];
-        for (int a = 0; a < 3; ++a) {
-            int e;
-            quantGrid(box.lo[a], box.hi[a], e, p[a]);
-            step[a] = std::ldexp(1.0, e);
-            nd.p[a] = static_cast<float>(p[a]);
-            nd.e[a] = static_cast<uint8_t>(e + 127);
+        {
+            const Aabb* slotBox[8];
+            for (int s = 0; s < 8; ++s) slotBox[s] = childIn[s] >= 0 ? &ch[childIn[s]].box : nullptr;
+            writeNodePlanes(nd, box, slotBox);
         }
         // children in slot order: internal ones get consecutive node indices; leaf
         // triangle i of slot s goes to position s + stride * i (GpuBvh8Node), the
@@ -1056,17 +1082,6 @@ void collapseQueue(const BvhBuildResult& bvh2, const CollapsePlan& plan, const B
             const int c = childIn[s];
             if (c < 0) continue;
             const Child8& k = ch[c];
-            for (int a = 0; a < 3; ++a) {
-                double ql = std::floor((static_cast<double>(k.box.lo[a]) - p[a]) / step[a]);
-                double qh = std::ceil((static_cast<double>(k.box.hi[a]) - p[a]) / step[a]);
-                ql = std::min(255.0, std::max(0.0, ql));
-                qh = std::min(255.0, std::max(0.0, qh));
-                // outward rounding, checked on the exact fp32 decode
-                while (ql > 0.0 && static_cast<double>(static_cast<float>(p[a] + ql * step[a])) > k.box.lo[a]) ql -= 1.0;
-                while (qh < 255.0 && static_cast<double>(static_cast<float>(p[a] + qh * step[a])) < k.box.hi[a]) qh += 1.0;
-                nd.qlo[a][s] = static_cast<uint8_t>(ql);
-                nd.qhi[a][s] = static_cast<uint8_t>(qh);
-            }
             if (k.code >= 0) {
                 nd.imask |= static_cast<uint8_t>(1u << s);
                 queue.push_back({ static_cast<uint32_t>(k.code), childBase + nInternal, it.depth + 1 });
@@ -1687,4 +1702,377 @@ extern "C" int ark_ddgi_debug_sun_choice(const float* triangles, uint64_t n, con
     out[2] = sun_bvh_pays(out[0], out[1]) ? 1.0 : 0.0;
     out[3] = static_cast<double>(origins.size() / 3);
     return 0;
+}
+
+// --- the device LBVH's build logic on the host (lbvh_build.h) and the checks shared by
+// ark_ddgi_debug_lbvh_check and ark_ddgi_debug_world_bvh_check ------------------------
+namespace ark {
+
+namespace {
+// writeNode's inflation of a child box (k_refit_nodes inflateBox)
+void inflateChildBox(Aabb& b, float inflateAbs)
+{
+    float m = 0.0f, e = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        m = std::max(m, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
+        e = std::max(e, b.hi[a] - b.lo[a]);
+    }
+    const float eps = m * 2e-6f + e * 1e-5f + 1e-7f + inflateAbs;
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] -= eps;
+        b.hi[a] += eps;
+    }
+}
+
+// the vertices Möller-Trumbore tests: v0, v0 + e1, v0 + e2
+void recordVertices(const GpuTriangle& g, float v[3][3])
+{
+    const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
+    for (int a = 0; a < 3; ++a) {
+        v[0][a] = g.t0[a];
+        v[1][a] = g.t0[a] + e1[a];
+        v[2][a] = g.t0[a] + e2[a];
+    }
+}
+} // namespace
+
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion)
+{
+    LbvhHostResult R;
+    // primitives: the records that are not holes, their boxes, the scene box
+    std::vector<uint32_t> idx;
+    std::vector<Aabb> pbox;
+    Aabb scene;
+    for (size_t i = 0; i < rec.size(); ++i) {
+        if (isHoleTriangle(rec[i])) continue;
+        float v[3][3];
+        recordVertices(rec[i], v);
+        Aabb b;
+        for (int k = 0; k < 3; ++k) b.grow(v[k]);
+        scene.grow(b);
+        idx.push_back(static_cast<uint32_t>(i));
+        pbox.push_back(b);
+    }
+    const uint32_t n = static_cast<uint32_t>(idx.size());
+    const float inflateAbs = n ? bvh8_inflation_box(scene.lo, scene.hi) : 0.0f;
+    float scale[3], extent[3];
+    for (int a = 0; a < 3; ++a) {
+        scale[a] = n ? lbvh::mortonScale(scene.lo[a], scene.hi[a]) : 0.0f;
+        extent[a] = n ? scene.hi[a] - scene.lo[a] : 0.0f;
+    }
+    auto instanceOf = [&](uint32_t record) {
+        uint32_t inst;
+        std::memcpy(&inst, &rec[record].t2[1], 4);
+        return inst;
+    };
+    std::vector<uint64_t> key(n);
+    uint32_t classCount[3] = { 0, 0, 0 };
+    for (uint32_t j = 0; j < n; ++j) {
+        float c[3];
+        for (int a = 0; a < 3; ++a) c[a] = 0.5f * pbox[j].lo[a] + 0.5f * pbox[j].hi[a];
+        const uint32_t inst = instanceOf(idx[j]);
+        const int cls = inst < classOf.size() ? classOf[inst] : 0;
+        classCount[cls]++;
+        key[j] = lbvh::mortonKey(c, scene.lo, scale, static_cast<uint32_t>(cls));
+    }
+    std::vector<uint32_t> sorted(n);
+    for (uint32_t j = 0; j < n; ++j) sorted[j] = j;
+    std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    std::vector<uint64_t> keys(n);
+    for (uint32_t j = 0; j < n; ++j) keys[j] = key[sorted[j]];
+    std::vector<uint32_t> split(n, 0u), position(n, 0u);
+    // hierarchy and collapse, class by class, level by level (the kernels' atomics: plain counters)
+    uint32_t records = 0, first = 0;
+    std::vector<std::vector<uint32_t>> levels; // node counts [depth][class]
+    for (int c = 0; c < 3; ++c) {
+        const uint32_t lo = first, hi = first + classCount[c];
+        first = hi;
+        if (lo == hi) continue;
+        for (uint32_t i = lo; i + 1u < hi; ++i) split[i] = lbvh::findSplit(keys.data(), lo, hi, lbvh::nodeRange(keys.data(), lo, hi, i));
+        R.roots[c] = static_cast<int32_t>(R.nodes.size());
+        std::vector<lbvh::Member> level(1), next;
+        level[0].r.first = lo;
+        level[0].r.last = hi - 1u;
+        level[0].node = lo;
+        R.nodes.resize(R.nodes.size() + 1);
+        uint32_t levelBase = static_cast<uint32_t>(R.roots[c]), depth = 0;
+        while (!level.empty()) {
+            ++depth;
+            next.clear();
+            const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
+            for (size_t i = 0; i < level.size(); ++i) {
+                lbvh::WideNode w;
+                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w);
+                const uint32_t slot0 = static_cast<uint32_t>(next.size());
+                const uint32_t triBase = w.rows.span ? records : 0u;
+                records += w.rows.span;
+                GpuBvh8Node nd;
+                std::memset(&nd, 0, sizeof(nd));
+                nd.imask = static_cast<uint8_t>(w.imask);
+                nd.child_base = nextBase + slot0;
+                nd.tri_base = triBase;
+                nd.leaf_tris = w.rows.leaf_tris;
+                nd.tri_stride = static_cast<uint8_t>(w.rows.stride);
+                nd.leaf_mask = static_cast<uint8_t>(w.rows.leaf_mask);
+                R.nodes[levelBase + i] = nd;
+                for (uint32_t s = 0; s < 8u; ++s) {
+                    const int k = lbvh::memberInSlot(w, s);
+                    if (k < 0) continue;
+                    const lbvh::Member& m = w.member[k];
+                    if ((w.imask >> s) & 1u) {
+                        next.push_back(m);
+                    } else {
+                        R.leafChildren++;
+                        for (uint32_t t = 0; t < lbvh::count(m.r); ++t) position[m.r.first + t] = triBase + s + w.rows.stride * t;
+                    }
+                }
+            }
+            R.nodes.resize(R.nodes.size() + next.size());
+            if (levels.size() < depth) levels.resize(depth, std::vector<uint32_t>(3, 0u));
+            levels[depth - 1][c] = static_cast<uint32_t>(level.size());
+            levelBase = nextBase;
+            level.swap(next);
+        }
+        if (c == 0) R.opaqueNodes = static_cast<uint32_t>(R.nodes.size());
+        R.depth = std::max(R.depth, depth);
+    }
+    // scatter
+    R.tris.assign(records, holeTriangle());
+    R.perm.assign(records, 0xffffffffu);
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint32_t src = idx[sorted[j]];
+        R.tris[position[j]] = rec[src];
+        R.perm[position[j]] = src;
+    }
+    R.triangles = n;
+    // level order: deepest first, ascending node index within a level (bvhLevelOrder's format)
+    {
+        std::vector<uint32_t> classBase(3, 0u);
+        for (int c = 0; c < 3; ++c) classBase[c] = R.roots[c] >= 0 ? static_cast<uint32_t>(R.roots[c]) : 0u;
+        std::vector<std::vector<uint32_t>> byDepth(levels.size());
+        for (size_t d = 0; d < levels.size(); ++d)
+            for (int c = 0; c < 3; ++c) {
+                for (uint32_t k = 0; k < levels[d][c]; ++k) byDepth[d].push_back(classBase[c] + k);
+                classBase[c] += levels[d][c];
+            }
+        R.levelOffsets.assign(1, 0u);
+        for (size_t d = byDepth.size(); d-- > 0;) {
+            R.order.insert(R.order.end(), byDepth[d].begin(), byDepth[d].end());
+            R.levelOffsets.push_back(static_cast<uint32_t>(R.order.size()));
+        }
+    }
+    // boxes from the records upward, the planes by the node writer (what k_refit_nodes
+    // does on the device): children have higher indices than their parent
+    std::vector<Aabb> nodeBox(R.nodes.size());
+    double sah = 0.0;
+    std::vector<double> childArea(R.nodes.size(), 0.0); // sum over a node's children of area x cost
+    std::vector<double> unionArea(R.nodes.size(), 0.0); // area of the union of a node's child boxes
+    for (size_t k = R.nodes.size(); k-- > 0;) {
+        GpuBvh8Node& nd = R.nodes[k];
+        Aabb slot[8], box;
+        const Aabb* slotBox[8];
+        uint32_t internal = 0;
+        for (int s = 0; s < 8; ++s) {
+            slotBox[s] = nullptr;
+            double cost = 1.0;
+            if ((nd.imask >> s) & 1u) {
+                slot[s] = nodeBox[nd.child_base + internal++];
+            } else if ((nd.leaf_mask >> s) & 1u) {
+                uint32_t t[kBvh8MaxLeafSize];
+                const int cnt = bvh8SlotTriangles(nd, s, t);
+                for (int i = 0; i < cnt; ++i) {
+                    float v[3][3];
+                    recordVertices(R.tris[t[i]], v);
+                    for (int q = 0; q < 3; ++q) slot[s].grow(v[q]);
+                }
+                inflateChildBox(slot[s], inflateAbs);
+                cost = std::max(cnt, 0);
+            } else {
+                continue;
+            }
+            slotBox[s] = &slot[s];
+            box.grow(slot[s]);
+            childArea[k] += static_cast<double>(slot[s].area()) * cost;
+        }
+        writeNodePlanes(nd, box, slotBox);
+        nodeBox[k] = box;
+        unionArea[k] = box.area();
+        inflateChildBox(nodeBox[k], inflateAbs);
+    }
+    // BVH8 SAH cost of the opaque class relative to its root's box (node 1, triangle 1: collapseQueue's)
+    if (R.roots[0] >= 0) {
+        const uint32_t r0 = static_cast<uint32_t>(R.roots[0]);
+        const double rootArea = std::max(1e-30, unionArea[r0]);
+        sah = 1.0;
+        for (uint32_t k = r0; k < r0 + R.opaqueNodes; ++k) sah += childArea[k] / rootArea;
+    }
+    R.sah = sah;
+    return R;
+}
+
+Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
+                                const std::vector<int>* classOf, const float* vertices)
+{
+    Bvh8CheckResult R;
+    struct Box {
+        float lo[3], hi[3];
+    };
+    struct Item {
+        uint32_t node;
+        int32_t parent; // item of the parent's slot box (-1: a root)
+        Box box;        // this node's box as its parent decodes it
+        uint32_t depth;
+    };
+    std::vector<uint8_t> seenTri(tris.size(), 0), seenNode(nodes.size(), 0);
+    for (int c = 0; c < nRoots; ++c) {
+        if (roots[c] < 0) continue;
+        // breadth first: the class's nodes must be roots[c], roots[c] + 1, ... in this order
+        std::vector<Item> items;
+        items.push_back({ static_cast<uint32_t>(roots[c]), -1, {}, 1u });
+        uint32_t lowest = 0xffffffffu, highest = 0u;
+        uint64_t classNodes = 0;
+        std::vector<uint32_t> levelLo, levelHi, levelCount; // of the nodes of each depth
+        for (size_t qi = 0; qi < items.size(); ++qi) {
+            const Item it = items[qi];
+            if (it.node >= nodes.size() || seenNode[it.node]) {
+                R.violations++;
+                continue;
+            }
+            seenNode[it.node] = 1;
+            R.nodes++;
+            if (levelLo.size() < it.depth) {
+                levelLo.resize(it.depth, 0xffffffffu);
+                levelHi.resize(it.depth, 0u);
+                levelCount.resize(it.depth, 0u);
+            }
+            levelLo[it.depth - 1] = std::min(levelLo[it.depth - 1], it.node);
+            levelHi[it.depth - 1] = std::max(levelHi[it.depth - 1], it.node);
+            levelCount[it.depth - 1]++;
+            lowest = std::min(lowest, it.node);
+            highest = std::max(highest, it.node);
+            classNodes++;
+            R.maxDepth = std::max<uint64_t>(R.maxDepth, it.depth);
+            const GpuBvh8Node& nd = nodes[it.node];
+            if ((nd.leaf_tris >> 24) || (nd.leaf_mask & nd.imask)) R.violations++;
+            uint32_t internal = 0;
+            for (int s = 0; s < 8; ++s) {
+                const bool in = (nd.imask >> s) & 1u;
+                uint32_t slotTris[kBvh8MaxLeafSize];
+                const int cnt = bvh8SlotTriangles(nd, s, slotTris);
+                if (cnt < 0) {
+                    R.violations++;
+                    continue;
+                }
+                if (!in && cnt == 0) continue;
+                Box b;
+                for (int a = 0; a < 3; ++a) {
+                    const float step = std::ldexp(1.0f, static_cast<int>(nd.e[a]) - 127);
+                    b.lo[a] = std::fma(static_cast<float>(nd.qlo[a][s]), step, nd.p[a]);
+                    b.hi[a] = std::fma(static_cast<float>(nd.qhi[a][s]), step, nd.p[a]);
+                    if (static_cast<double>(b.lo[a]) != static_cast<double>(nd.p[a]) + nd.qlo[a][s] * static_cast<double>(step)) R.violations++;
+                    if (static_cast<double>(b.hi[a]) != static_cast<double>(nd.p[a]) + nd.qhi[a][s] * static_cast<double>(step)) R.violations++;
+                }
+                if (in) {
+                    R.internalChildren++;
+                    items.push_back({ nd.child_base + internal++, static_cast<int32_t>(qi), b, it.depth + 1u });
+                    continue;
+                }
+                R.leafChildren++;
+                for (int ti = 0; ti < cnt; ++ti) {
+                    const uint32_t t = slotTris[ti];
+                    if (t >= tris.size() || isHoleTriangle(tris[t]) || seenTri[t]) {
+                        R.violations++;
+                        continue;
+                    }
+                    seenTri[t] = 1;
+                    R.triangles++;
+                    const GpuTriangle& g = tris[t];
+                    uint32_t inst, prim;
+                    std::memcpy(&inst, &g.t2[1], 4);
+                    std::memcpy(&prim, &g.t2[2], 4);
+                    if (classOf && (inst >= classOf->size() || (*classOf)[inst] != c)) R.violations++; // under the wrong class's root
+                    float v[6][3];
+                    recordVertices(g, v);
+                    int nv = 3;
+                    if (vertices) {
+                        std::memcpy(v[3], vertices + 9ull * prim, 9 * sizeof(float));
+                        nv = 6;
+                    }
+                    // inside the leaf slot's box and every ancestor's
+                    const Box* bx = &b;
+                    for (int32_t up = static_cast<int32_t>(qi);; up = items[up].parent) {
+                        for (int k = 0; k < nv; ++k)
+                            for (int a = 0; a < 3; ++a)
+                                if (!(v[k][a] >= bx->lo[a] && v[k][a] <= bx->hi[a])) R.violations++;
+                        if (items[up].parent < 0) break;
+                        bx = &items[up].box;
+                    }
+                }
+            }
+        }
+        // the class's nodes are the range [root, root + count)
+        if (classNodes && (lowest != static_cast<uint32_t>(roots[c]) || highest - lowest + 1u != classNodes)) R.notContiguous++;
+        // breadth first: each depth's nodes one range behind the depth above's
+        uint32_t at = static_cast<uint32_t>(roots[c]);
+        for (size_t d = 0; d < levelCount.size(); ++d) {
+            if (levelLo[d] != at || levelHi[d] - levelLo[d] + 1u != levelCount[d]) R.notBreadthFirst++;
+            at += levelCount[d];
+        }
+    }
+    for (size_t t = 0; t < tris.size(); ++t)
+        if (!seenTri[t] && !isHoleTriangle(tris[t])) R.violations++; // unreachable
+    R.violations += R.notContiguous;
+    return R;
+}
+
+} // namespace ark
+
+extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out)
+{
+    using namespace ark;
+    std::vector<GpuTriangle> rec(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        BuildTriangle t;
+        for (int a = 0; a < 3; ++a) {
+            t.v0[a] = triangles[9 * i + a];
+            t.v1[a] = triangles[9 * i + 3 + a];
+            t.v2[a] = triangles[9 * i + 6 + a];
+        }
+        t.instance = 0;
+        t.primitive = static_cast<uint32_t>(i);
+        t.flip_facing = 0;
+        rec[i] = make_gpu_triangle(t);
+    }
+    const std::vector<int> classOf(1, 0);
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion);
+    Bvh8CheckResult c = check_bvh8_full(r.nodes, r.tris, r.roots, 3, &classOf, triangles);
+    // every input triangle in exactly one leaf, bit for bit
+    std::vector<uint32_t> seen(n, 0);
+    for (size_t i = 0; i < r.tris.size(); ++i) {
+        if (isHoleTriangle(r.tris[i])) continue;
+        uint32_t prim;
+        std::memcpy(&prim, &r.tris[i].t2[2], 4);
+        if (prim >= n || r.perm[i] != prim || std::memcmp(&r.tris[i], &rec[prim], sizeof(GpuTriangle)) != 0) c.violations++;
+        else seen[prim]++;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (seen[i] != 1) c.violations++;
+    if (c.maxDepth != r.depth || c.nodes != r.nodes.size()) c.violations++;
+    c.violations += c.notBreadthFirst;
+    if (out) {
+        out[0] = r.nodes.size();
+        out[1] = c.leafChildren;
+        out[2] = r.depth;
+        out[3] = c.violations;
+        out[4] = c.triangles;
+        out[5] = n ? 2 * n - 1 : 0; // the radix tree's nodes
+        out[6] = c.internalChildren;
+        out[7] = static_cast<uint64_t>(r.sah * 1e6);
+    }
+    return c.violations == 0 ? 0 : 1;
+}
+
+extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out)
+{
+    return ark_ddgi_debug_lbvh_check_opts(triangles, n, ark::lbvh::kDefaultCriterion, out);
 }

@@ -8,6 +8,7 @@
 #include <vector>
 
 #include "ddgi_types.h"
+#include "lbvh_build.h"
 
 namespace ark {
 
@@ -92,6 +93,36 @@ bool isHoleTriangle(const GpuTriangle& t);
 // when a leaf slot has no triangle, an internal slot is marked leaf, or the slot's
 // spread reaches another slot's triangle (GpuBvh8Node)
 int bvh8SlotTriangles(const GpuBvh8Node& nd, int s, uint32_t out[kBvh8MaxLeafSize]);
+
+// The device LBVH build (ddgi_bvh_build.hip) restated serially on the host with the same
+// lbvh_build.h functions: the three classes' BVH8s over the records that are not holes
+// (classOf: instance -> class), each node's rows private, the records copied bit for
+// bit, the boxes from the records upward and the planes by the collapse's node writer.
+struct LbvhHostResult {
+    std::vector<GpuBvh8Node> nodes; // each class one breadth-first range from roots[c], opaque first
+    std::vector<GpuTriangle> tris;  // rows, holes included (no padding record)
+    std::vector<uint32_t> perm, order, levelOffsets;
+    int32_t roots[3] = { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, depth = 0;
+    uint64_t triangles = 0, leafChildren = 0;
+    double sah = 0.0; // BVH8 SAH cost of the opaque class (node 1, triangle 1), as Bvh8BuildResult::sah_cost
+};
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion);
+
+// The full check of a BVH8 set (ark_ddgi_debug_lbvh_check, ark_ddgi_debug_world_bvh_check):
+// every class's nodes one contiguous range from its root (counted in violations; depths
+// whose nodes are not one range behind the depth above's in notBreadthFirst alone: the
+// host collapse orders its subtrees' blocks breadth first, not the whole class), valid rows, every
+// plane exactly decodable, every record that is not a hole in exactly one leaf, under its
+// class's root (classOf: instance -> class, null: unchecked), its vertices (v0, v0 + e1,
+// v0 + e2; with `vertices`, also the 9 floats of its primitive) inside the decoded box of
+// its leaf slot and of every ancestor.
+struct Bvh8CheckResult {
+    uint64_t violations = 0, nodes = 0, leafChildren = 0, internalChildren = 0, maxDepth = 0, triangles = 0;
+    uint64_t notContiguous = 0, notBreadthFirst = 0;
+};
+Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
+                                const std::vector<int>* classOf, const float* vertices);
 
 // Absolute box inflation for the BVH8 slab test: 1e-6 of the diagonal of the
 // bounding box of nTriangles world-space triangles (9 floats each). It bounds

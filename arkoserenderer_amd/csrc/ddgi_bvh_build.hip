@@ -1,0 +1,232 @@
+// ddgi_bvh_build.hip — the world BVH8s' topology built on the device from a snapshot of
+// the triangle records (ark_ddgi.cpp runWorldJobGpu, ARK_DDGI_FLAG_GPU_REBUILD): an
+// LBVH (Karras 2012) per hit-mask class, collapsed into 8-wide nodes level by level.
+// The decisions are lbvh_build.h's (shared with the host check
+// ark_ddgi_debug_lbvh_check); the boxes, grids and planes are k_refit_nodes'
+// (ddgi_scene_update.hip), run over every level afterwards.
+//
+//   k_lbvh_prims      one thread per snapshot record: holes skipped, the survivors'
+//                     record indices compacted, the per-class counts, the all-class
+//                     scene box of the vertices (wave reduction, then atomics)
+//   k_lbvh_keys       class << 60 | Morton code of each survivor's centroid
+//   (rocPRIM radix_sort_pairs over the 62 key bits)
+//   k_lbvh_hierarchy  one thread per BVH2 internal node of a class range: its split
+//   k_lbvh_collapse   one level of one class, one thread per BVH8 node of the work
+//                     list: cut, slots and rows; the internal children's node indices
+//                     from one atomic add on the next level's counter, the rows' span
+//                     from one on the record counter; the next level's work list
+//   k_lbvh_fill / k_lbvh_scatter   hole records everywhere, then every record copied
+//                     bit for bit from the snapshot to its row position, perm
+//
+// No kernel here waits on, polls or spins on another workgroup: all ordering between
+// workgroups is by kernel boundaries on the job's stream. Atomics only allocate and
+// reduce, and a returned value is consumed by the thread that got it.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+
+#include <rocprim/device/device_radix_sort.hpp>
+
+#include "ddgi_kernels.h"
+#include "lbvh_build.h"
+
+namespace ark {
+namespace dev {
+
+// fp32 in an unsigned order (for integer atomic min / max)
+__device__ __forceinline__ uint32_t orderedBits(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ void recordVertices(const GpuTriangle* __restrict__ rec, float v[3][3], uint32_t& instance)
+{
+    const float4* q = reinterpret_cast<const float4*>(rec);
+    const float4 a = q[0], b = q[1], c = q[2];
+    instance = __float_as_uint(c.y);
+    const float v0[3] = { a.x, a.y, a.z }, e1[3] = { a.w, b.x, b.y }, e2[3] = { b.z, b.w, c.x };
+    for (int k = 0; k < 3; ++k) {
+        v[0][k] = v0[k];
+        v[1][k] = v0[k] + e1[k];
+        v[2][k] = v0[k] + e2[k];
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_prims(const GpuTriangle* __restrict__ snap, uint32_t records, const uint32_t* __restrict__ classOf,
+                                                    uint32_t instances, uint32_t* __restrict__ idx, LbvhHeader* __restrict__ hdr)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    if (i < records) {
+        float v[3][3];
+        uint32_t inst;
+        recordVertices(snap + i, v, inst);
+        if (inst != kHoleInstance) {
+            if (inst >= instances) {
+                atomicOr(&hdr->error, kLbvhErrorInstance);
+            } else {
+                idx[atomicAdd(&hdr->prims, 1u)] = i; // at most `records` survivors: in bounds
+                atomicAdd(&hdr->classCount[classOf[inst]], 1u);
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = fminf(v[0][a], fminf(v[1][a], v[2][a]));
+                    hi[a] = fmaxf(v[0][a], fmaxf(v[1][a], v[2][a]));
+                }
+            }
+        }
+    }
+    for (int m = 1; m < 64; m <<= 1)
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], m, 64));
+            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m, 64));
+        }
+    if ((threadIdx.x & 63u) == 0u && lo[0] <= hi[0])
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(&hdr->lo[a], orderedBits(lo[a]));
+            atomicMax(&hdr->hi[a], orderedBits(hi[a]));
+        }
+}
+
+__device__ __forceinline__ float fromOrdered(uint32_t u) { return __uint_as_float((u & 0x80000000u) ? (u & 0x7fffffffu) : ~u); }
+
+__global__ void __launch_bounds__(256) k_lbvh_keys(const GpuTriangle* __restrict__ snap, const uint32_t* __restrict__ idx, const uint32_t* __restrict__ classOf,
+                                                   const LbvhHeader* __restrict__ hdr, uint64_t* __restrict__ keys)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= hdr->prims) return;
+    float v[3][3];
+    uint32_t inst;
+    recordVertices(snap + idx[j], v, inst);
+    float lo[3], scale[3], c[3];
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fromOrdered(hdr->lo[a]);
+        scale[a] = lbvh::mortonScale(lo[a], fromOrdered(hdr->hi[a]));
+        // the centre of the triangle's box
+        c[a] = 0.5f * fminf(v[0][a], fminf(v[1][a], v[2][a])) + 0.5f * fmaxf(v[0][a], fmaxf(v[1][a], v[2][a]));
+    }
+    keys[j] = lbvh::mortonKey(c, lo, scale, classOf[inst]);
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t* __restrict__ split)
+{
+    const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
+    if (i + 1u >= hi) return; // internal nodes lo .. hi - 2
+    split[i] = lbvh::findSplit(keys, lo, hi, lbvh::nodeRange(keys, lo, hi, i));
+}
+
+__global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a)
+{
+    const uint32_t i = blockIdx.x * 128u + threadIdx.x;
+    if (i >= a.count) return;
+    const lbvh::Member top = a.items ? a.items[i] : a.root;
+    lbvh::WideNode w;
+    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w);
+    uint32_t slot0 = 0;
+    if (w.internal) {
+        slot0 = atomicAdd(&a.counters[kLbvhNextCount], w.internal);
+        if (slot0 + w.internal > a.nextCapacity) {
+            // more nodes than the scratch holds: nothing written past it, the job falls back
+            atomicOr(&a.counters[kLbvhOverflow], 1u);
+            return;
+        }
+    }
+    const uint32_t triBase = w.rows.span ? atomicAdd(&a.counters[kLbvhRecords], w.rows.span) : 0u;
+    GpuBvh8Node nd;
+    uint4* words = reinterpret_cast<uint4*>(&nd);
+    for (int k = 0; k < 5; ++k) words[k] = make_uint4(0u, 0u, 0u, 0u);
+    nd.imask = static_cast<uint8_t>(w.imask);
+    nd.child_base = a.nextBase + slot0;
+    nd.tri_base = triBase;
+    nd.leaf_tris = w.rows.leaf_tris;
+    nd.tri_stride = static_cast<uint8_t>(w.rows.stride);
+    nd.leaf_mask = static_cast<uint8_t>(w.rows.leaf_mask);
+    uint4* dst = reinterpret_cast<uint4*>(a.nodes + a.levelBase + i);
+    for (int k = 0; k < 5; ++k) dst[k] = words[k];
+    // children in slot order: internal ones consecutive from child_base
+    uint32_t nInternal = 0;
+    for (uint32_t s = 0; s < 8u; ++s) {
+        const int k = lbvh::memberInSlot(w, s);
+        if (k < 0) continue;
+        const lbvh::Member& m = w.member[k];
+        if ((w.imask >> s) & 1u) {
+            a.next[slot0 + nInternal++] = m;
+        } else {
+            for (uint32_t t = 0; t < lbvh::count(m.r); ++t) a.position[m.r.first + t] = triBase + s + w.rows.stride * t;
+        }
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_fill(float4* __restrict__ tris, uint32_t* __restrict__ perm, uint32_t records)
+{
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r > records) return; // records + 1 entries: the padding record last, all zero
+    float4* q = tris + 3ull * r;
+    q[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    q[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    q[2] = make_float4(0.0f, r < records ? __uint_as_float(kHoleInstance) : 0.0f, 0.0f, 0.0f);
+    if (r < records) perm[r] = 0xffffffffu;
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_scatter(const float4* __restrict__ snap, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ position,
+                                                      float4* __restrict__ tris, uint32_t* __restrict__ perm, uint32_t prims, uint32_t records)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= prims) return;
+    const uint32_t src = sorted[j], pos = position[j];
+    if (pos >= records) return; // (never: positions come from the record counter)
+    const float4* q = snap + 3ull * src;
+    float4* d = tris + 3ull * pos;
+    d[0] = q[0];
+    d[1] = q[1];
+    d[2] = q[2];
+    perm[pos] = src;
+}
+
+} // namespace dev
+
+hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const uint32_t* classOf, uint32_t instances, uint32_t* idx, uint64_t* keys,
+                             LbvhHeader* hdr, hipStream_t s)
+{
+    // counts and flags 0, the box empty (lo the largest, hi the smallest ordered value)
+    hipError_t e = hipMemsetAsync(hdr, 0, sizeof(LbvhHeader), s);
+    if (e == hipSuccess) e = hipMemsetAsync(hdr->lo, 0xff, sizeof(hdr->lo), s);
+    if (e != hipSuccess || records == 0) return e;
+    const dim3 grid((records + 255u) / 256u);
+    hipLaunchKernelGGL(dev::k_lbvh_prims, grid, dim3(256), 0, s, snap, records, classOf, instances, idx, hdr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::k_lbvh_keys, grid, dim3(256), 0, s, snap, idx, classOf, hdr, keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn, uint32_t* valuesOut, uint32_t count,
+                            hipStream_t s)
+{
+    return rocprim::radix_sort_pairs(temp, tempBytes, keysIn, keysOut, valuesIn, valuesOut, count, 0u, static_cast<unsigned int>(lbvh::kKeyBits), s);
+}
+
+hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s)
+{
+    if (hi - lo < 2u) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_lbvh_hierarchy, dim3((hi - lo - 1u + 255u) / 256u), dim3(256), 0, s, keys, lo, hi, split);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s)
+{
+    if (a.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_lbvh_collapse, dim3((a.count + 127u) / 128u), dim3(128), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_scatter(const GpuTriangle* snap, const uint32_t* sorted, const uint32_t* position, GpuTriangle* tris, uint32_t* perm, uint32_t prims,
+                               uint32_t records, hipStream_t s)
+{
+    hipLaunchKernelGGL(dev::k_lbvh_fill, dim3(records / 256u + 1u), dim3(256), 0, s, reinterpret_cast<float4*>(tris), perm, records);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || prims == 0) return e;
+    hipLaunchKernelGGL(dev::k_lbvh_scatter, dim3((prims + 255u) / 256u), dim3(256), 0, s, reinterpret_cast<const float4*>(snap), sorted, position,
+                       reinterpret_cast<float4*>(tris), perm, prims, records);
+    return hipGetLastError();
+}
+
+} // namespace ark

@@ -7,6 +7,7 @@
 
 #include "../../include/ark_ddgi.h"
 #include "ddgi_types.h"
+#include "lbvh_build.h"
 
 namespace ark {
 
@@ -303,6 +304,55 @@ hipError_t launch_refit_nodes(GpuBvh8Node* nodes, GpuTriangle* tris, float* boxe
                               const uint64_t* masks, const RefitInstance* inst, const uint32_t* indices, const float* positions, hipStream_t s);
 // dst[i] = src[perm[i]] (64-B shading records), perm ~0: zeros (an installed rebuild's record order)
 hipError_t launch_gather_records(float4* dst, const float4* src, const uint32_t* perm, uint64_t count, hipStream_t s);
+
+// The world BVH8s' topology built on the device (ddgi_bvh_build.hip, lbvh_build.h)
+// what k_lbvh_prims counts and reduces; lo / hi: the scene box in ordered bits
+struct LbvhHeader {
+    uint32_t prims;         // records that are not holes
+    uint32_t classCount[3]; // of each hit-mask class
+    uint32_t error;         // kLbvhError*
+    uint32_t lo[3], hi[3];
+};
+constexpr uint32_t kLbvhErrorInstance = 1u; // a record of an instance the job does not know
+// the box's coordinate of an ordered word
+inline float lbvhOrderedFloat(uint32_t u)
+{
+    u = (u & 0x80000000u) ? (u & 0x7fffffffu) : ~u;
+    float f;
+    __builtin_memcpy(&f, &u, 4);
+    return f;
+}
+// the collapse's counters
+enum : uint32_t { kLbvhNextCount = 0, kLbvhRecords = 1, kLbvhOverflow = 2, kLbvhCounters = 4 };
+// one level of one class (k_lbvh_collapse): node levelBase + i from items[i] (items null: the root)
+struct LbvhCollapseArgs {
+    const uint64_t* keys;      // sorted
+    const uint32_t* split;     // of the BVH2 internal nodes
+    const lbvh::Member* items; // this level's work list
+    lbvh::Member root;
+    uint32_t count;
+    uint32_t levelBase;        // node index of items[0]
+    uint32_t nextBase;         // node index of next[0] = levelBase + count
+    uint32_t nextCapacity;     // entries of next (and nodes left behind nextBase)
+    lbvh::Member* next;        // the next level's work list
+    GpuBvh8Node* nodes;        // topology words only; the planes are the refit's
+    uint32_t* position;        // sorted primitive -> record position
+    uint32_t* counters;        // kLbvhNextCount zeroed per level
+    float extent[3];           // of the scene box
+    int criterion;             // lbvh::Criterion
+};
+// hdr zeroed, then the survivors' record indices (idx), counts and box, then their keys
+hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const uint32_t* classOf, uint32_t instances, uint32_t* idx, uint64_t* keys,
+                             LbvhHeader* hdr, hipStream_t s);
+// rocPRIM's radix sort of the (key, record index) pairs; temp null: tempBytes out
+hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn, uint32_t* valuesOut, uint32_t count,
+                            hipStream_t s);
+// split[i] of the internal nodes lo .. hi - 2 of the class range [lo, hi)
+hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s);
+hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s);
+// tris[0 .. records]: holes and the zero padding record, then record sorted[j] of the snapshot at position[j]; perm
+hipError_t launch_lbvh_scatter(const GpuTriangle* snap, const uint32_t* sorted, const uint32_t* position, GpuTriangle* tris, uint32_t* perm, uint32_t prims,
+                               uint32_t records, hipStream_t s);
 
 // Windowed Z-slab exchange (ddgi_exchange.hip, ark_ddgi_pack_window / _unpack_window):
 // one packet per updated probe, its irradiance tile (10 x 10 RGBA16F, border included)

@@ -1,0 +1,354 @@
+// lbvh_build.h — the build logic of the device-side LBVH of the world BVH8s
+// (ddgi_bvh_build.hip), shared with its serial host restatement
+// (ark_ddgi_debug_lbvh_check, bvh_builder.cpp). Plain inline functions over plain
+// arrays, no HIP types: the host check and the kernels run the same code.
+//
+//   mortonKey      class << 60 | 60-bit Morton code (20 bits per axis, x highest) of a
+//                  record's centroid inside the all-class scene box
+//   delta / nodeRange / findSplit   the radix tree of Karras 2012 ("Maximizing
+//                  parallelism in the construction of BVHs, octrees, and k-d trees")
+//                  over one class's range [lo, hi) of the sorted keys. Equal keys are
+//                  told apart by their sorted index. Internal node i covers a contiguous
+//                  range whose first or last primitive is i, so a child is known by its
+//                  range alone: the left child [first, split] is internal node `split`,
+//                  the right one [split + 1, last] internal node `split + 1`, a range of
+//                  one primitive a leaf. Only split[] is stored.
+//   selectCut      the members of one BVH8 node: the BVH2 node's two children, then one
+//                  member of more than kBvh8MaxLeafSize triangles opened at a time until
+//                  there are 8 or none can be opened
+//   assignSlots    internal children into the octant slot of their Morton cell's centre
+//                  relative to the node's cell, leaf members into the slots left over
+//   placeRows      the leaf slots' triangle rows of one node (GpuBvh8Node)
+#pragma once
+
+#include <stdint.h>
+
+#include "ddgi_types.h"
+
+#if defined(__HIPCC__)
+#define ARK_LBVH_FN __host__ __device__ inline
+#else
+#define ARK_LBVH_FN inline
+#endif
+
+namespace ark {
+namespace lbvh {
+
+constexpr int kMortonBits = 20;         // per axis
+constexpr int kKeyBits = 62;            // 60 Morton bits + 2 class bits: the sort's end bit
+constexpr uint32_t kNoSlot = 0xffu;
+
+// A member of a cut: the sorted primitives [first, last] (global indices)
+struct Range {
+    uint32_t first, last;
+};
+ARK_LBVH_FN uint32_t count(const Range& r) { return r.last - r.first + 1u; }
+
+// Which member of a cut is opened next
+enum Criterion : int {
+    kOpenLargestCount = 0, // most triangles
+    kOpenLargestCell = 1,  // largest surface area of the range's Morton cell
+};
+// The default (EXPERIMENTS.md "Device LBVH build"): the cell area, the nearest an LBVH
+// has to the host collapse's largest-box-area opening; by the host check's BVH8 SAH cost
+// on the 20,000-triangle soup it beats the count.
+constexpr int kDefaultCriterion = kOpenLargestCell;
+
+ARK_LBVH_FN int clz64(uint64_t x)
+{
+    return x ? __builtin_clzll(x) : 64;
+}
+
+ARK_LBVH_FN uint64_t spread20(uint32_t v)
+{
+    // bit k of v to bit 3 k
+    uint64_t x = v & 0xfffffu;
+    x = (x | x << 32) & 0x001f00000000ffffull;
+    x = (x | x << 16) & 0x001f0000ff0000ffull;
+    x = (x | x << 8) & 0x100f00f00f00f00full;
+    x = (x | x << 4) & 0x10c30c30c30c30c3ull;
+    x = (x | x << 2) & 0x1249249249249249ull;
+    return x;
+}
+
+// The 20-bit cell of coordinate c in [lo, lo + extent]: scale = 2^20 / extent (0 for a flat box)
+ARK_LBVH_FN uint32_t mortonCell(float c, float lo, float scale)
+{
+    float q = (c - lo) * scale;
+    q = q > 0.0f ? q : 0.0f; // NaN to 0
+    q = q < 1048575.0f ? q : 1048575.0f;
+    return static_cast<uint32_t>(q);
+}
+
+ARK_LBVH_FN float mortonScale(float lo, float hi)
+{
+    const float ext = hi - lo;
+    return ext > 0.0f ? 1048576.0f / ext : 0.0f;
+}
+
+ARK_LBVH_FN uint64_t mortonKey(const float c[3], const float lo[3], const float scale[3], uint32_t cls)
+{
+    const uint64_t m = spread20(mortonCell(c[0], lo[0], scale[0])) << 2 | spread20(mortonCell(c[1], lo[1], scale[1])) << 1 |
+                       spread20(mortonCell(c[2], lo[2], scale[2]));
+    return static_cast<uint64_t>(cls) << 60 | m;
+}
+
+// Length of the common prefix of the (key, index) pairs i and j of the class range
+// [lo, hi); -1 when j lies outside it
+ARK_LBVH_FN int delta(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t i, int64_t j)
+{
+    if (j < static_cast<int64_t>(lo) || j >= static_cast<int64_t>(hi)) return -1;
+    const uint64_t a = keys[i], b = keys[j];
+    if (a != b) return clz64(a ^ b);
+    return 64 + (clz64(static_cast<uint64_t>(i ^ static_cast<uint32_t>(j))) - 32);
+}
+
+// The range of internal node i of the class range [lo, hi) (hi - lo >= 2, lo <= i < hi - 1)
+ARK_LBVH_FN Range nodeRange(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t i)
+{
+    const int64_t I = i;
+    const int d = delta(keys, lo, hi, i, I + 1) - delta(keys, lo, hi, i, I - 1) >= 0 ? 1 : -1;
+    const int dmin = delta(keys, lo, hi, i, I - d);
+    int64_t lmax = 2;
+    while (delta(keys, lo, hi, i, I + lmax * d) > dmin) lmax <<= 1;
+    int64_t l = 0;
+    for (int64_t t = lmax >> 1; t >= 1; t >>= 1)
+        if (delta(keys, lo, hi, i, I + (l + t) * d) > dmin) l += t;
+    const int64_t j = I + l * d;
+    Range r;
+    r.first = static_cast<uint32_t>(d > 0 ? I : j);
+    r.last = static_cast<uint32_t>(d > 0 ? j : I);
+    return r;
+}
+
+// The last primitive of the left child of the node covering r (r.first < r.last)
+ARK_LBVH_FN uint32_t findSplit(const uint64_t* keys, uint32_t lo, uint32_t hi, const Range& r)
+{
+    const int dnode = delta(keys, lo, hi, r.first, r.last);
+    uint32_t split = r.first, step = r.last - r.first;
+    do {
+        step = (step + 1u) >> 1;
+        const uint32_t m = split + step;
+        if (m < r.last && delta(keys, lo, hi, r.first, m) > dnode) split = m;
+    } while (step > 1u);
+    return split;
+}
+
+// The BVH2 internal node of a range of more than one primitive that is not a class's
+// root: a left child ends at its own index, a right child starts at it
+ARK_LBVH_FN uint32_t leftNode(const Range& r) { return r.last; }
+ARK_LBVH_FN uint32_t rightNode(const Range& r) { return r.first; }
+
+// A cut member while the cut is chosen: its range and its BVH2 internal node
+struct Member {
+    Range r;
+    uint32_t node;
+};
+
+// The Morton cell of a range: the axis-wise cell counts (log2) the common prefix of its
+// first and last key leaves free, as a relative surface area (extent: the scene box's)
+ARK_LBVH_FN float cellArea(const uint64_t* keys, const Range& r, const float extent[3])
+{
+    const uint64_t x = (keys[r.first] ^ keys[r.last]) << 4; // the class bits are equal
+    const int p = x ? clz64(x) : 60;                         // common Morton bits, x first
+    const int n[3] = { (p + 2) / 3, (p + 1) / 3, p / 3 };
+    float d[3];
+    for (int a = 0; a < 3; ++a) {
+        // extent * 2^-n, exactly
+        union {
+            uint32_t u;
+            float f;
+        } s;
+        s.u = static_cast<uint32_t>(127 - n[a]) << 23;
+        d[a] = extent[a] * s.f;
+    }
+    return d[0] * d[1] + d[1] * d[2] + d[2] * d[0];
+}
+
+// The members of the BVH8 node over `top` (top.node: its BVH2 node when it holds more
+// than one primitive): out[0 .. return). A node of at most kBvh8MaxLeafSize triangles
+// (only a class's root) is one leaf member.
+ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], Member out[8])
+{
+    if (count(top.r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        out[0] = top;
+        return 1;
+    }
+    int n = 0;
+    int open = -1;
+    Member cur = top;
+    for (;;) {
+        // open `cur` into its two children (at position `open`, the second appended)
+        const uint32_t sp = split[cur.node];
+        Member a, b;
+        a.r.first = cur.r.first;
+        a.r.last = sp;
+        a.node = leftNode(a.r);
+        b.r.first = sp + 1u;
+        b.r.last = cur.r.last;
+        b.node = rightNode(b.r);
+        if (open < 0) {
+            out[n++] = a;
+        } else {
+            out[open] = a;
+        }
+        out[n++] = b;
+        if (n == 8) break;
+        open = -1;
+        float best = -1.0f;
+        for (int k = 0; k < n; ++k) {
+            if (count(out[k].r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) continue;
+            const float v = criterion == kOpenLargestCell ? cellArea(keys, out[k].r, extent) : static_cast<float>(count(out[k].r));
+            if (v > best) {
+                best = v;
+                open = k;
+            }
+        }
+        if (open < 0) break;
+        cur = out[open];
+    }
+    return n;
+}
+
+// The centre of a range's Morton cell in half cells of the finest grid, per axis
+ARK_LBVH_FN void cellCentre(const uint64_t* keys, const Range& r, int64_t c[3])
+{
+    const uint64_t k = keys[r.first];
+    const uint64_t x = (k ^ keys[r.last]) << 4;
+    const int p = x ? clz64(x) : 60;
+    const int n[3] = { (p + 2) / 3, (p + 1) / 3, p / 3 };
+    for (int a = 0; a < 3; ++a) {
+        // the axis's 20 bits of the first key, its low (20 - n) bits replaced by the cell's middle
+        uint32_t v = 0;
+        for (int b = 0; b < kMortonBits; ++b) v |= static_cast<uint32_t>((k >> (3 * b + (2 - a))) & 1u) << b;
+        const int free = kMortonBits - n[a];
+        const int64_t lo = static_cast<int64_t>(v >> free) << free;
+        c[a] = 2 * lo + (int64_t(1) << free);
+    }
+}
+
+// Slots of a node's members. Internal members (more than kBvh8MaxLeafSize triangles) take
+// the octant slot of their cell's centre relative to the node's cell's centre (bit a of
+// the slot: the + side along axis a), a taken one the nearest free slot (fewest differing
+// axes, then the lowest). Leaf members decide only which triangles a hit slot adds, so
+// they fill the free slots in ascending order, most triangles first, which keeps the
+// node's rows compact (as the host collapse does). slotOf[k]: the slot of member k.
+ARK_LBVH_FN void assignSlots(const uint64_t* keys, const Range& node, const Member* m, int n, uint32_t slotOf[8])
+{
+    uint32_t taken = 0;
+    int64_t pc[3];
+    cellCentre(keys, node, pc);
+    for (int k = 0; k < n; ++k) {
+        slotOf[k] = kNoSlot;
+        if (count(m[k].r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) continue;
+        int64_t c[3];
+        cellCentre(keys, m[k].r, c);
+        const uint32_t want = (c[0] > pc[0] ? 1u : 0u) | (c[1] > pc[1] ? 2u : 0u) | (c[2] > pc[2] ? 4u : 0u);
+        uint32_t bestSlot = 0, bestDist = 99;
+        for (uint32_t s = 0; s < 8u; ++s) {
+            if ((taken >> s) & 1u) continue;
+            const uint32_t x = s ^ want;
+            const uint32_t dist = (x & 1u) + ((x >> 1) & 1u) + ((x >> 2) & 1u);
+            if (dist < bestDist) {
+                bestDist = dist;
+                bestSlot = s;
+            }
+        }
+        slotOf[k] = bestSlot;
+        taken |= 1u << bestSlot;
+    }
+    for (uint32_t c = static_cast<uint32_t>(kBvh8MaxLeafSize); c >= 1u; --c)
+        for (int k = 0; k < n; ++k) {
+            if (slotOf[k] != kNoSlot || count(m[k].r) != c) continue;
+            uint32_t s = 0;
+            while ((taken >> s) & 1u) ++s;
+            slotOf[k] = s;
+            taken |= 1u << s;
+        }
+}
+
+// The rows of one node's leaf slots (cnt[s] triangles in slot s, 0: not a leaf slot)
+struct Rows {
+    uint32_t stride;    // tri_stride
+    uint32_t leaf_tris; // bit s + stride i: triangle i of slot s
+    uint32_t leaf_mask;
+    uint32_t span;      // highest used position + 1 (0: no leaf slot)
+};
+
+// The smallest stride in 1..8 under which every position s + stride i (i < 3) of a leaf
+// slot s is free or s's own triangle i, and the rows fit in 24 positions (GpuBvh8Node;
+// bvh_builder.cpp leafRowStride). The node's rows are private: positions 0 .. span - 1
+// from its tri_base belong to it alone.
+ARK_LBVH_FN Rows placeRows(const uint32_t cnt[8])
+{
+    Rows r;
+    r.leaf_mask = 0;
+    for (uint32_t s = 0; s < 8u; ++s)
+        if (cnt[s]) r.leaf_mask |= 1u << s;
+    for (uint32_t st = 1u; st <= 8u; ++st) {
+        uint32_t used = 0;
+        bool ok = true;
+        for (uint32_t s = 0; s < 8u && ok; ++s)
+            for (uint32_t i = 0; i < cnt[s] && ok; ++i) {
+                const uint32_t p = s + st * i;
+                ok = p < 24u && !((used >> p) & 1u);
+                used |= ok ? 1u << p : 0u;
+            }
+        for (uint32_t s = 0; s < 8u && ok; ++s) {
+            if (!cnt[s]) continue;
+            uint32_t own = 0;
+            for (uint32_t i = 0; i < cnt[s]; ++i) own |= 1u << (s + st * i);
+            const uint32_t spread = bvh8SlotRow(st, static_cast<int>(s)) & 0xffffffu;
+            ok = ((spread & used) & ~own) == 0u;
+        }
+        if (ok || st == 8u) {
+            r.stride = st;
+            r.leaf_tris = used;
+            break;
+        }
+    }
+    r.span = 0;
+    for (uint32_t p = 0; p < 24u; ++p)
+        if ((r.leaf_tris >> p) & 1u) r.span = p + 1u;
+    return r;
+}
+
+// One BVH8 node of the collapse: what selectCut, assignSlots and placeRows decide
+struct WideNode {
+    Member member[8];
+    uint32_t slotOf[8];
+    int members;
+    uint32_t imask;     // slots of internal members
+    uint32_t internal;  // popcount(imask)
+    Rows rows;
+};
+
+ARK_LBVH_FN void planNode(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], WideNode& w)
+{
+    w.members = selectCut(keys, split, top, criterion, extent, w.member);
+    assignSlots(keys, top.r, w.member, w.members, w.slotOf);
+    uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+    w.imask = 0;
+    w.internal = 0;
+    for (int k = 0; k < w.members; ++k) {
+        const uint32_t c = count(w.member[k].r);
+        if (c <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+            cnt[w.slotOf[k]] = c;
+        } else {
+            w.imask |= 1u << w.slotOf[k];
+            w.internal++;
+        }
+    }
+    w.rows = placeRows(cnt);
+}
+
+// The member in slot s (-1: none)
+ARK_LBVH_FN int memberInSlot(const WideNode& w, uint32_t s)
+{
+    for (int k = 0; k < w.members; ++k)
+        if (w.slotOf[k] == s) return k;
+    return -1;
+}
+
+} // namespace lbvh
+} // namespace ark

@@ -71,6 +71,9 @@ class DDGIConfig:
     sun_bvh: int = abi.ARK_DDGI_SUN_BVH_AUTO
     serial_frames: bool = False
     background_rebuild: bool = True
+    # ARK_DDGI_FLAG_GPU_REBUILD (experimental): the world BVHs' background rebuild on the
+    # device (an LBVH), one host rebuild once the motion stops; background_rebuild=False wins
+    gpu_rebuild: bool = False
     build_threads: int = 0
 
 
@@ -108,6 +111,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.shard_count = int(shard_count)
     d.sun_bvh = int(config.sun_bvh)
     d.flags = (abi.ARK_DDGI_FLAG_SERIAL_FRAMES if config.serial_frames else 0) | (0 if config.background_rebuild else abi.ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD)
+    d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD if config.gpu_rebuild else 0
     d.build_threads = int(config.build_threads)
     return d
 
@@ -139,6 +143,11 @@ class DDGIContext:
 
     def check(self, rc, what):
         _check(self.lib, self.h, rc, what)
+
+    def last_error(self) -> str:
+        """ark_ddgi_last_error: the message of the last error (or of a failed background rebuild)."""
+        m = self.lib.ark_ddgi_last_error(self.h)
+        return m.decode() if m else ""
 
     def set_scene(self, scene: SceneData):
         s = scene.to_abi()
@@ -351,6 +360,31 @@ class DDGIContext:
         out = (C.c_uint64 * 4)()
         self.check(self.lib.ark_ddgi_debug_scene_digest(self.h, out), "ark_ddgi_debug_scene_digest")
         return tuple(int(v) for v in out)
+
+    def world_bvh_check(self) -> dict:
+        """ark_ddgi_debug_world_bvh_check: the world BVH8s the kernels read now, downloaded
+        and checked on the host (violations 0 = valid)."""
+        out = (C.c_uint64 * 8)()
+        rc = self.lib.ark_ddgi_debug_world_bvh_check(self.h, out)
+        if rc < 0:
+            self.check(rc, "ark_ddgi_debug_world_bvh_check")
+        keys = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
+        return dict(zip(keys, (int(v) for v in out)))
+
+
+def lbvh_check(triangles, criterion: int | None = None) -> tuple:
+    """ark_ddgi_debug_lbvh_check: the device LBVH build's logic run serially on the host
+    over world triangles (n x 9 floats). Returns (rc, out[8]) with out as
+    ark_ddgi_debug_bvh8_check: nodes, leaf children, max depth, violations, triangles,
+    radix-tree nodes, internal children, BVH8 SAH cost x 1e6. No GPU."""
+    lib = abi.load_library()
+    tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    out = (C.c_uint64 * 8)()
+    if criterion is None:
+        rc = lib.ark_ddgi_debug_lbvh_check(tris.ctypes.data, tris.shape[0], out)
+    else:
+        rc = lib.ark_ddgi_debug_lbvh_check_opts(tris.ctypes.data, tris.shape[0], int(criterion), out)
+    return rc, [int(v) for v in out]
 
 
 def frame_params(config: DDGIConfig, grid: ProbeGrid, app: AppState, first_probe_index: int,

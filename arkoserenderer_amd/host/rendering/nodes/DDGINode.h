@@ -28,6 +28,9 @@ public:
     void setApplyProbeOffsets(bool a) { m_applyProbeOffsets = a; }
     void setMaxProbeUpdates(int n) { m_maxProbeUpdates = n; }
     void setShard(int rank, int count) { m_shardRank = rank; m_shardCount = count; }
+    // ARK_DDGI_FLAG_GPU_REBUILD (before construct; experimental, off): the world BVHs'
+    // background rebuilds after moved instances run on the device instead of host threads
+    void setGpuRebuild(bool on) { m_gpuRebuild = on; }
     // Z-slab ranks: the atlas exchange after each update (RCCL all-gather, or device
     // copies for contexts in one process); frame n+1's shading waits for frame n's.
     void setSlabExchange(SlabExchange* exchange) { m_exchange = exchange; }
@@ -66,6 +69,7 @@ private:
     int m_maxProbeUpdates { MaxNumProbeUpdates };
     int m_shardRank { 0 };
     int m_shardCount { 1 };
+    bool m_gpuRebuild { false };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     SlabExchange* m_exchange { nullptr };

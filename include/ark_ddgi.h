@@ -162,9 +162,18 @@ typedef struct ArkDdgiDesc {
 /* ArkDdgiDesc.flags. SERIAL_FRAMES: every update runs in line on the caller's stream
  * (no traversal stream, no frames in flight); results are the same. NO_BACKGROUND_REBUILD:
  * after ark_ddgi_set_instances the BVHs are only refitted, never rebuilt in the background
- * (a set_scene restores their tightness); results are the same. */
+ * (a set_scene restores their tightness); results are the same. GPU_REBUILD
+ * (experimental, off by default; NO_BACKGROUND_REBUILD wins over it): the world BVHs'
+ * background rebuild runs on the device - an LBVH per hit-mask class over the snapshot,
+ * on a lowest-priority stream of its own - instead of the binned-SAH build on host
+ * threads, so rebuilds are installed while instances keep moving; once the motion stops
+ * one host rebuild replaces the LBVH (which traces worse than the SAH tree). A scene
+ * the device build cannot take is built by the host within the same job
+ * (ArkDdgiBvhStats.bvh_gpu_fallbacks). The light-space sun BVH stays a host build;
+ * results are the same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
+#define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {
@@ -544,6 +553,9 @@ typedef struct ArkDdgiBvhStats {
     uint32_t sun_built_refit_version; /* the same for the installed light-space sun BVH */
     uint32_t bvh_rebuild_failures;    /* background world rebuilds that failed (the refitted BVHs stay; no more
                                        * background rebuilds of this scene) */
+    uint32_t bvh_gpu_rebuilds;        /* installs since set_scene whose world BVHs the device built (ARK_DDGI_FLAG_GPU_REBUILD) */
+    uint32_t bvh_gpu_fallbacks;       /* device-build jobs that fell back to the host build */
+    uint32_t bvh_installed_builder;   /* the builder of the installed world BVHs: 0 host, 1 device */
 } ArkDdgiBvhStats;
 int ark_ddgi_get_bvh_stats(ArkDdgiCtx* ctx, ArkDdgiBvhStats* out_stats);
 

@@ -78,6 +78,32 @@ int ark_ddgi_debug_sun_choice(const float* triangles, uint64_t n, const float* s
  * one that reaches every node. Synchronous. */
 int ark_ddgi_debug_scene_digest(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* The device LBVH build of the world BVH8s (ARK_DDGI_FLAG_GPU_REBUILD) run serially on
+ * the host over n world triangles (9 floats each), with the very functions the kernels
+ * call (csrc/lbvh_build.h): Morton keys, the radix tree, the BVH2 -> BVH8 cut, slots and
+ * private rows; the boxes from the records upward and the planes by the host collapse's
+ * node writer. The checks and out[8] are ark_ddgi_debug_bvh8_check's (out[5]: the radix
+ * tree's nodes, 2 n - 1); also: the nodes are one contiguous range, each depth's one
+ * range behind the depth above's, and every record is the input's bit for bit. _opts: the member a cut opens next (0 the
+ * one of most triangles, 1 the one of the largest Morton cell area - the default).
+ * Returns 0 when the check passes, 1 when it found violations. No GPU. */
+int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out);
+int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out);
+
+/* The world BVH8s the context's kernels read now (the front copy, after everything it
+ * enqueued), downloaded and checked on the host. out[8] = {nodes, leaf children, max
+ * depth, violations, records that are not holes, records with holes, order-independent
+ * digest of the records that are not holes (sum of their FNV-1a 64), installed builder
+ * (0 host, 1 device)}. A violation: the structure check set_scene's and the rebuilds'
+ * BVHs pass fails; a plane is not exactly decodable; a triangle vertex (v0, v0 + e1,
+ * v0 + e2) lies outside the decoded box of its leaf slot or of an ancestor; a triangle
+ * sits under another hit-mask class's root; a class's nodes are not one contiguous
+ * range from its root (a device build's: each depth's nodes one range behind the depth
+ * above's; the host collapse orders each subtree's block breadth first instead); the
+ * refit's level order differs from the one recomputed from the
+ * downloaded nodes. Returns 0 when there is none, 1 otherwise. Synchronous. */
+int ark_ddgi_debug_world_bvh_check(struct ArkDdgiCtx* ctx, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,14 @@ move one instance (ark_ddgi_set_instances_async on the update's stream, no host 
 - the rate under motion, the background rebuilds installed meanwhile - then static
 frames until the rebuilds of the final state (world BVHs and the light-space sun BVH)
 are installed, and the rate again: it should be back at the static rate.
+
+--gpu-rebuild (with --continuous): ARK_DDGI_FLAG_GPU_REBUILD, the world BVHs rebuilt on the
+device while the instances move. The line then also tells the installs' builder, the
+device builds' time and footprint (nodes, records per triangle) as installed at the end
+of the motion, and the traversal phase's device time (ark_ddgi_get_last_timings [1]) on
+the tree traced at the start (set_scene's), right after the motion (the device build, or
+with the flag off the refit-loosened one) and once settled (the host rebuild). Run it
+with and without the flag in turn to compare.
 """
 import argparse
 import dataclasses
@@ -41,6 +49,7 @@ def main():
     ap.add_argument("--continuous", action="store_true", help="one instance moved every frame for --frames frames, then back to static")
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--no-background", action="store_true", help="ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: refits only (isolates the rebuild threads' cost)")
+    ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
     import torch
@@ -51,7 +60,7 @@ def main():
         sc, grid, R, zf = build(name)
         N = grid.probe_count()
         cfg = D.DDGIConfig(rays_per_probe=R, probe_updates_per_frame=N, max_rays_per_probe=R, max_probe_updates=N, compute_probe_offsets=True,
-                           background_rebuild=not args.no_background)
+                           background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild)
         node = D.DDGINode(cfg)
         node.construct(sc, grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
         app = [D.AppState(0)]
@@ -69,12 +78,32 @@ def main():
             nd.ctx.synchronize()
             return N * R * args.steps / (time.perf_counter() - t) / 1e6
 
+        def trace_ms(nd=None):
+            """median device time of the traversal phase and of the shadow rays' launch over 5 timed frames"""
+            nd = nd or node
+            nd.ctx.set_timing(True)
+            rows = []
+            for _ in range(5):
+                nd.execute(app[0])
+                app[0] = D.AppState(app[0].frame_index + 1)
+                nd.ctx.synchronize()
+                rows.append(nd.ctx.last_timings())
+            nd.ctx.set_timing(False)
+            return {"traversal": round(float(np.median([r[1] for r in rows])), 4), "shadow": round(float(np.median([r[4] for r in rows])), 4)}
+
+        def tree(st):
+            return {"builder": "device" if st.bvh_installed_builder else "host", "rebuilds": int(st.bvh_rebuilds), "device_rebuilds": int(st.bvh_gpu_rebuilds),
+                    "fallbacks": int(st.bvh_gpu_fallbacks), "failures": int(st.bvh_rebuild_failures), "rebuild_ms": round(st.bvh_rebuild_ms, 2),
+                    "nodes": int(st.node_count), "records_per_triangle": round(st.triangle_bytes / 48 / max(1, sc.triangle_count), 4),
+                    "built_refit_version": int(st.bvh_built_refit_version), "refit_version": int(st.refit_version)}
+
         had_sun_bvh = node.ctx.bvh_stats().sun_node_count > 0
         out = {"config": name, "triangles": int(sc.triangle_count), "instances": int(sc.instances.size),
                "build_ms": round(node.ctx.bvh_stats().build_ms, 1), "mrays_per_s_static": round(rate(), 1)}
         if args.continuous:
             sptr = torch.cuda.current_stream().cuda_stream
             static = [out["mrays_per_s_static"], round(rate(), 1)]
+            trees = {"start": {**tree(node.ctx.bvh_stats()), "ms": trace_ms()}}
             inst0 = sc.instances.copy()
             n = len(inst0)
             st0 = node.ctx.bvh_stats()
@@ -102,12 +131,15 @@ def main():
             motion_s = time.perf_counter() - t
             st1 = node.ctx.bvh_stats()
             refit_dev = sorted(e0.elapsed_time(e1) for e0, e1 in ev)
+            # the tree a moving scene traces, before anything newer is installed
+            trees["after_motion"] = {**tree(st1), "ms": trace_ms()}
             # static again: until BVHs built from the final records (after the last refit)
             # are installed - the world BVHs and the light-space sun BVH
             t = time.perf_counter()
             while time.perf_counter() - t < 120.0 and not args.no_background:
                 st = node.ctx.bvh_stats()
-                if st.bvh_built_refit_version == st.refit_version and (not had_sun_bvh or st.sun_built_refit_version == st.refit_version):
+                if st.bvh_built_refit_version == st.refit_version and (not had_sun_bvh or st.sun_built_refit_version == st.refit_version) and \
+                        not st.bvh_installed_builder:  # (--gpu-rebuild: until the settle rebuild has replaced the device build)
                     break
                 node.execute(app[0], sptr)
                 app[0] = D.AppState(app[0].frame_index + 1)
@@ -115,6 +147,7 @@ def main():
                 time.sleep(0.01)
             settle_s = time.perf_counter() - t
             st2 = node.ctx.bvh_stats()
+            trees["settled"] = {**tree(st2), "ms": trace_ms()}
             after = [round(rate(), 1) for _ in range(2)]
             # a context built from scratch on the final transforms, measured interleaved
             # with the rebuilt one: what "back at the static rate" means for the moved scene
@@ -130,6 +163,7 @@ def main():
                 "ms_per_frame_moving": round(motion_s / args.frames * 1e3, 4),
                 "refit_device_ms": {"median": round(refit_dev[len(refit_dev) // 2], 4), "max": round(refit_dev[-1], 4)},
                 "refit_host_enqueue_ms": round(host_refit / args.frames * 1e3, 4), "background_rebuild": not args.no_background,
+                "gpu_rebuild": bool(args.gpu_rebuild), "trees": trees,
                 "built_refit_version": {"world": int(st2.bvh_built_refit_version), "sun": int(st2.sun_built_refit_version), "refits": int(st2.refit_version)},
                 "installs_while_moving": {"world": int(st1.bvh_rebuilds - st0.bvh_rebuilds), "sun": int(st1.sun_rebuilds - st0.sun_rebuilds)},
                 "world_rebuild_ms": round(st2.bvh_rebuild_ms, 1), "sun_rebuild_ms": round(st2.sun_build_ms, 1),
