@@ -136,41 +136,54 @@ void sampleTraversalOrder(uint32_t R, std::vector<uint32_t>& order)
 
 } // namespace
 
-// The nodes of a BVH8 by depth, deepest first (a node's internal children are one level
-// deeper): the refit's launch order, order[offsets[i] .. offsets[i + 1]) one level.
-static bool bvhLevelOrder(const GpuBvh8Node* h, uint64_t n, const int32_t* roots, int nRoots, std::vector<uint32_t>& order, std::vector<uint32_t>& offsets)
+// One BVH8 set on the device - the world's three classes, or the sun's light-space BVH -
+// with what its refits need. One allocation: the nodes, then the triangle records at the
+// next 256-B boundary (the traversal addresses both through one buffer resource with a
+// 32-bit byte offset), then one padding record (a five-load fetch of the last record
+// stays in bounds, ARK_FETCH5).
+struct DeviceBvh {
+    DeviceBuffer buf; // the front copy: what the kernels read (SceneStore::Spare holds the others)
+    size_t triOffset = 0;
+    uint64_t nodeCount = 0, records = 0; // records: holes included, the padding record not
+    uint32_t depth = 0;
+    float inflateAbs = 0.0f; // the build's absolute box inflation (the refits' floor)
+    // the refit: order[levelOffsets[i] .. [i + 1]) on the device = the nodes of one depth,
+    // deepest first; its boxes scratch; the node masks (k_node_masks: per topology)
+    DeviceBuffer order, boxes, masks;
+    std::vector<uint32_t> levelOffsets;
+    bool masksValid = false;
+    static size_t triOffsetFor(uint64_t nodes) { return (nodes * sizeof(GpuBvh8Node) + 255) & ~static_cast<size_t>(255); }
+    static size_t bytesFor(uint64_t nodes, uint64_t records) { return triOffsetFor(nodes) + (records + 1) * sizeof(GpuTriangle); }
+    // nodes and records of a copy of it (the front one, or a spare)
+    GpuBvh8Node* nodes(const DeviceBuffer& copy) const { return copy.as<GpuBvh8Node>(); }
+    GpuTriangle* tris(const DeviceBuffer& copy) const { return reinterpret_cast<GpuTriangle*>(static_cast<char*>(copy.ptr) + triOffset); }
+    void release()
+    {
+        for (DeviceBuffer* b : { &buf, &order, &boxes, &masks }) b->release();
+    }
+};
+
+// `nodes` and `tris` into b.buf (allocated here; b's offset and counts set). s == nullptr:
+// synchronous copies; else stream-ordered on `s` and complete on return.
+static hipError_t uploadBvh(const std::vector<GpuBvh8Node>& nodes, std::vector<GpuTriangle>& tris, hipStream_t s, DeviceBvh& b)
 {
-    std::vector<std::vector<uint32_t>> byDepth;
-    std::vector<std::pair<uint32_t, uint32_t>> work; // (node, depth)
-    for (int r = 0; r < nRoots; ++r)
-        if (roots[r] >= 0) work.push_back({ static_cast<uint32_t>(roots[r]), 0u });
-    while (!work.empty()) {
-        const auto [node, d] = work.back();
-        work.pop_back();
-        if (node >= n) return false;
-        if (byDepth.size() <= d) byDepth.resize(d + 1);
-        byDepth[d].push_back(node);
-        const uint32_t internal = static_cast<uint32_t>(__builtin_popcount(h[node].imask));
-        for (uint32_t k = 0; k < internal; ++k) work.push_back({ h[node].child_base + k, d + 1 });
-    }
-    order.clear();
-    order.reserve(n);
-    offsets.assign(1, 0u);
-    for (size_t d = byDepth.size(); d-- > 0;) {
-        std::sort(byDepth[d].begin(), byDepth[d].end());
-        order.insert(order.end(), byDepth[d].begin(), byDepth[d].end());
-        offsets.push_back(static_cast<uint32_t>(order.size()));
-    }
-    return true;
+    b.triOffset = DeviceBvh::triOffsetFor(nodes.size());
+    b.nodeCount = nodes.size();
+    b.records = tris.size();
+    auto copy = [s](void* dst, const void* src, size_t n) { return s ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s) : hipMemcpy(dst, src, n, hipMemcpyHostToDevice); };
+    tris.push_back(GpuTriangle {}); // the padding record
+    hipError_t e = b.buf.alloc(DeviceBvh::bytesFor(b.nodeCount, b.records));
+    if (e == hipSuccess) e = copy(b.buf.ptr, nodes.data(), nodes.size() * sizeof(GpuBvh8Node));
+    if (e == hipSuccess) e = copy(b.tris(b.buf), tris.data(), tris.size() * sizeof(GpuTriangle));
+    if (e == hipSuccess && s) e = hipStreamSynchronize(s);
+    tris.pop_back();
+    return e;
 }
 
-// The scene of a context on the device (ark_ddgi_set_scene): BVH nodes + triangles,
-// shading records, RT mesh data, materials, textures, lights. Reference-counted:
-// ark_ddgi_share_scene lets the Z-slab contexts of one GPU use one copy.
 // A background rebuild of the sun's light-space BVH (sunRebuildStep): a host thread
 // waits for a device snapshot of the world BVHs' triangle records (taken in stream
 // order behind the refits, `snap` / `evSnap`), builds the BVH for `dir` and uploads it
-// into `buf`; `done` set last (release).
+// into `bvh`; `done` set last (release).
 struct SunJob {
     std::thread t;
     std::atomic<bool> done { false };
@@ -179,20 +192,15 @@ struct SunJob {
     uint32_t refitsAt = 0; // SceneStore::refitCount of the snapshot (later refits: refitted forward at install)
     DeviceBuffer snap;    // the records it builds from
     hipEvent_t evSnap = nullptr;
-    DeviceBuffer buf;     // nodes, then the triangle records at triOffset
-    size_t triOffset = 0;
-    uint64_t nodes = 0, triRecords = 0;
-    uint32_t depth = 0;
-    float frame[9] {};
-    double frameD[9] {};
-    float inflateAbs = 0.0f;
-    std::vector<uint32_t> levelOrder, levelOffsets;
+    DeviceBvh bvh;        // the result (its level order still on the host: levelOrder)
+    std::vector<uint32_t> levelOrder;
+    double frame[9] {};
     float ms = 0.0f;
     bool ok = false;
     ~SunJob()
     {
         if (t.joinable()) t.join();
-        buf.release(); // not installed (an installed buffer was moved to the scene)
+        bvh.release(); // not installed (an installed one was moved to the scene)
         snap.release();
         if (evSnap) (void)hipEventDestroy(evSnap);
     }
@@ -212,13 +220,11 @@ struct WorldJob {
     hipEvent_t evSnap = nullptr;
     uint64_t snapRecords = 0;
     std::vector<int> classOf; // instance -> hit-mask class (0 opaque, 1 masked, 2 blend)
-    DeviceBuffer buf, perm, order;
-    size_t triOffset = 0;
-    uint64_t nodes = 0, triRecords = 0, triangles = 0;
+    DeviceBvh bvh;            // the result, its level order uploaded
+    DeviceBuffer perm;
     int32_t roots[3] { -1, -1, -1 };
-    uint32_t opaqueNodes = 0, depth = 0, maxLeaf = 0;
+    uint32_t opaqueNodes = 0, maxLeaf = 0;
     float sah = 0.0f;
-    std::vector<uint32_t> levelOffsets;
     float ms = 0.0f;
     bool ok = false;
     // runWorldJobGpu: the device built the result; or it handed the job to the host build
@@ -229,7 +235,8 @@ struct WorldJob {
     ~WorldJob()
     {
         if (t.joinable()) t.join();
-        for (DeviceBuffer* b : { &buf, &perm, &order, &snap }) b->release();
+        bvh.release();
+        for (DeviceBuffer* b : { &perm, &snap }) b->release();
         if (evSnap) (void)hipEventDestroy(evSnap);
     }
 };
@@ -241,11 +248,17 @@ struct Retired {
     hipEvent_t done = nullptr;
 };
 
+// The scene of a context on the device (ark_ddgi_set_scene): BVH nodes + triangles,
+// shading records, RT mesh data, materials, textures, lights. Reference-counted:
+// ark_ddgi_share_scene lets the Z-slab contexts of one GPU use one copy.
 struct SceneStore {
     int device = 0;
-    DeviceBuffer nodes, triNormals, indices, vertices, positions, meshes, materials, instances, texInfos, texels;
-    DeviceBuffer sunNodes; // light-space BVH8 of the sun's shadow rays + its world-space triangle records
-    uint64_t sunBvhNodes = 0;
+    DeviceBuffer triNormals, indices, vertices, positions, meshes, materials, instances, texInfos, texels;
+    // the world BVHs (args) and the light-space BVH8 of the sun's shadow rays with its
+    // world-space triangle records (sunArgs; nodeCount 0: none). The light-space BVH follows
+    // the motion: refitted with the world BVHs (its records re-transformed, its boxes of
+    // their light coordinates, sunFrameD)
+    DeviceBvh world, sun;
     float sunCostWorld = 0.0f, sunCostLight = 0.0f; // sampled sun shadow-ray steps per ray (sun_shadow_cost)
     std::vector<ArkRTInstance> instHost;     // the AO bake (instance -> mesh segment), set_instances' topology check
     std::vector<ArkRTTriangleMesh> meshHost;
@@ -258,20 +271,10 @@ struct SceneStore {
     std::vector<GpuSpotLight> spotsScene;
     ArkDdgiBvhStats bvhStats {};
     uint32_t bvhMaxDepth = 0; // deepest of the world BVHs and the sun's (traversal spill)
-    uint32_t worldDepth = 0, sunDepth = 0;
     // ark_ddgi_set_instances: bumped by every refit and install (a sharing context
-    // re-derives its SceneArgs); the builder's absolute inflation; the refit's buffers
+    // re-derives its SceneArgs); the refit's transforms on the device
     uint32_t version = 0;
-    float inflateAbs = 0.0f;
-    uint64_t triRecords = 0; // triangle records of the world BVHs (holes included)
-    DeviceBuffer refitInst, refitBoxes, refitOrder;
-    std::vector<uint32_t> levelOffsets; // refitOrder[levelOffsets[i] .. [i + 1]): the nodes of one depth, deepest first
-    // the light-space BVH follows the motion: refitted with the world BVHs (its records
-    // re-transformed, its boxes of their light coordinates)
-    DeviceBuffer sunRefitOrder, sunRefitBoxes;
-    std::vector<uint32_t> sunLevelOffsets;
-    uint64_t sunTriRecords = 0;
-    float sunInflateAbs = 0.0f;
+    DeviceBuffer refitInst;
     double sunFrameD[9] {};
     // the refit's transforms: the last ones uploaded (dirty = changed since the records
     // were written); pinned staging of the stream-ordered uploads, two sets in turn
@@ -288,7 +291,7 @@ struct SceneStore {
     // object-space bounds of every instance's triangles (set_scene): the refit's world and
     // light-space bounds, for its box inflation, from the instances' transforms on the host
     std::vector<std::array<float, 6>> instObjBox;
-    // The geometry a refit writes comes in three copies: the front one (nodes, sunNodes,
+    // The geometry a refit writes comes in three copies: the front one (world.buf, sun.buf,
     // instances above: what the kernels read) and two spares. A refit brings the next
     // spare from the transforms it holds (xf[slot]) to the new ones on the context's
     // refit stream and makes it the front one: it waits only for the operations that read
@@ -298,16 +301,14 @@ struct SceneStore {
     // the frames ran one after the other: C4 4.3 ms per moving frame, static 3.3). An
     // install (a new topology) drops the spares; the next refit copies the front one.
     struct Spare {
-        DeviceBuffer nodes, sunNodes, instances;
+        DeviceBuffer world, sun, instances;
         bool valid = false;
         int slot = 0;
     };
     Spare spare[2]; // spare[0]: the next refit's target
-    // the refit's node masks (k_node_masks: per topology) and the inflations each copy's
-    // boxes hold; refitFull: the next refit reaches every node (a new topology, or boxes
-    // scratch not of this one)
-    DeviceBuffer nodeMasks, sunNodeMasks;
-    bool masksValid = false, sunMasksValid = false, refitFull = true;
+    // the inflations each copy's boxes hold ([slot][0 world, 1 sun]); refitFull: the next
+    // refit reaches every node (a new topology, or boxes scratch not of this one)
+    bool refitFull = true;
     float inflCopy[3][2] {};
     int front = 0; // slot of the front copy (xf index)
     std::vector<std::array<float, 12>> xf[3];
@@ -358,10 +359,10 @@ struct SceneStore {
             if (stage[i]) (void)hipHostFree(stage[i]);
             if (stageDone[i]) (void)hipEventDestroy(stageDone[i]);
         }
-        for (DeviceBuffer* b : { &nodes, &triNormals, &indices, &vertices, &positions, &meshes, &materials, &instances, &texInfos, &texels, &sunNodes, &refitInst,
-                                 &refitBoxes, &refitOrder, &sunRefitOrder, &sunRefitBoxes, &spare[0].nodes, &spare[0].sunNodes,
-                                 &spare[0].instances, &spare[1].nodes, &spare[1].sunNodes, &spare[1].instances,
-                                 &nodeMasks, &sunNodeMasks })
+        world.release();
+        sun.release();
+        for (DeviceBuffer* b : { &triNormals, &indices, &vertices, &positions, &meshes, &materials, &instances, &texInfos, &texels, &refitInst, &spare[0].world,
+                                 &spare[0].sun, &spare[0].instances, &spare[1].world, &spare[1].sun, &spare[1].instances })
             b->release();
     }
 };
@@ -793,7 +794,7 @@ hipError_t stagedUpload(SceneStore& st, void* dst, const void* src, size_t bytes
 // 2 x 1e-6 |light diagonal| + 2e-6 max |world coordinate|), here from bounds that
 // contain the records: every instance's object-space box (st.instObjBox) through its
 // current transform (st.refitHost), corner by corner in double, and those corners in the
-// sun's frame. Never less than the build's (st.inflateAbs, st.sunInflateAbs). Larger
+// sun's frame. Never less than the build's (DeviceBvh::inflateAbs). Larger
 // bounds only loosen the boxes; the hits do not depend on them.
 void refitInflations(const SceneStore& st, float& world, float& light)
 {
@@ -828,32 +829,8 @@ void refitInflations(const SceneStore& st, float& world, float& light)
         return 1e-6 * std::sqrt(d2);
     };
     // rounded up to fp32 (the bounds' own rounding to fp32 in the builds is within it)
-    world = std::max(st.inflateAbs, std::nextafter(static_cast<float>(box(lo, hi)), INFINITY));
-    light = std::max(st.sunInflateAbs, std::nextafter(static_cast<float>(2.0 * box(llo, lhi) + 2e-6 * maxAbs), INFINITY));
-}
-
-// The refit of every BVH of the scene on `s`: the records of dirty instances re-transformed
-// (st.refitInst), the world BVHs' boxes level by level, and the light-space sun BVH's
-// records and light-space boxes. The boxes' inflations from the instances' bounds
-// (refitInflations, host).
-struct RefitTarget {
-    GpuBvh8Node* nodes;
-    GpuBvh8Node* sunNodes; // the light-space BVH's buffer (its records at the front copy's offset)
-};
-RefitTarget frontTarget(SceneStore& st) { return { st.nodes.as<GpuBvh8Node>(), st.sunNodes.as<GpuBvh8Node>() }; }
-RefitTarget spareTarget(SceneStore::Spare& c) { return { c.nodes.as<GpuBvh8Node>(), c.sunNodes.as<GpuBvh8Node>() }; }
-
-// The instance masks of a BVH's nodes (k_node_masks), level by level on `s`, into `masks`
-int computeMasks(ArkDdgiCtx* ctx, SceneStore& st, DeviceBuffer& masks, const GpuBvh8Node* nodes, const GpuTriangle* tris, uint64_t nodeCount,
-                 const DeviceBuffer& order, const std::vector<uint32_t>& offsets, hipStream_t s)
-{
-    if (masks.bytes < std::max<uint64_t>(8, nodeCount * 8)) {
-        ARK_HIP(retireBuffer(st, masks, s));
-        ARK_HIP(masks.alloc(std::max<uint64_t>(8, nodeCount * 8)));
-    }
-    for (size_t l = 0; l + 1 < offsets.size(); ++l)
-        ARK_HIP(launch_node_masks(nodes, tris, masks.as<uint64_t>(), order.as<uint32_t>() + offsets[l], offsets[l + 1] - offsets[l], s));
-    return ARK_DDGI_OK;
+    world = std::max(st.world.inflateAbs, std::nextafter(static_cast<float>(box(lo, hi)), INFINITY));
+    light = std::max(st.sun.inflateAbs, std::nextafter(static_cast<float>(2.0 * box(llo, lhi) + 2e-6 * maxAbs), INFINITY));
 }
 
 // The inflation of the refitted boxes rounded up to a power of two: it changes only when
@@ -861,52 +838,54 @@ int computeMasks(ArkDdgiCtx* ctx, SceneStore& st, DeviceBuffer& masks, const Gpu
 // instances that did not move (a change refits every node).
 float inflationStep(float x) { return x > 0.0f ? std::ldexp(1.0f, static_cast<int>(std::ceil(std::log2(static_cast<double>(x))))) : x; }
 
-// The refit of the copy `t` (slot: the transforms and inflations it holds) of every BVH
-// of the scene on `s`, level by level, the nodes with a moved instance below them
-// (st.refitInst's dirty flags: the instances whose transform differs from the copy's):
-// their moved records re-transformed, their boxes and planes recomputed. Every node after
-// an install or a new scene (refitFull) or a change of the inflation.
-int enqueueRefit(ArkDdgiCtx* ctx, SceneStore& st, hipStream_t s, const RefitTarget& t, int slot)
+// The refit of one BVH's copy `copy` on `s`, level by level: the nodes with an instance of
+// `dirty` below them (the node masks, k_node_masks, computed first when the topology is
+// new), or every node (refitFull, or an inflation other than the one the copy's boxes
+// hold, `held`: updated).
+int refitBvh(ArkDdgiCtx* ctx, SceneStore& st, DeviceBvh& b, const DeviceBuffer& copy, RefitBoxArgs args, uint64_t dirty, float& held, hipStream_t s)
+{
+    GpuBvh8Node* nodes = b.nodes(copy);
+    GpuTriangle* tris = b.tris(copy);
+    const uint32_t* order = b.order.as<uint32_t>();
+    const std::vector<uint32_t>& lv = b.levelOffsets;
+    if (!b.masksValid) {
+        if (b.masks.bytes < std::max<uint64_t>(8, b.nodeCount * 8)) {
+            ARK_HIP(retireBuffer(st, b.masks, s));
+            ARK_HIP(b.masks.alloc(std::max<uint64_t>(8, b.nodeCount * 8)));
+        }
+        for (size_t l = 0; l + 1 < lv.size(); ++l) ARK_HIP(launch_node_masks(nodes, tris, b.masks.as<uint64_t>(), order + lv[l], lv[l + 1] - lv[l], s));
+        b.masksValid = true;
+    }
+    args.dirty = (st.refitFull || args.inflate != held) ? ~0ull : dirty;
+    for (size_t l = 0; l + 1 < lv.size(); ++l)
+        ARK_HIP(launch_refit_nodes(nodes, tris, b.boxes.as<float>(), order + lv[l], lv[l + 1] - lv[l], args, b.masks.as<uint64_t>(), st.refitInst.as<RefitInstance>(),
+                                   st.indices.as<uint32_t>(), st.positions.as<float>(), s));
+    held = args.inflate;
+    return ARK_DDGI_OK;
+}
+
+// The refit of the copy (`world`, `sun`; slot: the transforms and inflations it holds) of
+// every BVH of the scene on `s`: the records of the moved instances (st.refitInst's dirty
+// flags: those whose transform differs from the copy's) re-transformed, the boxes and
+// planes above them recomputed - the world BVHs, then the light-space sun BVH (its boxes
+// of the records' light coordinates). The boxes' inflations from the instances' bounds
+// (refitInflations, host).
+int enqueueRefit(ArkDdgiCtx* ctx, SceneStore& st, hipStream_t s, const DeviceBuffer& world, const DeviceBuffer& sun, int slot)
 {
     float inflateWorld = 0.0f, inflateLight = 0.0f;
     refitInflations(st, inflateWorld, inflateLight);
-    inflateWorld = inflationStep(inflateWorld);
-    inflateLight = inflationStep(inflateLight);
     uint64_t dirty = 0;
     for (size_t i = 0; i < st.refitHost.size(); ++i)
         if (st.refitHost[i].dirty) dirty |= 1ull << (i & 63u);
-    GpuTriangle* tris = reinterpret_cast<GpuTriangle*>(reinterpret_cast<char*>(t.nodes) + st.args.tri_byte_offset);
-    const RefitInstance* inst = st.refitInst.as<RefitInstance>();
-    if (!st.masksValid) {
-        if (const int rc = computeMasks(ctx, st, st.nodeMasks, t.nodes, tris, st.bvhStats.node_count, st.refitOrder, st.levelOffsets, s)) return rc;
-        st.masksValid = true;
-    }
-    RefitBoxArgs world {};
-    world.inflate = inflateWorld;
-    world.light = 0;
-    world.dirty = (st.refitFull || inflateWorld != st.inflCopy[slot][0]) ? ~0ull : dirty;
-    const uint32_t* order = st.refitOrder.as<uint32_t>();
-    for (size_t l = 0; l + 1 < st.levelOffsets.size(); ++l)
-        ARK_HIP(launch_refit_nodes(t.nodes, tris, st.refitBoxes.as<float>(), order + st.levelOffsets[l], st.levelOffsets[l + 1] - st.levelOffsets[l],
-                                   world, st.nodeMasks.as<uint64_t>(), inst, st.indices.as<uint32_t>(), st.positions.as<float>(), s));
-    st.inflCopy[slot][0] = inflateWorld;
-    if (st.sunArgs.sun_root >= 0 && st.sunTriRecords && !st.sunLevelOffsets.empty()) {
-        const size_t sunTriOffset = reinterpret_cast<const char*>(st.sunArgs.sun_tris) - static_cast<const char*>(st.sunNodes.ptr);
-        GpuTriangle* stris = reinterpret_cast<GpuTriangle*>(reinterpret_cast<char*>(t.sunNodes) + sunTriOffset);
-        if (!st.sunMasksValid) {
-            if (const int rc = computeMasks(ctx, st, st.sunNodeMasks, t.sunNodes, stris, st.sunBvhNodes, st.sunRefitOrder, st.sunLevelOffsets, s)) return rc;
-            st.sunMasksValid = true;
-        }
-        RefitBoxArgs light {};
-        std::memcpy(light.frame, st.sunFrameD, sizeof(light.frame));
-        light.inflate = inflateLight;
-        light.light = 1;
-        light.dirty = (st.refitFull || inflateLight != st.inflCopy[slot][1]) ? ~0ull : dirty;
-        const uint32_t* so = st.sunRefitOrder.as<uint32_t>();
-        for (size_t l = 0; l + 1 < st.sunLevelOffsets.size(); ++l)
-            ARK_HIP(launch_refit_nodes(t.sunNodes, stris, st.sunRefitBoxes.as<float>(), so + st.sunLevelOffsets[l], st.sunLevelOffsets[l + 1] - st.sunLevelOffsets[l],
-                                       light, st.sunNodeMasks.as<uint64_t>(), inst, st.indices.as<uint32_t>(), st.positions.as<float>(), s));
-        st.inflCopy[slot][1] = inflateLight;
+    RefitBoxArgs a {};
+    a.inflate = inflationStep(inflateWorld);
+    a.light = 0;
+    if (const int rc = refitBvh(ctx, st, st.world, world, a, dirty, st.inflCopy[slot][0], s)) return rc;
+    if (st.sunArgs.sun_root >= 0 && st.sun.records && !st.sun.levelOffsets.empty()) {
+        std::memcpy(a.frame, st.sunFrameD, sizeof(a.frame));
+        a.inflate = inflationStep(inflateLight);
+        a.light = 1;
+        if (const int rc = refitBvh(ctx, st, st.sun, sun, a, dirty, st.inflCopy[slot][1], s)) return rc;
     }
     st.refitFull = false;
     return ARK_DDGI_OK;
@@ -941,8 +920,8 @@ int uploadRefitInstances(ArkDdgiCtx* ctx, SceneStore& st, const ArkRTInstance* i
 // next refit reaches every node.
 void markTopologyChanged(SceneStore& st)
 {
-    st.masksValid = false;
-    st.sunMasksValid = false;
+    st.world.masksValid = false;
+    st.sun.masksValid = false;
     st.refitFull = true;
 }
 
@@ -951,7 +930,7 @@ hipError_t dropSpares(SceneStore& st, hipStream_t s)
 {
     hipError_t e = hipSuccess;
     for (SceneStore::Spare& c : st.spare) {
-        for (DeviceBuffer* b : { &c.nodes, &c.sunNodes, &c.instances })
+        for (DeviceBuffer* b : { &c.world, &c.sun, &c.instances })
             if (e == hipSuccess) e = retireBuffer(st, *b, s);
         c.valid = false;
     }
@@ -978,17 +957,16 @@ hipError_t installedGeometry(ArkDdgiCtx* ctx, SceneStore& st, hipStream_t s)
 // the live records could see a half-refitted set).
 hipError_t snapshotRecords(SceneStore& st, DeviceBuffer& snap, hipEvent_t& ev, hipStream_t s)
 {
-    const size_t bytes = st.triRecords * sizeof(GpuTriangle);
+    const size_t bytes = st.world.records * sizeof(GpuTriangle);
     hipError_t e = snap.alloc(std::max<size_t>(bytes, 16));
-    if (e == hipSuccess && bytes)
-        e = hipMemcpyAsync(snap.ptr, static_cast<const char*>(st.nodes.ptr) + st.args.tri_byte_offset, bytes, hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && bytes) e = hipMemcpyAsync(snap.ptr, st.world.tris(st.world.buf), bytes, hipMemcpyDeviceToDevice, s);
     if (e == hipSuccess && !ev) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     if (e == hipSuccess) e = hipEventRecord(ev, s);
     return e;
 }
 
 // The sun rebuild's thread: the snapshot of the world records, the light-space BVH of
-// job->dir on the host (as set_scene builds it), uploaded into job->buf.
+// job->dir on the host (as set_scene builds it), uploaded into job->bvh.
 void runSunJob(SunJob* job, int device, uint64_t count, int threads)
 {
     const auto t0 = std::chrono::steady_clock::now();
@@ -1009,79 +987,18 @@ void runSunJob(SunJob* job, int device, uint64_t count, int threads)
         Bvh8CollapseOptions copt;
         copt.threads = threads;
         ok = build_sun_bvh(in, opt, copt, r) && !r.nodes.empty();
-        for (int i = 0; i < 3; ++i)
-            for (int k = 0; k < 3; ++k) {
-                job->frame[i * 3 + k] = static_cast<float>(in.frame[i][k]);
-                job->frameD[i * 3 + k] = in.frame[i][k];
-            }
-        job->inflateAbs = in.inflateAbs;
+        std::memcpy(job->frame, in.frame, sizeof(job->frame));
+        job->bvh.inflateAbs = in.inflateAbs;
+        job->bvh.depth = r.max_depth;
         const int32_t root = 0;
-        ok = ok && bvhLevelOrder(r.nodes.data(), r.nodes.size(), &root, 1, job->levelOrder, job->levelOffsets);
+        ok = ok && bvhLevelOrder(r.nodes.data(), r.nodes.size(), &root, 1, job->levelOrder, job->bvh.levelOffsets);
     }
-    if (ok) {
-        const size_t nb = r.nodes.size() * sizeof(GpuBvh8Node);
-        job->triOffset = (nb + 255) & ~static_cast<size_t>(255);
-        job->triRecords = r.tris.size();
-        r.tris.push_back(GpuTriangle {}); // padding record (five-load fetch)
-        ok = job->buf.alloc(job->triOffset + r.tris.size() * sizeof(GpuTriangle)) == hipSuccess &&
-             hipMemcpyAsync(job->buf.ptr, r.nodes.data(), nb, hipMemcpyHostToDevice, s) == hipSuccess &&
-             hipMemcpyAsync(static_cast<char*>(job->buf.ptr) + job->triOffset, r.tris.data(), r.tris.size() * sizeof(GpuTriangle), hipMemcpyHostToDevice, s) == hipSuccess &&
-             hipStreamSynchronize(s) == hipSuccess;
-        job->nodes = r.nodes.size();
-        job->depth = r.max_depth;
-    }
+    ok = ok && uploadBvh(r.nodes, r.tris, s, job->bvh) == hipSuccess;
     if (s) (void)hipStreamDestroy(s);
     job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     job->ok = ok;
     job->done.store(true, std::memory_order_release);
 }
-
-// Structural check of a BVH8 before anything reaches the GPU: every node is
-// referenced once from a root-reachable parent (no cycles, no sharing), every leaf's
-// triangles lie inside the triangle array and every triangle (every record but the
-// holes of the rows) is covered once.
-bool checkBvh8Structure(const std::vector<GpuBvh8Node>& allNodes, const std::vector<GpuTriangle>& allTris, const int32_t* roots, int nRoots, std::string& why)
-{
-    char buf[128];
-    auto bad = [&](const char* fmt, uint64_t v) {
-        std::snprintf(buf, sizeof(buf), fmt, static_cast<unsigned long long>(v));
-        why = buf;
-        return false;
-    };
-    std::vector<uint8_t> seenNode(allNodes.size(), 0);
-    std::vector<uint8_t> seenTri(allTris.size(), 0);
-    std::vector<uint32_t> work;
-    for (int c = 0; c < nRoots; ++c)
-        if (roots[c] >= 0) work.push_back(static_cast<uint32_t>(roots[c]));
-    while (!work.empty()) {
-        const uint32_t n = work.back();
-        work.pop_back();
-        if (n >= allNodes.size() || seenNode[n]) return bad("BVH invalid: node %llu", n);
-        seenNode[n] = 1;
-        const GpuBvh8Node& nd = allNodes[n];
-        uint32_t internal = 0;
-        if ((nd.leaf_tris >> 24) || (nd.leaf_mask & nd.imask)) return bad("BVH invalid: node %llu leaf rows", n);
-        for (int sl = 0; sl < 8; ++sl) {
-            const bool isInternal = (nd.imask >> sl) & 1u;
-            uint32_t slotTris[kBvh8MaxLeafSize];
-            const int cnt = bvh8SlotTriangles(nd, sl, slotTris);
-            if (cnt < 0) return bad("BVH invalid: node %llu slot", n);
-            if (isInternal) work.push_back(nd.child_base + internal++);
-            for (int i = 0; i < cnt; ++i) {
-                const uint32_t t = slotTris[i];
-                if (t >= allTris.size() || isHoleTriangle(allTris[t])) return bad("BVH invalid: leaf range%.0llu", 0);
-                if (seenTri[t]) return bad("BVH invalid: triangle %llu in two leaves", t);
-                seenTri[t] = 1;
-            }
-            for (int a = 0; a < 3; ++a)
-                if ((isInternal || cnt > 0) && nd.qlo[a][sl] > nd.qhi[a][sl]) return bad("BVH invalid: child box%.0llu", 0);
-        }
-    }
-    for (size_t t = 0; t < seenTri.size(); ++t)
-        if (!seenTri[t] && !isHoleTriangle(allTris[t])) return bad("BVH invalid: triangle %llu unreachable", t);
-    return true;
-}
-
 
 // The world rebuild's thread: the three classes' BVHs from the snapshot's records (their
 // vertices v0, v0 + e1, v0 + e2; each leaf record then replaced by its source record,
@@ -1122,73 +1039,38 @@ void runWorldJob(WorldJob* job, int device, int threads)
             cls[job->classOf[inst]].push_back(t);
         }
     }
-    std::vector<GpuBvh8Node> allNodes;
-    std::vector<GpuTriangle> allTris;
+    WorldBvh8 w;
+    std::vector<uint32_t> perm, order;
     if (ok) {
         BvhBuildOptions opt;
-        opt.max_leaf_size = kBvh8MaxLeafSize;
         opt.threads = threads;
-        {
-            float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-            for (int c = 0; c < 3; ++c)
-                for (const BuildTriangle& t : cls[c])
-                    for (const float* v : { t.v0, t.v1, t.v2 })
-                        for (int a = 0; a < 3; ++a) {
-                            lo[a] = std::min(lo[a], v[a]);
-                            hi[a] = std::max(hi[a], v[a]);
-                        }
-            opt.inflate_abs = bvh8_inflation_box(lo, hi);
-        }
         Bvh8CollapseOptions copt;
         copt.threads = threads;
-        for (int c = 0; c < 3 && ok; ++c) {
-            if (cls[c].empty()) continue;
-            BvhBuildResult r2 = build_bvh(cls[c], opt, 0u, 0u);
-            std::vector<BuildTriangle>().swap(cls[c]);
-            if (r2.max_leaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
-                ok = false;
-                job->error = "BVH2 leaf over the leaf size";
-                break;
-            }
-            if (c == 0) job->sah = r2.sah_cost;
-            job->maxLeaf = std::max(job->maxLeaf, r2.max_leaf);
-            Bvh8BuildResult r = collapse_bvh8(r2, static_cast<uint32_t>(allNodes.size()), static_cast<uint32_t>(allTris.size()), copt);
-            job->roots[c] = static_cast<int32_t>(allNodes.size());
-            if (c == 0) job->opaqueNodes = static_cast<uint32_t>(r.nodes.size());
-            job->depth = std::max(job->depth, r.max_depth);
-            job->triangles += r.triangles;
-            allNodes.insert(allNodes.end(), r.nodes.begin(), r.nodes.end());
-            allTris.insert(allTris.end(), r.tris.begin(), r.tris.end());
-        }
+        ok = build_world_bvh8(cls, opt, copt, w, job->error);
+        if (w.maxLeaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) job->error = "BVH2 leaf over the leaf size";
     }
-    std::vector<uint32_t> perm;
     if (ok) {
-        perm.assign(allTris.size(), 0xffffffffu);
-        for (size_t i = 0; i < allTris.size(); ++i) {
-            GpuTriangle& g = allTris[i];
+        perm.assign(w.tris.size(), 0xffffffffu);
+        for (size_t i = 0; i < w.tris.size(); ++i) {
+            GpuTriangle& g = w.tris[i];
             if (isHoleTriangle(g)) continue;
             uint32_t src;
             std::memcpy(&src, &g.t2[2], 4);
             perm[i] = src;
             g = rec[src];
         }
-        ok = checkBvh8Structure(allNodes, allTris, job->roots, 3, job->error);
+        std::copy(w.roots, w.roots + 3, job->roots);
+        job->opaqueNodes = w.opaqueNodes;
+        job->maxLeaf = w.maxLeaf;
+        job->sah = w.sah;
+        job->bvh.depth = w.depth;
+        ok = bvhLevelOrder(w.nodes.data(), w.nodes.size(), w.roots, 3, order, job->bvh.levelOffsets);
     }
-    std::vector<uint32_t> order;
-    ok = ok && bvhLevelOrder(allNodes.data(), allNodes.size(), job->roots, 3, order, job->levelOffsets);
     if (ok) {
-        const size_t nb = allNodes.size() * sizeof(GpuBvh8Node);
-        job->triOffset = (nb + 255) & ~static_cast<size_t>(255);
-        job->triRecords = allTris.size();
-        job->nodes = allNodes.size();
-        allTris.push_back(GpuTriangle {}); // padding record (five-load fetch)
-        ok = job->triOffset + allTris.size() * sizeof(GpuTriangle) < (1ull << 32) &&
-             job->buf.alloc(job->triOffset + allTris.size() * sizeof(GpuTriangle)) == hipSuccess &&
-             job->perm.alloc(std::max<size_t>(16, perm.size() * 4)) == hipSuccess && job->order.alloc(std::max<size_t>(16, order.size() * 4)) == hipSuccess &&
-             hipMemcpyAsync(job->buf.ptr, allNodes.data(), nb, hipMemcpyHostToDevice, s) == hipSuccess &&
-             hipMemcpyAsync(static_cast<char*>(job->buf.ptr) + job->triOffset, allTris.data(), allTris.size() * sizeof(GpuTriangle), hipMemcpyHostToDevice, s) == hipSuccess &&
+        ok = DeviceBvh::bytesFor(w.nodes.size(), w.tris.size()) < (1ull << 32) && job->perm.alloc(std::max<size_t>(16, perm.size() * 4)) == hipSuccess &&
+             job->bvh.order.alloc(std::max<size_t>(16, order.size() * 4)) == hipSuccess &&
              hipMemcpyAsync(job->perm.ptr, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
-             hipMemcpyAsync(job->order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
+             hipMemcpyAsync(job->bvh.order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess && uploadBvh(w.nodes, w.tris, s, job->bvh) == hipSuccess;
         if (!ok && job->error.empty()) job->error = "upload failed";
     }
     if (s) (void)hipStreamDestroy(s);
@@ -1198,7 +1080,7 @@ void runWorldJob(WorldJob* job, int device, int threads)
 }
 
 // The deepest BVH8 the device build installs. The traversal's spill area is sized from the
-// installed depth (ensureSpill: depth + 2 - kStackLds entries per lane, st.worldDepth),
+// installed depth (ensureSpill: depth + 2 - kStackLds entries per lane, DeviceBvh::depth),
 // and the deepest tree the host builds hand it is bounded by the BVH2 builder's depth cap
 // (BvhBuildOptions::max_depth, 60); a radix tree over coincident centroids can be
 // deeper, and such a scene is left to the host build.
@@ -1353,24 +1235,24 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
         if (c == 0) job->opaqueNodes = nodeTotal;
     }
     const uint32_t outRecords = counters[kLbvhRecords];
-    const size_t nb = nodeTotal * sizeof(GpuBvh8Node);
-    job->triOffset = (nb + 255) & ~static_cast<size_t>(255);
-    if (!(job->triOffset + (outRecords + 1ull) * sizeof(GpuTriangle) < (1ull << 32))) {
+    if (!(DeviceBvh::bytesFor(nodeTotal, outRecords) < (1ull << 32))) {
         why = "nodes and records of 4 GiB or more";
         return hipSuccess;
     }
     // the installed buffers, sized from the counts read back
-    ARK_GB(job->buf.alloc(job->triOffset + (outRecords + 1ull) * sizeof(GpuTriangle)));
+    DeviceBvh& b = job->bvh;
+    b.triOffset = DeviceBvh::triOffsetFor(nodeTotal);
+    ARK_GB(b.buf.alloc(DeviceBvh::bytesFor(nodeTotal, outRecords)));
     ARK_GB(job->perm.alloc(std::max<size_t>(16, outRecords * 4ull)));
-    GpuBvh8Node* nodes = job->buf.as<GpuBvh8Node>();
-    GpuTriangle* tris = reinterpret_cast<GpuTriangle*>(static_cast<char*>(job->buf.ptr) + job->triOffset);
-    ARK_GB(hipMemcpyAsync(nodes, w.nodes.ptr, nb, hipMemcpyDeviceToDevice, s));
+    GpuBvh8Node* nodes = b.nodes(b.buf);
+    GpuTriangle* tris = b.tris(b.buf);
+    ARK_GB(hipMemcpyAsync(nodes, w.nodes.ptr, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToDevice, s));
     ARK_GB(launch_lbvh_scatter(snap, w.idxSorted.as<uint32_t>(), w.position.as<uint32_t>(), tris, job->perm.as<uint32_t>(), n, outRecords, s));
     // the refit's level order from the level counts (bvhLevelOrder's format: deepest level
     // first, ascending node index within a level; each class one breadth-first range)
     std::vector<uint32_t> order;
     order.reserve(nodeTotal);
-    job->levelOffsets.assign(1, 0u);
+    b.levelOffsets.assign(1, 0u);
     {
         std::vector<std::array<uint32_t, 3>> base(levels.size());
         uint32_t at[3];
@@ -1383,11 +1265,11 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
         for (size_t d = levels.size(); d-- > 0;) {
             for (int c = 0; c < 3; ++c)
                 for (uint32_t k = 0; k < levels[d][c]; ++k) order.push_back(base[d][c] + k);
-            job->levelOffsets.push_back(static_cast<uint32_t>(order.size()));
+            b.levelOffsets.push_back(static_cast<uint32_t>(order.size()));
         }
     }
-    ARK_GB(job->order.alloc(std::max<size_t>(16, order.size() * 4)));
-    ARK_GB(hipMemcpyAsync(job->order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
+    ARK_GB(b.order.alloc(std::max<size_t>(16, order.size() * 4)));
+    ARK_GB(hipMemcpyAsync(b.order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
     // boxes, grids and planes: the refit over every level, deepest first, every node live
     // (all mask bits set, no instance dirty: no record is touched), the inflation runWorldJob's
     ARK_GB(hipMemsetAsync(w.masks.ptr, 0xff, nodeTotal * 8ull, s));
@@ -1396,15 +1278,14 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
     ra.inflate = bvh8_inflation_box(lo, hi);
     ra.light = 0;
     ra.dirty = ~0ull;
-    for (size_t l = 0; l + 1 < job->levelOffsets.size(); ++l)
-        ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), job->order.as<uint32_t>() + job->levelOffsets[l], job->levelOffsets[l + 1] - job->levelOffsets[l], ra,
+    for (size_t l = 0; l + 1 < b.levelOffsets.size(); ++l)
+        ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), b.order.as<uint32_t>() + b.levelOffsets[l], b.levelOffsets[l + 1] - b.levelOffsets[l], ra,
                                   w.masks.as<uint64_t>(), w.inst.as<RefitInstance>(), nullptr, nullptr, s));
     ARK_GB(hipStreamSynchronize(s));
 #undef ARK_GB
-    job->nodes = nodeTotal;
-    job->triRecords = outRecords;
-    job->triangles = n;
-    job->depth = static_cast<uint32_t>(levels.size());
+    b.nodeCount = nodeTotal;
+    b.records = outRecords;
+    b.depth = static_cast<uint32_t>(levels.size());
     job->maxLeaf = std::min<uint32_t>(n, static_cast<uint32_t>(kBvh8MaxLeafSize));
     job->sah = 0.0f; // not evaluated on the device
     return hipSuccess;
@@ -1441,10 +1322,11 @@ void runWorldJobGpu(WorldJob* job, int device, int threads)
         return;
     }
     // the host build from the same snapshot
-    for (DeviceBuffer* b : { &job->buf, &job->perm, &job->order }) b->release();
+    job->bvh.release();
+    job->bvh = DeviceBvh {};
+    job->perm.release();
     job->roots[0] = job->roots[1] = job->roots[2] = -1;
     job->opaqueNodes = 0;
-    job->levelOffsets.clear();
     job->gpuFallback = true;
     runWorldJob(job, device, threads);
 }
@@ -1464,6 +1346,103 @@ hipError_t installDone(ArkDdgiCtx* ctx, hipStream_t s)
 {
     if (ctx->sceneStore.use_count() > 1) return hipStreamSynchronize(s);
     return hipSuccess;
+}
+
+// instance -> hit-mask class (the world rebuild's input, the world BVH check)
+std::vector<int> instanceClasses(const SceneStore& st)
+{
+    std::vector<int> c(st.instHost.size());
+    for (size_t i = 0; i < c.size(); ++i) c[i] = hit_mask_class(st.instHost[i].hit_mask);
+    return c;
+}
+
+// The kernels' view of the front copies (set_scene, the installs, rotateGeometry)
+void setWorldArgs(SceneStore& st)
+{
+    st.args.nodes = st.world.nodes(st.world.buf);
+    st.args.tris = st.world.tris(st.world.buf);
+    st.args.tri_byte_offset = static_cast<uint32_t>(st.world.triOffset);
+    st.args.instances = st.instances.as<GpuInstance>();
+}
+
+void setWorldRoots(SceneStore& st, const int32_t roots[3], uint32_t opaqueNodes)
+{
+    st.args.root_opaque = roots[0];
+    st.args.root_masked = roots[1];
+    st.args.root_blend = roots[2];
+    st.args.opaque_nodes = opaqueNodes;
+}
+
+void setSunArgs(SceneStore& st)
+{
+    st.sunArgs.sun_nodes = st.sun.nodes(st.sun.buf);
+    st.sunArgs.sun_tris = st.sun.tris(st.sun.buf);
+    st.sunArgs.sun_root = 0;
+}
+
+// The refit's boxes scratch of `b` for its node count, with a quarter to spare (a smaller
+// one retired behind `s`)
+hipError_t growBoxes(SceneStore& st, DeviceBvh& b, hipStream_t s)
+{
+    const size_t need = b.nodeCount * 6 * sizeof(float);
+    if (b.boxes.bytes >= need) return hipSuccess;
+    const hipError_t e = retireBuffer(st, b.boxes, s);
+    return e == hipSuccess ? b.boxes.alloc(std::max<size_t>(16, need * 5 / 4)) : e;
+}
+
+// A finished build `b` (buffer, level order, counts) replaces `cur`: the old buffer and
+// level order retired behind everything enqueued on `s` so far, the refit's scratch kept
+// (growBoxes follows).
+hipError_t replaceBvh(SceneStore& st, DeviceBvh& cur, DeviceBvh& b, hipStream_t s)
+{
+    hipError_t e = retireBuffer(st, cur.buf, s);
+    if (e == hipSuccess) e = retireBuffer(st, cur.order, s);
+    if (e != hipSuccess) return e;
+    b.boxes = cur.boxes;
+    b.masks = cur.masks;
+    b.masksValid = false;
+    cur = std::move(b);
+    b = DeviceBvh {};
+    return hipSuccess;
+}
+
+// The light-space BVH `b` (its level order on the host) built for the sun direction `dir`
+// in `frame` becomes the scene's: uploaded by the job (sunCollect: host null), or here from
+// `host` (set_scene, synchronously).
+int installSunBvh(ArkDdgiCtx* ctx, SceneStore& st, DeviceBvh& b, Bvh8BuildResult* host, const std::vector<uint32_t>& levelOrder, const double* frame, const float* dir,
+                  hipStream_t s)
+{
+    ARK_HIP(replaceBvh(st, st.sun, b, s));
+    ARK_HIP(st.sun.order.alloc(std::max<size_t>(16, levelOrder.size() * 4)));
+    ARK_HIP(hipMemcpy(st.sun.order.ptr, levelOrder.data(), levelOrder.size() * 4, hipMemcpyHostToDevice));
+    st.sun.nodeCount = levelOrder.size();
+    ARK_HIP(growBoxes(st, st.sun, s));
+    if (host) ARK_HIP(uploadBvh(host->nodes, host->tris, nullptr, st.sun));
+    setSunArgs(st);
+    for (int k = 0; k < 9; ++k) {
+        st.sunArgs.sun_frame[k] = static_cast<float>(frame[k]);
+        st.sunFrameD[k] = frame[k];
+    }
+    std::memcpy(st.sunDirBuilt, dir, sizeof(st.sunDirBuilt));
+    return ARK_DDGI_OK;
+}
+
+// The end of an install on `s` (sunCollect, worldCollect): the new topology refitted
+// forward when refits came in while it was built (every instance re-transformed), the
+// spares dropped, the next traversal and refit ordered behind it, the scene's version bumped.
+int finishInstall(ArkDdgiCtx* ctx, SceneStore& st, uint32_t refitsSince, hipStream_t s)
+{
+    markTopologyChanged(st);
+    if (refitsSince) {
+        if (const int rc = uploadRefitInstances(ctx, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
+        if (const int rc = enqueueRefit(ctx, st, s, st.world.buf, st.sun.buf, st.front)) return rc;
+    }
+    ARK_HIP(installedGeometry(ctx, st, s));
+    ARK_HIP(hipEventRecord(ctx->evRefit, s));
+    ARK_HIP(installDone(ctx, s));
+    ctx->refitPending = true;
+    ++st.version;
+    return refreshScene(ctx);
 }
 
 // The light-space sun BVH follows the context's sun (called by every update and by
@@ -1504,49 +1483,18 @@ int sunCollect(ArkDdgiCtx* ctx, hipStream_t s)
             std::unique_ptr<SunJob> job = std::move(st.sunJob);
             job->t.join();
             ARK_HIP(installBarrier(ctx, s));
-            ARK_HIP(retireBuffer(st, st.sunNodes, s));
-            ARK_HIP(retireBuffer(st, st.sunRefitOrder, s));
-            st.sunNodes = job->buf;
-            job->buf = DeviceBuffer {};
-            st.sunArgs.sun_nodes = st.sunNodes.as<GpuBvh8Node>();
-            st.sunArgs.sun_tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st.sunNodes.ptr) + job->triOffset);
-            st.sunArgs.sun_root = 0;
-            std::memcpy(st.sunArgs.sun_frame, job->frame, sizeof(job->frame));
-            std::memcpy(st.sunFrameD, job->frameD, sizeof(job->frameD));
-            std::memcpy(st.sunDirBuilt, job->dir, sizeof(job->dir));
-            st.sunInflateAbs = job->inflateAbs;
-            st.sunTriRecords = job->triRecords;
-            st.sunLevelOffsets = job->levelOffsets;
-            ARK_HIP(st.sunRefitOrder.alloc(std::max<size_t>(16, job->levelOrder.size() * 4)));
-            ARK_HIP(hipMemcpy(st.sunRefitOrder.ptr, job->levelOrder.data(), job->levelOrder.size() * 4, hipMemcpyHostToDevice));
-            if (st.sunRefitBoxes.bytes < job->nodes * 6 * sizeof(float)) {
-                ARK_HIP(retireBuffer(st, st.sunRefitBoxes, s));
-                ARK_HIP(st.sunRefitBoxes.alloc(std::max<size_t>(16, job->nodes * 6 * sizeof(float) * 5 / 4)));
-            }
-            st.sunBvhNodes = job->nodes;
-            st.sunDepth = job->depth;
-            st.bvhMaxDepth = std::max(st.bvhMaxDepth, job->depth);
+            if (const int rc = installSunBvh(ctx, st, job->bvh, nullptr, job->levelOrder, job->frame, job->dir, s)) return rc;
+            ARK_HIP(retireBuffer(st, job->snap, s));
+            st.bvhMaxDepth = std::max(st.bvhMaxDepth, st.sun.depth);
             st.bvhStats.max_depth = st.bvhMaxDepth;
-            st.bvhStats.sun_node_count = job->nodes;
-            st.bvhStats.sun_max_depth = job->depth;
+            st.bvhStats.sun_node_count = st.sun.nodeCount;
+            st.bvhStats.sun_max_depth = st.sun.depth;
             st.bvhStats.sun_rebuilds = ++st.sunRebuilds;
             st.bvhStats.sun_build_ms = job->ms;
             st.sunRefitsSinceBuild = st.refitCount - job->refitsAt;
             st.bvhStats.sun_built_refit_version = job->refitsAt;
-            markTopologyChanged(st);
-            if (st.sunRefitsSinceBuild) {
-                // refits came in while it was built: its records follow them (every
-                // instance re-transformed, the light-space boxes refitted)
-                if (const int rc = uploadRefitInstances(ctx, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
-                if (const int rc = enqueueRefit(ctx, st, s, frontTarget(st), st.front)) return rc;
-            }
-            ARK_HIP(retireBuffer(st, job->snap, s));
-            ARK_HIP(installedGeometry(ctx, st, s));
-            ARK_HIP(hipEventRecord(ctx->evRefit, s));
-            ARK_HIP(installDone(ctx, s));
-            ctx->refitPending = true;
-            ++st.version;
-            if (const int rc = refreshScene(ctx)) return rc;
+            // (refits that came in while it was built: its records follow them)
+            if (const int rc = finishInstall(ctx, st, st.sunRefitsSinceBuild, s)) return rc;
         }
         // else: built for another context's sun; that context installs it
     }
@@ -1599,7 +1547,7 @@ int sunStart(ArkDdgiCtx* ctx, hipStream_t s)
     job->refitsAt = st.refitCount;
     ARK_HIP(orderBegin(ctx, s));
     ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
-    job->t = std::thread(runSunJob, job.get(), st.device, st.triRecords, std::max(1, st.buildThreads / 2));
+    job->t = std::thread(runSunJob, job.get(), st.device, st.world.records, std::max(1, st.buildThreads / 2));
     st.sunJob = std::move(job);
     st.lastBackground = SceneStore::kBackgroundSun;
     return ARK_DDGI_OK;
@@ -1650,41 +1598,25 @@ int worldCollect(ArkDdgiCtx* ctx, hipStream_t s)
         ARK_HIP(installBarrier(ctx, s));
         // the shading records in the new record order (before the old ones are retired)
         DeviceBuffer tn;
-        ARK_HIP(tn.alloc(std::max<size_t>(64, job->triRecords * 64)));
-        ARK_HIP(launch_gather_records(tn.as<float4>(), st.triNormals.as<float4>(), job->perm.as<uint32_t>(), job->triRecords, s));
+        ARK_HIP(tn.alloc(std::max<size_t>(64, job->bvh.records * 64)));
+        ARK_HIP(launch_gather_records(tn.as<float4>(), st.triNormals.as<float4>(), job->perm.as<uint32_t>(), job->bvh.records, s));
         ARK_HIP(retireBuffer(st, st.triNormals, s));
-        ARK_HIP(retireBuffer(st, st.nodes, s));
-        ARK_HIP(retireBuffer(st, st.refitOrder, s));
+        st.triNormals = tn;
+        job->bvh.inflateAbs = st.world.inflateAbs; // the refits' floor stays set_scene's
+        ARK_HIP(replaceBvh(st, st.world, job->bvh, s));
         ARK_HIP(retireBuffer(st, job->perm, s));
         ARK_HIP(retireBuffer(st, job->snap, s));
-        st.triNormals = tn;
-        st.nodes = job->buf;
-        job->buf = DeviceBuffer {};
-        st.refitOrder = job->order;
-        job->order = DeviceBuffer {};
-        st.levelOffsets = job->levelOffsets;
-        if (st.refitBoxes.bytes < job->nodes * 6 * sizeof(float)) {
-            ARK_HIP(retireBuffer(st, st.refitBoxes, s));
-            ARK_HIP(st.refitBoxes.alloc(std::max<size_t>(16, job->nodes * 6 * sizeof(float) * 5 / 4)));
-        }
-        SceneArgs& sc = st.args;
-        sc.nodes = st.nodes.as<GpuBvh8Node>();
-        sc.tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st.nodes.ptr) + job->triOffset);
-        sc.tri_byte_offset = static_cast<uint32_t>(job->triOffset);
-        sc.tri_normals = st.triNormals.as<float4>();
-        sc.root_opaque = job->roots[0];
-        sc.root_masked = job->roots[1];
-        sc.root_blend = job->roots[2];
-        sc.opaque_nodes = job->opaqueNodes;
-        st.triRecords = job->triRecords;
-        st.worldDepth = job->depth;
-        st.bvhMaxDepth = std::max(job->depth, st.sunArgs.sun_root >= 0 ? st.sunDepth : 0u);
-        st.bvhStats.node_count = job->nodes;
+        ARK_HIP(growBoxes(st, st.world, s));
+        setWorldArgs(st);
+        setWorldRoots(st, job->roots, job->opaqueNodes);
+        st.args.tri_normals = st.triNormals.as<float4>();
+        st.bvhMaxDepth = std::max(st.world.depth, st.sunArgs.sun_root >= 0 ? st.sun.depth : 0u);
+        st.bvhStats.node_count = st.world.nodeCount;
         st.bvhStats.max_depth = st.bvhMaxDepth;
         st.bvhStats.max_leaf_size = job->maxLeaf;
         st.bvhStats.sah_cost = job->sah;
-        st.bvhStats.node_bytes = job->nodes * sizeof(GpuBvh8Node);
-        st.bvhStats.triangle_bytes = job->triRecords * sizeof(GpuTriangle);
+        st.bvhStats.node_bytes = st.world.nodeCount * sizeof(GpuBvh8Node);
+        st.bvhStats.triangle_bytes = st.world.records * sizeof(GpuTriangle);
         st.bvhStats.bvh_rebuilds = ++st.worldRebuilds;
         st.bvhStats.bvh_rebuild_ms = job->ms;
         st.worldGpuBuilt = job->gpu;
@@ -1692,17 +1624,7 @@ int worldCollect(ArkDdgiCtx* ctx, hipStream_t s)
         if (job->gpu) st.bvhStats.bvh_gpu_rebuilds++;
         st.refitsSinceBuild = st.refitCount - job->refitsAt; // refits since its snapshot
         st.bvhStats.bvh_built_refit_version = job->refitsAt;
-        markTopologyChanged(st);
-        if (st.refitsSinceBuild) {
-            if (const int rc = uploadRefitInstances(ctx, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
-            if (const int rc = enqueueRefit(ctx, st, s, frontTarget(st), st.front)) return rc;
-        }
-        ARK_HIP(installedGeometry(ctx, st, s));
-        ARK_HIP(hipEventRecord(ctx->evRefit, s));
-        ARK_HIP(installDone(ctx, s));
-        ctx->refitPending = true;
-        ++st.version;
-        if (const int rc = refreshScene(ctx)) return rc;
+        return finishInstall(ctx, st, st.refitsSinceBuild, s);
     }
     return ARK_DDGI_OK;
 }
@@ -1713,12 +1635,8 @@ int worldStart(ArkDdgiCtx* ctx, hipStream_t s, bool gpu)
     auto job = std::make_unique<WorldJob>();
     job->version = st.version;
     job->refitsAt = st.refitCount;
-    job->snapRecords = st.triRecords;
-    job->classOf.resize(st.instHost.size());
-    for (size_t i = 0; i < st.instHost.size(); ++i) {
-        const uint32_t m = st.instHost[i].hit_mask;
-        job->classOf[i] = (m & ARK_RT_HIT_MASK_OPAQUE) ? 0 : (m & ARK_RT_HIT_MASK_MASKED) ? 1 : 2;
-    }
+    job->snapRecords = st.world.records;
+    job->classOf = instanceClasses(st);
     ARK_HIP(orderBegin(ctx, s));
     ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
     // half the host threads: the other half stays with the frames being enqueued meanwhile
@@ -1934,28 +1852,11 @@ void ark_ddgi_destroy(ArkDdgiCtx* ctx)
 
 const char* ark_ddgi_last_error(const ArkDdgiCtx* ctx) { return ctx ? ctx->lastError.c_str() : "null context"; }
 
-static int checkBvh8(ArkDdgiCtx* ctx, const std::vector<GpuBvh8Node>& allNodes, const std::vector<GpuTriangle>& allTris, const int32_t* roots, int nRoots)
-{
-    std::string why;
-    if (!checkBvh8Structure(allNodes, allTris, roots, nRoots, why)) return ctx->fail(ARK_DDGI_E_DEVICE, "%s", why.c_str());
-    return ARK_DDGI_OK;
-}
+namespace {
+// ark_ddgi_set_scene's steps, in the order they run
 
-int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
+int validateScene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
 {
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
-    if (!s || s->struct_size != sizeof(ArkDdgiScene)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiScene");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    // the previous scene goes first (its memory is reused), unless another context
-    // shares it; a failure below leaves the context without a scene
-    ctx->hasScene = false;
-    ctx->sceneStore.reset();
-    auto st = std::make_shared<SceneStore>();
-    st->device = ctx->device;
-    const auto t0 = std::chrono::steady_clock::now();
-    // validate
     for (uint32_t i = 0; i < s->instance_count; ++i) {
         const ArkRTInstance& inst = s->instances[i];
         if (inst.rt_mesh_index >= s->mesh_count) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "instance %u: rt_mesh_index out of range", i);
@@ -1967,24 +1868,37 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
     }
     if (s->spot_light_count > ARK_DDGI_MAX_SPOT_LIGHTS || (s->spot_light_count && !s->spot_lights))
         return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "at most %d spot lights (GpuScene.cpp:430)", ARK_DDGI_MAX_SPOT_LIGHTS);
-    // World-space triangles per hit-mask class (GpuScene.cpp:883-929: one TLAS
-    // instance per mesh segment; flattened here into one BVH per class).
-    std::vector<BuildTriangle> cls[3];
-    std::vector<GpuInstance> ginst(s->instance_count);
+    return ARK_DDGI_OK;
+}
+
+// An instance in the shading kernels' table: the rows of its transform, its facing flip
+// (det(ObjectToWorld) < 0), hit mask and material
+GpuInstance gpuInstance(const ArkRTInstance& inst, const ArkRTTriangleMesh& mesh)
+{
+    const float* M = inst.object_to_world;
+    const float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
+    GpuInstance g;
+    std::memset(&g, 0, sizeof(g));
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) g.normal_matrix[r * 4 + c] = M[r * 4 + c];
+    g.rt_mesh_index = static_cast<int32_t>(inst.rt_mesh_index);
+    g.flip_facing = det < 0.0f ? 1 : 0;
+    g.hit_mask = static_cast<int32_t>(inst.hit_mask);
+    g.material_index = mesh.material_index;
+    return g;
+}
+
+// World-space triangles per hit-mask class (GpuScene.cpp:883-929: one TLAS instance per
+// mesh segment; flattened here into one BVH per class) and the instance table.
+int flattenInstances(ArkDdgiCtx* ctx, const ArkDdgiScene* s, std::vector<BuildTriangle> cls[3], std::vector<GpuInstance>& ginst)
+{
+    ginst.resize(s->instance_count);
     for (uint32_t ii = 0; ii < s->instance_count; ++ii) {
         const ArkRTInstance& inst = s->instances[ii];
         const ArkRTTriangleMesh& m = s->meshes[inst.rt_mesh_index];
         const float* M = inst.object_to_world;
-        const float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
-        GpuInstance& g = ginst[ii];
-        std::memset(&g, 0, sizeof(g));
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) g.normal_matrix[r * 4 + c] = M[r * 4 + c];
-        g.rt_mesh_index = static_cast<int32_t>(inst.rt_mesh_index);
-        g.flip_facing = det < 0.0f ? 1 : 0;
-        g.hit_mask = static_cast<int32_t>(inst.hit_mask);
-        g.material_index = m.material_index;
-        const int c = (inst.hit_mask & ARK_RT_HIT_MASK_OPAQUE) ? 0 : (inst.hit_mask & ARK_RT_HIT_MASK_MASKED) ? 1 : 2;
+        const GpuInstance& g = ginst[ii] = gpuInstance(inst, m);
+        const int c = hit_mask_class(inst.hit_mask);
         for (uint32_t p = 0; p < inst.triangle_count; ++p) {
             BuildTriangle t;
             float* w[3] = { t.v0, t.v1, t.v2 };
@@ -2003,80 +1917,12 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
             cls[c].push_back(t);
         }
     }
-    BvhBuildOptions opt;
-    opt.max_leaf_size = kBvh8MaxLeafSize;
-    {
-        float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-        for (int c = 0; c < 3; ++c)
-            for (const BuildTriangle& t : cls[c])
-                for (const float* v : { t.v0, t.v1, t.v2 })
-                    for (int a = 0; a < 3; ++a) {
-                        lo[a] = std::min(lo[a], v[a]);
-                        hi[a] = std::max(hi[a], v[a]);
-                    }
-        opt.inflate_abs = bvh8_inflation_box(lo, hi); // one inflation for all classes (shadow rays test all)
-    }
-    // host threads for the build (ArkDdgiDesc.build_threads; 0: the box's CPU share per
-    // GPU, 16 cores)
-    opt.threads = ctx->desc.build_threads > 0 ? ctx->desc.build_threads : 16;
-    // BVH2 -> BVH8 child selection: SAH-optimal (Ylitie et al. 2017 DP) with the default
-    // node / triangle costs (a lower triangle cost and the greedy collapse measured no
-    // better, DESIGN.md §3)
-    Bvh8CollapseOptions copt;
-    copt.threads = opt.threads;
-    // the sun's light-space BVH input, before the class builds free their triangles; the
-    // build itself on its own thread beside the class builds (each build's top levels
-    // leave cores idle: C4 setup 13.5 -> s)
-    const bool sunBvh = s->has_directional_light && ctx->sunBvh != 0;
-    SunBvhInput sunIn;
-    Bvh8BuildResult r; // the sun's
-    bool sunBuilt = false, sunOk = true;
-    float sunBuildMs = 0.0f;
-    struct Joiner {
-        std::thread t;
-        ~Joiner()
-        {
-            if (t.joinable()) t.join();
-        }
-    } sunThread;
-    if (sunBvh) {
-        const auto ts0 = std::chrono::steady_clock::now();
-        sun_frame(s->directional_light.world_space_direction, sunIn.frame);
-        for (int c = 0; c < 3; ++c) sun_add_triangles(sunIn, cls[c], opt.threads);
-        sunBuilt = !sunIn.tris.empty();
-        if (sunBuilt)
-            sunThread.t = std::thread([&sunIn, &opt, &copt, &r, &sunOk, &sunBuildMs, ts0] {
-                sunOk = build_sun_bvh(sunIn, opt, copt, r);
-                sunBuildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
-            });
-    }
-    std::vector<GpuBvh8Node> allNodes;
-    std::vector<GpuTriangle> allTris;
-    int32_t roots[3] = { -1, -1, -1 };
-    uint32_t opaqueNodes = 0;
-    uint32_t maxDepth = 0, maxLeaf = 0;
-    uint64_t triangles = 0;
-    float sah = 0.0f;
-    for (int c = 0; c < 3; ++c) {
-        if (cls[c].empty()) continue;
-        BvhBuildResult r2 = build_bvh(cls[c], opt, 0u, 0u);
-        std::vector<BuildTriangle>().swap(cls[c]);
-        if (r2.max_leaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) return ctx->fail(ARK_DDGI_E_DEVICE, "BVH2 leaf of %u triangles", r2.max_leaf);
-        if (c == 0) sah = r2.sah_cost;
-        maxLeaf = std::max(maxLeaf, r2.max_leaf);
-        Bvh8BuildResult r = collapse_bvh8(r2, static_cast<uint32_t>(allNodes.size()), static_cast<uint32_t>(allTris.size()), copt);
-        roots[c] = static_cast<int32_t>(allNodes.size());
-        if (c == 0) opaqueNodes = static_cast<uint32_t>(r.nodes.size());
-        maxDepth = std::max(maxDepth, r.max_depth);
-        triangles += r.triangles;
-        allNodes.insert(allNodes.end(), r.nodes.begin(), r.nodes.end());
-        allTris.insert(allTris.end(), r.tris.begin(), r.tris.end());
-    }
-    if (allNodes.size() >= (1ull << 31) || allTris.size() >= (1ull << 31)) return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "scene too large for 31-bit BVH indices");
-    if (const int rc = checkBvh8(ctx, allNodes, allTris, roots, 3)) return rc;
-    // textures: decoded to float4 texels (sRGB EOTF per texel), + trailing 1x1 white
-    std::vector<GpuTextureInfo> infos;
-    std::vector<float> texels;
+    return ARK_DDGI_OK;
+}
+
+// textures: decoded to float4 texels (sRGB EOTF per texel), + trailing 1x1 white
+int decodeTextures(ArkDdgiCtx* ctx, const ArkDdgiScene* s, std::vector<GpuTextureInfo>& infos, std::vector<float>& texels)
+{
     for (uint32_t i = 0; i <= s->texture_count; ++i) {
         GpuTextureInfo ti {};
         ti.texel_offset = texels.size() / 4;
@@ -2114,88 +1960,19 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
         }
         infos.push_back(ti);
     }
-    std::vector<GpuSpotLight> gspots(s->spot_light_count);
-    for (uint32_t i = 0; i < s->spot_light_count; ++i) gspots[i] = gpuSpotLight(s->spot_lights[i]);
-    int rc;
-    // nodes and triangles in ONE allocation (triangles after the nodes, 256-B aligned):
-    // the traversal addresses both through one buffer resource with a per-lane
-    // byte offset (32 bits: the pair must stay below 4 GiB)
-    const size_t nodeBytes = allNodes.size() * sizeof(GpuBvh8Node);
-    const size_t triOffset = (nodeBytes + 255) & ~static_cast<size_t>(255);
-    const size_t triBytes = (allTris.size() + 1) * sizeof(GpuTriangle); // + padding record
-    if (triOffset + triBytes >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "BVH nodes + triangles exceed 4 GiB");
-    ARK_HIP(st->nodes.alloc(triOffset + triBytes));
-    ARK_HIP(hipMemcpy(st->nodes.ptr, allNodes.data(), nodeBytes, hipMemcpyHostToDevice));
-    allTris.push_back(GpuTriangle {}); // padding: a five-load fetch of the last triangle stays in bounds (ARK_FETCH5)
-    ARK_HIP(hipMemcpy(static_cast<char*>(st->nodes.ptr) + triOffset, allTris.data(), allTris.size() * sizeof(GpuTriangle), hipMemcpyHostToDevice));
-    allTris.pop_back();
-    uint64_t sunNodeCount = 0;
-    uint32_t sunMaxDepth = 0;
-    size_t sunTriOffset = 0;
-    if (sunThread.t.joinable()) sunThread.t.join();
-    const auto ts0 = std::chrono::steady_clock::now();
-    if (sunBuilt) {
-        if (!sunOk) return ctx->fail(ARK_DDGI_E_DEVICE, "sun BVH2 leaf over %d triangles", kBvh8MaxLeafSize);
-        const int32_t sroot = 0;
-        if (const int rc2 = checkBvh8(ctx, r.nodes, r.tris, &sroot, 1)) return rc2;
-        // by cost unless forced: sample sun shadow rays through both structures on the host
-        const float* sd = s->directional_light.world_space_direction;
-        const float dd = sd[0] * sd[0] + sd[1] * sd[1] + sd[2] * sd[2];
-        const float isc = 1.0f / std::sqrt(dd);
-        const float L[3] = { -(sd[0] * isc), -(sd[1] * isc), -(sd[2] * isc) };
-        std::vector<float> origins;
-        sun_sample_origins(allTris, L, 4096u, origins);
-        st->sunCostWorld = static_cast<float>(sun_shadow_cost(allNodes, allTris, roots, 3, nullptr, L, origins));
-        st->sunCostLight = static_cast<float>(sun_shadow_cost(r.nodes, r.tris, &sroot, 1, sunIn.frame, L, origins));
-    }
-    const uint32_t worldDepth = maxDepth;
-    if (sunBuilt && (ctx->sunBvh == 1 || sun_bvh_pays(st->sunCostWorld, st->sunCostLight))) {
-        const size_t nb = r.nodes.size() * sizeof(GpuBvh8Node);
-        sunTriOffset = (nb + 255) & ~static_cast<size_t>(255);
-        // what its refits need (enqueueRefit): the level order, the build's inflation and
-        // frame, the record count (padding excluded)
-        {
-            const int32_t sroot = 0;
-            std::vector<uint32_t> order;
-            if (!bvhLevelOrder(r.nodes.data(), r.nodes.size(), &sroot, 1, order, st->sunLevelOffsets)) return ctx->fail(ARK_DDGI_E_DEVICE, "sun BVH: a node outside it");
-            if ((rc = upload(ctx, st->sunRefitOrder, order.data(), order.size())) != 0) return rc;
-            ARK_HIP(st->sunRefitBoxes.alloc(std::max<size_t>(16, r.nodes.size() * 6 * sizeof(float) * 5 / 4)));
-            st->sunTriRecords = r.tris.size();
-            st->sunInflateAbs = sunIn.inflateAbs;
-            for (int i = 0; i < 3; ++i)
-                for (int k = 0; k < 3; ++k) st->sunFrameD[i * 3 + k] = sunIn.frame[i][k];
-            st->sunDepth = r.max_depth;
-        }
-        r.tris.push_back(GpuTriangle {}); // padding record (five-load fetch)
-        ARK_HIP(st->sunNodes.alloc(sunTriOffset + r.tris.size() * sizeof(GpuTriangle)));
-        ARK_HIP(hipMemcpy(st->sunNodes.ptr, r.nodes.data(), nb, hipMemcpyHostToDevice));
-        ARK_HIP(hipMemcpy(static_cast<char*>(st->sunNodes.ptr) + sunTriOffset, r.tris.data(), r.tris.size() * sizeof(GpuTriangle), hipMemcpyHostToDevice));
-        sunNodeCount = r.nodes.size();
-        // the sun's traversal pushes onto the same spill area (its depth counts)
-        maxDepth = std::max(maxDepth, r.max_depth);
-        sunMaxDepth = r.max_depth;
-    }
-    sunBuildMs += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
-    std::vector<GpuTriangle>().swap(sunIn.world);
-    if ((rc = upload(ctx, st->indices, s->indices, s->index_count)) != 0) return rc;
-    if ((rc = upload(ctx, st->vertices, reinterpret_cast<const float*>(s->vertices), s->vertex_count * 9)) != 0) return rc;
-    if ((rc = upload(ctx, st->positions, s->positions, s->vertex_count * 3)) != 0) return rc;
-    st->instHost.assign(s->instances, s->instances + s->instance_count);
-    // the transforms both geometry copies hold (the back one is made at the first refit)
-    st->xf[0].resize(s->instance_count);
-    for (uint32_t ii = 0; ii < s->instance_count; ++ii) std::memcpy(st->xf[0][ii].data(), s->instances[ii].object_to_world, sizeof(float) * 12);
-    st->xf[1] = st->xf[2] = st->xf[0];
-    st->spare[0].slot = 1;
-    st->spare[1].slot = 2;
-    st->meshHost.assign(s->meshes, s->meshes + s->mesh_count);
-    // every instance's object-space box (refitInflations)
-    st->instObjBox.assign(s->instance_count, { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY });
+    return ARK_DDGI_OK;
+}
+
+// every instance's object-space box (refitInflations)
+void instanceObjectBoxes(const ArkDdgiScene* s, int threads, std::vector<std::array<float, 6>>& boxes)
+{
+    boxes.assign(s->instance_count, { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY });
     for (uint32_t ii = 0; ii < s->instance_count; ++ii) {
         const ArkRTInstance& in = s->instances[ii];
         const ArkRTTriangleMesh& mesh = s->meshes[in.rt_mesh_index];
-        std::array<float, 6>& box = st->instObjBox[ii];
+        std::array<float, 6>& box = boxes[ii];
         std::mutex mu;
-        parallelFor(static_cast<size_t>(in.triangle_count) * 3u, opt.threads, [&](size_t b, size_t e) {
+        parallelFor(static_cast<size_t>(in.triangle_count) * 3u, threads, [&](size_t b, size_t e) {
             float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
             for (size_t k = b; k < e; ++k) {
                 const float* P = s->positions + (static_cast<int64_t>(mesh.first_vertex) + s->indices[static_cast<size_t>(mesh.first_index) + k]) * 3;
@@ -2211,89 +1988,186 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
             }
         });
     }
+}
+
+// per-triangle shading records (GpuTriangle order, 64 B): the three vertex normals, the
+// instance and the three UVs, copied from the vertex pool, so the shading and shadow-ray
+// kernels reach a hit's surface in one fetch instead of instance -> mesh -> indices ->
+// vertices
+void shadingRecords(const ArkDdgiScene* s, const std::vector<GpuTriangle>& tris, int threads, std::vector<float>& tn)
+{
+    tn.assign(tris.size() * 16, 0.0f);
+    parallelFor(tris.size(), threads, [&](size_t b, size_t e) {
+        for (size_t t = b; t < e; ++t) {
+            if (isHoleTriangle(tris[t])) continue; // never hit: no record
+            uint32_t inst, prim;
+            std::memcpy(&inst, &tris[t].t2[1], 4);
+            std::memcpy(&prim, &tris[t].t2[2], 4);
+            const ArkRTTriangleMesh& mesh = s->meshes[s->instances[inst].rt_mesh_index];
+            float* o = tn.data() + t * 16;
+            for (int q = 0; q < 3; ++q) {
+                const uint32_t idx = s->indices[static_cast<size_t>(mesh.first_index) + 3u * prim + q];
+                const float* v = reinterpret_cast<const float*>(s->vertices) + (static_cast<size_t>(mesh.first_vertex) + idx) * 9;
+                for (int k = 0; k < 3; ++k) o[q * 3 + k] = v[2 + k];
+                o[10 + 2 * q] = v[0];
+                o[11 + 2 * q] = v[1];
+            }
+            std::memcpy(o + 9, &inst, 4);
+        }
+    });
+    if (tn.empty()) tn.assign(16, 0.0f);
+}
+} // namespace
+
+int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    ctx->pipeReady = false; // the next update's traversal waits for this
+    if (!s || s->struct_size != sizeof(ArkDdgiScene)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiScene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    // the previous scene goes first (its memory is reused), unless another context
+    // shares it; a failure below leaves the context without a scene
+    ctx->hasScene = false;
+    ctx->sceneStore.reset();
+    auto st = std::make_shared<SceneStore>();
+    st->device = ctx->device;
+    const auto t0 = std::chrono::steady_clock::now();
+    int rc;
+    if ((rc = validateScene(ctx, s)) != 0) return rc;
+    std::vector<BuildTriangle> cls[3];
+    std::vector<GpuInstance> ginst;
+    if ((rc = flattenInstances(ctx, s, cls, ginst)) != 0) return rc;
+    // host threads for the build (ArkDdgiDesc.build_threads; 0: the box's CPU share per
+    // GPU, 16 cores)
+    BvhBuildOptions opt;
+    opt.threads = ctx->desc.build_threads > 0 ? ctx->desc.build_threads : 16;
+    // BVH2 -> BVH8 child selection: SAH-optimal (Ylitie et al. 2017 DP) with the default
+    // node / triangle costs (a lower triangle cost and the greedy collapse measured no
+    // better, DESIGN.md §3)
+    Bvh8CollapseOptions copt;
+    copt.threads = opt.threads;
+    // the sun's light-space BVH input, before the class builds free their triangles; the
+    // build itself on its own thread beside the class builds (each build's top levels
+    // leave cores idle: C4 setup 13.5 -> s)
+    const bool sunBvh = s->has_directional_light && ctx->sunBvh != 0;
+    SunBvhInput sunIn;
+    Bvh8BuildResult r; // the sun's
+    bool sunBuilt = false, sunOk = true;
+    float sunBuildMs = 0.0f;
+    struct Joiner {
+        std::thread t;
+        ~Joiner()
+        {
+            if (t.joinable()) t.join();
+        }
+    } sunThread;
+    if (sunBvh) {
+        const auto ts0 = std::chrono::steady_clock::now();
+        sun_frame(s->directional_light.world_space_direction, sunIn.frame);
+        for (int c = 0; c < 3; ++c) sun_add_triangles(sunIn, cls[c], opt.threads);
+        sunBuilt = !sunIn.tris.empty();
+        if (sunBuilt)
+            sunThread.t = std::thread([&sunIn, &opt, &copt, &r, &sunOk, &sunBuildMs, ts0] {
+                sunOk = build_sun_bvh(sunIn, opt, copt, r);
+                sunBuildMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
+            });
+    }
+    WorldBvh8 w;
+    std::string why;
+    if (!build_world_bvh8(cls, opt, copt, w, why)) return ctx->fail(w.tooLarge ? ARK_DDGI_E_UNSUPPORTED : ARK_DDGI_E_DEVICE, "%s", why.c_str());
+    std::vector<GpuTextureInfo> infos;
+    std::vector<float> texels;
+    if ((rc = decodeTextures(ctx, s, infos, texels)) != 0) return rc;
+    std::vector<GpuSpotLight> gspots(s->spot_light_count);
+    for (uint32_t i = 0; i < s->spot_light_count; ++i) gspots[i] = gpuSpotLight(s->spot_lights[i]);
+    // (the traversal's 32-bit byte offset: nodes and records must stay below 4 GiB)
+    if (DeviceBvh::bytesFor(w.nodes.size(), w.tris.size()) >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "BVH nodes + triangles exceed 4 GiB");
+    ARK_HIP(uploadBvh(w.nodes, w.tris, nullptr, st->world));
+    st->world.depth = w.depth;
+    st->world.inflateAbs = w.inflateAbs;
+    if (sunThread.t.joinable()) sunThread.t.join();
+    const auto ts0 = std::chrono::steady_clock::now();
+    const int32_t sroot = 0;
+    if (sunBuilt) {
+        if (!sunOk) return ctx->fail(ARK_DDGI_E_DEVICE, "sun BVH2 leaf over %d triangles", kBvh8MaxLeafSize);
+        if (!checkBvh8Structure(r.nodes, r.tris, &sroot, 1, why)) return ctx->fail(ARK_DDGI_E_DEVICE, "%s", why.c_str());
+        // by cost unless forced: sample sun shadow rays through both structures on the host
+        const float* sd = s->directional_light.world_space_direction;
+        const float dd = sd[0] * sd[0] + sd[1] * sd[1] + sd[2] * sd[2];
+        const float isc = 1.0f / std::sqrt(dd);
+        const float L[3] = { -(sd[0] * isc), -(sd[1] * isc), -(sd[2] * isc) };
+        std::vector<float> origins;
+        sun_sample_origins(w.tris, L, 4096u, origins);
+        st->sunCostWorld = static_cast<float>(sun_shadow_cost(w.nodes, w.tris, w.roots, 3, nullptr, L, origins));
+        st->sunCostLight = static_cast<float>(sun_shadow_cost(r.nodes, r.tris, &sroot, 1, sunIn.frame, L, origins));
+    }
+    st->sunArgs.sun_root = -1;
+    if (sunBuilt && (ctx->sunBvh == 1 || sun_bvh_pays(st->sunCostWorld, st->sunCostLight))) {
+        DeviceBvh sb;
+        std::vector<uint32_t> order;
+        if (!bvhLevelOrder(r.nodes.data(), r.nodes.size(), &sroot, 1, order, sb.levelOffsets)) return ctx->fail(ARK_DDGI_E_DEVICE, "sun BVH: a node outside it");
+        sb.depth = r.max_depth;
+        sb.inflateAbs = sunIn.inflateAbs;
+        if ((rc = installSunBvh(ctx, *st, sb, &r, order, &sunIn.frame[0][0], s->directional_light.world_space_direction, nullptr)) != 0) return rc;
+    }
+    sunBuildMs += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
+    std::vector<GpuTriangle>().swap(sunIn.world);
+    if ((rc = upload(ctx, st->indices, s->indices, s->index_count)) != 0) return rc;
+    if ((rc = upload(ctx, st->vertices, reinterpret_cast<const float*>(s->vertices), s->vertex_count * 9)) != 0) return rc;
+    if ((rc = upload(ctx, st->positions, s->positions, s->vertex_count * 3)) != 0) return rc;
+    st->instHost.assign(s->instances, s->instances + s->instance_count);
+    // the transforms both geometry copies hold (the back one is made at the first refit)
+    st->xf[0].resize(s->instance_count);
+    for (uint32_t ii = 0; ii < s->instance_count; ++ii) std::memcpy(st->xf[0][ii].data(), s->instances[ii].object_to_world, sizeof(float) * 12);
+    st->xf[1] = st->xf[2] = st->xf[0];
+    st->spare[0].slot = 1;
+    st->spare[1].slot = 2;
+    st->meshHost.assign(s->meshes, s->meshes + s->mesh_count);
+    instanceObjectBoxes(s, opt.threads, st->instObjBox);
     if ((rc = upload(ctx, st->meshes, s->meshes, s->mesh_count)) != 0) return rc;
     if ((rc = upload(ctx, st->materials, s->materials, s->material_count)) != 0) return rc;
     if ((rc = upload(ctx, st->instances, ginst.data(), ginst.size())) != 0) return rc;
     if ((rc = upload(ctx, st->texInfos, infos.data(), infos.size())) != 0) return rc;
     if ((rc = upload(ctx, st->texels, texels.data(), texels.size())) != 0) return rc;
     {
-        // per-triangle shading records (GpuTriangle order, 64 B): the three vertex
-        // normals, the instance and the three UVs, copied from the vertex pool, so
-        // the shading and shadow-ray kernels reach a hit's surface in one fetch
-        // instead of instance -> mesh -> indices -> vertices
-        std::vector<float> tn(allTris.size() * 16, 0.0f);
-        parallelFor(allTris.size(), opt.threads, [&](size_t b, size_t e) {
-            for (size_t t = b; t < e; ++t) {
-                if (isHoleTriangle(allTris[t])) continue; // never hit: no record
-                uint32_t inst, prim;
-                std::memcpy(&inst, &allTris[t].t2[1], 4);
-                std::memcpy(&prim, &allTris[t].t2[2], 4);
-                const ArkRTTriangleMesh& mesh = s->meshes[s->instances[inst].rt_mesh_index];
-                float* o = tn.data() + t * 16;
-                for (int q = 0; q < 3; ++q) {
-                    const uint32_t idx = s->indices[static_cast<size_t>(mesh.first_index) + 3u * prim + q];
-                    const float* v = reinterpret_cast<const float*>(s->vertices) + (static_cast<size_t>(mesh.first_vertex) + idx) * 9;
-                    for (int k = 0; k < 3; ++k) o[q * 3 + k] = v[2 + k];
-                    o[10 + 2 * q] = v[0];
-                    o[11 + 2 * q] = v[1];
-                }
-                std::memcpy(o + 9, &inst, 4);
-            }
-        });
-        if (tn.empty()) tn.assign(16, 0.0f);
+        std::vector<float> tn;
+        shadingRecords(s, w.tris, opt.threads, tn);
         if ((rc = upload(ctx, st->triNormals, tn.data(), tn.size())) != 0) return rc;
     }
     SceneArgs& sc = st->args;
-    sc.nodes = st->nodes.as<GpuBvh8Node>();
-    sc.tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st->nodes.ptr) + triOffset);
-    sc.tri_byte_offset = static_cast<uint32_t>(triOffset);
+    setWorldArgs(*st);
+    setWorldRoots(*st, w.roots, w.opaqueNodes);
     sc.tri_normals = st->triNormals.as<float4>();
-    sc.root_opaque = roots[0];
-    sc.root_masked = roots[1];
-    sc.root_blend = roots[2];
-    sc.opaque_nodes = opaqueNodes;
     sc.texture_count = static_cast<int32_t>(s->texture_count);
     sc.indices = st->indices.as<uint32_t>();
     sc.vertices = st->vertices.as<float>();
     sc.meshes = st->meshes.as<ArkRTTriangleMesh>();
     sc.materials = st->materials.as<ArkShaderMaterial>();
-    sc.instances = st->instances.as<GpuInstance>();
     sc.tex_infos = st->texInfos.as<GpuTextureInfo>();
     sc.texels = st->texels.as<float4>();
     sc.white_texture = static_cast<int32_t>(s->texture_count);
     sc.env_texture = (s->environment_texture >= 0 && static_cast<uint32_t>(s->environment_texture) < s->texture_count) ? s->environment_texture : sc.white_texture;
+    sc.sun_root = -1;
     // lights: the scene's are each context's until ark_ddgi_set_lights (deriveSceneArgs)
     st->hasSunScene = s->has_directional_light ? 1 : 0;
     st->sunScene = s->directional_light;
     st->spotsScene = std::move(gspots);
-    sc.sun_root = -1;
-    st->sunArgs.sun_root = -1;
-    if (sunNodeCount) {
-        st->sunArgs.sun_nodes = st->sunNodes.as<GpuBvh8Node>();
-        st->sunArgs.sun_tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st->sunNodes.ptr) + sunTriOffset);
-        st->sunArgs.sun_root = 0;
-        for (int r = 0; r < 3; ++r)
-            for (int k = 0; k < 3; ++k) st->sunArgs.sun_frame[r * 3 + k] = static_cast<float>(sunIn.frame[r][k]);
-        for (int k = 0; k < 3; ++k) st->sunDirBuilt[k] = s->directional_light.world_space_direction[k];
-    }
-    st->sunBvhNodes = sunNodeCount;
-    st->sunWanted = sunNodeCount > 0;
+    st->sunWanted = st->sun.nodeCount > 0;
     st->buildThreads = opt.threads;
-    st->bvhMaxDepth = maxDepth;
-    st->worldDepth = worldDepth;
-    st->inflateAbs = opt.inflate_abs;
-    st->triRecords = allTris.size();
+    // the sun's traversal pushes onto the same spill area (its depth counts)
+    st->bvhMaxDepth = std::max(st->world.depth, st->sun.depth);
     const auto t1 = std::chrono::steady_clock::now();
-    st->bvhStats.node_count = allNodes.size();
-    st->bvhStats.triangle_count = triangles;
-    st->bvhStats.max_depth = maxDepth;
-    st->bvhStats.max_leaf_size = maxLeaf;
-    st->bvhStats.sah_cost = sah;
+    st->bvhStats.node_count = w.nodes.size();
+    st->bvhStats.triangle_count = w.triangles;
+    st->bvhStats.max_depth = st->bvhMaxDepth;
+    st->bvhStats.max_leaf_size = w.maxLeaf;
+    st->bvhStats.sah_cost = w.sah;
     st->bvhStats.build_ms = std::chrono::duration<float, std::milli>(t1 - t0).count();
-    st->bvhStats.node_bytes = allNodes.size() * sizeof(GpuBvh8Node);
-    st->bvhStats.triangle_bytes = allTris.size() * sizeof(GpuTriangle);
-    st->bvhStats.sun_node_count = sunNodeCount;
-    st->bvhStats.sun_max_depth = sunMaxDepth;
+    st->bvhStats.node_bytes = w.nodes.size() * sizeof(GpuBvh8Node);
+    st->bvhStats.triangle_bytes = w.tris.size() * sizeof(GpuTriangle);
+    st->bvhStats.sun_node_count = st->sun.nodeCount;
+    st->bvhStats.sun_max_depth = st->sun.depth;
     st->bvhStats.sun_cost_world = st->sunCostWorld;
     st->bvhStats.sun_cost_light = st->sunCostLight;
     st->bvhStats.sun_build_ms = sunBuildMs;
@@ -2373,15 +2247,16 @@ namespace {
 // first, and the refit's work buffers (a topology download: refits never change it)
 int prepareRefit(ArkDdgiCtx* ctx, SceneStore& st)
 {
-    const uint64_t n = st.bvhStats.node_count;
+    DeviceBvh& w = st.world;
+    const uint64_t n = w.nodeCount;
     std::vector<GpuBvh8Node> h(n);
-    if (n) ARK_HIP(hipMemcpy(h.data(), st.nodes.ptr, n * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
+    if (n) ARK_HIP(hipMemcpy(h.data(), w.buf.ptr, n * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
     const int32_t roots[3] = { st.args.root_opaque, st.args.root_masked, st.args.root_blend };
     std::vector<uint32_t> order;
-    if (!bvhLevelOrder(h.data(), n, roots, 3, order, st.levelOffsets)) return ctx->fail(ARK_DDGI_E_DEVICE, "refit: a node outside the BVH");
+    if (!bvhLevelOrder(h.data(), n, roots, 3, order, w.levelOffsets)) return ctx->fail(ARK_DDGI_E_DEVICE, "refit: a node outside the BVH");
     int rc;
-    if ((rc = upload(ctx, st.refitOrder, order.data(), order.size())) != 0) return rc;
-    ARK_HIP(st.refitBoxes.alloc(std::max<size_t>(16, n * 6 * sizeof(float))));
+    if ((rc = upload(ctx, w.order, order.data(), order.size())) != 0) return rc;
+    ARK_HIP(w.boxes.alloc(std::max<size_t>(16, n * 6 * sizeof(float))));
     return ARK_DDGI_OK;
 }
 } // namespace
@@ -2391,27 +2266,21 @@ namespace {
 // spare: the kernel views follow.
 void rotateGeometry(SceneStore& st)
 {
-    const bool sun = st.sunArgs.sun_root >= 0 && st.sunNodes.ptr;
-    const size_t sunTriOffset = sun ? static_cast<size_t>(reinterpret_cast<const char*>(st.sunArgs.sun_tris) - static_cast<const char*>(st.sunNodes.ptr)) : 0;
+    const bool sun = st.sunArgs.sun_root >= 0 && st.sun.buf.ptr;
     SceneStore::Spare old;
-    old.nodes = st.nodes;
-    old.sunNodes = st.sunNodes;
+    old.world = st.world.buf;
+    old.sun = st.sun.buf;
     old.instances = st.instances;
     old.valid = true;
     old.slot = st.front;
-    st.nodes = st.spare[0].nodes;
-    st.sunNodes = st.spare[0].sunNodes;
+    st.world.buf = st.spare[0].world;
+    st.sun.buf = st.spare[0].sun;
     st.instances = st.spare[0].instances;
     st.front = st.spare[0].slot;
     st.spare[0] = st.spare[1];
     st.spare[1] = old;
-    st.args.nodes = st.nodes.as<GpuBvh8Node>();
-    st.args.tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st.nodes.ptr) + st.args.tri_byte_offset);
-    st.args.instances = st.instances.as<GpuInstance>();
-    if (sun) {
-        st.sunArgs.sun_nodes = st.sunNodes.as<GpuBvh8Node>();
-        st.sunArgs.sun_tris = reinterpret_cast<const GpuTriangle*>(static_cast<const char*>(st.sunNodes.ptr) + sunTriOffset);
-    }
+    setWorldArgs(st);
+    if (sun) setSunArgs(st);
 }
 } // namespace
 
@@ -2440,7 +2309,7 @@ int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances
     const bool shared = ctx->sceneStore.use_count() > 1;
     if (shared) ARK_HIP(hipDeviceSynchronize());
     int rc;
-    if (st.levelOffsets.empty() && (rc = prepareRefit(ctx, st)) != 0) return rc;
+    if (st.world.levelOffsets.empty() && (rc = prepareRefit(ctx, st)) != 0) return rc;
     // everything this context enqueued so far ends with its last operation (orderBegin
     // chains the others into it): the front copy's readers among them. Events that mark
     // that point are recorded on `s` behind it (orderBegin) - not on the last operation's
@@ -2450,13 +2319,13 @@ int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances
     ARK_HIP(orderBegin(ctx, s));
     const hipStream_t last = s;
     // a light-space sun BVH without a refit order (none recorded) cannot follow: dropped
-    if (st.sunArgs.sun_root >= 0 && st.sunLevelOffsets.empty()) {
+    if (st.sunArgs.sun_root >= 0 && st.sun.levelOffsets.empty()) {
         st.sunArgs.sun_root = -1;
         st.sunArgs.sun_nodes = nullptr;
         st.sunArgs.sun_tris = nullptr;
-        ARK_HIP(retireBuffer(st, st.sunNodes, last));
+        ARK_HIP(retireBuffer(st, st.sun.buf, last));
         ARK_HIP(dropSpares(st, last));
-        st.sunBvhNodes = 0;
+        st.sun.nodeCount = 0;
         st.bvhStats.sun_node_count = 0;
         st.bvhStats.sun_max_depth = 0;
     }
@@ -2485,8 +2354,8 @@ int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances
             }
             return hipMemcpyAsync(dst.ptr, src.ptr, src.bytes, hipMemcpyDeviceToDevice, rs);
         };
-        ARK_HIP(copy(tgt.nodes, st.nodes));
-        ARK_HIP(copy(tgt.sunNodes, st.sunNodes));
+        ARK_HIP(copy(tgt.world, st.world.buf));
+        ARK_HIP(copy(tgt.sun, st.sun.buf));
         ARK_HIP(copy(tgt.instances, st.instances));
         st.xf[ts] = st.xf[fs];
         st.inflCopy[ts][0] = st.inflCopy[fs][0];
@@ -2495,22 +2364,10 @@ int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances
     }
     // the instance table of the shading kernels (set_scene's determinant and rows)
     std::vector<GpuInstance> ginst(count);
-    for (uint32_t ii = 0; ii < count; ++ii) {
-        const float* M = instances[ii].object_to_world;
-        const float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
-        const ArkRTTriangleMesh& mesh = st.meshHost[instances[ii].rt_mesh_index];
-        GpuInstance& g = ginst[ii];
-        std::memset(&g, 0, sizeof(g));
-        for (int r = 0; r < 3; ++r)
-            for (int c = 0; c < 3; ++c) g.normal_matrix[r * 4 + c] = M[r * 4 + c];
-        g.rt_mesh_index = static_cast<int32_t>(instances[ii].rt_mesh_index);
-        g.flip_facing = det < 0.0f ? 1 : 0;
-        g.hit_mask = static_cast<int32_t>(instances[ii].hit_mask);
-        g.material_index = mesh.material_index;
-    }
+    for (uint32_t ii = 0; ii < count; ++ii) ginst[ii] = gpuInstance(instances[ii], st.meshHost[instances[ii].rt_mesh_index]);
     ARK_HIP(stagedUpload(st, tgt.instances.ptr, ginst.data(), count * sizeof(GpuInstance), rs));
     if ((rc = uploadRefitInstances(ctx, st, instances, count, &st.xf[ts], rs)) != 0) return rc;
-    if ((rc = enqueueRefit(ctx, st, rs, spareTarget(tgt), ts)) != 0) return rc;
+    if ((rc = enqueueRefit(ctx, st, rs, tgt.world, tgt.sun, ts)) != 0) return rc;
     ARK_HIP(hipEventRecord(ctx->evRefit, rs));
     if (shared) ARK_HIP(hipStreamSynchronize(rs));
     // the refitted copy becomes the front one
@@ -2550,11 +2407,11 @@ int ark_ddgi_debug_scene_digest(ArkDdgiCtx* ctx, uint64_t* out)
         for (unsigned char c : b) h = (h ^ c) * 1099511628211ull;
         return e;
     };
-    ARK_HIP(digest(st.args.nodes, st.bvhStats.node_count * sizeof(GpuBvh8Node), out[0]));
-    ARK_HIP(digest(st.args.tris, st.triRecords * sizeof(GpuTriangle), out[1]));
+    ARK_HIP(digest(st.args.nodes, st.world.nodeCount * sizeof(GpuBvh8Node), out[0]));
+    ARK_HIP(digest(st.args.tris, st.world.records * sizeof(GpuTriangle), out[1]));
     const bool sun = st.sunArgs.sun_root >= 0;
-    ARK_HIP(digest(sun ? st.sunArgs.sun_nodes : nullptr, st.sunBvhNodes * sizeof(GpuBvh8Node), out[2]));
-    ARK_HIP(digest(sun ? st.sunArgs.sun_tris : nullptr, st.sunTriRecords * sizeof(GpuTriangle), out[3]));
+    ARK_HIP(digest(sun ? st.sunArgs.sun_nodes : nullptr, st.sun.nodeCount * sizeof(GpuBvh8Node), out[2]));
+    ARK_HIP(digest(sun ? st.sunArgs.sun_tris : nullptr, st.sun.records * sizeof(GpuTriangle), out[3]));
     if (!sun) out[2] = out[3] = 0;
     return ARK_DDGI_OK;
 }
@@ -2566,17 +2423,13 @@ int ark_ddgi_debug_world_bvh_check(ArkDdgiCtx* ctx, uint64_t* out)
     ARK_HIP(hipSetDevice(ctx->device));
     ARK_HIP(hipDeviceSynchronize());
     const SceneStore& st = *ctx->sceneStore;
-    std::vector<GpuBvh8Node> nodes(st.bvhStats.node_count);
-    std::vector<GpuTriangle> tris(st.triRecords);
+    std::vector<GpuBvh8Node> nodes(st.world.nodeCount);
+    std::vector<GpuTriangle> tris(st.world.records);
     std::vector<uint32_t> order(nodes.size());
     if (!nodes.empty()) ARK_HIP(hipMemcpy(nodes.data(), st.args.nodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
     if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), st.args.tris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
-    if (!order.empty() && st.refitOrder.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.refitOrder.ptr, order.size() * 4, hipMemcpyDeviceToHost));
-    std::vector<int> classOf(st.instHost.size());
-    for (size_t i = 0; i < st.instHost.size(); ++i) {
-        const uint32_t m = st.instHost[i].hit_mask;
-        classOf[i] = (m & ARK_RT_HIT_MASK_OPAQUE) ? 0 : (m & ARK_RT_HIT_MASK_MASKED) ? 1 : 2;
-    }
+    if (!order.empty() && st.world.order.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.world.order.ptr, order.size() * 4, hipMemcpyDeviceToHost));
+    const std::vector<int> classOf = instanceClasses(st);
     const int32_t roots[3] = { st.args.root_opaque, st.args.root_masked, st.args.root_blend };
     Bvh8CheckResult c = check_bvh8_full(nodes, tris, roots, 3, &classOf, nullptr);
     std::string why;
@@ -2590,7 +2443,7 @@ int ark_ddgi_debug_world_bvh_check(ArkDdgiCtx* ctx, uint64_t* out)
     std::vector<uint32_t> wantOrder, wantOffsets;
     if (!bvhLevelOrder(nodes.data(), nodes.size(), roots, 3, wantOrder, wantOffsets)) {
         c.violations++;
-    } else if (!st.levelOffsets.empty() && (wantOrder != order || wantOffsets != st.levelOffsets)) {
+    } else if (!st.world.levelOffsets.empty() && (wantOrder != order || wantOffsets != st.world.levelOffsets)) {
         c.violations++;
         why += " level order";
     }

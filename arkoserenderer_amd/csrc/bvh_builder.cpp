@@ -1,6 +1,7 @@
 // bvh_builder.cpp — binned SAH BVH2 over world-space triangles (host, C++ threads).
 #include "bvh_builder.h"
 
+#include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include <cstring>
 #include <memory>
 #include <thread>
+#include <utility>
 
 namespace ark {
 namespace {
@@ -1183,6 +1185,115 @@ BvhBuildResult build_bvh(const std::vector<BuildTriangle>& tris, const BvhBuildO
     if (tris.empty()) return {};
     Builder b(tris, opt, node_base, tri_base);
     return b.run(tris);
+}
+
+int hit_mask_class(uint32_t hit_mask) { return (hit_mask & ARK_RT_HIT_MASK_OPAQUE) ? 0 : (hit_mask & ARK_RT_HIT_MASK_MASKED) ? 1 : 2; }
+
+bool checkBvh8Structure(const std::vector<GpuBvh8Node>& allNodes, const std::vector<GpuTriangle>& allTris, const int32_t* roots, int nRoots, std::string& why)
+{
+    char buf[128];
+    auto bad = [&](const char* fmt, uint64_t v) {
+        std::snprintf(buf, sizeof(buf), fmt, static_cast<unsigned long long>(v));
+        why = buf;
+        return false;
+    };
+    std::vector<uint8_t> seenNode(allNodes.size(), 0);
+    std::vector<uint8_t> seenTri(allTris.size(), 0);
+    std::vector<uint32_t> work;
+    for (int c = 0; c < nRoots; ++c)
+        if (roots[c] >= 0) work.push_back(static_cast<uint32_t>(roots[c]));
+    while (!work.empty()) {
+        const uint32_t n = work.back();
+        work.pop_back();
+        if (n >= allNodes.size() || seenNode[n]) return bad("BVH invalid: node %llu", n);
+        seenNode[n] = 1;
+        const GpuBvh8Node& nd = allNodes[n];
+        uint32_t internal = 0;
+        if ((nd.leaf_tris >> 24) || (nd.leaf_mask & nd.imask)) return bad("BVH invalid: node %llu leaf rows", n);
+        for (int sl = 0; sl < 8; ++sl) {
+            const bool isInternal = (nd.imask >> sl) & 1u;
+            uint32_t slotTris[kBvh8MaxLeafSize];
+            const int cnt = bvh8SlotTriangles(nd, sl, slotTris);
+            if (cnt < 0) return bad("BVH invalid: node %llu slot", n);
+            if (isInternal) work.push_back(nd.child_base + internal++);
+            for (int i = 0; i < cnt; ++i) {
+                const uint32_t t = slotTris[i];
+                if (t >= allTris.size() || isHoleTriangle(allTris[t])) return bad("BVH invalid: leaf range%.0llu", 0);
+                if (seenTri[t]) return bad("BVH invalid: triangle %llu in two leaves", t);
+                seenTri[t] = 1;
+            }
+            for (int a = 0; a < 3; ++a)
+                if ((isInternal || cnt > 0) && nd.qlo[a][sl] > nd.qhi[a][sl]) return bad("BVH invalid: child box%.0llu", 0);
+        }
+    }
+    for (size_t t = 0; t < seenTri.size(); ++t)
+        if (!seenTri[t] && !isHoleTriangle(allTris[t])) return bad("BVH invalid: triangle %llu unreachable", t);
+    return true;
+}
+
+bool bvhLevelOrder(const GpuBvh8Node* h, uint64_t n, const int32_t* roots, int nRoots, std::vector<uint32_t>& order, std::vector<uint32_t>& offsets)
+{
+    std::vector<std::vector<uint32_t>> byDepth;
+    std::vector<std::pair<uint32_t, uint32_t>> work; // (node, depth)
+    for (int r = 0; r < nRoots; ++r)
+        if (roots[r] >= 0) work.push_back({ static_cast<uint32_t>(roots[r]), 0u });
+    while (!work.empty()) {
+        const auto [node, d] = work.back();
+        work.pop_back();
+        if (node >= n) return false;
+        if (byDepth.size() <= d) byDepth.resize(d + 1);
+        byDepth[d].push_back(node);
+        const uint32_t internal = static_cast<uint32_t>(__builtin_popcount(h[node].imask));
+        for (uint32_t k = 0; k < internal; ++k) work.push_back({ h[node].child_base + k, d + 1 });
+    }
+    order.clear();
+    order.reserve(n);
+    offsets.assign(1, 0u);
+    for (size_t d = byDepth.size(); d-- > 0;) {
+        std::sort(byDepth[d].begin(), byDepth[d].end());
+        order.insert(order.end(), byDepth[d].begin(), byDepth[d].end());
+        offsets.push_back(static_cast<uint32_t>(order.size()));
+    }
+    return true;
+}
+
+bool build_world_bvh8(std::vector<BuildTriangle> cls[3], BvhBuildOptions opt, const Bvh8CollapseOptions& copt, WorldBvh8& out, std::string& why)
+{
+    out = WorldBvh8 {};
+    opt.max_leaf_size = kBvh8MaxLeafSize;
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    for (int c = 0; c < 3; ++c)
+        for (const BuildTriangle& t : cls[c])
+            for (const float* v : { t.v0, t.v1, t.v2 })
+                for (int a = 0; a < 3; ++a) {
+                    lo[a] = std::min(lo[a], v[a]);
+                    hi[a] = std::max(hi[a], v[a]);
+                }
+    out.inflateAbs = opt.inflate_abs = bvh8_inflation_box(lo, hi);
+    for (int c = 0; c < 3; ++c) {
+        if (cls[c].empty()) continue;
+        BvhBuildResult r2 = build_bvh(cls[c], opt, 0u, 0u);
+        std::vector<BuildTriangle>().swap(cls[c]);
+        out.maxLeaf = std::max(out.maxLeaf, r2.max_leaf);
+        if (r2.max_leaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+            why = "BVH2 leaf of " + std::to_string(r2.max_leaf) + " triangles";
+            return false;
+        }
+        if (c == 0) out.sah = r2.sah_cost;
+        Bvh8BuildResult r = collapse_bvh8(r2, static_cast<uint32_t>(out.nodes.size()), static_cast<uint32_t>(out.tris.size()), copt);
+        out.roots[c] = static_cast<int32_t>(out.nodes.size());
+        if (c == 0) out.opaqueNodes = static_cast<uint32_t>(r.nodes.size());
+        out.depth = std::max(out.depth, r.max_depth);
+        out.triangles += r.triangles;
+        out.nodes.insert(out.nodes.end(), r.nodes.begin(), r.nodes.end());
+        out.tris.insert(out.tris.end(), r.tris.begin(), r.tris.end());
+    }
+    if (out.nodes.size() >= (1ull << 31) || out.tris.size() >= (1ull << 31)) {
+        out.tooLarge = true;
+        why = "scene too large for 31-bit BVH indices";
+        return false;
+    }
+    return checkBvh8Structure(out.nodes, out.tris, out.roots, 3, why);
 }
 
 } // namespace ark

@@ -5,6 +5,7 @@
 #pragma once
 
 #include <stdint.h>
+#include <string>
 #include <vector>
 
 #include "ddgi_types.h"
@@ -80,6 +81,36 @@ struct Bvh8CollapseOptions {
     int threads = 0; // subtrees collapsed in parallel (0 = hardware concurrency)
 };
 Bvh8BuildResult collapse_bvh8(const BvhBuildResult& bvh2, uint32_t node_base, uint32_t tri_base, const Bvh8CollapseOptions& opt);
+
+// The hit-mask class of an instance (ARK_RT_HIT_MASK_*): 0 opaque, 1 masked, 2 blend
+int hit_mask_class(uint32_t hit_mask);
+
+// The world BVHs: one BVH8 per hit-mask class, packed into one node array and one record
+// array (opaque first; roots[c] -1: the class is empty).
+struct WorldBvh8 {
+    std::vector<GpuBvh8Node> nodes;
+    std::vector<GpuTriangle> tris; // leaf triangle rows, holes included
+    int32_t roots[3] = { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, depth = 0, maxLeaf = 0;
+    uint64_t triangles = 0;   // records that are not holes
+    float sah = 0.0f;         // BVH2 SAH cost of the opaque class
+    float inflateAbs = 0.0f;  // one absolute box inflation for all classes (shadow rays test all): bvh8_inflation_box of their bounds
+    bool tooLarge = false;    // failed on the 31-bit index limit
+};
+// Builds them from the classes' world-space triangles (each class's input freed once its
+// BVH2 stands): opt's leaf size and inflation are set here; false with `why` when a BVH2
+// leaf exceeds kBvh8MaxLeafSize (out.maxLeaf), the set exceeds 31-bit indices
+// (out.tooLarge) or checkBvh8Structure fails.
+bool build_world_bvh8(std::vector<BuildTriangle> cls[3], BvhBuildOptions opt, const Bvh8CollapseOptions& copt, WorldBvh8& out, std::string& why);
+
+// Structural check of a BVH8 before anything reaches the GPU: every node is
+// referenced once from a root-reachable parent (no cycles, no sharing), every leaf's
+// triangles lie inside the triangle array and every triangle (every record but the
+// holes of the rows) is covered once.
+bool checkBvh8Structure(const std::vector<GpuBvh8Node>& allNodes, const std::vector<GpuTriangle>& allTris, const int32_t* roots, int nRoots, std::string& why);
+// The nodes of a BVH8 by depth, deepest first (a node's internal children are one level
+// deeper): the refit's launch order, order[offsets[i] .. offsets[i + 1]) one level.
+bool bvhLevelOrder(const GpuBvh8Node* h, uint64_t n, const int32_t* roots, int nRoots, std::vector<uint32_t>& order, std::vector<uint32_t>& offsets);
 
 // The 48-B triangle record of a build triangle (v0, e1 = v1 - v0, e2 = v2 - v0 in
 // fp32, instance, primitive, facing flip): what the traversal's Möller–Trumbore reads.

@@ -533,7 +533,8 @@ typedef struct ArkDdgiBvhStats {
     uint64_t triangle_bytes;
     /* the sun's light-space BVH8: its node count (0 = the sun's shadow rays traverse the
      * world BVHs), and the sampled any-hit steps per sun shadow ray of both structures
-     * that chose it (0 when not sampled: no sun, or ARK_SUN_BVH=0) */
+     * that chose it (0 when not sampled: no sun, or ArkDdgiDesc.sun_bvh =
+     * ARK_DDGI_SUN_BVH_WORLD) */
     uint64_t sun_node_count;
     float sun_cost_world;
     float sun_cost_light;

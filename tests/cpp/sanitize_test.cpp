@@ -1,12 +1,15 @@
 // ASan + UBSan run of the host-side code on the path (SURVEY §5 "race detection /
 // sanitizers"): the CPU oracle (frames with offsets, the AO bake, lighting compose),
-// the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check.
+// the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check,
+// the three hit-mask classes' build (build_world_bvh8) and the refit's level order.
 // Built by tests/test_sanitizers.py with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=all; any report aborts with a non-zero status.
 #include <cstdio>
 #include <cstring>
+#include <string>
 #include <vector>
 
+#include "bvh_builder.h"
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
 #include "../../include/ark_scene.h"
@@ -22,6 +25,64 @@ int oracle_bake_ao(void* ctx, uint32_t instance, uint32_t W, uint32_t H, uint32_
 }
 
 #define CHECK(c) do { if (!(c)) { std::printf("FAIL %s:%d %s\n", __FILE__, __LINE__, #c); return 1; } } while (0)
+
+// build_world_bvh8 over the first `n` soup triangles dealt to the hit-mask classes:
+// triangle 0 alone in class `single`, the others alternating between the two other
+// classes, or all in one of them (`emptyClass`: the other stays empty); 4 threads.
+static int worldBvh8Case(const std::vector<float>& tri, uint32_t n, int single, bool emptyClass)
+{
+    using namespace ark;
+    std::vector<BuildTriangle> cls[3];
+    std::vector<int> classOf(n);
+    const int other[2] = { (single + 1) % 3, (single + 2) % 3 };
+    for (uint32_t i = 0; i < n; ++i) {
+        BuildTriangle t;
+        std::memcpy(t.v0, &tri[9 * i], 12);
+        std::memcpy(t.v1, &tri[9 * i + 3], 12);
+        std::memcpy(t.v2, &tri[9 * i + 6], 12);
+        t.instance = i; // one instance per triangle: classOf by record
+        t.primitive = i;
+        t.flip_facing = 0;
+        classOf[i] = i == 0 ? single : other[emptyClass ? 0 : i & 1];
+        cls[classOf[i]].push_back(t);
+    }
+    uint64_t count[3];
+    for (int c = 0; c < 3; ++c) count[c] = cls[c].size();
+    BvhBuildOptions opt;
+    opt.threads = 4;
+    Bvh8CollapseOptions copt;
+    copt.threads = 4;
+    WorldBvh8 w;
+    std::string why;
+    CHECK(build_world_bvh8(cls, opt, copt, w, why));
+    CHECK(cls[0].empty() && cls[1].empty() && cls[2].empty()); // each class's input freed
+    CHECK(w.triangles == n && w.maxLeaf >= 1 && w.maxLeaf <= static_cast<uint32_t>(kBvh8MaxLeafSize) && w.inflateAbs > 0.0f && !w.tooLarge);
+    for (int c = 0; c < 3; ++c) CHECK((w.roots[c] >= 0) == (count[c] > 0));
+    CHECK(checkBvh8Structure(w.nodes, w.tris, w.roots, 3, why));
+    const Bvh8CheckResult chk = check_bvh8_full(w.nodes, w.tris, w.roots, 3, &classOf, nullptr);
+    CHECK(chk.violations == 0 && chk.triangles == n && chk.nodes == w.nodes.size());
+    // the refit's level order: every node once, the levels' offsets ascending to the count
+    std::vector<uint32_t> order, offsets;
+    CHECK(bvhLevelOrder(w.nodes.data(), w.nodes.size(), w.roots, 3, order, offsets));
+    std::vector<uint8_t> seen(w.nodes.size(), 0);
+    CHECK(order.size() == w.nodes.size());
+    for (uint32_t node : order) {
+        CHECK(node < seen.size() && !seen[node]);
+        seen[node] = 1;
+    }
+    CHECK(offsets.size() == chk.maxDepth + 1u && offsets.front() == 0 && offsets.back() == order.size());
+    for (size_t l = 0; l + 1 < offsets.size(); ++l) CHECK(offsets[l] < offsets[l + 1]);
+    // the opaque class's nodes: from its root to the next root (or the end)
+    if (w.roots[0] >= 0) {
+        const int32_t next = w.roots[1] >= 0 ? w.roots[1] : w.roots[2] >= 0 ? w.roots[2] : static_cast<int32_t>(w.nodes.size());
+        CHECK(w.opaqueNodes == static_cast<uint32_t>(next - w.roots[0]));
+    } else {
+        CHECK(w.opaqueNodes == 0);
+    }
+    std::printf("world bvh8: %u triangles in classes %llu/%llu/%llu, %zu nodes, depth %u\n", n, static_cast<unsigned long long>(count[0]),
+                static_cast<unsigned long long>(count[1]), static_cast<unsigned long long>(count[2]), w.nodes.size(), w.depth);
+    return 0;
+}
 
 int main()
 {
@@ -50,6 +111,13 @@ int main()
     CHECK(ark_ddgi_debug_bvh8_check(tri.data(), nTri, stats) == 0);
     CHECK(stats[3] == 0 && stats[4] == nTri); // no violations, every triangle in a leaf
     std::printf("bvh8: %llu triangles, %llu nodes\n", static_cast<unsigned long long>(nTri), static_cast<unsigned long long>(stats[0]));
+
+    // the three hit-mask classes' shared host build (set_scene, the background rebuild):
+    // each class in turn holding a single triangle, and a run with an empty class
+    CHECK(nTri >= 301);
+    for (int single = 0; single < 3; ++single) CHECK(worldBvh8Case(tri, 301, single, false) == 0);
+    CHECK(worldBvh8Case(tri, 301, 0, true) == 0);
+    CHECK(worldBvh8Case(tri, 301, 1, true) == 0);
 
     // oracle: 4x4x4 probes x 64 rays, offsets on, three frames
     ArkDdgiDesc d;

@@ -595,3 +595,73 @@ def test_shared_scene_reflections_after_other_context_installs():
         a.close()
         b.close()
         orc.close()
+
+
+def test_host_rebuild_three_classes_with_sun_bvh():
+    """The host rebuild path with all three hit-mask classes and a light-space sun BVH,
+    through the build, upload and install code set_scene shares with it: instances move
+    for three frames and stop; the world BVHs are rebuilt on the host from the settled
+    records and installed, the sun BVH after them. Every frame before, across and after
+    the installs is bit-exact against the oracle; the installed BVHs are valid and hold,
+    bit for bit, the records a fresh context refitted to the same transforms holds."""
+    import time
+
+    sc = scenes.features_scene()
+    grid = D.ProbeGrid((4, 4, 4), (1.0, 0.8, 1.0), (-1.5, 0.3, -1.5))
+    kw = dict(rays_per_probe=32, probe_updates_per_frame=64, max_rays_per_probe=32, max_probe_updates=64,
+              sun_bvh=abi.ARK_DDGI_SUN_BVH_LIGHT_SPACE)
+    cfg = D.DDGIConfig(**kw)
+    ctx = D.DDGIContext(grid, 100.0, cfg)
+    ref = D.DDGIContext(grid, 100.0, D.DDGIConfig(background_rebuild=False, **kw))
+    orc = O.Oracle(ctx.desc)
+    try:
+        ctx.set_scene(sc)
+        orc.set_scene(sc)
+        assert ctx.bvh_stats().sun_node_count > 0
+        assert {int(m) for m in sc.instances["hit_mask"]} == {abi.ARK_RT_HIT_MASK_OPAQUE, abi.ARK_RT_HIT_MASK_MASKED, abi.ARK_RT_HIT_MASK_BLEND}
+        inst = sc.instances.copy()
+
+        def frame(f, what):
+            p = D.frame_params(cfg, grid, D.AppState(f), 0, light_pre_exposure=1.0, ambient_illuminance=0.05, environment_brightness=0.5)
+            ctx.update(p)
+            orc.update(p)
+            ctx.synchronize()
+            _compare(ctx, orc, f, what)
+
+        frame(0, "initial")
+        for f in range(1, 4):  # the box turns and slides, the masked quads rise, the translucent quad turns
+            M = inst["object_to_world"].reshape(-1, 3, 4).copy()
+            M[3, :, :3] = _rot_y(0.3) @ M[3, :, :3]
+            M[3, :, 3] += np.float32(0.1)
+            M[1, 1, 3] += np.float32(0.1)
+            M[2, :, :3] = _rot_y(0.2) @ M[2, :, :3]
+            inst["object_to_world"] = M.reshape(len(inst), 12)
+            ctx.set_instances(inst)
+            orc.set_instances(inst)
+            frame(f, "instances moved")
+        f, t0 = 4, time.time()
+        while True:  # the motion has stopped: until both BVHs were built from the last refit's records
+            frame(f, "settling")
+            f += 1
+            st = ctx.bvh_stats()
+            if (st.bvh_rebuilds >= 1 and st.bvh_built_refit_version == st.refit_version
+                    and st.sun_rebuilds >= 1 and st.sun_built_refit_version == st.refit_version):
+                break
+            assert time.time() - t0 < 60, (f"rebuilds not installed within 60 s (world {st.bvh_rebuilds} of refit {st.bvh_built_refit_version}, "
+                                           f"sun {st.sun_rebuilds} of refit {st.sun_built_refit_version}): {ctx.last_error()}")
+        for _ in range(2):
+            frame(f, "after the installs")
+            f += 1
+        st = ctx.bvh_stats()
+        assert st.refit_version == 3 and st.bvh_rebuild_failures == 0 and st.sun_rebuild_failures == 0 and st.sun_node_count > 0
+        chk = ctx.world_bvh_check()
+        assert chk["violations"] == 0 and chk["installed_builder"] == 0, (chk, ctx.last_error())
+        ref.set_scene(sc)
+        ref.set_instances(inst)
+        want = ref.world_bvh_check()
+        assert want["violations"] == 0 and ref.bvh_stats().bvh_rebuilds == 0
+        assert (chk["records"], chk["record_digest"]) == (want["records"], want["record_digest"])
+    finally:
+        ctx.close()
+        ref.close()
+        orc.close()

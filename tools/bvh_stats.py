@@ -2,6 +2,8 @@
 probe ray of the C4 workload (or a scaled soup) under the BVH8 builds selected by
 environment (ARK_BVH8_COLLAPSE=sah|greedy, ARK_BVH8_TRI_COST, ARK_BVH_INTERSECTION_COST),
 through ark_ddgi_debug_bvh8_trace_stats (a host simulation of k_trace's visiting order).
+Only the simulator library (tools/sim) reads these variables: libark_ddgi.so reads no
+build knob from the environment (its contexts take ArkDdgiDesc.sun_bvh and .flags).
 Rays: the frame-0 probe rays (rotated spherical Fibonacci, ddgi/common.glsl:12-25) of
 a sample of probes spread over the grid.
 
