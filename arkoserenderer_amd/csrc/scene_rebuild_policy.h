@@ -1,0 +1,69 @@
+// scene_rebuild_policy.h — which background BVH build a scene call starts (scene_store.cpp:
+// sceneMaintenance, sceneSunStep). Pure host logic over a plain struct: no device call, so
+// that the turn-taking is tested on the CPU (tests/cpp/sanitize_test.cpp).
+#pragma once
+
+#include <cstdint>
+
+#include "../../include/ark_ddgi.h"
+
+namespace ark {
+
+// the background build started last (loosened BVHs take turns)
+enum : uint8_t { kBackgroundNone, kBackgroundWorld, kBackgroundSun };
+
+// What a scene call knows when it decides, after it collected the finished jobs.
+struct RebuildState {
+    bool sunWanted = false;      // set_scene chose the light-space sun BVH
+    bool hasSun = false;         // the calling context has a sun
+    bool sunJobRunning = false, worldJobRunning = false;
+    bool sunInstalled = false;   // a light-space BVH is installed for the caller's sun direction
+    bool requestStable = false;  // the scene's contexts asked for this direction at least twice in a row
+    bool sunFailedHere = false;  // a sun build failed for this direction and scene version
+    bool worldRebuildFailed = false;
+    bool worldGpuBuilt = false;  // the installed world BVHs are a device build
+    uint32_t refitsSinceBuild = 0, sunRefitsSinceBuild = 0; // refits since the installed BVHs' snapshots
+    uint32_t flags = 0;          // ArkDdgiDesc.flags of the caller
+    uint8_t lastBackground = kBackgroundNone;
+    bool sunOnly = false;        // set_lights: the world BVHs' rebuilds are left to the next update or set_instances
+};
+
+enum class RebuildStart { None, Sun, WorldHost, WorldDevice };
+
+// The one build to start now.
+//  - A light-space BVH missing for the caller's sun starts at once, even beside a running
+//    world rebuild (until it is installed the sun's shadow rays traverse the world BVHs);
+//    only on a stable request, and not again after a failure for the same direction and
+//    scene version. Nothing else starts in that call.
+//  - Loosened BVHs (refits since their build; not with ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD,
+//    the world ones not after a failed rebuild) start only while no background build runs,
+//    and when both the world BVHs and the light-space one are loosened they take turns
+//    (under continuous motion each would otherwise start again the moment its last one is
+//    installed).
+//  - ARK_DDGI_FLAG_GPU_REBUILD: loosened world BVHs are rebuilt on the device; once the
+//    motion has stopped (a device build installed, no refit since its snapshot) one host
+//    rebuild replaces the LBVH with the SAH tree a static scene traces faster.
+//  - sunOnly never starts a world rebuild; the sun's turn there yields to loosened world
+//    BVHs (not to a settle rebuild).
+inline RebuildStart rebuildToStart(const RebuildState& q)
+{
+    const bool background = !(q.flags & ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD);
+    bool sunMissing = false, sunLoosened = false;
+    if (q.sunWanted && q.hasSun && !q.sunJobRunning && q.requestStable && !q.sunFailedHere) {
+        sunMissing = !q.sunInstalled;
+        sunLoosened = q.sunInstalled && q.sunRefitsSinceBuild != 0 && background;
+    }
+    if (sunMissing) return RebuildStart::Sun;
+    if (q.sunJobRunning || q.worldJobRunning) return RebuildStart::None;
+    const bool worldOk = background && !q.worldRebuildFailed;
+    const bool worldLoosened = worldOk && q.refitsSinceBuild != 0;
+    const bool worldSettle = worldOk && (q.flags & ARK_DDGI_FLAG_GPU_REBUILD) && q.worldGpuBuilt && q.refitsSinceBuild == 0;
+    const bool world = !q.sunOnly && (worldLoosened || worldSettle);
+    if (world && (!sunLoosened || q.lastBackground != kBackgroundWorld))
+        return worldLoosened && (q.flags & ARK_DDGI_FLAG_GPU_REBUILD) ? RebuildStart::WorldDevice : RebuildStart::WorldHost;
+    const bool sunYields = q.sunOnly ? worldLoosened : world;
+    if (sunLoosened && (!sunYields || q.lastBackground != kBackgroundSun)) return RebuildStart::Sun;
+    return RebuildStart::None;
+}
+
+} // namespace ark

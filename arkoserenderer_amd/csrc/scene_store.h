@@ -1,0 +1,267 @@
+// scene_store.h — the scene of the DDGI contexts on the device (include/ark_ddgi.h:
+// ark_ddgi_set_scene, _share_scene, _set_instances) and what maintains it: the
+// stream-ordered refits of its three geometry copies and the background rebuilds of its
+// BVHs. ark_ddgi.cpp holds the contexts; a store knows none of them, and contexts that
+// share a store call into it one at a time (the C ABI's rule for one GPU's contexts).
+//
+// Stream order is a precondition, not a call. Every entry point that takes a stream `s`
+// requires that the caller has ordered `s` behind everything its context enqueued before
+// (ark_ddgi.cpp: orderBegin); whatever it enqueues - an install on `s`, a snapshot on `s`,
+// a refit on the store's own stream that `s` then waits for - is ordered behind that point,
+// and the caller ends the operation on `s` (orderEnd). After any scene call the caller
+// compares SceneStore::version with the one its kernel view was derived at and derives it
+// again when it moved (refreshScene); before its next traversal it waits for evGeometry
+// when geometrySeq moved.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <array>
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "../../include/ark_ddgi.h"
+#include "ddgi_kernels.h"
+#include "scene_rebuild_policy.h"
+
+namespace ark {
+
+// Where a failing call leaves its message (ark_ddgi_last_error): a context is one.
+struct ErrorSink {
+    std::string lastError;
+    int fail(int code, const char* fmt, ...)
+    {
+        char buf[512];
+        va_list ap;
+        va_start(ap, fmt);
+        std::vsnprintf(buf, sizeof(buf), fmt, ap);
+        va_end(ap);
+        lastError = buf;
+        return code;
+    }
+    int hipFail(hipError_t e, const char* what)
+    {
+        return fail(ARK_DDGI_E_DEVICE, "%s: %s", what, hipGetErrorString(e));
+    }
+};
+
+// returns sink->hipFail(...) from the enclosing function when a HIP call fails
+#define ARK_HIP_TO(sink, expr)                                          \
+    do {                                                                \
+        hipError_t _e = (expr);                                         \
+        if (_e != hipSuccess) return (sink)->hipFail(_e, #expr);        \
+    } while (0)
+
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    hipError_t alloc(size_t n)
+    {
+        release();
+        bytes = n;
+        if (n == 0) return hipSuccess;
+        return hipMalloc(&ptr, n);
+    }
+    void release()
+    {
+        if (ptr) (void)hipFree(ptr);
+        ptr = nullptr;
+        bytes = 0;
+    }
+    template<typename T> T* as() const { return static_cast<T*>(ptr); }
+};
+
+// One BVH8 set on the device - the world's three classes, or the sun's light-space BVH -
+// with what its refits need. One allocation: the nodes, then the triangle records at the
+// next 256-B boundary (the traversal addresses both through one buffer resource with a
+// 32-bit byte offset), then one padding record (a five-load fetch of the last record
+// stays in bounds, ARK_FETCH5).
+struct DeviceBvh {
+    DeviceBuffer buf; // the front copy: what the kernels read (SceneStore::Spare holds the others)
+    size_t triOffset = 0;
+    uint64_t nodeCount = 0, records = 0; // records: holes included, the padding record not
+    uint32_t depth = 0;
+    float inflateAbs = 0.0f; // the build's absolute box inflation (the refits' floor)
+    // the refit: order[levelOffsets[i] .. [i + 1]) on the device = the nodes of one depth,
+    // deepest first; its boxes scratch; the node masks (k_node_masks: per topology)
+    DeviceBuffer order, boxes, masks;
+    std::vector<uint32_t> levelOffsets;
+    bool masksValid = false;
+    static size_t triOffsetFor(uint64_t nodes) { return (nodes * sizeof(GpuBvh8Node) + 255) & ~static_cast<size_t>(255); }
+    static size_t bytesFor(uint64_t nodes, uint64_t records) { return triOffsetFor(nodes) + (records + 1) * sizeof(GpuTriangle); }
+    // nodes and records of a copy of it (the front one, or a spare)
+    GpuBvh8Node* nodes(const DeviceBuffer& copy) const { return copy.as<GpuBvh8Node>(); }
+    GpuTriangle* tris(const DeviceBuffer& copy) const { return reinterpret_cast<GpuTriangle*>(static_cast<char*>(copy.ptr) + triOffset); }
+    void release()
+    {
+        for (DeviceBuffer* b : { &buf, &order, &boxes, &masks }) b->release();
+    }
+};
+
+struct SunJob; // the background rebuilds (scene_store.cpp)
+struct WorldJob;
+
+// A buffer replaced while launches enqueued before may still read it: freed once `done`
+// (recorded behind them) has completed.
+struct Retired {
+    DeviceBuffer buf;
+    hipEvent_t done = nullptr;
+};
+
+// The scene of a context on the device (ark_ddgi_set_scene): BVH nodes + triangles,
+// shading records, RT mesh data, materials, textures, lights. Reference-counted:
+// ark_ddgi_share_scene lets the Z-slab contexts of one GPU use one copy.
+struct SceneStore {
+    int device = 0;
+    DeviceBuffer triNormals, indices, vertices, positions, meshes, materials, instances, texInfos, texels;
+    // the world BVHs (args) and the light-space BVH8 of the sun's shadow rays with its
+    // world-space triangle records (sunArgs; nodeCount 0: none). The light-space BVH follows
+    // the motion: refitted with the world BVHs (its records re-transformed, its boxes of
+    // their light coordinates, sunFrameD)
+    DeviceBvh world, sun;
+    float sunCostWorld = 0.0f, sunCostLight = 0.0f; // sampled sun shadow-ray steps per ray (sun_shadow_cost)
+    std::vector<ArkRTInstance> instHost;     // the AO bake (instance -> mesh segment), set_instances' topology check
+    std::vector<ArkRTTriangleMesh> meshHost;
+    SceneArgs args {};    // the world BVHs, pools, materials, textures (lights: per context, deriveSceneArgs)
+    SceneArgs sunArgs {}; // sun_nodes / sun_tris / sun_root / sun_frame of the light-space BVH (sun_root -1: none)
+    float sunDirBuilt[3] { 0, 0, 0 }; // the sun direction the light-space BVH was built for
+    // the scene's lights as set_scene got them: a context's lights until ark_ddgi_set_lights
+    int32_t hasSunScene = 0;
+    ArkDirectionalLight sunScene {};
+    std::vector<GpuSpotLight> spotsScene;
+    ArkDdgiBvhStats bvhStats {};
+    uint32_t bvhMaxDepth = 0; // deepest of the world BVHs and the sun's (traversal spill)
+    // ark_ddgi_set_instances: bumped by every refit and install (a sharing context
+    // re-derives its SceneArgs); the refit's transforms on the device
+    uint32_t version = 0;
+    DeviceBuffer refitInst;
+    double sunFrameD[9] {};
+    // the refit's transforms: the last ones uploaded (dirty = changed since the records
+    // were written); pinned staging of the stream-ordered uploads, two sets in turn
+    std::vector<RefitInstance> refitHost;
+    // pinned staging of the per-frame uploads, a ring: a slot is reused once its copy (a
+    // few calls back) has run, so the host runs up to kStageSlots / 2 frames of
+    // set_instances_async ahead of the device (two slots: one frame, and every call
+    // waited for the previous frame's refit)
+    static constexpr int kStageSlots = 8;
+    void* stage[kStageSlots] {};
+    size_t stageBytes[kStageSlots] {};
+    hipEvent_t stageDone[kStageSlots] {};
+    int stageNext = 0;
+    // object-space bounds of every instance's triangles (set_scene): the refit's world and
+    // light-space bounds, for its box inflation, from the instances' transforms on the host
+    std::vector<std::array<float, 6>> instObjBox;
+    // The geometry a refit writes comes in three copies: the front one (world.buf, sun.buf,
+    // instances above: what the kernels read) and two spares. A refit brings the next
+    // spare from the transforms it holds (xf[slot]) to the new ones on the store's
+    // refit stream and makes it the front one: it waits only for the operations that read
+    // that copy while it was the front one, two refits before (the frame before last),
+    // so that it runs beside the frame in flight's traversal and the next traversal does
+    // not wait for it (with two copies it waited for the previous frame's shading, and
+    // the frames ran one after the other: C4 4.3 ms per moving frame, static 3.3). An
+    // install (a new topology) drops the spares; the next refit copies the front one.
+    struct Spare {
+        DeviceBuffer world, sun, instances;
+        bool valid = false;
+        int slot = 0;
+    };
+    Spare spare[2]; // spare[0]: the next refit's target
+    // the inflations each copy's boxes hold ([slot][0 world, 1 sun]); refitFull: the next
+    // refit reaches every node (a new topology, or boxes scratch not of this one)
+    bool refitFull = true;
+    float inflCopy[3][2] {};
+    int front = 0; // slot of the front copy (xf index)
+    std::vector<std::array<float, 12>> xf[3];
+    // the light-space BVH follows the sun: set_scene chose it (sunWanted), and after a
+    // sun-direction change it is rebuilt in the background (sceneSunStep)
+    bool sunWanted = false;
+    int buildThreads = 16;
+    std::unique_ptr<SunJob> sunJob;
+    uint32_t sunRebuilds = 0;
+    // rebuild requests (sceneSunStep): the sun direction the contexts sharing this scene
+    // asked for last and how many calls in a row asked for it; a rebuild starts only on a
+    // stable request (>= 2), so contexts under different suns never start rebuilds that
+    // undo each other. A failed build is remembered (direction and
+    // scene version) and not retried until either changes.
+    float sunReqDir[3] { 0, 0, 0 };
+    uint32_t sunReqStreak = 0;
+    bool sunFailed = false;
+    float sunFailedDir[3] { 0, 0, 0 };
+    uint32_t sunFailedVersion = 0;
+    uint32_t sunFailures = 0;
+    // the world BVHs' background rebuild (worldCollect / worldStart): refits since the installed
+    // BVHs were built, the running job, rebuilds installed
+    uint32_t refitsSinceBuild = 0, sunRefitsSinceBuild = 0;
+    std::unique_ptr<WorldJob> worldJob;
+    uint32_t worldRebuilds = 0, refitCount = 0;
+    bool worldRebuildFailed = false;
+    // ARK_DDGI_FLAG_GPU_REBUILD: the installed world BVHs are a device build (an LBVH: once
+    // the motion stops one host rebuild replaces it, rebuildToStart)
+    bool worldGpuBuilt = false;
+    // the background build started last (rebuildToStart: loosened BVHs take turns)
+    uint8_t lastBackground = kBackgroundNone;
+    std::vector<Retired> retired;
+    // The order of the writes to the three geometry copies, owned with them (the contexts
+    // sharing the store see one record of who read which copy): refits run on refitStream,
+    // at the device's highest priority (its per-level launches are dispatched ahead of the
+    // frame in flight's work when both wait for a CU). evFree[slot] ends with the operations
+    // that read that slot's copy while it was the front one (recorded when a refit swapped
+    // it out, on the refitting call's stream, which follows the others); evInstalled with
+    // the last install (a rebuild installed on a caller's stream writes the front copy).
+    // evGeometry ends with the last refit or install, geometrySeq counts its recordings: a
+    // context's next traversal waits for it when the count has moved since its last wait.
+    hipStream_t refitStream = nullptr;
+    hipEvent_t evFree[3] = {};
+    bool freeValid[3] = { false, false, false };
+    hipEvent_t evInstalled = nullptr;
+    bool installValid = false;
+    hipEvent_t evGeometry = nullptr;
+    uint32_t geometrySeq = 0;
+    SceneStore();
+    SceneStore(const SceneStore&) = delete;
+    SceneStore& operator=(const SceneStore&) = delete;
+    ~SceneStore(); // after a device sync: joins the jobs, frees the copies, the stream and the events
+};
+
+// What a scene call needs from the context that makes it.
+struct SceneCall {
+    ErrorSink* err;   // where a failure's message goes
+    uint32_t flags;   // ArkDdgiDesc.flags
+    bool hasSun;      // the context's sun (ark_ddgi_set_lights) ...
+    float sunDir[3];  // ... and its direction
+    bool shared;      // other contexts use the store too
+};
+
+// ark_ddgi_set_scene: the device scene of `s` built on `device` (the world BVHs, the
+// light-space sun BVH when it pays or sunBvh forces it: 0 never, 1 always, -1 by cost).
+// buildThreads: ArkDdgiDesc.build_threads. Synchronous; the device is idle.
+int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThreads, int sunBvh, std::shared_ptr<SceneStore>& out);
+
+// Everything an operation on `s` does to the scene first: buffers retired by earlier
+// installs freed, finished rebuilds installed on `s`, new ones started (scene_rebuild_policy.h).
+int sceneMaintenance(SceneStore& st, const SceneCall& c, hipStream_t s);
+
+// ark_ddgi_set_lights: the request for the caller's sun direction noted, failed and stale
+// sun builds dropped, and - only when mayEnqueue, i.e. `s` meets the precondition - a
+// finished sun rebuild installed on `s` or a new one started (never a world rebuild).
+int sceneSunStep(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueue);
+// whether such a step has an install or a start to consider (else the caller orders no stream)
+bool sunStepMayEnqueue(const SceneStore& st, const SceneCall& c);
+bool sunJobPending(const SceneStore& st);
+
+// ark_ddgi_set_instances_async: the refit of the next spare copy to `instances` on the
+// store's stream, which then becomes the front copy; `s` follows the refit.
+int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s);
+
+// ark_ddgi_debug_scene_digest / _world_bvh_check over the front copy (the device is idle)
+int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out);
+int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
+
+// SpotLightData as the closest hit reads it
+GpuSpotLight gpuSpotLight(const ArkSpotLight& sl);
+
+} // namespace ark

@@ -1,7 +1,8 @@
 // ASan + UBSan run of the host-side code on the path (SURVEY §5 "race detection /
 // sanitizers"): the CPU oracle (frames with offsets, the AO bake, lighting compose),
 // the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check,
-// the three hit-mask classes' build (build_world_bvh8) and the refit's level order.
+// the three hit-mask classes' build (build_world_bvh8) and the refit's level order, and
+// the background rebuilds' scheduling (scene_rebuild_policy.h, a table of cases).
 // Built by tests/test_sanitizers.py with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=all; any report aborts with a non-zero status.
 #include <cstdio>
@@ -10,6 +11,7 @@
 #include <vector>
 
 #include "bvh_builder.h"
+#include "scene_rebuild_policy.h"
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
 #include "../../include/ark_scene.h"
@@ -84,8 +86,159 @@ static int worldBvh8Case(const std::vector<float>& tri, uint32_t n, int single, 
     return 0;
 }
 
+// Which background BVH build a scene call starts (scene_rebuild_policy.h), case by case.
+static int rebuildPolicyCases()
+{
+    using namespace ark;
+    using S = RebuildStart;
+    const uint32_t kNoBg = ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD, kGpu = ARK_DDGI_FLAG_GPU_REBUILD;
+    // a context with a sun whose light-space BVH is installed, the request stable
+    RebuildState base;
+    base.sunWanted = base.hasSun = base.sunInstalled = base.requestStable = true;
+    CHECK(rebuildToStart(base) == S::None); // nothing loosened
+    RebuildState both = base; // world and sun both loosened
+    both.refitsSinceBuild = both.sunRefitsSinceBuild = 3;
+
+    // turn-taking: the world first, then strict alternation (each job collected before the next call)
+    {
+        RebuildState q = both;
+        for (int round = 0; round < 6; ++round) {
+            const S got = rebuildToStart(q);
+            CHECK(got == (round % 2 == 0 ? S::WorldHost : S::Sun));
+            q.lastBackground = got == S::Sun ? kBackgroundSun : kBackgroundWorld;
+        }
+        // only one of them loosened: it starts whatever started last
+        for (uint8_t last : { kBackgroundNone, kBackgroundWorld, kBackgroundSun }) {
+            q = both;
+            q.lastBackground = last;
+            q.sunRefitsSinceBuild = 0;
+            CHECK(rebuildToStart(q) == S::WorldHost);
+            q = both;
+            q.lastBackground = last;
+            q.refitsSinceBuild = 0;
+            CHECK(rebuildToStart(q) == S::Sun);
+        }
+    }
+    // a job is running: nothing loosened starts; a missing sun BVH starts beside a world
+    // job, not beside a sun job
+    for (int running = 0; running < 2; ++running) {
+        RebuildState q = both;
+        (running ? q.sunJobRunning : q.worldJobRunning) = true;
+        CHECK(rebuildToStart(q) == S::None);
+        q.sunInstalled = false;
+        CHECK(rebuildToStart(q) == (running ? S::None : S::Sun));
+    }
+    // a missing sun BVH starts at once, ahead of a loosened world whose turn it is
+    {
+        RebuildState q = both;
+        q.sunInstalled = false;
+        q.lastBackground = kBackgroundSun;
+        CHECK(rebuildToStart(q) == S::Sun);
+        // ... but only on a stable request for this direction, with no remembered failure,
+        // a sun, and a scene that chose the light-space BVH: else the world's turn
+        RebuildState r = q;
+        r.requestStable = false; // a streak below 2, or a request for another direction
+        CHECK(rebuildToStart(r) == S::WorldHost);
+        r.refitsSinceBuild = 0;
+        CHECK(rebuildToStart(r) == S::None);
+        r = q;
+        r.sunFailedHere = true;
+        CHECK(rebuildToStart(r) == S::WorldHost);
+        r.refitsSinceBuild = 0;
+        CHECK(rebuildToStart(r) == S::None);
+        r = q;
+        r.hasSun = false;
+        CHECK(rebuildToStart(r) == S::WorldHost);
+        r = q;
+        r.sunWanted = false;
+        CHECK(rebuildToStart(r) == S::WorldHost);
+    }
+    // an unstable request or a remembered failure also holds back a loosened sun BVH
+    {
+        RebuildState q = both;
+        q.refitsSinceBuild = 0;
+        q.requestStable = false;
+        CHECK(rebuildToStart(q) == S::None);
+        q = both;
+        q.refitsSinceBuild = 0;
+        q.sunFailedHere = true;
+        CHECK(rebuildToStart(q) == S::None);
+    }
+    // ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: nothing loosened starts, a missing sun BVH does
+    {
+        RebuildState q = both;
+        q.flags = kNoBg;
+        CHECK(rebuildToStart(q) == S::None);
+        q.flags = kNoBg | kGpu;
+        q.worldGpuBuilt = true;
+        CHECK(rebuildToStart(q) == S::None);
+        q.refitsSinceBuild = 0; // (no settle rebuild either)
+        CHECK(rebuildToStart(q) == S::None);
+        q.sunInstalled = false;
+        CHECK(rebuildToStart(q) == S::Sun);
+    }
+    // ARK_DDGI_FLAG_GPU_REBUILD: loosened world BVHs on the device; settled ones the device
+    // built once on the host; neither after a failed rebuild
+    {
+        RebuildState q = base;
+        q.flags = kGpu;
+        q.refitsSinceBuild = 2;
+        CHECK(rebuildToStart(q) == S::WorldDevice);
+        q.worldGpuBuilt = true;
+        CHECK(rebuildToStart(q) == S::WorldDevice);
+        q.refitsSinceBuild = 0;
+        CHECK(rebuildToStart(q) == S::WorldHost); // the settle rebuild
+        q.worldGpuBuilt = false;                  // ... installed: a host build, nothing more
+        CHECK(rebuildToStart(q) == S::None);
+        q = base;
+        q.flags = kGpu;
+        q.worldRebuildFailed = true;
+        q.refitsSinceBuild = 2;
+        CHECK(rebuildToStart(q) == S::None);
+        q.refitsSinceBuild = 0;
+        q.worldGpuBuilt = true;
+        CHECK(rebuildToStart(q) == S::None);
+        // without the flag a loosened world builds on the host
+        q = base;
+        q.refitsSinceBuild = 2;
+        CHECK(rebuildToStart(q) == S::WorldHost);
+        q.worldRebuildFailed = true;
+        CHECK(rebuildToStart(q) == S::None);
+        // a settle rebuild takes turns with a loosened sun BVH like a loosened world
+        q = base;
+        q.flags = kGpu;
+        q.worldGpuBuilt = true;
+        q.sunRefitsSinceBuild = 1;
+        q.lastBackground = kBackgroundWorld;
+        CHECK(rebuildToStart(q) == S::Sun);
+        q.lastBackground = kBackgroundSun;
+        CHECK(rebuildToStart(q) == S::WorldHost);
+    }
+    // sunOnly (set_lights): the world never starts; the sun's loosened turn yields to a
+    // loosened world as in the full path: not twice in a row (there the world, offered
+    // the turn first, also takes it when nothing has started yet)
+    for (uint8_t last : { kBackgroundNone, kBackgroundWorld, kBackgroundSun }) {
+        RebuildState q = both;
+        q.lastBackground = last;
+        CHECK(rebuildToStart(q) == (last == kBackgroundWorld ? S::Sun : S::WorldHost));
+        q.sunOnly = true;
+        CHECK(rebuildToStart(q) == (last == kBackgroundSun ? S::None : S::Sun));
+        q.sunRefitsSinceBuild = 0; // only the world loosened
+        CHECK(rebuildToStart(q) == S::None);
+        q.flags = kGpu;
+        CHECK(rebuildToStart(q) == S::None);
+        q.sunInstalled = false; // a missing sun BVH
+        CHECK(rebuildToStart(q) == S::Sun);
+        q.worldJobRunning = true;
+        CHECK(rebuildToStart(q) == S::Sun);
+    }
+    std::printf("rebuild policy: OK\n");
+    return 0;
+}
+
 int main()
 {
+    CHECK(rebuildPolicyCases() == 0);
     ArkSoupParams sp;
     ark_soup_default_params(&sp);
     sp.triangle_count = 4096;

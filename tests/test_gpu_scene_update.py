@@ -251,6 +251,68 @@ def test_shared_scene_refit_reaches_every_context():
         c.close()
 
 
+def test_shared_scene_refits_through_both_contexts():
+    """Two Z-slab contexts share one scene and refit it in turn: six frames, each moving an
+    instance a little further (one frame a second one too), refitted through `a` on even
+    frames and through `b` on odd ones, so the store's three geometry copies wrap twice and
+    every copy is rewritten by the context that did not write it last. Both shards update
+    every frame on one stream with no host wait between an update and the next refit.
+    The ordering of the copies belongs to the store, not to the refitting context: at the
+    end the geometry the kernels read is byte-identical to that of contexts that share
+    nothing, given the same transforms (no background rebuilds: the topology stays, so the
+    digests compare), and so is everything each shard computed.
+
+    The references are the same two shards with a scene of their own each. An unsharded
+    context cannot serve past the first frame: a surfel carries the indirect light of the
+    previous frame's atlas (sampleDDGI), and without an exchange a shard's atlas holds its
+    own slab only - measured with the existing test's slab indexing, 4105 of 4608 surfels
+    of the lower slab differ after six frames, before and after the store took over the
+    ordering."""
+    import torch
+
+    sc = scenes.features_scene()
+    cfg = _cfg(64, 144)
+    cfg.sun_bvh = _sun_mode("1")
+    cfg.background_rebuild = False
+    shard = [D.DDGIContext(GRID, 100.0, cfg, shard_rank=r, shard_count=2) for r in (0, 1)]
+    refs = [D.DDGIContext(GRID, 100.0, cfg, shard_rank=r, shard_count=2) for r in (0, 1)]
+    a, b = shard
+    a.set_scene(sc)
+    b.share_scene(a)
+    for r in refs:
+        r.set_scene(sc)
+    stream = torch.cuda.Stream()
+    inst = sc.instances.copy()
+    M = inst["object_to_world"].reshape(-1, 3, 4).copy()
+    try:
+        for f in range(6):
+            M[3, :, 3] += np.float32(0.05)
+            if f == 2:
+                M[1, 1, 3] += np.float32(0.1)
+            inst["object_to_world"] = M.reshape(len(inst), 12)
+            shard[f % 2].set_instances_async(inst, stream.cuda_stream)
+            for r in refs:
+                r.set_instances_async(inst, stream.cuda_stream)
+            p = D.frame_params(cfg, GRID, D.AppState(f), 0, light_pre_exposure=1.0, ambient_illuminance=0.05, environment_brightness=0.5)
+            for c in shard + refs:
+                c.update(p, stream.cuda_stream)
+        stream.synchronize()
+        for c in shard + refs:
+            c.synchronize()
+        assert [c.bvh_stats().refit_version for c in shard + refs] == [6, 6, 6, 6]
+        digests = [c.scene_digest() for c in shard + refs]
+        assert digests[2][2] != 0, "no light-space sun BVH"
+        assert digests[0] == digests[1] == digests[2] == digests[3], digests
+        for c, r in zip(shard, refs):
+            assert np.array_equal(c.read(abi.ARK_DDGI_SURFELS), r.read(abi.ARK_DDGI_SURFELS))
+            for k, w in RESOURCES.items():
+                d = diff_report(k, c.read(w), r.read(w))
+                assert d["mismatch"] == 0, d
+    finally:
+        for c in shard + refs:
+            c.close()
+
+
 @pytest.mark.parametrize("cause", ["direction", "refit"])
 def test_sun_bvh_rebuilt_in_background(cause):
     """The light-space sun BVH follows the sun: after a sun-direction change (or a refit,

@@ -213,7 +213,7 @@ def main():
             moves.append({"move": label, "set_instances_ms": round(wall, 2), "refit_ms": round(st.refit_ms, 2), "mrays_per_s": round(rate(), 1)})
         out["refits"] = moves
         # the light-space sun BVH, dropped by the refit, comes back from the background
-        # rebuild (sunRebuildStep): frames until it is installed, then the rate again
+        # rebuild (sceneSunStep): frames until it is installed, then the rate again
         st = node.ctx.bvh_stats()
         if had_sun_bvh:
             t = time.perf_counter()
