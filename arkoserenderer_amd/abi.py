@@ -53,6 +53,7 @@ ARK_DDGI_SUN_BVH_LIGHT_SPACE = 2
 ARK_DDGI_FLAG_SERIAL_FRAMES = 0x1
 ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD = 0x2
 ARK_DDGI_FLAG_GPU_REBUILD = 0x4
+ARK_DDGI_FLAG_GPU_REBUILD_SUN = 0x8
 
 ARK_TEX_RGBA8_UNORM = 0
 ARK_TEX_RGBA8_SRGB = 1
@@ -292,6 +293,9 @@ class ArkDdgiBvhStats(C.Structure):
         ("bvh_gpu_rebuilds", C.c_uint32),
         ("bvh_gpu_fallbacks", C.c_uint32),
         ("bvh_installed_builder", C.c_uint32),
+        ("sun_gpu_rebuilds", C.c_uint32),
+        ("sun_gpu_fallbacks", C.c_uint32),
+        ("sun_installed_builder", C.c_uint32),
     ]
 
 
@@ -511,6 +515,9 @@ EXPORTS = {
     "ark_ddgi_debug_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_world_bvh_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_bvh_installed_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

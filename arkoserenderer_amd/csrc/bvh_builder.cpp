@@ -1453,19 +1453,15 @@ static void sunAddRecords(SunBvhInput& in, size_t n, RecordOf rec, int threads)
         for (size_t i = b; i < e; ++i) {
             const GpuTriangle rc = rec(i);
             // the triangle Möller–Trumbore tests: v0, v0 + e1, v0 + e2 (exact, from the record)
-            double V[3][3];
-            for (int a = 0; a < 3; ++a) V[0][a] = rc.t0[a];
-            const double e1[3] = { rc.t0[3], rc.t1[0], rc.t1[1] }, e2[3] = { rc.t1[2], rc.t1[3], rc.t2[0] };
-            for (int a = 0; a < 3; ++a) {
-                V[1][a] = V[0][a] + e1[a];
-                V[2][a] = V[0][a] + e2[a];
-                maxAbs[t] = std::max(maxAbs[t], static_cast<float>(std::max({ std::fabs(V[0][a]), std::fabs(V[1][a]), std::fabs(V[2][a]) })));
-            }
+            // (lbvh_build.h: the refit and the device build box the same light coordinates)
+            const float e1[3] = { rc.t0[3], rc.t1[0], rc.t1[1] }, e2[3] = { rc.t1[2], rc.t1[3], rc.t2[0] };
+            float Lv[3][3], m;
+            lbvh::lightVertices(rc.t0, e1, e2, &in.frame[0][0], Lv, m);
+            maxAbs[t] = std::max(maxAbs[t], m);
             BuildTriangle& l = in.tris[base + i];
             float* dst[3] = { l.v0, l.v1, l.v2 };
             for (int k = 0; k < 3; ++k)
-                for (int r = 0; r < 3; ++r)
-                    dst[k][r] = static_cast<float>(in.frame[r][0] * V[k][0] + in.frame[r][1] * V[k][1] + in.frame[r][2] * V[k][2]);
+                for (int r = 0; r < 3; ++r) dst[k][r] = Lv[k][r];
             l.instance = 0;
             l.primitive = static_cast<uint32_t>(base + i);
             l.flip_facing = 0;
@@ -1641,33 +1637,17 @@ double sun_shadow_cost(const std::vector<GpuBvh8Node>& nodes, const std::vector<
 // force), occluded (BVH), mismatches, node visits, triangle tests, BVH8 nodes, max
 // stack depth}. A mismatch would be a culled occluder: the node test must be
 // conservative.
-extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
-                                             uint64_t* out)
+namespace {
+// A sun shadow ray per origin traced through the light-space BVH (nodes, tris) by the host
+// restatement of visitNodeSun and against every record of `world`: out[0..7] as
+// ark_ddgi_debug_sun_bvh_check's; the mismatching rays returned
+uint64_t sunRayCompare(const std::vector<ark::GpuBvh8Node>& nodes, const std::vector<ark::GpuTriangle>& tris, const std::vector<ark::GpuTriangle>& world,
+                       const double frame[3][3], const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, uint64_t* out)
 {
     using namespace ark;
-    std::vector<BuildTriangle> tris(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) {
-            tris[i].v0[a] = triangles[9 * i + a];
-            tris[i].v1[a] = triangles[9 * i + 3 + a];
-            tris[i].v2[a] = triangles[9 * i + 6 + a];
-        }
-        tris[i].instance = 0;
-        tris[i].primitive = static_cast<uint32_t>(i);
-        tris[i].flip_facing = 0;
-    }
-    SunBvhInput in;
-    sun_frame(sun_dir, in.frame);
-    sun_add_triangles(in, tris);
-    std::vector<GpuTriangle> world = in.world;
-    BvhBuildOptions opt;
-    opt.threads = 8;
-    Bvh8CollapseOptions copt;
-    Bvh8BuildResult r;
-    if (n == 0 || !build_sun_bvh(in, opt, copt, r)) return 1;
     float F[9];
     for (int a = 0; a < 3; ++a)
-        for (int k = 0; k < 3; ++k) F[a * 3 + k] = static_cast<float>(in.frame[a][k]);
+        for (int k = 0; k < 3; ++k) F[a * 3 + k] = static_cast<float>(frame[a][k]);
     const float dd = sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2];
     const float sc = 1.0f / std::sqrt(dd);
     const float L[3] = { -(sun_dir[0] * sc), -(sun_dir[1] * sc), -(sun_dir[2] * sc) };
@@ -1709,7 +1689,7 @@ extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, 
             bool bvh = false;
             uint64_t nv = 0, nt = 0, md = 0;
             while (!stack.empty() && !bvh) {
-                const GpuBvh8Node& nd = r.nodes[stack.back()];
+                const GpuBvh8Node& nd = nodes[stack.back()];
                 stack.pop_back();
                 nv++;
                 int F_[2], C_[3];
@@ -1737,7 +1717,7 @@ extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, 
                     const int cnt = bvh8SlotTriangles(nd, sl, st);
                     for (int i = 0; i < cnt && !bvh; ++i) {
                         nt++;
-                        bvh = mt(o, r.tris[st[i]]);
+                        bvh = mt(o, tris[st[i]]);
                     }
                 }
                 for (size_t i = push.size(); i-- > 0;) stack.push_back(push[i]);
@@ -1763,10 +1743,41 @@ extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, 
         out[3] = mism.load();
         out[4] = visits.load();
         out[5] = tests.load();
-        out[6] = r.nodes.size();
+        out[6] = nodes.size();
         out[7] = maxDepth.load();
     }
-    return mism.load() == 0 ? 0 : 2;
+    return mism.load();
+}
+} // namespace
+
+
+
+
+extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                             uint64_t* out)
+{
+    using namespace ark;
+    std::vector<BuildTriangle> tris(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) {
+            tris[i].v0[a] = triangles[9 * i + a];
+            tris[i].v1[a] = triangles[9 * i + 3 + a];
+            tris[i].v2[a] = triangles[9 * i + 6 + a];
+        }
+        tris[i].instance = 0;
+        tris[i].primitive = static_cast<uint32_t>(i);
+        tris[i].flip_facing = 0;
+    }
+    SunBvhInput in;
+    sun_frame(sun_dir, in.frame);
+    sun_add_triangles(in, tris);
+    std::vector<GpuTriangle> world = in.world;
+    BvhBuildOptions opt;
+    opt.threads = 8;
+    Bvh8CollapseOptions copt;
+    Bvh8BuildResult r;
+    if (n == 0 || !build_sun_bvh(in, opt, copt, r)) return 1;
+    return sunRayCompare(r.nodes, r.tris, world, in.frame, sun_dir, origins, n_rays, tmax, out) == 0 ? 0 : 2;
 }
 
 
@@ -1847,9 +1858,20 @@ void recordVertices(const GpuTriangle& g, float v[3][3])
 }
 } // namespace
 
-LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion)
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun)
 {
     LbvhHostResult R;
+    const lbvh::KeyLayout layout = { sun ? sun->wBits : lbvh::kMortonBits };
+    const int slotRule = sun ? lbvh::kSlotsAscendingW : lbvh::kSlotsOctant;
+    // the vertices a record is boxed by: the world ones, or their light coordinates
+    float maxAbs = 0.0f;
+    auto boxVertices = [&](const GpuTriangle& g, float v[3][3]) {
+        if (!sun) return recordVertices(g, v);
+        const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
+        float m;
+        lbvh::lightVertices(g.t0, e1, e2, sun->frame, v, m);
+        maxAbs = std::max(maxAbs, m);
+    };
     // primitives: the records that are not holes, their boxes, the scene box
     std::vector<uint32_t> idx;
     std::vector<Aabb> pbox;
@@ -1857,7 +1879,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
     for (size_t i = 0; i < rec.size(); ++i) {
         if (isHoleTriangle(rec[i])) continue;
         float v[3][3];
-        recordVertices(rec[i], v);
+        boxVertices(rec[i], v);
         Aabb b;
         for (int k = 0; k < 3; ++k) b.grow(v[k]);
         scene.grow(b);
@@ -1865,7 +1887,9 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
         pbox.push_back(b);
     }
     const uint32_t n = static_cast<uint32_t>(idx.size());
-    const float inflateAbs = n ? bvh8_inflation_box(scene.lo, scene.hi) : 0.0f;
+    // (the light-space inflation: build_sun_bvh's expression)
+    const float inflateAbs = !n ? 0.0f : sun ? 2.0f * bvh8_inflation_box(scene.lo, scene.hi) + 2e-6f * maxAbs : bvh8_inflation_box(scene.lo, scene.hi);
+    R.inflateAbs = inflateAbs;
     float scale[3], extent[3];
     for (int a = 0; a < 3; ++a) {
         scale[a] = n ? lbvh::mortonScale(scene.lo[a], scene.hi[a]) : 0.0f;
@@ -1882,9 +1906,9 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
         float c[3];
         for (int a = 0; a < 3; ++a) c[a] = 0.5f * pbox[j].lo[a] + 0.5f * pbox[j].hi[a];
         const uint32_t inst = instanceOf(idx[j]);
-        const int cls = inst < classOf.size() ? classOf[inst] : 0;
+        const int cls = sun ? 0 : inst < classOf.size() ? classOf[inst] : 0; // the sun's: one tree for all classes
         classCount[cls]++;
-        key[j] = lbvh::mortonKey(c, scene.lo, scale, static_cast<uint32_t>(cls));
+        key[j] = sun ? lbvh::lightKey(c, scene.lo, scene.hi, layout) : lbvh::mortonKey(c, scene.lo, scale, static_cast<uint32_t>(cls));
     }
     std::vector<uint32_t> sorted(n);
     for (uint32_t j = 0; j < n; ++j) sorted[j] = j;
@@ -1913,7 +1937,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
             const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
             for (size_t i = 0; i < level.size(); ++i) {
                 lbvh::WideNode w;
-                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w);
+                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout);
                 const uint32_t slot0 = static_cast<uint32_t>(next.size());
                 const uint32_t triBase = w.rows.span ? records : 0u;
                 records += w.rows.span;
@@ -1926,10 +1950,19 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
                 nd.tri_stride = static_cast<uint8_t>(w.rows.stride);
                 nd.leaf_mask = static_cast<uint8_t>(w.rows.leaf_mask);
                 R.nodes[levelBase + i] = nd;
+                int64_t lastLow = -1;
                 for (uint32_t s = 0; s < 8u; ++s) {
                     const int k = lbvh::memberInSlot(w, s);
                     if (k < 0) continue;
                     const lbvh::Member& m = w.member[k];
+                    if (sun) {
+                        // the occupied slots' Morton cells ascend in their low w edge, without a gap
+                        int64_t clo[3];
+                        int cfree[3];
+                        lbvh::cellBounds(keys.data(), m.r, layout, clo, cfree);
+                        if (clo[2] < lastLow || s >= static_cast<uint32_t>(w.members)) R.slotOrderViolations++;
+                        lastLow = clo[2];
+                    }
                     if ((w.imask >> s) & 1u) {
                         next.push_back(m);
                     } else {
@@ -1993,7 +2026,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
                 const int cnt = bvh8SlotTriangles(nd, s, t);
                 for (int i = 0; i < cnt; ++i) {
                     float v[3][3];
-                    recordVertices(R.tris[t[i]], v);
+                    boxVertices(R.tris[t[i]], v);
                     for (int q = 0; q < 3; ++q) slot[s].grow(v[q]);
                 }
                 inflateChildBox(slot[s], inflateAbs);
@@ -2022,7 +2055,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
 }
 
 Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
-                                const std::vector<int>* classOf, const float* vertices)
+                                const std::vector<int>* classOf, const float* vertices, const double* lightFrame)
 {
     Bvh8CheckResult R;
     struct Box {
@@ -2104,6 +2137,11 @@ Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std
                     if (classOf && (inst >= classOf->size() || (*classOf)[inst] != c)) R.violations++; // under the wrong class's root
                     float v[6][3];
                     recordVertices(g, v);
+                    if (lightFrame) {
+                        const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
+                        float m;
+                        lbvh::lightVertices(g.t0, e1, e2, lightFrame, v, m);
+                    }
                     int nv = 3;
                     if (vertices) {
                         std::memcpy(v[3], vertices + 9ull * prim, 9 * sizeof(float));
@@ -2186,4 +2224,115 @@ extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n
 extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out)
 {
     return ark_ddgi_debug_lbvh_check_opts(triangles, n, ark::lbvh::kDefaultCriterion, out);
+}
+
+// ark_ddgi_debug.h: the device build of the sun's light-space BVH8 (ddgi_bvh_build.hip:
+// k_lbvh_prims_light, k_lbvh_keys_light, the collapse under lbvh::kSlotsAscendingW) restated
+// serially on the host with the same lbvh_build.h functions, over sun_frame's frame and
+// sunAddRecords' light triangles; then ark_ddgi_debug_sun_bvh_check's ray comparison.
+extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                                   int w_bits, uint64_t* out)
+{
+    using namespace ark;
+    if (out) std::fill(out, out + 16, uint64_t(0));
+    if (w_bits < 0) w_bits = lbvh::kSunKeyBitsW;
+    if (n == 0 || w_bits > lbvh::kMortonBits || (w_bits & 1)) return 1;
+    std::vector<BuildTriangle> tris(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) {
+            tris[i].v0[a] = triangles[9 * i + a];
+            tris[i].v1[a] = triangles[9 * i + 3 + a];
+            tris[i].v2[a] = triangles[9 * i + 6 + a];
+        }
+        tris[i].instance = 0;
+        tris[i].primitive = static_cast<uint32_t>(i);
+        tris[i].flip_facing = 0;
+    }
+    SunBvhInput in;
+    sun_frame(sun_dir, in.frame);
+    sun_add_triangles(in, tris);
+    const std::vector<GpuTriangle> world = in.world;
+    double frame[3][3];
+    std::memcpy(frame, in.frame, sizeof(frame));
+    // the host's tree of the same triangles: its inflation and its cost
+    BvhBuildOptions opt;
+    opt.threads = 8;
+    Bvh8CollapseOptions copt;
+    Bvh8BuildResult sah;
+    if (!build_sun_bvh(in, opt, copt, sah)) return 1;
+    LbvhSunOptions so;
+    std::memcpy(so.frame, frame, sizeof(so.frame));
+    so.wBits = w_bits;
+    const std::vector<int> classOf(1, 0);
+    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so);
+    if (r.nodes.empty() || r.roots[0] != 0) return 1;
+    // structure: one tree from node 0, each depth one range behind the depth above's, every
+    // record the input's bit for bit (the light-space boxes are covered by the ray comparison:
+    // check_bvh8_full's containment is of world coordinates)
+    uint64_t violations = r.slotOrderViolations;
+    std::string why;
+    const int32_t root = 0;
+    if (!checkBvh8Structure(r.nodes, r.tris, &root, 1, why)) violations++;
+    std::vector<uint32_t> order, offsets;
+    if (!bvhLevelOrder(r.nodes.data(), r.nodes.size(), &root, 1, order, offsets) || order != r.order || offsets != r.levelOffsets) violations++;
+    if (offsets.size() != static_cast<size_t>(r.depth) + 1u) violations++;
+    {
+        // bvhLevelOrder's levels, deepest first, must be consecutive ranges ending at the node count
+        uint32_t end = static_cast<uint32_t>(r.nodes.size());
+        for (size_t l = 0; l + 1 < offsets.size(); ++l) {
+            const uint32_t cnt = offsets[l + 1] - offsets[l];
+            for (uint32_t k = 0; k < cnt; ++k)
+                if (order[offsets[l] + k] != end - cnt + k) {
+                    violations++;
+                    break;
+                }
+            end -= cnt;
+        }
+        if (end != 0) violations++;
+    }
+    uint64_t leafChildren = 0;
+    for (const GpuBvh8Node& nd : r.nodes) {
+        if (nd.leaf_mask & nd.imask) violations++;
+        leafChildren += static_cast<uint64_t>(__builtin_popcount(nd.leaf_mask));
+    }
+    std::vector<uint32_t> seen(n, 0);
+    for (size_t i = 0; i < r.tris.size(); ++i) {
+        if (isHoleTriangle(r.tris[i])) continue;
+        uint32_t prim;
+        std::memcpy(&prim, &r.tris[i].t2[2], 4);
+        if (prim >= n || r.perm[i] != prim || std::memcmp(&r.tris[i], &world[prim], sizeof(GpuTriangle)) != 0) violations++;
+        else seen[prim]++;
+    }
+    for (uint64_t i = 0; i < n; ++i)
+        if (seen[i] != 1) violations++;
+    uint32_t ia, ib;
+    std::memcpy(&ia, &r.inflateAbs, 4);
+    std::memcpy(&ib, &in.inflateAbs, 4);
+    const uint64_t mism = sunRayCompare(r.nodes, r.tris, world, frame, sun_dir, origins, n_rays, tmax, out);
+    const float dd = sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2];
+    const float sc = 1.0f / std::sqrt(dd);
+    const float L[3] = { -(sun_dir[0] * sc), -(sun_dir[1] * sc), -(sun_dir[2] * sc) };
+    const std::vector<float> o(origins, origins + 3 * n_rays);
+    if (out) {
+        out[6] = r.nodes.size();
+        out[8] = violations;
+        out[9] = ia != ib ? 1 : 0;
+        out[10] = static_cast<uint64_t>(sun_shadow_cost(r.nodes, r.tris, &root, 1, frame, L, o) * 1e6);
+        out[11] = static_cast<uint64_t>(sun_shadow_cost(sah.nodes, sah.tris, &root, 1, frame, L, o) * 1e6);
+        // the tree's shape (_opts only)
+        out[12] = leafChildren;
+        out[13] = r.depth;
+        out[14] = r.tris.size();
+        out[15] = static_cast<uint64_t>(w_bits);
+    }
+    if (violations || ia != ib) return 1;
+    return mism == 0 ? 0 : 2;
+}
+
+extern "C" int ark_ddgi_debug_sun_lbvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, uint64_t* out)
+{
+    uint64_t all[16];
+    const int rc = ark_ddgi_debug_sun_lbvh_check_opts(triangles, n, sun_dir, origins, n_rays, tmax, ark::lbvh::kSunKeyBitsW, all);
+    if (out) std::copy(all, all + 12, out);
+    return rc;
 }

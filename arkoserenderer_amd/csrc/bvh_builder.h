@@ -137,8 +137,17 @@ struct LbvhHostResult {
     uint32_t opaqueNodes = 0, depth = 0;
     uint64_t triangles = 0, leafChildren = 0;
     double sah = 0.0; // BVH8 SAH cost of the opaque class (node 1, triangle 1), as Bvh8BuildResult::sah_cost
+    float inflateAbs = 0.0f;            // the boxes' absolute inflation
+    uint64_t slotOrderViolations = 0;   // sun: nodes whose occupied slots do not ascend in their cells' low w edge
 };
-LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion);
+// sun: the light-space BVH8 of the sun's shadow rays instead (k_lbvh_prims_light /
+// k_lbvh_keys_light): one tree over every class (roots[0]), keys and boxes of the records'
+// light coordinates in `frame` (rows u, v, w), w given wBits of the key, slots by ascending w
+struct LbvhSunOptions {
+    double frame[9];
+    int wBits = lbvh::kSunKeyBitsW;
+};
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun = nullptr);
 
 // The full check of a BVH8 set (ark_ddgi_debug_lbvh_check, ark_ddgi_debug_world_bvh_check):
 // every class's nodes one contiguous range from its root (counted in violations; depths
@@ -147,13 +156,14 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const st
 // plane exactly decodable, every record that is not a hole in exactly one leaf, under its
 // class's root (classOf: instance -> class, null: unchecked), its vertices (v0, v0 + e1,
 // v0 + e2; with `vertices`, also the 9 floats of its primitive) inside the decoded box of
-// its leaf slot and of every ancestor.
+// its leaf slot and of every ancestor. lightFrame (rows u, v, w): the sun's light-space BVH,
+// whose boxes hold the records' light coordinates (lbvh::lightVertices) instead.
 struct Bvh8CheckResult {
     uint64_t violations = 0, nodes = 0, leafChildren = 0, internalChildren = 0, maxDepth = 0, triangles = 0;
     uint64_t notContiguous = 0, notBreadthFirst = 0;
 };
 Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
-                                const std::vector<int>* classOf, const float* vertices);
+                                const std::vector<int>* classOf, const float* vertices, const double* lightFrame = nullptr);
 
 // Absolute box inflation for the BVH8 slab test: 1e-6 of the diagonal of the
 // bounding box of nTriangles world-space triangles (9 floats each). It bounds

@@ -9,6 +9,11 @@
 //                     record indices compacted, the per-class counts, the all-class
 //                     scene box of the vertices (wave reduction, then atomics)
 //   k_lbvh_keys       class << 60 | Morton code of each survivor's centroid
+//   k_lbvh_prims_light / k_lbvh_keys_light   the same for the sun's light-space BVH8
+//                     (ARK_DDGI_FLAG_GPU_REBUILD_SUN): one tree over every class, the box
+//                     and the keys of the records' light coordinates, the largest |world
+//                     coordinate|; the survivors compacted by one ballot and one atomic add
+//                     per wave
 //   (rocPRIM radix_sort_pairs over the 62 key bits)
 //   k_lbvh_hierarchy  one thread per BVH2 internal node of a class range: its split
 //   k_lbvh_collapse   one level of one class, one thread per BVH8 node of the work
@@ -107,6 +112,81 @@ __global__ void __launch_bounds__(256) k_lbvh_keys(const GpuTriangle* __restrict
     keys[j] = lbvh::mortonKey(c, lo, scale, classOf[inst]);
 }
 
+// A record's light-space box (lbvh::lightVertices: the coordinates build_sun_bvh and the
+// refit box) and its largest |world coordinate|
+__device__ __forceinline__ void recordLightBox(const GpuTriangle* __restrict__ rec, const double* F, float lo[3], float hi[3], float& maxAbs, uint32_t& instance)
+{
+    const float4* q = reinterpret_cast<const float4*>(rec);
+    const float4 a = q[0], b = q[1], c = q[2];
+    instance = __float_as_uint(c.y);
+    const float v0[3] = { a.x, a.y, a.z }, e1[3] = { a.w, b.x, b.y }, e2[3] = { b.z, b.w, c.x };
+    float L[3][3];
+    lbvh::lightVertices(v0, e1, e2, F, L, maxAbs);
+    for (int k = 0; k < 3; ++k) {
+        lo[k] = fminf(L[0][k], fminf(L[1][k], L[2][k]));
+        hi[k] = fmaxf(L[0][k], fmaxf(L[1][k], L[2][k]));
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_prims_light(const GpuTriangle* __restrict__ snap, uint32_t records, uint32_t instances, LbvhFrame frame,
+                                                          uint32_t* __restrict__ idx, LbvhHeader* __restrict__ hdr)
+{
+    const uint32_t i = blockIdx.x * 256u + threadIdx.x;
+    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+    float maxAbs = 0.0f;
+    bool live = false;
+    if (i < records) {
+        const uint32_t inst = __float_as_uint(reinterpret_cast<const float4*>(snap + i)[2].y);
+        if (inst != kHoleInstance) {
+            if (inst >= instances) {
+                atomicOr(&hdr->error, kLbvhErrorInstance);
+            } else {
+                uint32_t unused;
+                recordLightBox(snap + i, frame.m, lo, hi, maxAbs, unused);
+                live = true;
+            }
+        }
+    }
+    // the survivors' record indices: a rank within the wave, one atomic add per wave
+    const uint64_t alive = __ballot(live);
+    const uint32_t rank = __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(alive >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(alive), 0u));
+    uint32_t base = 0;
+    if ((threadIdx.x & 63u) == 0u && alive) base = atomicAdd(&hdr->prims, static_cast<uint32_t>(__popcll(alive)));
+    base = __shfl(base, 0, 64);
+    if (live) idx[base + rank] = i; // at most `records` survivors: in bounds
+    for (int m = 1; m < 64; m <<= 1) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = fminf(lo[a], __shfl_xor(lo[a], m, 64));
+            hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m, 64));
+        }
+        maxAbs = fmaxf(maxAbs, __shfl_xor(maxAbs, m, 64));
+    }
+    if ((threadIdx.x & 63u) == 0u && alive) {
+        for (int a = 0; a < 3; ++a) {
+            atomicMin(&hdr->lo[a], orderedBits(lo[a]));
+            atomicMax(&hdr->hi[a], orderedBits(hi[a]));
+        }
+        atomicMax(&hdr->maxAbs, __float_as_uint(maxAbs));
+    }
+}
+
+__global__ void __launch_bounds__(256) k_lbvh_keys_light(const GpuTriangle* __restrict__ snap, const uint32_t* __restrict__ idx, const LbvhHeader* __restrict__ hdr,
+                                                         LbvhFrame frame, int wBits, uint64_t* __restrict__ keys)
+{
+    const uint32_t j = blockIdx.x * 256u + threadIdx.x;
+    if (j >= hdr->prims) return;
+    float blo[3], bhi[3], m, lo[3], hi[3], c[3];
+    uint32_t inst;
+    recordLightBox(snap + idx[j], frame.m, blo, bhi, m, inst);
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = fromOrdered(hdr->lo[a]);
+        hi[a] = fromOrdered(hdr->hi[a]);
+        c[a] = 0.5f * blo[a] + 0.5f * bhi[a]; // the centre of the triangle's light-space box
+    }
+    const lbvh::KeyLayout layout = { wBits };
+    keys[j] = lbvh::lightKey(c, lo, hi, layout);
+}
+
 __global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t* __restrict__ split)
 {
     const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
@@ -120,7 +200,8 @@ __global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a)
     if (i >= a.count) return;
     const lbvh::Member top = a.items ? a.items[i] : a.root;
     lbvh::WideNode w;
-    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w);
+    const lbvh::KeyLayout layout = { a.wBits };
+    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w, a.slotRule, layout);
     uint32_t slot0 = 0;
     if (w.internal) {
         slot0 = atomicAdd(&a.counters[kLbvhNextCount], w.internal);
@@ -164,7 +245,7 @@ __global__ void __launch_bounds__(256) k_lbvh_fill(float4* __restrict__ tris, ui
     q[0] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     q[1] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
     q[2] = make_float4(0.0f, r < records ? __uint_as_float(kHoleInstance) : 0.0f, 0.0f, 0.0f);
-    if (r < records) perm[r] = 0xffffffffu;
+    if (r < records && perm) perm[r] = 0xffffffffu; // (the sun's BVH needs no perm)
 }
 
 __global__ void __launch_bounds__(256) k_lbvh_scatter(const float4* __restrict__ snap, const uint32_t* __restrict__ sorted, const uint32_t* __restrict__ position,
@@ -179,7 +260,7 @@ __global__ void __launch_bounds__(256) k_lbvh_scatter(const float4* __restrict__
     d[0] = q[0];
     d[1] = q[1];
     d[2] = q[2];
-    perm[pos] = src;
+    if (perm) perm[pos] = src;
 }
 
 } // namespace dev
@@ -195,6 +276,19 @@ hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const ui
     hipLaunchKernelGGL(dev::k_lbvh_prims, grid, dim3(256), 0, s, snap, records, classOf, instances, idx, hdr);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     hipLaunchKernelGGL(dev::k_lbvh_keys, grid, dim3(256), 0, s, snap, idx, classOf, hdr, keys);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_prims_light(const GpuTriangle* snap, uint32_t records, uint32_t instances, const LbvhFrame& frame, int wBits, uint32_t* idx, uint64_t* keys,
+                                   LbvhHeader* hdr, hipStream_t s)
+{
+    hipError_t e = hipMemsetAsync(hdr, 0, sizeof(LbvhHeader), s);
+    if (e == hipSuccess) e = hipMemsetAsync(hdr->lo, 0xff, sizeof(hdr->lo), s);
+    if (e != hipSuccess || records == 0) return e;
+    const dim3 grid((records + 255u) / 256u);
+    hipLaunchKernelGGL(dev::k_lbvh_prims_light, grid, dim3(256), 0, s, snap, records, instances, frame, idx, hdr);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    hipLaunchKernelGGL(dev::k_lbvh_keys_light, grid, dim3(256), 0, s, snap, idx, hdr, frame, wBits, keys);
     return hipGetLastError();
 }
 

@@ -312,6 +312,7 @@ struct LbvhHeader {
     uint32_t classCount[3]; // of each hit-mask class
     uint32_t error;         // kLbvhError*
     uint32_t lo[3], hi[3];
+    uint32_t maxAbs;        // k_lbvh_prims_light: the largest |world coordinate|, fp32 bits (never negative: ordered as they are)
 };
 constexpr uint32_t kLbvhErrorInstance = 1u; // a record of an instance the job does not know
 // the box's coordinate of an ordered word
@@ -340,10 +341,20 @@ struct LbvhCollapseArgs {
     uint32_t* counters;        // kLbvhNextCount zeroed per level
     float extent[3];           // of the scene box
     int criterion;             // lbvh::Criterion
+    int slotRule;              // lbvh::SlotRule
+    int wBits;                 // lbvh::KeyLayout of the keys
 };
 // hdr zeroed, then the survivors' record indices (idx), counts and box, then their keys
 hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const uint32_t* classOf, uint32_t instances, uint32_t* idx, uint64_t* keys,
                              LbvhHeader* hdr, hipStream_t s);
+// The same for the sun's light-space BVH8 (one tree over every class): the box of the
+// records' light coordinates in `frame` (rows u, v, w; lbvh::lightVertices) and the largest
+// |world coordinate| (hdr->maxAbs), then the light-space keys (lbvh::lightKey, wBits)
+struct LbvhFrame {
+    double m[9];
+};
+hipError_t launch_lbvh_prims_light(const GpuTriangle* snap, uint32_t records, uint32_t instances, const LbvhFrame& frame, int wBits, uint32_t* idx, uint64_t* keys,
+                                   LbvhHeader* hdr, hipStream_t s);
 // rocPRIM's radix sort of the (key, record index) pairs; temp null: tempBytes out
 hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn, uint32_t* valuesOut, uint32_t count,
                             hipStream_t s);

@@ -94,19 +94,8 @@ __global__ void __launch_bounds__(256) k_node_masks(const GpuBvh8Node* __restric
 // frame in double and rounded to fp32), and the largest |world coordinate|.
 __device__ __forceinline__ void lightVertices(const float4 t0, const float4 t1, const float4 t2, const double* F, float L[3][3], float& maxAbs)
 {
-    double V[3][3];
-    const double e1[3] = { t0.w, t1.x, t1.y }, e2[3] = { t1.z, t1.w, t2.x };
-    V[0][0] = t0.x;
-    V[0][1] = t0.y;
-    V[0][2] = t0.z;
-    maxAbs = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        V[1][a] = V[0][a] + e1[a];
-        V[2][a] = V[0][a] + e2[a];
-        maxAbs = fmaxf(maxAbs, static_cast<float>(fmax(fabs(V[0][a]), fmax(fabs(V[1][a]), fabs(V[2][a])))));
-    }
-    for (int k = 0; k < 3; ++k)
-        for (int r = 0; r < 3; ++r) L[k][r] = static_cast<float>(F[3 * r + 0] * V[k][0] + F[3 * r + 1] * V[k][1] + F[3 * r + 2] * V[k][2]);
+    const float v0[3] = { t0.x, t0.y, t0.z }, e1[3] = { t0.w, t1.x, t1.y }, e2[3] = { t1.z, t1.w, t2.x };
+    lbvh::lightVertices(v0, e1, e2, F, L, maxAbs);
 }
 
 // bvh_builder.cpp writeNode's inflation of a child box: relative to its magnitude and

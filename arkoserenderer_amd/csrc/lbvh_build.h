@@ -19,6 +19,12 @@
 //   assignSlots    internal children into the octant slot of their Morton cell's centre
 //                  relative to the node's cell, leaf members into the slots left over
 //   placeRows      the leaf slots' triangle rows of one node (GpuBvh8Node)
+//
+// The sun's light-space BVH8 (ARK_DDGI_FLAG_GPU_REBUILD_SUN) is built by the same functions
+// over one range [0, n): lightVertices (a record's vertices in the sun's frame, shared with
+// build_sun_bvh and the refit), lightKey (a Morton code of the light-space box's centre,
+// class bits 0, w given wBits of the 60 and u, v the rest: KeyLayout) and the slot rule
+// kSlotsAscendingW (every ray goes along +w and visits a node's children in slot order).
 #pragma once
 
 #include <stdint.h>
@@ -37,6 +43,50 @@ namespace lbvh {
 constexpr int kMortonBits = 20;         // per axis
 constexpr int kKeyBits = 62;            // 60 Morton bits + 2 class bits: the sort's end bit
 constexpr uint32_t kNoSlot = 0xffu;
+
+// How the 60 Morton bits are split across the axes: w bits for axis 2, (60 - w) / 2 for
+// axes 0 and 1 each. From the top the key interleaves pairs of axes 0 and 1 (axis 0
+// higher) - the bits they have more than axis 2 - then w triples (axis 0 highest).
+// w = kMortonBits is the world's 20 / 20 / 20.
+struct KeyLayout {
+    int w;
+};
+constexpr KeyLayout kWorldLayout = { kMortonBits };
+// The light-space key's split (EXPERIMENTS.md "Device LBVH build": the cheapest of the
+// candidates by sun_shadow_cost on the soup and the city block)
+constexpr int kSunKeyBitsW = 18;
+
+ARK_LBVH_FN int axisBits(const KeyLayout& L, int a) { return a == 2 ? L.w : (60 - L.w) / 2; }
+
+// Of the top p Morton bits of a key, the number that belong to each axis
+ARK_LBVH_FN void prefixBits(const KeyLayout& L, int p, int n[3])
+{
+    const int pairs = (60 - L.w) / 2 - L.w; // top bits of axes 0 and 1 that stand in pairs
+    if (p <= 2 * pairs) {
+        n[0] = (p + 1) / 2;
+        n[1] = p / 2;
+        n[2] = 0;
+    } else {
+        const int q = p - 2 * pairs;
+        n[0] = pairs + (q + 2) / 3;
+        n[1] = pairs + (q + 1) / 3;
+        n[2] = q / 3;
+    }
+}
+
+// The key's bit that holds bit b (0: the lowest) of axis a's cell
+ARK_LBVH_FN int keyBit(const KeyLayout& L, int a, int b)
+{
+    if (a == 2) return 3 * b;
+    if (b < L.w) return 3 * b + (2 - a);
+    return 3 * L.w + 2 * (b - L.w) + (1 - a);
+}
+
+// Which slots the members of a node take (assignSlots)
+enum SlotRule : int {
+    kSlotsOctant = 0,     // the world BVHs: rays of every direction, visited in slot ^ ray octant order
+    kSlotsAscendingW = 1, // the sun's BVH: every ray along +w, visited in slot order
+};
 
 // A member of a cut: the sorted primitives [first, last] (global indices)
 struct Range {
@@ -93,6 +143,60 @@ ARK_LBVH_FN uint64_t mortonKey(const float c[3], const float lo[3], const float 
     return static_cast<uint64_t>(cls) << 60 | m;
 }
 
+// The light coordinates of a record's three vertices (v0, v0 + e1, v0 + e2 in double, each
+// rotated into the frame F - rows u, v, w - in double and rounded to fp32) and the largest
+// |world coordinate|: what build_sun_bvh boxes, the refit of the light-space BVH boxes
+// again (k_refit_nodes) and the device build's keys and scene box are taken from.
+ARK_LBVH_FN void lightVertices(const float v0[3], const float e1[3], const float e2[3], const double* F, float L[3][3], float& maxAbs)
+{
+    double V[3][3];
+    maxAbs = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        V[0][a] = v0[a];
+        V[1][a] = V[0][a] + static_cast<double>(e1[a]);
+        V[2][a] = V[0][a] + static_cast<double>(e2[a]);
+        double m = __builtin_fabs(V[0][a]);
+        for (int k = 1; k < 3; ++k) m = m < __builtin_fabs(V[k][a]) ? __builtin_fabs(V[k][a]) : m;
+        const float mf = static_cast<float>(m);
+        maxAbs = maxAbs < mf ? mf : maxAbs;
+    }
+    for (int k = 0; k < 3; ++k)
+        for (int r = 0; r < 3; ++r) L[k][r] = static_cast<float>(F[3 * r + 0] * V[k][0] + F[3 * r + 1] * V[k][1] + F[3 * r + 2] * V[k][2]);
+}
+
+// The cell of coordinate c in [lo, lo + extent] on a grid of 2^bits cells: scale = 2^bits / extent
+ARK_LBVH_FN float layoutScale(float lo, float hi, int bits)
+{
+    const float ext = hi - lo;
+    union {
+        uint32_t u;
+        float f;
+    } s;
+    s.u = static_cast<uint32_t>(127 + bits) << 23;
+    return ext > 0.0f ? s.f / ext : 0.0f;
+}
+
+ARK_LBVH_FN uint32_t layoutCell(float c, float lo, float scale, int bits)
+{
+    float q = (c - lo) * scale;
+    q = q > 0.0f ? q : 0.0f; // NaN to 0
+    const uint32_t last = (1u << bits) - 1u;
+    return q < static_cast<float>(last) ? static_cast<uint32_t>(q) : last;
+}
+
+// The light-space key: the Morton code (layout L) of the centre c of a record's light-space
+// box inside the scene's light-space box; the class bits are 0 (one tree for all classes)
+ARK_LBVH_FN uint64_t lightKey(const float c[3], const float lo[3], const float hi[3], const KeyLayout& L)
+{
+    uint64_t key = 0;
+    for (int a = 0; a < 3; ++a) {
+        const int bits = axisBits(L, a);
+        const uint32_t cell = layoutCell(c[a], lo[a], layoutScale(lo[a], hi[a], bits), bits);
+        for (int b = 0; b < bits; ++b) key |= static_cast<uint64_t>((cell >> b) & 1u) << keyBit(L, a, b);
+    }
+    return key;
+}
+
 // Length of the common prefix of the (key, index) pairs i and j of the class range
 // [lo, hi); -1 when j lies outside it
 ARK_LBVH_FN int delta(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t i, int64_t j)
@@ -147,11 +251,12 @@ struct Member {
 
 // The Morton cell of a range: the axis-wise cell counts (log2) the common prefix of its
 // first and last key leaves free, as a relative surface area (extent: the scene box's)
-ARK_LBVH_FN float cellArea(const uint64_t* keys, const Range& r, const float extent[3])
+ARK_LBVH_FN float cellArea(const uint64_t* keys, const Range& r, const float extent[3], const KeyLayout& L = kWorldLayout)
 {
     const uint64_t x = (keys[r.first] ^ keys[r.last]) << 4; // the class bits are equal
     const int p = x ? clz64(x) : 60;                         // common Morton bits, x first
-    const int n[3] = { (p + 2) / 3, (p + 1) / 3, p / 3 };
+    int n[3];
+    prefixBits(L, p, n);
     float d[3];
     for (int a = 0; a < 3; ++a) {
         // extent * 2^-n, exactly
@@ -168,7 +273,8 @@ ARK_LBVH_FN float cellArea(const uint64_t* keys, const Range& r, const float ext
 // The members of the BVH8 node over `top` (top.node: its BVH2 node when it holds more
 // than one primitive): out[0 .. return). A node of at most kBvh8MaxLeafSize triangles
 // (only a class's root) is one leaf member.
-ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], Member out[8])
+ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], Member out[8],
+                          const KeyLayout& L = kWorldLayout)
 {
     if (count(top.r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
         out[0] = top;
@@ -198,7 +304,7 @@ ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Mem
         float best = -1.0f;
         for (int k = 0; k < n; ++k) {
             if (count(out[k].r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) continue;
-            const float v = criterion == kOpenLargestCell ? cellArea(keys, out[k].r, extent) : static_cast<float>(count(out[k].r));
+            const float v = criterion == kOpenLargestCell ? cellArea(keys, out[k].r, extent, L) : static_cast<float>(count(out[k].r));
             if (v > best) {
                 best = v;
                 open = k;
@@ -210,21 +316,32 @@ ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Mem
     return n;
 }
 
-// The centre of a range's Morton cell in half cells of the finest grid, per axis
-ARK_LBVH_FN void cellCentre(const uint64_t* keys, const Range& r, int64_t c[3])
+// The Morton cell of a range per axis: its low edge in cells of the axis's finest grid and
+// the log2 of its width in them
+ARK_LBVH_FN void cellBounds(const uint64_t* keys, const Range& r, const KeyLayout& L, int64_t lo[3], int free[3])
 {
     const uint64_t k = keys[r.first];
     const uint64_t x = (k ^ keys[r.last]) << 4;
     const int p = x ? clz64(x) : 60;
-    const int n[3] = { (p + 2) / 3, (p + 1) / 3, p / 3 };
+    int n[3];
+    prefixBits(L, p, n);
     for (int a = 0; a < 3; ++a) {
-        // the axis's 20 bits of the first key, its low (20 - n) bits replaced by the cell's middle
+        // the axis's bits of the first key, its low (bits - n) ones cleared
+        const int bits = axisBits(L, a);
         uint32_t v = 0;
-        for (int b = 0; b < kMortonBits; ++b) v |= static_cast<uint32_t>((k >> (3 * b + (2 - a))) & 1u) << b;
-        const int free = kMortonBits - n[a];
-        const int64_t lo = static_cast<int64_t>(v >> free) << free;
-        c[a] = 2 * lo + (int64_t(1) << free);
+        for (int b = 0; b < bits; ++b) v |= static_cast<uint32_t>((k >> keyBit(L, a, b)) & 1u) << b;
+        free[a] = bits - n[a];
+        lo[a] = static_cast<int64_t>(v >> free[a]) << free[a];
     }
+}
+
+// The centre of a range's Morton cell in half cells of the finest grid, per axis
+ARK_LBVH_FN void cellCentre(const uint64_t* keys, const Range& r, int64_t c[3], const KeyLayout& L = kWorldLayout)
+{
+    int64_t lo[3];
+    int free[3];
+    cellBounds(keys, r, L, lo, free);
+    for (int a = 0; a < 3; ++a) c[a] = 2 * lo[a] + (int64_t(1) << free[a]);
 }
 
 // Slots of a node's members. Internal members (more than kBvh8MaxLeafSize triangles) take
@@ -233,8 +350,29 @@ ARK_LBVH_FN void cellCentre(const uint64_t* keys, const Range& r, int64_t c[3])
 // axes, then the lowest). Leaf members decide only which triangles a hit slot adds, so
 // they fill the free slots in ascending order, most triangles first, which keeps the
 // node's rows compact (as the host collapse does). slotOf[k]: the slot of member k.
-ARK_LBVH_FN void assignSlots(const uint64_t* keys, const Range& node, const Member* m, int n, uint32_t slotOf[8])
+// kSlotsAscendingW (the sun's BVH, whose rays all go along +w and visit a node's children
+// in slot order, as the host collapse's slot_sort_axis = 2): internal and leaf members
+// alike take slots 0, 1, ... in ascending order of the low w edge of their Morton cell,
+// ties to the lower first key; placeRows finds rows for any such assignment (stride 8).
+ARK_LBVH_FN void assignSlots(const uint64_t* keys, const Range& node, const Member* m, int n, uint32_t slotOf[8], int rule = kSlotsOctant,
+                             const KeyLayout& L = kWorldLayout)
 {
+    if (rule == kSlotsAscendingW) {
+        int64_t low[8];
+        for (int k = 0; k < n; ++k) {
+            int64_t lo[3];
+            int free[3];
+            cellBounds(keys, m[k].r, L, lo, free);
+            low[k] = lo[2];
+        }
+        for (int k = 0; k < n; ++k) {
+            uint32_t rank = 0;
+            for (int j = 0; j < n; ++j)
+                if (low[j] < low[k] || (low[j] == low[k] && m[j].r.first < m[k].r.first)) ++rank;
+            slotOf[k] = rank;
+        }
+        return;
+    }
     uint32_t taken = 0;
     int64_t pc[3];
     cellCentre(keys, node, pc);
@@ -323,10 +461,11 @@ struct WideNode {
     Rows rows;
 };
 
-ARK_LBVH_FN void planNode(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], WideNode& w)
+ARK_LBVH_FN void planNode(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], WideNode& w,
+                          int slotRule = kSlotsOctant, const KeyLayout& L = kWorldLayout)
 {
-    w.members = selectCut(keys, split, top, criterion, extent, w.member);
-    assignSlots(keys, top.r, w.member, w.members, w.slotOf);
+    w.members = selectCut(keys, split, top, criterion, extent, w.member, L);
+    assignSlots(keys, top.r, w.member, w.members, w.slotOf, slotRule, L);
     uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     w.imask = 0;
     w.internal = 0;

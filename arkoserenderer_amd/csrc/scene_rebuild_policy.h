@@ -22,13 +22,14 @@ struct RebuildState {
     bool sunFailedHere = false;  // a sun build failed for this direction and scene version
     bool worldRebuildFailed = false;
     bool worldGpuBuilt = false;  // the installed world BVHs are a device build
+    bool sunGpuBuilt = false;    // the light-space BVH installed for the caller's sun direction is a device build
     uint32_t refitsSinceBuild = 0, sunRefitsSinceBuild = 0; // refits since the installed BVHs' snapshots
     uint32_t flags = 0;          // ArkDdgiDesc.flags of the caller
     uint8_t lastBackground = kBackgroundNone;
     bool sunOnly = false;        // set_lights: the world BVHs' rebuilds are left to the next update or set_instances
 };
 
-enum class RebuildStart { None, Sun, WorldHost, WorldDevice };
+enum class RebuildStart { None, Sun, WorldHost, WorldDevice, SunDevice };
 
 // The one build to start now.
 //  - A light-space BVH missing for the caller's sun starts at once, even beside a running
@@ -43,26 +44,34 @@ enum class RebuildStart { None, Sun, WorldHost, WorldDevice };
 //  - ARK_DDGI_FLAG_GPU_REBUILD: loosened world BVHs are rebuilt on the device; once the
 //    motion has stopped (a device build installed, no refit since its snapshot) one host
 //    rebuild replaces the LBVH with the SAH tree a static scene traces faster.
+//  - ARK_DDGI_FLAG_GPU_REBUILD_SUN: a missing or loosened light-space BVH is built on the
+//    device (SunDevice), under the conditions above; once the installed one is a device
+//    build for the caller's direction and no refit has come since its snapshot, one host
+//    rebuild (Sun) replaces it - the settle rule, in turns with a world settle rebuild like
+//    any other pair of background builds. Without the bit nothing here changes.
 //  - sunOnly never starts a world rebuild; the sun's turn there yields to loosened world
 //    BVHs (not to a settle rebuild).
 inline RebuildStart rebuildToStart(const RebuildState& q)
 {
     const bool background = !(q.flags & ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD);
-    bool sunMissing = false, sunLoosened = false;
+    const bool sunDevice = (q.flags & ARK_DDGI_FLAG_GPU_REBUILD_SUN) != 0;
+    bool sunMissing = false, sunLoosened = false, sunSettle = false;
     if (q.sunWanted && q.hasSun && !q.sunJobRunning && q.requestStable && !q.sunFailedHere) {
         sunMissing = !q.sunInstalled;
         sunLoosened = q.sunInstalled && q.sunRefitsSinceBuild != 0 && background;
+        sunSettle = sunDevice && q.sunInstalled && q.sunGpuBuilt && q.sunRefitsSinceBuild == 0;
     }
-    if (sunMissing) return RebuildStart::Sun;
+    if (sunMissing) return sunDevice ? RebuildStart::SunDevice : RebuildStart::Sun;
     if (q.sunJobRunning || q.worldJobRunning) return RebuildStart::None;
     const bool worldOk = background && !q.worldRebuildFailed;
     const bool worldLoosened = worldOk && q.refitsSinceBuild != 0;
     const bool worldSettle = worldOk && (q.flags & ARK_DDGI_FLAG_GPU_REBUILD) && q.worldGpuBuilt && q.refitsSinceBuild == 0;
     const bool world = !q.sunOnly && (worldLoosened || worldSettle);
-    if (world && (!sunLoosened || q.lastBackground != kBackgroundWorld))
+    const bool sun = sunLoosened || sunSettle;
+    if (world && (!sun || q.lastBackground != kBackgroundWorld))
         return worldLoosened && (q.flags & ARK_DDGI_FLAG_GPU_REBUILD) ? RebuildStart::WorldDevice : RebuildStart::WorldHost;
     const bool sunYields = q.sunOnly ? worldLoosened : world;
-    if (sunLoosened && (!sunYields || q.lastBackground != kBackgroundSun)) return RebuildStart::Sun;
+    if (sun && (!sunYields || q.lastBackground != kBackgroundSun)) return sunLoosened && sunDevice ? RebuildStart::SunDevice : RebuildStart::Sun;
     return RebuildStart::None;
 }
 

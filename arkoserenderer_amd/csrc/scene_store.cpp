@@ -54,6 +54,11 @@ struct SunJob {
     double frame[9] {};
     float ms = 0.0f;
     bool ok = false;
+    // runSunJobGpu: the device built the result; or it handed the job to the host build
+    // (t0: the job's start, so that ms stays the whole job's wall time)
+    bool gpu = false, gpuFallback = false, gpuFallbackCounted = false;
+    uint32_t instances = 0; // of the scene (the device build checks the records' against it)
+    std::chrono::steady_clock::time_point t0 {};
     ~SunJob()
     {
         if (t.joinable()) t.join();
@@ -386,7 +391,7 @@ hipError_t snapshotRecords(SceneStore& st, DeviceBuffer& snap, hipEvent_t& ev, h
 // job->dir on the host (as set_scene builds it), uploaded into job->bvh.
 void runSunJob(SunJob* job, int device, uint64_t count, int threads)
 {
-    const auto t0 = std::chrono::steady_clock::now();
+    const auto t0 = job->gpuFallback ? job->t0 : std::chrono::steady_clock::now();
     bool ok = hipSetDevice(device) == hipSuccess;
     hipStream_t s = nullptr;
     ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
@@ -510,9 +515,28 @@ bool isDeviceFault(hipError_t e)
            e == hipErrorNoDevice || e == hipErrorInvalidDevice;
 }
 
-// The device build of runWorldJobGpu on `s`: hipSuccess and `why` empty when job holds the
-// result; `why` set when the host has to build this scene.
-hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
+// What the device builds of the world BVH8s and of the sun's light-space BVH8 differ in
+// (buildLbvhGpu): the class ranges, the key kernels, the slot rule and the refit's boxes.
+struct LbvhGpuBuild {
+    // in
+    const GpuTriangle* snap = nullptr; // the snapshot's records, ready once evSnap has completed
+    hipEvent_t evSnap = nullptr;
+    uint32_t records = 0;
+    std::vector<uint32_t> classHost;   // instance -> class (its size: the instances)
+    bool light = false;                // the sun's: one range over every class, keys and boxes in `frame`
+    double frame[9] {};
+    int slotRule = lbvh::kSlotsOctant, wBits = lbvh::kMortonBits;
+    DeviceBvh* bvh = nullptr;          // out: buffer, level order (device and offsets), counts, depth, inflateAbs
+    DeviceBuffer* perm = nullptr;      // out: the record order's source indices (null: not wanted)
+    // out
+    int32_t roots[3] { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, prims = 0;
+    std::vector<uint32_t> order;       // the level order on the host
+};
+
+// The device build on `s`: hipSuccess and `why` empty when g.bvh holds the result; `why`
+// set when the host has to build this scene.
+hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
 {
     // Scratch in two allocations (one sized from the snapshot, one from the count of
     // triangles read back): a free waits for the device's streams, frames in flight included
@@ -538,24 +562,31 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
     do {                                      \
         if ((e = (expr)) != hipSuccess) return e; \
     } while (0)
-    if (job->snapRecords == 0 || job->snapRecords > 0x7fffffffull || job->classOf.empty()) {
+    if (g.records == 0 || g.classHost.empty()) {
         why = "no records";
         return hipSuccess;
     }
-    const uint32_t records = static_cast<uint32_t>(job->snapRecords), instances = static_cast<uint32_t>(job->classOf.size());
-    const GpuTriangle* snap = job->snap.as<GpuTriangle>();
-    std::vector<uint32_t> classHost(job->classOf.begin(), job->classOf.end());
+    const uint32_t records = g.records, instances = static_cast<uint32_t>(g.classHost.size());
+    const GpuTriangle* snap = g.snap;
+    const std::vector<uint32_t>& classHost = g.classHost;
     ARK_GB(arenaA.buf.alloc(Arena::pad(instances * 4ull) + Arena::pad(sizeof(LbvhHeader)) + Arena::pad(records * 4ull) + Arena::pad(records * 8ull)));
     w.classOf = arenaA.take(instances * 4ull);
     w.hdr = arenaA.take(sizeof(LbvhHeader));
     w.idx = arenaA.take(records * 4ull);
     w.keys = arenaA.take(records * 8ull);
     ARK_GB(hipMemcpyAsync(w.classOf.ptr, classHost.data(), instances * 4ull, hipMemcpyHostToDevice, s));
-    ARK_GB(hipStreamWaitEvent(s, job->evSnap, 0));
-    ARK_GB(launch_lbvh_prims(snap, records, w.classOf.as<uint32_t>(), instances, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
+    ARK_GB(hipStreamWaitEvent(s, g.evSnap, 0));
+    if (g.light) {
+        LbvhFrame fr;
+        std::memcpy(fr.m, g.frame, sizeof(fr.m));
+        ARK_GB(launch_lbvh_prims_light(snap, records, instances, fr, g.wBits, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
+    } else {
+        ARK_GB(launch_lbvh_prims(snap, records, w.classOf.as<uint32_t>(), instances, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
+    }
     LbvhHeader hdr {};
     ARK_GB(hipMemcpyAsync(&hdr, w.hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost, s));
     ARK_GB(hipStreamSynchronize(s));
+    if (g.light && !hdr.error) hdr.classCount[0] = hdr.prims; // one range [0, n): the keys' class bits are 0
     if (hdr.error || hdr.prims == 0 || hdr.prims > records || hdr.classCount[0] + hdr.classCount[1] + hdr.classCount[2] != hdr.prims) {
         why = hdr.error ? "record of an unknown instance" : "no triangles";
         return hipSuccess;
@@ -612,11 +643,13 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
     a.position = w.position.as<uint32_t>();
     a.counters = w.counters.as<uint32_t>();
     a.criterion = lbvh::kDefaultCriterion;
+    a.slotRule = g.slotRule;
+    a.wBits = g.wBits;
     std::vector<std::array<uint32_t, 3>> levels; // node counts [depth][class]
     uint32_t nodeTotal = 0, counters[kLbvhCounters] = {};
     for (int c = 0; c < 3; ++c) {
         if (!hdr.classCount[c]) continue;
-        job->roots[c] = static_cast<int32_t>(nodeTotal);
+        g.roots[c] = static_cast<int32_t>(nodeTotal);
         a.items = nullptr;
         a.root.r.first = classLo[c];
         a.root.r.last = classLo[c] + hdr.classCount[c] - 1u;
@@ -649,7 +682,7 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
             pong ^= 1;
         }
         nodeTotal = a.levelBase;
-        if (c == 0) job->opaqueNodes = nodeTotal;
+        if (c == 0) g.opaqueNodes = nodeTotal;
     }
     const uint32_t outRecords = counters[kLbvhRecords];
     if (!(DeviceBvh::bytesFor(nodeTotal, outRecords) < (1ull << 32))) {
@@ -657,23 +690,24 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
         return hipSuccess;
     }
     // the installed buffers, sized from the counts read back
-    DeviceBvh& b = job->bvh;
+    DeviceBvh& b = *g.bvh;
     b.triOffset = DeviceBvh::triOffsetFor(nodeTotal);
     ARK_GB(b.buf.alloc(DeviceBvh::bytesFor(nodeTotal, outRecords)));
-    ARK_GB(job->perm.alloc(std::max<size_t>(16, outRecords * 4ull)));
+    if (g.perm) ARK_GB(g.perm->alloc(std::max<size_t>(16, outRecords * 4ull)));
     GpuBvh8Node* nodes = b.nodes(b.buf);
     GpuTriangle* tris = b.tris(b.buf);
     ARK_GB(hipMemcpyAsync(nodes, w.nodes.ptr, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToDevice, s));
-    ARK_GB(launch_lbvh_scatter(snap, w.idxSorted.as<uint32_t>(), w.position.as<uint32_t>(), tris, job->perm.as<uint32_t>(), n, outRecords, s));
+    ARK_GB(launch_lbvh_scatter(snap, w.idxSorted.as<uint32_t>(), w.position.as<uint32_t>(), tris, g.perm ? g.perm->as<uint32_t>() : nullptr, n, outRecords, s));
     // the refit's level order from the level counts (bvhLevelOrder's format: deepest level
     // first, ascending node index within a level; each class one breadth-first range)
-    std::vector<uint32_t> order;
+    std::vector<uint32_t>& order = g.order;
+    order.clear();
     order.reserve(nodeTotal);
     b.levelOffsets.assign(1, 0u);
     {
         std::vector<std::array<uint32_t, 3>> base(levels.size());
         uint32_t at[3];
-        for (int c = 0; c < 3; ++c) at[c] = job->roots[c] >= 0 ? static_cast<uint32_t>(job->roots[c]) : 0u;
+        for (int c = 0; c < 3; ++c) at[c] = g.roots[c] >= 0 ? static_cast<uint32_t>(g.roots[c]) : 0u;
         for (size_t d = 0; d < levels.size(); ++d)
             for (int c = 0; c < 3; ++c) {
                 base[d][c] = at[c];
@@ -689,11 +723,21 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
     ARK_GB(hipMemcpyAsync(b.order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
     // boxes, grids and planes: the refit over every level, deepest first, every node live
     // (all mask bits set, no instance dirty: no record is touched), the inflation runWorldJob's
+    // or, in light coordinates, build_sun_bvh's (the box and the largest |coordinate| are
+    // min / max reductions: the same bits whatever the order)
     ARK_GB(hipMemsetAsync(w.masks.ptr, 0xff, nodeTotal * 8ull, s));
     ARK_GB(hipMemsetAsync(w.inst.ptr, 0, instances * sizeof(RefitInstance), s));
     RefitBoxArgs ra {};
     ra.inflate = bvh8_inflation_box(lo, hi);
     ra.light = 0;
+    if (g.light) {
+        float maxAbs;
+        std::memcpy(&maxAbs, &hdr.maxAbs, 4);
+        ra.inflate = 2.0f * bvh8_inflation_box(lo, hi) + 2e-6f * maxAbs;
+        ra.light = 1;
+        std::memcpy(ra.frame, g.frame, sizeof(ra.frame));
+    }
+    b.inflateAbs = ra.inflate;
     ra.dirty = ~0ull;
     for (size_t l = 0; l + 1 < b.levelOffsets.size(); ++l)
         ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), b.order.as<uint32_t>() + b.levelOffsets[l], b.levelOffsets[l + 1] - b.levelOffsets[l], ra,
@@ -703,9 +747,94 @@ hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
     b.nodeCount = nodeTotal;
     b.records = outRecords;
     b.depth = static_cast<uint32_t>(levels.size());
-    job->maxLeaf = std::min<uint32_t>(n, static_cast<uint32_t>(kBvh8MaxLeafSize));
-    job->sah = 0.0f; // not evaluated on the device
+    g.prims = n;
     return hipSuccess;
+}
+
+// The device build of runWorldJobGpu: the three classes' BVH8s into job
+hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
+{
+    if (job->snapRecords > 0x7fffffffull) {
+        why = "no records";
+        return hipSuccess;
+    }
+    LbvhGpuBuild g;
+    g.snap = job->snap.as<GpuTriangle>();
+    g.evSnap = job->evSnap;
+    g.records = static_cast<uint32_t>(job->snapRecords);
+    g.classHost.assign(job->classOf.begin(), job->classOf.end());
+    g.bvh = &job->bvh;
+    g.perm = &job->perm;
+    const float inflateAbs = job->bvh.inflateAbs; // (worldCollect sets the installed one's)
+    const hipError_t e = buildLbvhGpu(g, s, why);
+    job->bvh.inflateAbs = inflateAbs;
+    std::copy(g.roots, g.roots + 3, job->roots);
+    job->opaqueNodes = g.opaqueNodes;
+    job->maxLeaf = std::min<uint32_t>(g.prims, static_cast<uint32_t>(kBvh8MaxLeafSize));
+    job->sah = 0.0f; // not evaluated on the device
+    return e;
+}
+
+
+// The sun rebuild's thread with ARK_DDGI_FLAG_GPU_REBUILD_SUN: the same inputs and outputs as
+// runSunJob (job->bvh, levelOrder, frame, inflateAbs, depth, ms), the light-space BVH8 built
+// on the device - one LBVH over every class's records, keyed and boxed in the sun's frame,
+// its slots in ascending w - on a stream of the lowest priority that waits for the snapshot
+// on the device. A scene the device build does not take (no records, 4 GiB, depth, node
+// scratch, an error that is not a device fault) is built by runSunJob within this job; a
+// device fault fails the job (a sun rebuild failure: not retried).
+void runSunJobGpu(SunJob* job, int device, uint64_t count, int threads)
+{
+    job->t0 = std::chrono::steady_clock::now();
+    hipStream_t s = nullptr;
+    std::string why;
+    hipError_t e = hipSetDevice(device);
+    int least = 0, greatest = 0;
+    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
+    if (e == hipSuccess) {
+        double frame[3][3];
+        sun_frame(job->dir, frame);
+        std::memcpy(job->frame, frame, sizeof(job->frame));
+        if (count > 0x7fffffffull) {
+            why = "no records";
+        } else {
+            LbvhGpuBuild g;
+            g.snap = job->snap.as<GpuTriangle>();
+            g.evSnap = job->evSnap;
+            g.records = static_cast<uint32_t>(count);
+            g.classHost.assign(job->instances, 0u); // one tree: only the instance count matters
+            g.light = true;
+            std::memcpy(g.frame, job->frame, sizeof(g.frame));
+            g.slotRule = lbvh::kSlotsAscendingW;
+            g.wBits = lbvh::kSunKeyBitsW;
+            g.bvh = &job->bvh;
+            e = buildLbvhGpu(g, s, why);
+            job->levelOrder = std::move(g.order);
+            // (installSunBvh uploads the level order from the host, as after a host build)
+            job->bvh.order.release();
+        }
+    }
+    if (s) (void)hipStreamDestroy(s);
+    if (e == hipSuccess && why.empty()) {
+        job->gpu = true;
+        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
+        job->ok = true;
+        job->done.store(true, std::memory_order_release);
+        return;
+    }
+    if (isDeviceFault(e)) {
+        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
+        job->ok = false;
+        job->done.store(true, std::memory_order_release);
+        return;
+    }
+    // the host build from the same snapshot
+    job->bvh.release();
+    job->bvh = DeviceBvh {};
+    job->levelOrder.clear();
+    job->gpuFallback = true;
+    runSunJob(job, device, count, threads);
 }
 
 // The world rebuild's thread with ARK_DDGI_FLAG_GPU_REBUILD: the same inputs and outputs as
@@ -886,6 +1015,10 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
     }
     if (st.sunJob && st.sunJob->done.load(std::memory_order_acquire)) {
         SunJob& j = *st.sunJob;
+        if (j.gpuFallback && !j.gpuFallbackCounted) {
+            st.bvhStats.sun_gpu_fallbacks++;
+            j.gpuFallbackCounted = true;
+        }
         if (!j.ok) {
             // remembered: not started again for this direction and scene version
             st.sunFailed = true;
@@ -910,6 +1043,9 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
             st.bvhStats.sun_max_depth = st.sun.depth;
             st.bvhStats.sun_rebuilds = ++st.sunRebuilds;
             st.bvhStats.sun_build_ms = job->ms;
+            st.sunGpuBuilt = job->gpu;
+            st.bvhStats.sun_installed_builder = job->gpu ? 1u : 0u;
+            if (job->gpu) st.bvhStats.sun_gpu_rebuilds++;
             st.sunRefitsSinceBuild = st.refitCount - job->refitsAt;
             st.bvhStats.sun_built_refit_version = job->refitsAt;
             // (refits that came in while it was built: its records follow them)
@@ -921,7 +1057,7 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
     return ARK_DDGI_OK;
 }
 
-int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s)
+int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
 {
     ErrorSink* err = c.err;
     auto job = std::make_unique<SunJob>();
@@ -929,7 +1065,8 @@ int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s)
     job->version = st.version;
     job->refitsAt = st.refitCount;
     ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
-    job->t = std::thread(runSunJob, job.get(), st.device, st.world.records, std::max(1, st.buildThreads / 2));
+    job->instances = static_cast<uint32_t>(st.instHost.size());
+    job->t = std::thread(gpu ? runSunJobGpu : runSunJob, job.get(), st.device, st.world.records, std::max(1, st.buildThreads / 2));
     st.sunJob = std::move(job);
     st.lastBackground = kBackgroundSun;
     return ARK_DDGI_OK;
@@ -1022,13 +1159,15 @@ int startRebuild(SceneStore& st, const SceneCall& c, hipStream_t s, bool sunOnly
     q.sunFailedHere = st.sunFailed && st.sunFailedVersion == st.version && sameDir(st.sunFailedDir, c.sunDir);
     q.worldRebuildFailed = st.worldRebuildFailed;
     q.worldGpuBuilt = st.worldGpuBuilt;
+    q.sunGpuBuilt = st.sunGpuBuilt && q.sunInstalled;
     q.refitsSinceBuild = st.refitsSinceBuild;
     q.sunRefitsSinceBuild = st.sunRefitsSinceBuild;
     q.flags = c.flags;
     q.lastBackground = st.lastBackground;
     q.sunOnly = sunOnly;
     switch (rebuildToStart(q)) {
-    case RebuildStart::Sun: return sunStart(st, c, s);
+    case RebuildStart::Sun: return sunStart(st, c, s, false);
+    case RebuildStart::SunDevice: return sunStart(st, c, s, true);
     case RebuildStart::WorldHost: return worldStart(st, c, s, false);
     case RebuildStart::WorldDevice: return worldStart(st, c, s, true);
     case RebuildStart::None: break;
@@ -1525,6 +1664,8 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
         st.sun.nodeCount = 0;
         st.bvhStats.sun_node_count = 0;
         st.bvhStats.sun_max_depth = 0;
+        st.sunGpuBuilt = false;
+        st.bvhStats.sun_installed_builder = 0;
     }
     // The refit writes the next spare copy on the refit stream, after the operations that
     // read it (while it was the front one: evFree) and the last install; the frames in
@@ -1627,6 +1768,52 @@ int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
     out[6] = digest;
     out[7] = st.worldGpuBuilt ? 1u : 0u;
     if (c.violations) err->lastError = "world BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
+    return c.violations ? 1 : ARK_DDGI_OK;
+}
+
+int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
+{
+    std::fill(out, out + 8, uint64_t(0));
+    if (st.sunArgs.sun_root < 0 || !st.sun.nodeCount) return 1; // no light-space BVH
+    std::vector<GpuBvh8Node> nodes(st.sun.nodeCount);
+    std::vector<GpuTriangle> tris(st.sun.records);
+    std::vector<uint32_t> order(nodes.size());
+    ARK_HIP(hipMemcpy(nodes.data(), st.sunArgs.sun_nodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
+    if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), st.sunArgs.sun_tris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
+    if (st.sun.order.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.sun.order.ptr, order.size() * 4, hipMemcpyDeviceToHost));
+    const int32_t root = 0;
+    // (one tree for every class: classOf unchecked; the boxes hold light coordinates)
+    Bvh8CheckResult c = check_bvh8_full(nodes, tris, &root, 1, nullptr, nullptr, st.sunFrameD);
+    std::string why;
+    if (!checkBvh8Structure(nodes, tris, &root, 1, why)) c.violations++;
+    if (c.nodes != nodes.size()) c.violations++; // a node outside the tree
+    if (st.sunGpuBuilt) c.violations += c.notBreadthFirst; // the device build's order
+    std::vector<uint32_t> wantOrder, wantOffsets;
+    if (!bvhLevelOrder(nodes.data(), nodes.size(), &root, 1, wantOrder, wantOffsets)) {
+        c.violations++;
+    } else if (wantOrder != order || wantOffsets != st.sun.levelOffsets) {
+        c.violations++;
+        why += " level order";
+    }
+    uint64_t live = 0, digest = 0;
+    for (const GpuTriangle& g : tris) {
+        if (isHoleTriangle(g)) continue;
+        ++live;
+        uint64_t h = 1469598103934665603ull;
+        const unsigned char* b = reinterpret_cast<const unsigned char*>(&g);
+        for (size_t k = 0; k < sizeof(GpuTriangle); ++k) h = (h ^ b[k]) * 1099511628211ull;
+        digest += h;
+    }
+    if (live != c.triangles) c.violations++;
+    out[0] = nodes.size();
+    out[1] = c.leafChildren;
+    out[2] = c.maxDepth;
+    out[3] = c.violations;
+    out[4] = live;
+    out[5] = tris.size();
+    out[6] = digest;
+    out[7] = st.sunGpuBuilt ? 1u : 0u;
+    if (c.violations) err->lastError = "sun BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
     return c.violations ? 1 : ARK_DDGI_OK;
 }
 

@@ -202,6 +202,8 @@ struct SceneStore {
     // ARK_DDGI_FLAG_GPU_REBUILD: the installed world BVHs are a device build (an LBVH: once
     // the motion stops one host rebuild replaces it, rebuildToStart)
     bool worldGpuBuilt = false;
+    // ARK_DDGI_FLAG_GPU_REBUILD_SUN: the same for the installed light-space sun BVH
+    bool sunGpuBuilt = false;
     // the background build started last (rebuildToStart: loosened BVHs take turns)
     uint8_t lastBackground = kBackgroundNone;
     std::vector<Retired> retired;
@@ -260,6 +262,8 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
 // ark_ddgi_debug_scene_digest / _world_bvh_check over the front copy (the device is idle)
 int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out);
 int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
+// ark_ddgi_debug_sun_bvh_installed_check over the front copy (1 with out zeroed: none installed)
+int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
 
 // SpotLightData as the closest hit reads it
 GpuSpotLight gpuSpotLight(const ArkSpotLight& sl);

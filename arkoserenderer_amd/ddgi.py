@@ -74,6 +74,10 @@ class DDGIConfig:
     # ARK_DDGI_FLAG_GPU_REBUILD (experimental): the world BVHs' background rebuild on the
     # device (an LBVH), one host rebuild once the motion stops; background_rebuild=False wins
     gpu_rebuild: bool = False
+    # ARK_DDGI_FLAG_GPU_REBUILD_SUN (experimental): the light-space sun BVH's background build
+    # on the device too (after a sun-direction change and after refits), one host rebuild once
+    # no refit has come since; independent of gpu_rebuild
+    gpu_rebuild_sun: bool = False
     build_threads: int = 0
 
 
@@ -112,6 +116,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.sun_bvh = int(config.sun_bvh)
     d.flags = (abi.ARK_DDGI_FLAG_SERIAL_FRAMES if config.serial_frames else 0) | (0 if config.background_rebuild else abi.ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD)
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD if config.gpu_rebuild else 0
+    d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SUN if config.gpu_rebuild_sun else 0
     d.build_threads = int(config.build_threads)
     return d
 
@@ -368,8 +373,45 @@ class DDGIContext:
         rc = self.lib.ark_ddgi_debug_world_bvh_check(self.h, out)
         if rc < 0:
             self.check(rc, "ark_ddgi_debug_world_bvh_check")
-        keys = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
-        return dict(zip(keys, (int(v) for v in out)))
+        return dict(zip(_BVH_CHECK_KEYS, (int(v) for v in out)))
+
+    def sun_bvh_installed_check(self) -> dict:
+        """ark_ddgi_debug_sun_bvh_installed_check: the light-space sun BVH8 the kernels read
+        now, downloaded and checked on the host (violations 0 = valid); "installed": False
+        (and every count 0) when there is none."""
+        out = (C.c_uint64 * 8)()
+        rc = self.lib.ark_ddgi_debug_sun_bvh_installed_check(self.h, out)
+        if rc < 0:
+            self.check(rc, "ark_ddgi_debug_sun_bvh_installed_check")
+        r = dict(zip(_BVH_CHECK_KEYS, (int(v) for v in out)))
+        r["installed"] = r["nodes"] > 0
+        return r
+
+
+_BVH_CHECK_KEYS = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
+
+
+def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int | None = None) -> tuple:
+    """ark_ddgi_debug_sun_lbvh_check: the device build of the sun's light-space BVH8 run
+    serially on the host over world triangles (n x 9 floats), then a sun shadow ray from
+    each origin (m x 3 floats) through it against brute force. Returns (rc, dict): rays,
+    occluded_brute, occluded_bvh, mismatches, node_visits, triangle_tests, nodes,
+    max_stack_depth, violations, inflation_differs, cost_lbvh, cost_host (any-hit steps per
+    ray) and the tree's leaf_children, depth, records_with_holes, w_bits. w_bits: the
+    key's Morton bits given to w (None: the default). No GPU."""
+    lib = abi.load_library()
+    tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    sd = np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
+    org = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
+    out = (C.c_uint64 * 16)()
+    rc = lib.ark_ddgi_debug_sun_lbvh_check_opts(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
+                                                -1 if w_bits is None else int(w_bits), out)
+    keys = ("rays", "occluded_brute", "occluded_bvh", "mismatches", "node_visits", "triangle_tests", "nodes", "max_stack_depth", "violations",
+            "inflation_differs", "cost_lbvh", "cost_host", "leaf_children", "depth", "records_with_holes", "w_bits")
+    r = dict(zip(keys, (int(v) for v in out)))
+    r["cost_lbvh"] /= 1e6
+    r["cost_host"] /= 1e6
+    return rc, r
 
 
 def lbvh_check(triangles, criterion: int | None = None) -> tuple:

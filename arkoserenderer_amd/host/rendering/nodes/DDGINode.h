@@ -31,6 +31,9 @@ public:
     // ARK_DDGI_FLAG_GPU_REBUILD (before construct; experimental, off): the world BVHs'
     // background rebuilds after moved instances run on the device instead of host threads
     void setGpuRebuild(bool on) { m_gpuRebuild = on; }
+    // ARK_DDGI_FLAG_GPU_REBUILD_SUN (before construct; experimental, off; either may be set
+    // alone): the light-space sun BVH's background builds run on the device too
+    void setGpuRebuildSun(bool on) { m_gpuRebuildSun = on; }
     // Z-slab ranks: the atlas exchange after each update (RCCL all-gather, or device
     // copies for contexts in one process); frame n+1's shading waits for frame n's.
     void setSlabExchange(SlabExchange* exchange) { m_exchange = exchange; }
@@ -70,6 +73,7 @@ private:
     int m_shardRank { 0 };
     int m_shardCount { 1 };
     bool m_gpuRebuild { false };
+    bool m_gpuRebuildSun { false };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     SlabExchange* m_exchange { nullptr };

@@ -169,11 +169,19 @@ typedef struct ArkDdgiDesc {
  * threads, so rebuilds are installed while instances keep moving; once the motion stops
  * one host rebuild replaces the LBVH (which traces worse than the SAH tree). A scene
  * the device build cannot take is built by the host within the same job
- * (ArkDdgiBvhStats.bvh_gpu_fallbacks). The light-space sun BVH stays a host build;
- * results are the same. */
+ * (ArkDdgiBvhStats.bvh_gpu_fallbacks). Without GPU_REBUILD_SUN the light-space sun BVH
+ * stays a host build; results are the same. GPU_REBUILD_SUN (experimental, off by
+ * default; independent of GPU_REBUILD, either may be set alone; NO_BACKGROUND_REBUILD wins
+ * over it for the rebuilds after refits): the light-space sun BVH's background build -
+ * after a sun-direction change (ark_ddgi_set_lights) and after refits - runs on the device
+ * too, one LBVH over all classes' records keyed and boxed in the sun's frame, its slots in
+ * ascending w; once no refit has come since its snapshot one host rebuild replaces it. A
+ * scene the device build cannot take is built by the host within the same job
+ * (sun_gpu_fallbacks); results are the same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
 #define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
+#define ARK_DDGI_FLAG_GPU_REBUILD_SUN 0x8u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {
@@ -557,6 +565,9 @@ typedef struct ArkDdgiBvhStats {
     uint32_t bvh_gpu_rebuilds;        /* installs since set_scene whose world BVHs the device built (ARK_DDGI_FLAG_GPU_REBUILD) */
     uint32_t bvh_gpu_fallbacks;       /* device-build jobs that fell back to the host build */
     uint32_t bvh_installed_builder;   /* the builder of the installed world BVHs: 0 host, 1 device */
+    uint32_t sun_gpu_rebuilds;        /* installs since set_scene whose light-space sun BVH the device built (ARK_DDGI_FLAG_GPU_REBUILD_SUN) */
+    uint32_t sun_gpu_fallbacks;       /* device-build jobs of the sun BVH that fell back to the host build */
+    uint32_t sun_installed_builder;   /* the builder of the installed light-space sun BVH: 0 host (and while none is installed), 1 device */
 } ArkDdgiBvhStats;
 int ark_ddgi_get_bvh_stats(ArkDdgiCtx* ctx, ArkDdgiBvhStats* out_stats);
 

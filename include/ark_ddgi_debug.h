@@ -104,6 +104,37 @@ int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int crite
  * downloaded nodes. Returns 0 when there is none, 1 otherwise. Synchronous. */
 int ark_ddgi_debug_world_bvh_check(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* The device build of the sun's light-space BVH8 (ARK_DDGI_FLAG_GPU_REBUILD_SUN) run
+ * serially on the host over n world triangles (9 floats each) with the very functions the
+ * kernels call (csrc/lbvh_build.h: the light vertices, the light-space key, the radix
+ * tree, the cut, the slots in ascending w, the rows), in sun_frame's frame; the boxes from
+ * the records' light coordinates upward and the planes by the host collapse's node
+ * writer. Then ark_ddgi_debug_sun_bvh_check's ray comparison through it. out[12]: [0..7]
+ * as that function's; [8] structure violations (the structure check, the level order, each
+ * depth one range behind the depth above's, every record the input's bit for bit, a node
+ * whose occupied slots do not ascend in the low w edge of their Morton cells); [9] 1 when
+ * the boxes' absolute inflation differs in bits from the host build's of the same input;
+ * [10], [11] any-hit steps per ray x 1e6 (sun_shadow_cost) from these origins through the
+ * LBVH and through the host build's tree. Returns 0 when clean, 2 on a ray mismatch, 1 on
+ * a build error, a violation or an inflation difference. _opts: w_bits of the key's 60
+ * Morton bits go to w (even, at most 20; negative: the default), the rest to u and v in halves; out[16], with
+ * [12] leaf children, [13] depth, [14] records with holes, [15] w_bits. No GPU. */
+int ark_ddgi_debug_sun_lbvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                  uint64_t* out);
+int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                       int w_bits, uint64_t* out);
+
+/* ark_ddgi_debug_world_bvh_check for the installed light-space sun BVH. out[8] = {nodes,
+ * leaf children, max depth, violations, records that are not holes, records with holes,
+ * the order-independent record digest (equal to the world BVHs': the same records),
+ * installed builder (0 host, 1 device)}. A violation: the structure check fails; a plane is
+ * not exactly decodable; a light vertex of a record lies outside the decoded box of its
+ * leaf slot or of an ancestor; the nodes are not one contiguous range from node 0 (a
+ * device build's: each depth one range behind the depth above's); the refit's level order
+ * differs from the recomputed one. Returns 0 when there is none, 1 otherwise - also when
+ * no light-space BVH is installed (out all zero). Synchronous. */
+int ark_ddgi_debug_sun_bvh_installed_check(struct ArkDdgiCtx* ctx, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,6 +20,12 @@ of the motion, and the traversal phase's device time (ark_ddgi_get_last_timings 
 the tree traced at the start (set_scene's), right after the motion (the device build, or
 with the flag off the refit-loosened one) and once settled (the host rebuild). Run it
 with and without the flag in turn to compare.
+
+--gpu-rebuild-sun (combines with --gpu-rebuild): ARK_DDGI_FLAG_GPU_REBUILD_SUN, the
+light-space sun BVH rebuilt on the device too. The trees then also tell the sun BVH's
+builder and device builds; with --sun-turn each turn records the shadow phase on the world
+BVHs (while the build runs), on the device-built tree and on the host rebuild that settles
+it, and the time from set_lights to each install.
 """
 import argparse
 import dataclasses
@@ -50,6 +56,7 @@ def main():
     ap.add_argument("--frames", type=int, default=300)
     ap.add_argument("--no-background", action="store_true", help="ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: refits only (isolates the rebuild threads' cost)")
     ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
+    ap.add_argument("--gpu-rebuild-sun", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SUN: the light-space sun BVH's background builds on the device")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
     import torch
@@ -60,7 +67,7 @@ def main():
         sc, grid, R, zf = build(name)
         N = grid.probe_count()
         cfg = D.DDGIConfig(rays_per_probe=R, probe_updates_per_frame=N, max_rays_per_probe=R, max_probe_updates=N, compute_probe_offsets=True,
-                           background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild)
+                           background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild, gpu_rebuild_sun=args.gpu_rebuild_sun)
         node = D.DDGINode(cfg)
         node.construct(sc, grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
         app = [D.AppState(0)]
@@ -95,7 +102,10 @@ def main():
             return {"builder": "device" if st.bvh_installed_builder else "host", "rebuilds": int(st.bvh_rebuilds), "device_rebuilds": int(st.bvh_gpu_rebuilds),
                     "fallbacks": int(st.bvh_gpu_fallbacks), "failures": int(st.bvh_rebuild_failures), "rebuild_ms": round(st.bvh_rebuild_ms, 2),
                     "nodes": int(st.node_count), "records_per_triangle": round(st.triangle_bytes / 48 / max(1, sc.triangle_count), 4),
-                    "built_refit_version": int(st.bvh_built_refit_version), "refit_version": int(st.refit_version)}
+                    "built_refit_version": int(st.bvh_built_refit_version), "refit_version": int(st.refit_version),
+                    "sun": {"builder": "device" if st.sun_installed_builder else "host", "rebuilds": int(st.sun_rebuilds), "device_rebuilds": int(st.sun_gpu_rebuilds),
+                            "fallbacks": int(st.sun_gpu_fallbacks), "failures": int(st.sun_rebuild_failures), "build_ms": round(st.sun_build_ms, 2),
+                            "nodes": int(st.sun_node_count), "built_refit_version": int(st.sun_built_refit_version)}}
 
         had_sun_bvh = node.ctx.bvh_stats().sun_node_count > 0
         out = {"config": name, "triangles": int(sc.triangle_count), "instances": int(sc.instances.size),
@@ -139,7 +149,7 @@ def main():
             while time.perf_counter() - t < 120.0 and not args.no_background:
                 st = node.ctx.bvh_stats()
                 if st.bvh_built_refit_version == st.refit_version and (not had_sun_bvh or st.sun_built_refit_version == st.refit_version) and \
-                        not st.bvh_installed_builder:  # (--gpu-rebuild: until the settle rebuild has replaced the device build)
+                        not st.bvh_installed_builder and not st.sun_installed_builder:  # (until the settle rebuilds have replaced the device builds)
                     break
                 node.execute(app[0], sptr)
                 app[0] = D.AppState(app[0].frame_index + 1)
@@ -163,7 +173,7 @@ def main():
                 "ms_per_frame_moving": round(motion_s / args.frames * 1e3, 4),
                 "refit_device_ms": {"median": round(refit_dev[len(refit_dev) // 2], 4), "max": round(refit_dev[-1], 4)},
                 "refit_host_enqueue_ms": round(host_refit / args.frames * 1e3, 4), "background_rebuild": not args.no_background,
-                "gpu_rebuild": bool(args.gpu_rebuild), "trees": trees,
+                "gpu_rebuild": bool(args.gpu_rebuild), "gpu_rebuild_sun": bool(args.gpu_rebuild_sun), "trees": trees,
                 "built_refit_version": {"world": int(st2.bvh_built_refit_version), "sun": int(st2.sun_built_refit_version), "refits": int(st2.refit_version)},
                 "installs_while_moving": {"world": int(st1.bvh_rebuilds - st0.bvh_rebuilds), "sun": int(st1.sun_rebuilds - st0.sun_rebuilds)},
                 "world_rebuild_ms": round(st2.bvh_rebuild_ms, 1), "sun_rebuild_ms": round(st2.sun_build_ms, 1),
@@ -181,16 +191,38 @@ def main():
             c, s_ = np.cos(np.radians(10.0)), np.sin(np.radians(10.0))
             d1 = np.array([c * d0[0] + s_ * d0[2], d0[1], -s_ * d0[0] + c * d0[2]])
             for label, d in (("turned", d1), ("back", d0)):
-                node.ctx.set_lights((sc.sun[0], tuple(float(x) for x in d)), ())
-                world = rate()  # the world BVHs carry the sun's rays meanwhile
                 t = time.perf_counter()
+                node.ctx.set_lights((sc.sun[0], tuple(float(x) for x in d)), ())
+                if args.gpu_rebuild_sun:
+                    # each install since set_lights: the device build, then the host rebuild that settles it
+                    turn = {"sun": label, "installs": []}
+                    # (five timed frames at once: on the world BVHs unless the device build is installed within them)
+                    turn["ms_world"] = trace_ms()
+                    turn["installed_within_ms_world"] = bool(node.ctx.bvh_stats().sun_rebuilds != base)
+                    while time.perf_counter() - t < 120.0:
+                        node.execute(app[0])
+                        app[0] = D.AppState(app[0].frame_index + 1)
+                        node.ctx.synchronize()
+                        st = node.ctx.bvh_stats()
+                        if st.sun_rebuilds == base:
+                            continue
+                        base = st.sun_rebuilds
+                        after_s = time.perf_counter() - t
+                        turn["installs"].append({"builder": "device" if st.sun_installed_builder else "host", "installed_after_s": round(after_s, 3),
+                                                 "build_ms": round(st.sun_build_ms, 1), "nodes": int(st.sun_node_count), "ms": trace_ms()})
+                        if not st.sun_installed_builder:
+                            break
+                    turns.append(turn)
+                    continue
+                world = rate()  # the world BVHs carry the sun's rays meanwhile
+                world_ms = trace_ms()
                 while node.ctx.bvh_stats().sun_rebuilds == base and time.perf_counter() - t < 60.0:
                     node.execute(app[0])
                     app[0] = D.AppState(app[0].frame_index + 1)
                     node.ctx.synchronize()
                 base = node.ctx.bvh_stats().sun_rebuilds
-                turns.append({"sun": label, "mrays_per_s_world": round(world, 1), "installed_after_s": round(time.perf_counter() - t, 2),
-                              "rebuild_ms": round(node.ctx.bvh_stats().sun_build_ms, 1), "mrays_per_s_rebuilt": round(rate(), 1)})
+                turns.append({"sun": label, "mrays_per_s_world": round(world, 1), "ms_world": world_ms, "installed_after_s": round(time.perf_counter() - t, 2),
+                              "rebuild_ms": round(node.ctx.bvh_stats().sun_build_ms, 1), "mrays_per_s_rebuilt": round(rate(), 1), "ms_rebuilt": trace_ms()})
             out["sun_turns"] = turns
             print(json.dumps(out), flush=True)
             node.ctx.close()
