@@ -1858,7 +1858,8 @@ void recordVertices(const GpuTriangle& g, float v[3][3])
 }
 } // namespace
 
-LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun)
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun,
+                               const std::vector<uint32_t>* primOrder)
 {
     LbvhHostResult R;
     const lbvh::KeyLayout layout = { sun ? sun->wBits : lbvh::kMortonBits };
@@ -1876,14 +1877,18 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
     std::vector<uint32_t> idx;
     std::vector<Aabb> pbox;
     Aabb scene;
-    for (size_t i = 0; i < rec.size(); ++i) {
-        if (isHoleTriangle(rec[i])) continue;
+    if (primOrder) {
+        idx = *primOrder;
+    } else {
+        for (size_t i = 0; i < rec.size(); ++i)
+            if (!isHoleTriangle(rec[i])) idx.push_back(static_cast<uint32_t>(i));
+    }
+    for (uint32_t i : idx) {
         float v[3][3];
         boxVertices(rec[i], v);
         Aabb b;
         for (int k = 0; k < 3; ++k) b.grow(v[k]);
         scene.grow(b);
-        idx.push_back(static_cast<uint32_t>(i));
         pbox.push_back(b);
     }
     const uint32_t n = static_cast<uint32_t>(idx.size());
@@ -1980,6 +1985,16 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
         if (c == 0) R.opaqueNodes = static_cast<uint32_t>(R.nodes.size());
         R.depth = std::max(R.depth, depth);
     }
+    for (int c = 0; c < 3; ++c) R.classCount[c] = classCount[c];
+    for (int a = 0; a < 3 && n; ++a) {
+        R.sceneLo[a] = scene.lo[a];
+        R.sceneHi[a] = scene.hi[a];
+    }
+    R.maxAbs = maxAbs;
+    R.idxSorted.resize(n);
+    for (uint32_t j = 0; j < n; ++j) R.idxSorted[j] = idx[sorted[j]];
+    R.keysSorted = keys;
+    R.split = split;
     // scatter
     R.tris.assign(records, holeTriangle());
     R.perm.assign(records, 0xffffffffu);
@@ -2174,7 +2189,342 @@ Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std
     return R;
 }
 
+Bvh8CanonicalDiff compare_bvh8_canonical(const Bvh8TreeView& A, const Bvh8TreeView& B)
+{
+    Bvh8CanonicalDiff D;
+    const Bvh8TreeView* T[2] = { &A, &B };
+    const std::vector<GpuBvh8Node>& na = *A.nodes;
+    const std::vector<GpuBvh8Node>& nb = *B.nodes;
+    auto span = [](const GpuBvh8Node& nd) { return nd.leaf_tris ? 32u - static_cast<uint32_t>(__builtin_clz(nd.leaf_tris)) : 0u; };
+    // each tree on its own: the level order, the padding record, the rows exactly the records
+    std::vector<uint64_t> perDepth[2];
+    for (int t = 0; t < 2; ++t) {
+        const std::vector<GpuBvh8Node>& nodes = *T[t]->nodes;
+        std::vector<uint32_t> order, offsets;
+        const bool walked = bvhLevelOrder(nodes.data(), nodes.size(), T[t]->roots, 3, order, offsets);
+        if (!walked) D.children++;
+        if (T[t]->order && T[t]->levelOffsets && (!walked || order != *T[t]->order || offsets != *T[t]->levelOffsets)) D.levelOrder++;
+        for (size_t l = 0; walked && l + 1 < offsets.size(); ++l) perDepth[t].push_back(offsets[l + 1] - offsets[l]); // (deepest first)
+        if (walked && (order.size() != nodes.size() || offsets.size() != static_cast<size_t>(T[t]->depth) + 1u)) D.shape++;
+        uint64_t rows = 0;
+        for (const GpuBvh8Node& nd : nodes) rows += span(nd);
+        if (rows != T[t]->tris->size()) D.shape++;
+        if (T[t]->perm && T[t]->perm->size() != T[t]->tris->size()) D.shape++;
+        if (T[t]->padding) {
+            const GpuTriangle zero {};
+            if (std::memcmp(T[t]->padding, &zero, sizeof(zero)) != 0) D.padding++;
+        }
+    }
+    if (perDepth[0] != perDepth[1]) D.shape++;
+    if (na.size() != nb.size() || A.tris->size() != B.tris->size() || A.opaqueNodes != B.opaqueNodes || A.depth != B.depth) D.shape++;
+    const bool perms = A.perm && B.perm && A.perm->size() == A.tris->size() && B.perm->size() == B.tris->size();
+    std::vector<uint8_t> seenA(na.size(), 0), seenB(nb.size(), 0);
+    std::vector<std::pair<uint32_t, uint32_t>> work;
+    for (int c = 0; c < 3; ++c) {
+        if ((A.roots[c] >= 0) != (B.roots[c] >= 0)) D.shape++;
+        else if (A.roots[c] >= 0) work.push_back({ static_cast<uint32_t>(A.roots[c]), static_cast<uint32_t>(B.roots[c]) });
+    }
+    while (!work.empty()) {
+        const auto [ia, ib] = work.back();
+        work.pop_back();
+        const uint64_t before = D.total();
+        if (ia >= na.size() || ib >= nb.size() || seenA[ia] || seenB[ib]) {
+            D.children++;
+        } else {
+            seenA[ia] = seenB[ib] = 1;
+            D.pairs++;
+            const GpuBvh8Node& a = na[ia];
+            const GpuBvh8Node& b = nb[ib];
+            const bool sameHeader = a.imask == b.imask && a.leaf_mask == b.leaf_mask && a.leaf_tris == b.leaf_tris && a.tri_stride == b.tri_stride;
+            if (!sameHeader) D.header++;
+            if (std::memcmp(a.p, b.p, sizeof(a.p)) != 0 || std::memcmp(a.e, b.e, sizeof(a.e)) != 0) D.grid++;
+            if (sameHeader) {
+                for (int s = 0; s < 8; ++s) {
+                    if (!(((a.imask | a.leaf_mask) >> s) & 1u)) continue;
+                    for (int ax = 0; ax < 3; ++ax)
+                        if (a.qlo[ax][s] != b.qlo[ax][s] || a.qhi[ax][s] != b.qhi[ax][s]) D.planes++;
+                }
+                // the rows, position by position: a leaf slot's records, holes elsewhere
+                for (uint32_t pos = 0; pos < span(a); ++pos) {
+                    const uint64_t ra = static_cast<uint64_t>(a.tri_base) + pos, rb = static_cast<uint64_t>(b.tri_base) + pos;
+                    if (ra >= A.tris->size() || rb >= B.tris->size()) {
+                        D.records++;
+                        continue;
+                    }
+                    const GpuTriangle& ta = (*A.tris)[ra];
+                    const GpuTriangle& tb = (*B.tris)[rb];
+                    if ((a.leaf_tris >> pos) & 1u) {
+                        if (std::memcmp(&ta, &tb, sizeof(GpuTriangle)) != 0 || isHoleTriangle(ta)) D.records++;
+                        if (perms && (*A.perm)[ra] != (*B.perm)[rb]) D.perm++;
+                    } else {
+                        const GpuTriangle hole = holeTriangle();
+                        if (std::memcmp(&ta, &hole, sizeof(hole)) != 0 || std::memcmp(&tb, &hole, sizeof(hole)) != 0) D.holes++;
+                        if (perms && ((*A.perm)[ra] != 0xffffffffu || (*B.perm)[rb] != 0xffffffffu)) D.holes++;
+                    }
+                }
+            }
+            // internal children by rank (as far as both have them)
+            const uint32_t ka = static_cast<uint32_t>(__builtin_popcount(a.imask)), kb = static_cast<uint32_t>(__builtin_popcount(b.imask));
+            for (uint32_t k = std::min(ka, kb); k-- > 0;) work.push_back({ a.child_base + k, b.child_base + k });
+        }
+        if (D.total() != before && D.firstA < 0) {
+            D.firstA = ia;
+            D.firstB = ib;
+        }
+    }
+    return D;
+}
+
 } // namespace ark
+
+// ark_ddgi_debug.h: what compare_bvh8_canonical notices, without a GPU
+namespace {
+using namespace ark;
+
+struct HostTree {
+    std::vector<GpuBvh8Node> nodes;
+    std::vector<GpuTriangle> tris;
+    std::vector<uint32_t> perm, order, levelOffsets;
+    int32_t roots[3] = { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, depth = 0;
+    Bvh8TreeView view() const
+    {
+        Bvh8TreeView v;
+        v.nodes = &nodes;
+        v.tris = &tris;
+        v.perm = &perm;
+        v.order = &order;
+        v.levelOffsets = &levelOffsets;
+        std::copy(roots, roots + 3, v.roots);
+        v.opaqueNodes = opaqueNodes;
+        v.depth = depth;
+        return v;
+    }
+};
+
+uint32_t rowSpan(const GpuBvh8Node& nd) { return nd.leaf_tris ? 32u - static_cast<uint32_t>(__builtin_clz(nd.leaf_tris)) : 0u; }
+
+// What the device's atomics do to a tree: within each level of each class, the blocks of
+// siblings (child_base) and the rows (tri_base) handed out in another order
+HostTree shuffledTwin(const LbvhHostResult& r, uint64_t seed)
+{
+    HostTree t;
+    const uint32_t N = static_cast<uint32_t>(r.nodes.size());
+    uint64_t state = seed * 0x9e3779b97f4a7c15ull + 1u;
+    auto rnd = [&](uint32_t n) { // xorshift64*
+        state ^= state >> 12;
+        state ^= state << 25;
+        state ^= state >> 27;
+        return static_cast<uint32_t>(((state * 0x2545f4914f6cdd1dull) >> 33) % n);
+    };
+    auto shuffle = [&](std::vector<uint32_t>& v) {
+        for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[rnd(static_cast<uint32_t>(i))]);
+    };
+    t.nodes.resize(N);
+    t.tris.assign(r.tris.size(), holeTriangle());
+    t.perm.assign(r.perm.size(), 0xffffffffu);
+    uint32_t records = 0;
+    for (int c = 0; c < 3; ++c) {
+        t.roots[c] = r.roots[c];
+        if (r.roots[c] < 0) continue;
+        std::vector<uint32_t> level(1, static_cast<uint32_t>(r.roots[c])); // old indices, in new index order
+        uint32_t levelBase = level[0];
+        while (!level.empty()) {
+            const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
+            // the sibling blocks of the next level, parent by parent in a shuffled order
+            std::vector<uint32_t> parents(level.size()), next;
+            for (uint32_t i = 0; i < parents.size(); ++i) parents[i] = i;
+            shuffle(parents);
+            std::vector<uint32_t> childBase(level.size(), 0u);
+            for (uint32_t i : parents) {
+                const GpuBvh8Node& nd = r.nodes[level[i]];
+                childBase[i] = nextBase + static_cast<uint32_t>(next.size());
+                for (int k = 0; k < __builtin_popcount(nd.imask); ++k) {
+                    next.push_back(nd.child_base + k);
+                }
+            }
+            // this level's rows in another shuffled order
+            shuffle(parents);
+            for (uint32_t i : parents) {
+                const GpuBvh8Node& nd = r.nodes[level[i]];
+                GpuBvh8Node out = nd;
+                out.child_base = childBase[i];
+                out.tri_base = rowSpan(nd) ? records : 0u;
+                for (uint32_t pos = 0; pos < rowSpan(nd); ++pos) {
+                    t.tris[out.tri_base + pos] = r.tris[nd.tri_base + pos];
+                    t.perm[out.tri_base + pos] = r.perm[nd.tri_base + pos];
+                }
+                records += rowSpan(nd);
+                t.nodes[levelBase + i] = out;
+            }
+            levelBase = nextBase;
+            level.swap(next);
+        }
+    }
+    t.opaqueNodes = r.opaqueNodes;
+    t.depth = r.depth;
+    bvhLevelOrder(t.nodes.data(), t.nodes.size(), t.roots, 3, t.order, t.levelOffsets);
+    return t;
+}
+
+void swapSlotPlanes(GpuBvh8Node& nd, int s1, int s2)
+{
+    for (int a = 0; a < 3; ++a) {
+        std::swap(nd.qlo[a][s1], nd.qlo[a][s2]);
+        std::swap(nd.qhi[a][s1], nd.qhi[a][s2]);
+    }
+}
+
+// Applies mutation `which` (0 .. 5: ark_ddgi_debug.h's (a) .. (f)) to the first node that
+// allows it; false when none does
+bool mutateTree(HostTree& t, int which)
+{
+    if (which == 5) {
+        for (uint32_t& p : t.perm)
+            if (p != 0xffffffffu) {
+                p ^= 1u;
+                return true;
+            }
+        return false;
+    }
+    for (size_t k = 0; k < t.nodes.size(); ++k) {
+        GpuBvh8Node& nd = t.nodes[k];
+        const uint32_t occupied = nd.imask | nd.leaf_mask;
+        int in[8], nIn = 0, leaf[8], nLeaf = 0, cnt[8];
+        for (int s = 0; s < 8; ++s) {
+            uint32_t tri[kBvh8MaxLeafSize];
+            cnt[s] = std::max(0, bvh8SlotTriangles(nd, s, tri));
+            if ((nd.imask >> s) & 1u) in[nIn++] = s;
+            else if (cnt[s]) leaf[nLeaf++] = s;
+        }
+        if (which == 0) { // (a) one plane one quantum looser
+            for (int s = 0; s < 8; ++s) {
+                if (!((occupied >> s) & 1u)) continue;
+                if (nd.qlo[0][s] > 0) {
+                    nd.qlo[0][s]--;
+                    return true;
+                }
+                if (nd.qhi[0][s] < 255) {
+                    nd.qhi[0][s]++;
+                    return true;
+                }
+            }
+        } else if (which == 1) { // (b) one axis's grid one exponent coarser, the planes re-quantised outward
+            // (p stays: it is a multiple of the old step, and every plane stays exact in
+            // fp32 while |p / old step| + 512 < 2^24)
+            const int a = 1;
+            const double step = std::ldexp(1.0, static_cast<int>(nd.e[a]) - 127);
+            if (nd.e[a] >= 250 || std::fabs(nd.p[a] / step) + 512.0 >= 16777216.0) continue;
+            nd.e[a]++;
+            for (int s = 0; s < 8; ++s) {
+                if (!((occupied >> s) & 1u)) continue;
+                nd.qlo[a][s] = static_cast<uint8_t>(nd.qlo[a][s] / 2);       // floor
+                nd.qhi[a][s] = static_cast<uint8_t>((nd.qhi[a][s] + 1) / 2); // ceil
+            }
+            return true;
+        } else if (which == 2) { // (c) two internal children exchanged, with their planes
+            if (nIn < 2) continue;
+            std::swap(t.nodes[nd.child_base], t.nodes[nd.child_base + 1]);
+            swapSlotPlanes(nd, in[0], in[1]);
+            return true;
+        } else { // (d), (e): two leaf slots with as many triangles
+            for (int i = 0; i < nLeaf; ++i)
+                for (int j = i + 1; j < nLeaf; ++j) {
+                    if (cnt[leaf[i]] != cnt[leaf[j]]) continue;
+                    const int s1 = leaf[i], s2 = leaf[j];
+                    // (d) every member, the rows rewritten and the planes with them;
+                    // (e) one record each, both slots' planes widened to their union
+                    const int members = which == 3 ? cnt[s1] : 1;
+                    for (int m = 0; m < members; ++m) {
+                        const uint32_t p1 = nd.tri_base + s1 + nd.tri_stride * m, p2 = nd.tri_base + s2 + nd.tri_stride * m;
+                        std::swap(t.tris[p1], t.tris[p2]);
+                        std::swap(t.perm[p1], t.perm[p2]);
+                    }
+                    if (which == 3) {
+                        swapSlotPlanes(nd, s1, s2);
+                    } else {
+                        for (int a = 0; a < 3; ++a) {
+                            nd.qlo[a][s1] = nd.qlo[a][s2] = std::min(nd.qlo[a][s1], nd.qlo[a][s2]);
+                            nd.qhi[a][s1] = nd.qhi[a][s2] = std::max(nd.qhi[a][s1], nd.qhi[a][s2]);
+                        }
+                    }
+                    return true;
+                }
+        }
+    }
+    return false;
+}
+} // namespace
+
+extern "C" int ark_ddgi_debug_bvh8_compare_selftest(const float* triangles, uint64_t n, const float* sun_dir, uint64_t seed, uint64_t* out)
+{
+    using namespace ark;
+    if (!triangles || n == 0 || !out) return -1;
+    std::fill(out, out + 16, uint64_t(0));
+    std::vector<GpuTriangle> rec(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        BuildTriangle t;
+        for (int a = 0; a < 3; ++a) {
+            t.v0[a] = triangles[9 * i + a];
+            t.v1[a] = triangles[9 * i + 3 + a];
+            t.v2[a] = triangles[9 * i + 6 + a];
+        }
+        t.instance = static_cast<uint32_t>(i % 3u); // three instances, one of each class
+        t.primitive = static_cast<uint32_t>(i);
+        t.flip_facing = 0;
+        rec[i] = make_gpu_triangle(t);
+    }
+    const std::vector<int> classOf = { 0, 1, 2 };
+    LbvhSunOptions so;
+    if (sun_dir) {
+        double frame[3][3];
+        sun_frame(sun_dir, frame);
+        std::memcpy(so.frame, frame, sizeof(so.frame));
+    }
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr);
+    HostTree ref;
+    ref.nodes = r.nodes;
+    ref.tris = r.tris;
+    ref.perm = r.perm;
+    ref.order = r.order;
+    ref.levelOffsets = r.levelOffsets;
+    std::copy(r.roots, r.roots + 3, ref.roots);
+    ref.opaqueNodes = r.opaqueNodes;
+    ref.depth = r.depth;
+    const HostTree twin = shuffledTwin(r, seed);
+    uint64_t moved = 0;
+    for (size_t k = 0; k < ref.nodes.size(); ++k)
+        if (ref.nodes[k].child_base != twin.nodes[k].child_base || ref.nodes[k].tri_base != twin.nodes[k].tri_base) moved++;
+    const Bvh8CanonicalDiff same = compare_bvh8_canonical(ref.view(), twin.view());
+    out[0] = ref.nodes.size();
+    out[1] = moved;
+    out[2] = same.total();
+    out[3] = same.pairs;
+    const Bvh8CheckResult twinCheck = check_bvh8_full(twin.nodes, twin.tris, twin.roots, 3, sun_dir ? nullptr : &classOf, nullptr, sun_dir ? so.frame : nullptr);
+    out[4] = twinCheck.violations;
+    int rc = same.total() == 0 && same.pairs == ref.nodes.size() && twinCheck.violations == 0 && moved > 0 ? 0 : 1;
+    for (int which = 0; which < 6; ++which) {
+        HostTree m = twin;
+        if (!mutateTree(m, which)) {
+            rc = 1;
+            continue;
+        }
+        const Bvh8CanonicalDiff d = compare_bvh8_canonical(ref.view(), m.view());
+        // the kind of difference each mutation has to show: (a) planes, (b) grid, (c) the
+        // exchanged children's nodes or planes, (d), (e) records, (f) perm and nothing else
+        const uint64_t kind[6] = { d.planes, d.grid, d.header + d.grid + d.planes + d.records, d.records, d.records, d.perm == d.total() ? d.perm : 0 };
+        out[5 + which] = kind[which];
+        if (kind[which] == 0 || d.firstA < 0) rc = 1;
+        if (which < 2) {
+            // (a) and (b) stay valid trees: what check_bvh8_full, the only check of a device
+            // build's boxes before, could not tell from the tree the design describes
+            const Bvh8CheckResult c = check_bvh8_full(m.nodes, m.tris, m.roots, 3, sun_dir ? nullptr : &classOf, nullptr, sun_dir ? so.frame : nullptr);
+            out[11 + which] = c.violations;
+            if (c.violations) rc = 1;
+        }
+    }
+    return rc;
+}
 
 extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out)
 {

@@ -139,6 +139,14 @@ struct LbvhHostResult {
     double sah = 0.0; // BVH8 SAH cost of the opaque class (node 1, triangle 1), as Bvh8BuildResult::sah_cost
     float inflateAbs = 0.0f;            // the boxes' absolute inflation
     uint64_t slotOrderViolations = 0;   // sun: nodes whose occupied slots do not ascend in their cells' low w edge
+    // the stages before the tree, as the device build holds them (ark_ddgi_debug_lbvh_device_parity):
+    // the header's counts, box and largest |world coordinate| (sun; else 0), the sorted keys,
+    // the record of each sorted primitive, and split[] (set at the internal indices
+    // [first, last) of each class range, 0 elsewhere)
+    uint32_t classCount[3] = { 0, 0, 0 };
+    float sceneLo[3] = { 0, 0, 0 }, sceneHi[3] = { 0, 0, 0 }, maxAbs = 0.0f;
+    std::vector<uint64_t> keysSorted;
+    std::vector<uint32_t> idxSorted, split;
 };
 // sun: the light-space BVH8 of the sun's shadow rays instead (k_lbvh_prims_light /
 // k_lbvh_keys_light): one tree over every class (roots[0]), keys and boxes of the records'
@@ -147,7 +155,42 @@ struct LbvhSunOptions {
     double frame[9];
     int wBits = lbvh::kSunKeyBitsW;
 };
-LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun = nullptr);
+// primOrder: the compacted primitive order (a permutation of the indices of the records that
+// are not holes; null: ascending). The device's comes from atomics, and the stable sort
+// carries it into runs of equal keys: given the device's order, the result is the tree the
+// device has to build, ties included.
+LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun = nullptr,
+                               const std::vector<uint32_t>* primOrder = nullptr);
+
+// Two BVH8 sets of the same records compared in canonical form (ark_ddgi_debug_lbvh_device_parity:
+// the device build against build_lbvh_host). Node numbers within a level and tri_base come
+// from atomics on the device, so both trees are walked from each root in slot order, internal
+// children matched by rank. At every pair of nodes: equal imask, leaf_mask, leaf_tris and
+// tri_stride (header); equal p and e (grid); equal qlo / qhi bytes of every occupied slot
+// (planes); every row position of a leaf slot the same 48 bytes (records) and the same source
+// record in perm (perm; skipped when either perm is null); every other position of the rows a
+// hole (holes). shape: the classes' roots present alike, opaqueNodes, depth, the node count of
+// every depth, the node and record counts, and each tree's rows together exactly its records.
+// children: a child index outside the nodes, or a node met twice. levelOrder: a tree's order /
+// levelOffsets (when given) differ from bvhLevelOrder of its nodes. padding: a tree's padding
+// record (when given) is not all zero.
+struct Bvh8TreeView {
+    const std::vector<GpuBvh8Node>* nodes = nullptr;
+    const std::vector<GpuTriangle>* tris = nullptr; // rows, holes included, no padding record
+    const std::vector<uint32_t>* perm = nullptr;
+    const std::vector<uint32_t>* order = nullptr;
+    const std::vector<uint32_t>* levelOffsets = nullptr;
+    const GpuTriangle* padding = nullptr;
+    int32_t roots[3] = { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, depth = 0;
+};
+struct Bvh8CanonicalDiff {
+    uint64_t shape = 0, header = 0, grid = 0, planes = 0, children = 0, records = 0, perm = 0, holes = 0, levelOrder = 0, padding = 0;
+    int64_t firstA = -1, firstB = -1; // the first differing pair of nodes (-1: none)
+    uint64_t pairs = 0;               // pairs of nodes visited
+    uint64_t total() const { return shape + header + grid + planes + children + records + perm + holes + levelOrder + padding; }
+};
+Bvh8CanonicalDiff compare_bvh8_canonical(const Bvh8TreeView& a, const Bvh8TreeView& b);
 
 // The full check of a BVH8 set (ark_ddgi_debug_lbvh_check, ark_ddgi_debug_world_bvh_check):
 // every class's nodes one contiguous range from its root (counted in violations; depths

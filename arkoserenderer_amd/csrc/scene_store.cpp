@@ -515,6 +515,22 @@ bool isDeviceFault(hipError_t e)
            e == hipErrorNoDevice || e == hipErrorInvalidDevice;
 }
 
+// What a traced device build keeps on the host (ark_ddgi_debug_lbvh_device_parity): every
+// stage's result, downloaded before buildLbvhGpu returns (the stages after a fallback: empty)
+struct LbvhGpuTrace {
+    LbvhHeader hdr {};                            // as the build uses it (the light build's classCount[0] = prims)
+    std::vector<uint32_t> idx, idxSorted, split;  // hdr.prims each (split: set at the internal indices of each class range)
+    std::vector<uint64_t> keysSorted;
+    std::vector<GpuBvh8Node> nodes;
+    std::vector<GpuTriangle> tris;                // the rows, then the padding record
+    std::vector<uint32_t> perm, order, levelOffsets;
+    int32_t roots[3] { -1, -1, -1 };
+    uint32_t opaqueNodes = 0, depth = 0;
+    float inflateAbs = 0.0f;
+    bool built = false;
+    std::string why;                              // the fallback reason
+};
+
 // What the device builds of the world BVH8s and of the sun's light-space BVH8 differ in
 // (buildLbvhGpu): the class ranges, the key kernels, the slot rule and the refit's boxes.
 struct LbvhGpuBuild {
@@ -528,6 +544,7 @@ struct LbvhGpuBuild {
     int slotRule = lbvh::kSlotsOctant, wBits = lbvh::kMortonBits;
     DeviceBvh* bvh = nullptr;          // out: buffer, level order (device and offsets), counts, depth, inflateAbs
     DeviceBuffer* perm = nullptr;      // out: the record order's source indices (null: not wanted)
+    LbvhGpuTrace* trace = nullptr;     // out: the stages' results (null in the product paths: nothing more is enqueued)
     // out
     int32_t roots[3] { -1, -1, -1 };
     uint32_t opaqueNodes = 0, prims = 0;
@@ -558,6 +575,14 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes;
     } w;
     hipError_t e = hipSuccess;
+    struct KeepWhy {
+        LbvhGpuTrace* trace;
+        const std::string& why;
+        ~KeepWhy()
+        {
+            if (trace) trace->why = why;
+        }
+    } keepWhy { g.trace, why };
 #define ARK_GB(expr)                          \
     do {                                      \
         if ((e = (expr)) != hipSuccess) return e; \
@@ -587,6 +612,7 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
     ARK_GB(hipMemcpyAsync(&hdr, w.hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost, s));
     ARK_GB(hipStreamSynchronize(s));
     if (g.light && !hdr.error) hdr.classCount[0] = hdr.prims; // one range [0, n): the keys' class bits are 0
+    if (g.trace) g.trace->hdr = hdr;
     if (hdr.error || hdr.prims == 0 || hdr.prims > records || hdr.classCount[0] + hdr.classCount[1] + hdr.classCount[2] != hdr.prims) {
         why = hdr.error ? "record of an unknown instance" : "no triangles";
         return hipSuccess;
@@ -743,6 +769,30 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), b.order.as<uint32_t>() + b.levelOffsets[l], b.levelOffsets[l + 1] - b.levelOffsets[l], ra,
                                   w.masks.as<uint64_t>(), w.inst.as<RefitInstance>(), nullptr, nullptr, s));
     ARK_GB(hipStreamSynchronize(s));
+    if (LbvhGpuTrace* t = g.trace) {
+        t->idx.resize(n);
+        t->idxSorted.resize(n);
+        t->split.resize(n);
+        t->keysSorted.resize(n);
+        t->nodes.resize(nodeTotal);
+        t->tris.resize(outRecords + 1ull);
+        t->perm.resize(g.perm ? outRecords : 0u);
+        ARK_GB(hipMemcpyAsync(t->idx.data(), w.idx.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
+        ARK_GB(hipMemcpyAsync(t->idxSorted.data(), w.idxSorted.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
+        ARK_GB(hipMemcpyAsync(t->split.data(), w.split.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
+        ARK_GB(hipMemcpyAsync(t->keysSorted.data(), w.keysSorted.ptr, n * 8ull, hipMemcpyDeviceToHost, s));
+        ARK_GB(hipMemcpyAsync(t->nodes.data(), nodes, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost, s));
+        ARK_GB(hipMemcpyAsync(t->tris.data(), tris, (outRecords + 1ull) * sizeof(GpuTriangle), hipMemcpyDeviceToHost, s));
+        if (!t->perm.empty()) ARK_GB(hipMemcpyAsync(t->perm.data(), g.perm->ptr, outRecords * 4ull, hipMemcpyDeviceToHost, s));
+        ARK_GB(hipStreamSynchronize(s));
+        t->order = order;
+        t->levelOffsets = b.levelOffsets;
+        std::copy(g.roots, g.roots + 3, t->roots);
+        t->opaqueNodes = g.opaqueNodes;
+        t->depth = static_cast<uint32_t>(levels.size());
+        t->inflateAbs = ra.inflate;
+        t->built = true;
+    }
 #undef ARK_GB
     b.nodeCount = nodeTotal;
     b.records = outRecords;
@@ -1818,3 +1868,176 @@ int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
 }
 
 } // namespace ark
+
+// ark_ddgi_debug.h: one traced device build (buildLbvhGpu, the product's kernels and
+// nothing else) of the given records on a stream of its own, without a context, against
+// build_lbvh_host of the same records in the device's compaction order, stage by stage.
+extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                                  const float* sun_dir, int w_bits, uint64_t* out)
+{
+    using namespace ark;
+    if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
+    std::fill(out, out + 32, uint64_t(0));
+    for (uint32_t i = 0; i < n_instances; ++i)
+        if (class_of[i] < 0 || class_of[i] > 2) return -1; // (the kernels index the class counts by it)
+    int wBits = lbvh::kMortonBits;
+    if (sun_dir) {
+        wBits = w_bits < 0 ? lbvh::kSunKeyBitsW : w_bits;
+        if (wBits > lbvh::kMortonBits || (wBits & 1)) return -1;
+    }
+    const uint32_t n = static_cast<uint32_t>(n_records);
+    std::vector<GpuTriangle> rec(n);
+    std::memcpy(rec.data(), records, n * sizeof(GpuTriangle));
+
+    // the device build
+    struct Device {
+        hipStream_t s = nullptr;
+        hipEvent_t ev = nullptr;
+        DeviceBuffer snap, perm;
+        DeviceBvh bvh;
+        ~Device()
+        {
+            if (s) (void)hipStreamSynchronize(s);
+            bvh.release();
+            perm.release();
+            snap.release();
+            if (ev) (void)hipEventDestroy(ev);
+            if (s) (void)hipStreamDestroy(s);
+        }
+    } d;
+    LbvhGpuTrace trace;
+    LbvhGpuBuild g;
+    std::string why;
+    hipError_t e = hipSetDevice(device);
+    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = d.snap.alloc(std::max<size_t>(16, n * sizeof(GpuTriangle)));
+    if (e == hipSuccess) e = hipMemcpyAsync(d.snap.ptr, rec.data(), n * sizeof(GpuTriangle), hipMemcpyHostToDevice, d.s);
+    if (e == hipSuccess) e = hipEventRecord(d.ev, d.s);
+    if (e == hipSuccess) {
+        g.snap = d.snap.as<GpuTriangle>();
+        g.evSnap = d.ev;
+        g.records = n;
+        g.classHost.assign(class_of, class_of + n_instances);
+        if (sun_dir) {
+            double frame[3][3];
+            sun_frame(sun_dir, frame);
+            g.light = true;
+            std::memcpy(g.frame, frame, sizeof(g.frame));
+            g.slotRule = lbvh::kSlotsAscendingW;
+            g.wBits = wBits;
+        }
+        g.bvh = &d.bvh;
+        g.perm = &d.perm;
+        g.trace = &trace;
+        e = buildLbvhGpu(g, d.s, why);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(d.s);
+    out[26] = static_cast<uint64_t>(e);
+    if (e != hipSuccess) return -5;
+    static const char* const kWhy[] = { "", "no records", "no triangles", "record of an unknown instance", "BVH8 deeper than the device build installs",
+                                        "more nodes than the device build's scratch", "nodes and records of 4 GiB or more" };
+    out[4] = 7;
+    for (uint64_t k = 0; k < sizeof(kWhy) / sizeof(kWhy[0]); ++k)
+        if (trace.why == kWhy[k]) out[4] = k;
+    out[0] = trace.hdr.prims;
+    if (!trace.why.empty() || !trace.built) return 2; // the host's scene: nothing was built
+
+    // the compaction: a permutation of exactly the records that are not holes
+    std::vector<uint32_t> live;
+    for (uint32_t i = 0; i < n; ++i)
+        if (!isHoleTriangle(rec[i])) live.push_back(i);
+    {
+        std::vector<uint32_t> sorted = trace.idx;
+        std::sort(sorted.begin(), sorted.end());
+        out[5] = sorted.size() != live.size() ? 1u : 0u;
+        for (size_t j = 0; j < std::min(sorted.size(), live.size()); ++j) out[5] += sorted[j] != live[j] ? 1u : 0u;
+    }
+    if (sun_dir && !out[5] && !live.empty()) {
+        // k_lbvh_prims_light: a wave's survivors one run, ascending
+        uint64_t runs = 1, waves = 1;
+        for (size_t j = 0; j + 1 < trace.idx.size(); ++j) {
+            if ((trace.idx[j] >> 6) != (trace.idx[j + 1] >> 6)) runs++;
+            else if (trace.idx[j] >= trace.idx[j + 1]) out[6]++;
+            if ((live[j] >> 6) != (live[j + 1] >> 6)) waves++;
+        }
+        if (runs != waves) out[6]++;
+    }
+    std::vector<int> classOf(class_of, class_of + n_instances);
+    LbvhSunOptions so;
+    std::memcpy(so.frame, g.frame, sizeof(so.frame));
+    so.wBits = wBits;
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx);
+    auto bits = [](float f) {
+        uint32_t u;
+        std::memcpy(&u, &f, 4);
+        return u;
+    };
+    // the header
+    const uint32_t prims = static_cast<uint32_t>(live.size());
+    out[7] = (trace.hdr.prims != prims ? 1u : 0u) + (trace.hdr.error ? 1u : 0u);
+    for (int c = 0; c < 3; ++c) out[7] += trace.hdr.classCount[c] != r.classCount[c] ? 1u : 0u;
+    for (int k = 0; k < 3; ++k) {
+        // (== of floats: the ordered-bits atomics tell -0 from +0, std::min does not, and nothing later depends on a zero's sign)
+        out[8] += lbvhOrderedFloat(trace.hdr.lo[k]) == r.sceneLo[k] ? 0u : 1u;
+        out[8] += lbvhOrderedFloat(trace.hdr.hi[k]) == r.sceneHi[k] ? 0u : 1u;
+    }
+    out[9] = trace.hdr.maxAbs != bits(r.maxAbs) ? 1u : 0u;
+    out[10] = bits(trace.inflateAbs) != bits(r.inflateAbs) ? 1u : 0u;
+    // keys, sorted records, splits
+    if (trace.keysSorted.size() != prims || trace.idxSorted.size() != prims || trace.split.size() != prims || r.keysSorted.size() != prims) {
+        out[11] = out[12] = out[13] = 1;
+    } else {
+        for (uint32_t j = 0; j < prims; ++j) {
+            out[11] += trace.keysSorted[j] != r.keysSorted[j] ? 1u : 0u;
+            out[12] += trace.idxSorted[j] != r.idxSorted[j] ? 1u : 0u;
+        }
+        uint32_t first = 0;
+        for (int c = 0; c < 3; ++c) {
+            for (uint32_t i = first; i + 1u < first + r.classCount[c]; ++i) out[13] += trace.split[i] != r.split[i] ? 1u : 0u;
+            first += r.classCount[c];
+        }
+    }
+    // the tree
+    const GpuTriangle padding = trace.tris.back(); // (records + 1 entries)
+    trace.tris.pop_back();
+    Bvh8TreeView dv, hv;
+    dv.nodes = &trace.nodes;
+    dv.tris = &trace.tris;
+    dv.perm = &trace.perm;
+    dv.order = &trace.order;
+    dv.levelOffsets = &trace.levelOffsets;
+    dv.padding = &padding;
+    std::copy(trace.roots, trace.roots + 3, dv.roots);
+    dv.opaqueNodes = trace.opaqueNodes;
+    dv.depth = trace.depth;
+    hv.nodes = &r.nodes;
+    hv.tris = &r.tris;
+    hv.perm = &r.perm;
+    hv.order = &r.order;
+    hv.levelOffsets = &r.levelOffsets;
+    std::copy(r.roots, r.roots + 3, hv.roots);
+    hv.opaqueNodes = r.opaqueNodes;
+    hv.depth = r.depth;
+    const Bvh8CanonicalDiff diff = compare_bvh8_canonical(dv, hv);
+    out[1] = trace.nodes.size();
+    out[2] = trace.tris.size();
+    out[3] = trace.depth;
+    out[14] = diff.shape;
+    out[15] = diff.header;
+    out[16] = diff.grid;
+    out[17] = diff.planes;
+    out[18] = diff.children;
+    out[19] = diff.records;
+    out[20] = diff.perm;
+    out[21] = diff.holes;
+    out[22] = diff.levelOrder;
+    out[23] = diff.padding;
+    out[24] = static_cast<uint64_t>(diff.firstA);
+    out[25] = static_cast<uint64_t>(diff.firstB);
+    out[27] = diff.pairs;
+    out[28] = r.nodes.size();
+    uint64_t mismatches = 0;
+    for (int k = 5; k <= 23; ++k) mismatches += out[k];
+    return mismatches ? 1 : 0;
+}

@@ -429,6 +429,65 @@ def lbvh_check(triangles, criterion: int | None = None) -> tuple:
     return rc, [int(v) for v in out]
 
 
+def triangle_records(triangles, instances, holes=None) -> np.ndarray:
+    """The 48-byte triangle records of world triangles (n x 9 floats) as a snapshot of the
+    world BVHs holds them (make_gpu_triangle: v0, e1 = v1 - v0, e2 = v2 - v0 in fp32,
+    instance, primitive = the triangle's index, flip 0): n x 12 uint32 words. holes: a
+    boolean mask of records replaced by hole records (all zero, instance 0xffffffff)."""
+    t = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    rec = np.zeros((t.shape[0], 12), np.uint32)
+    f = rec.view(np.float32)
+    f[:, 0:3] = t[:, 0:3]
+    f[:, 3:6] = t[:, 3:6] - t[:, 0:3]
+    f[:, 6:9] = t[:, 6:9] - t[:, 0:3]
+    rec[:, 9] = np.asarray(instances, np.uint32)
+    rec[:, 10] = np.arange(t.shape[0], dtype=np.uint32)
+    if holes is not None:
+        h = np.asarray(holes, bool)
+        rec[h] = 0
+        rec[h, 9] = 0xFFFFFFFF
+    return rec
+
+
+_LBVH_PARITY_KEYS = ("prims", "nodes", "records_with_holes", "depth", "why", "compaction", "wave_order", "header_counts", "header_box", "max_abs",
+                     "inflation", "keys", "sorted_indices", "splits", "shape", "node_header", "grid", "planes", "children", "records", "perm", "holes",
+                     "level_order", "padding", "first_device_node", "first_host_node", "hip_error", "pairs", "host_nodes")
+LBVH_PARITY_MISMATCHES = _LBVH_PARITY_KEYS[5:24]
+LBVH_WHY = ("", "no records", "no triangles", "record of an unknown instance", "too deep", "node scratch", "4 GiB", "other")
+
+
+def lbvh_device_parity(records, class_of, sun_dir=None, w_bits: int | None = None, device: int = 0) -> tuple:
+    """ark_ddgi_debug_lbvh_device_parity: the device LBVH build (the world's, or with sun_dir
+    the sun's light-space one) run once over triangle records (triangle_records) and compared
+    bit for bit, stage by stage, with its host restatement. class_of: instance -> hit-mask
+    class. Returns (rc, dict): prims, nodes, records_with_holes, depth, why (LBVH_WHY's text)
+    and one mismatch count per stage (LBVH_PARITY_MISMATCHES). Needs a GPU."""
+    lib = abi.load_library()
+    rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 12)
+    cls = np.ascontiguousarray(class_of, dtype=np.int32).reshape(-1)
+    sd = None if sun_dir is None else np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
+    out = (C.c_uint64 * 32)()
+    rc = lib.ark_ddgi_debug_lbvh_device_parity(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
+                                               None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits), out)
+    r = dict(zip(_LBVH_PARITY_KEYS, (int(v) for v in out)))
+    r["why"] = LBVH_WHY[r["why"]] if rc >= 0 else "error"
+    return rc, r
+
+
+def bvh8_compare_selftest(triangles, sun_dir=None, seed: int = 1) -> tuple:
+    """ark_ddgi_debug_bvh8_compare_selftest: the canonical tree comparison of
+    lbvh_device_parity tried on a renumbered twin of the host LBVH tree of the triangles and on
+    six mutations of it. Returns (rc, dict). No GPU."""
+    lib = abi.load_library()
+    tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
+    sd = None if sun_dir is None else np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
+    out = (C.c_uint64 * 16)()
+    rc = lib.ark_ddgi_debug_bvh8_compare_selftest(tris.ctypes.data, tris.shape[0], None if sd is None else sd.ctypes.data, int(seed), out)
+    keys = ("nodes", "renumbered", "twin_differences", "pairs", "twin_violations", "plane_looser", "grid_coarser", "children_exchanged",
+            "leaf_members_exchanged", "records_exchanged", "perm_altered", "full_check_plane_looser", "full_check_grid_coarser")
+    return rc, dict(zip(keys, (int(v) for v in out)))
+
+
 def frame_params(config: DDGIConfig, grid: ProbeGrid, app: AppState, first_probe_index: int,
                  light_pre_exposure: float = 1.0, ambient_illuminance: float = 0.0,
                  environment_brightness: float = 1.0) -> abi.ArkDdgiFrameParams:

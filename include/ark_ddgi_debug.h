@@ -90,6 +90,50 @@ int ark_ddgi_debug_scene_digest(struct ArkDdgiCtx* ctx, uint64_t* out);
 int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out);
 int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out);
 
+/* The device LBVH build itself (ARK_DDGI_FLAG_GPU_REBUILD, ARK_DDGI_FLAG_GPU_REBUILD_SUN: the
+ * product's driver and kernels, nothing else) run once on `device`, synchronously and without
+ * a context, over n_records 48-byte triangle records as a snapshot holds them (holes -
+ * instance 0xffffffff - included), and compared bit for bit with the host restatement
+ * (ark_ddgi_debug_lbvh_check's) of the same records. class_of[n_instances]: instance -> hit-mask
+ * class 0..2. sun_dir null: the world build; set: the light build in sun_frame's frame with
+ * slots in ascending w, w_bits of the key's Morton bits for w (negative: the default; the
+ * world build ignores it). The device's compaction order of the records comes from atomics;
+ * it is checked to be a permutation of exactly the records that are not holes and handed to
+ * the host restatement, which makes every later stage comparable, ties included. out[32]:
+ * [0] primitives, [1] nodes, [2] records with holes, [3] depth (of the device build), [4] the
+ * reason the device left the scene to the host (0 none, 1 no records, 2 no triangles, 3 a
+ * record of an unknown instance, 4 too deep, 5 node scratch, 6 4 GiB, 7 another), then the
+ * mismatch counts: [5] compaction not that permutation, [6] light build: a wave's survivors
+ * not one ascending run, [7] header counts and error word, [8] header box (compared with ==
+ * as floats), [9] largest |coordinate| bits, [10] inflation bits, [11] sorted keys, [12]
+ * sorted record indices, [13] splits (every internal index of every class range), and the
+ * trees in canonical form (walked from each root in slot order, internal children by rank):
+ * [14] shape (roots, opaqueNodes, depth, nodes per depth, counts), [15] imask / leaf_mask /
+ * leaf_tris / tri_stride, [16] p and e, [17] qlo / qhi bytes of occupied slots, [18] child
+ * indices, [19] records of leaf slots (48 bytes, row by row), [20] their perm entries, [21]
+ * row positions that are not holes, [22] the level order against the one recomputed from the
+ * nodes, [23] the padding record not all zero; [24], [25] the first differing node pair
+ * (device, host; ~0: none), [26] the HIP error, [27] node pairs visited, [28] host nodes.
+ * Returns 0 when every count is 0, 1 on a mismatch, 2 when the device left the scene to the
+ * host ([4]; nothing built, nothing compared), negative on an invalid argument or a HIP error. */
+int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                      const float* sun_dir, int w_bits, uint64_t* out);
+
+/* compare_bvh8_canonical (the tree comparison of ark_ddgi_debug_lbvh_device_parity) tried on
+ * the host: the LBVH restatement's tree of n triangles (9 floats each; triangle i of instance
+ * and class i mod 3; sun_dir set: the light build instead) against a twin whose sibling blocks
+ * and rows within each level are renumbered in a seeded random order, as the device's atomics
+ * do, and against six mutations of the twin: (a) one occupied plane one quantum looser, (b) one
+ * node's grid exponent raised by one with its planes re-quantised outward, (c) two internal
+ * children of a node exchanged, (d) two leaf members of a node exchanged between slots, (e) two
+ * records of different leaf slots exchanged, (f) one perm entry altered. out[16]: [0] nodes,
+ * [1] nodes the twin renumbered, [2] differences reported for the twin (0 expected), [3] node
+ * pairs visited, [4] the full check's violations for the twin, [5..10] differences of the
+ * expected kind reported for (a)..(f) (non-zero expected), [11], [12] the full check's
+ * violations for (a), (b) (0: it cannot tell them from the intended tree). Returns 0 when all
+ * is as expected. No GPU. */
+int ark_ddgi_debug_bvh8_compare_selftest(const float* triangles, uint64_t n, const float* sun_dir, uint64_t seed, uint64_t* out);
+
 /* The world BVH8s the context's kernels read now (the front copy, after everything it
  * enqueued), downloaded and checked on the host. out[8] = {nodes, leaf children, max
  * depth, violations, records that are not holes, records with holes, order-independent

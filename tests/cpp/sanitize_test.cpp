@@ -1,7 +1,8 @@
 // ASan + UBSan run of the host-side code on the path (SURVEY §5 "race detection /
 // sanitizers"): the CPU oracle (frames with offsets, the AO bake, lighting compose),
 // the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check,
-// the three hit-mask classes' build (build_world_bvh8) and the refit's level order, and
+// the three hit-mask classes' build (build_world_bvh8) and the refit's level order, the
+// LBVH restatement with the canonical tree comparison (compare_bvh8_canonical), and
 // the background rebuilds' scheduling (scene_rebuild_policy.h, a table of cases).
 // Built by tests/test_sanitizers.py with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=all; any report aborts with a non-zero status.
@@ -271,6 +272,19 @@ int main()
     for (int single = 0; single < 3; ++single) CHECK(worldBvh8Case(tri, 301, single, false) == 0);
     CHECK(worldBvh8Case(tri, 301, 0, true) == 0);
     CHECK(worldBvh8Case(tri, 301, 1, true) == 0);
+
+    // the device-build parity tests' tree comparison (compare_bvh8_canonical) over the LBVH
+    // restatement's trees, three classes and the sun's: a renumbered twin compares clean,
+    // six mutations of it are reported (tests/test_bvh8_compare.py, here under the sanitizers)
+    {
+        const float sunDir[3] = { 0.3f, -1.0f, -0.4f };
+        uint64_t cmp[16] = {};
+        CHECK(ark_ddgi_debug_bvh8_compare_selftest(tri.data(), nTri, nullptr, 5, cmp) == 0);
+        CHECK(cmp[2] == 0 && cmp[3] == cmp[0] && cmp[11] == 0 && cmp[12] == 0);
+        CHECK(ark_ddgi_debug_bvh8_compare_selftest(tri.data(), nTri, sunDir, 5, cmp) == 0);
+        CHECK(cmp[2] == 0 && cmp[3] == cmp[0] && cmp[11] == 0 && cmp[12] == 0);
+        std::printf("bvh8 compare: %llu nodes\n", static_cast<unsigned long long>(cmp[0]));
+    }
 
     // oracle: 4x4x4 probes x 64 rays, offsets on, three frames
     ArkDdgiDesc d;
