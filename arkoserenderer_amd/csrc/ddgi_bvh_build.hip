@@ -1,5 +1,5 @@
 // ddgi_bvh_build.hip — the world BVH8s' topology built on the device from a snapshot of
-// the triangle records (ark_ddgi.cpp runWorldJobGpu, ARK_DDGI_FLAG_GPU_REBUILD): an
+// the triangle records (lbvh_device_build.cpp buildLbvhGpu, ARK_DDGI_FLAG_GPU_REBUILD): an
 // LBVH (Karras 2012) per hit-mask class, collapsed into 8-wide nodes level by level.
 // The decisions are lbvh_build.h's (shared with the host check
 // ark_ddgi_debug_lbvh_check); the boxes, grids and planes are k_refit_nodes'

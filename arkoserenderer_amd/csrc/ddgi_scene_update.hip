@@ -9,7 +9,7 @@
 //   k_refit_nodes    one BVH8 level (deepest first), the nodes with a moved instance below
 //                    them: the moved instances' records of their leaf slots re-transformed
 //                    from the object-space pools in set_scene's fp32 operation order
-//                    (ark_ddgi.cpp), each node's child boxes - leaf slots
+//                    (scene_store.cpp), each node's child boxes - leaf slots
 //                    from their triangle records, internal children from the level below
 //                    - inflated as the builder inflates them (bvh_builder.cpp writeNode),
 //                    the node's quantization grid and outward-rounded child planes

@@ -1,6 +1,7 @@
 // scene_rebuild_policy.h — which background BVH build a scene call starts (scene_store.cpp:
-// sceneMaintenance, sceneSunStep). Pure host logic over a plain struct: no device call, so
-// that the turn-taking is tested on the CPU (tests/cpp/sanitize_test.cpp).
+// sceneMaintenance, sceneSunStep) and how a job goes on after its device build
+// (runRebuildJob). Pure host logic over plain values: no device call, so that the
+// turn-taking and the fallback decision are tested on the CPU (tests/cpp/sanitize_test.cpp).
 #pragma once
 
 #include <cstdint>
@@ -73,6 +74,20 @@ inline RebuildStart rebuildToStart(const RebuildState& q)
     const bool sunYields = q.sunOnly ? worldLoosened : world;
     if (sun && (!sunYields || q.lastBackground != kBackgroundSun)) return sunLoosened && sunDevice ? RebuildStart::SunDevice : RebuildStart::Sun;
     return RebuildStart::None;
+}
+
+// How a rebuild job goes on after its device build (scene_store.cpp: runRebuildJob): the
+// result is Installed as built; the job has Failed (the device is not used again by it);
+// or the HostBuild builds this scene from the same snapshot, within the job.
+enum class DeviceBuildOutcome { Installed, HostBuild, Failed };
+
+// hipOk: every HIP call of the attempt succeeded; deviceFault: the failing one's error is a
+// device fault (isDeviceFault); declined: the build named a reason to leave the scene to
+// the host. A HIP error that is not a device fault is the host's too.
+inline DeviceBuildOutcome deviceBuildOutcome(bool hipOk, bool deviceFault, bool declined)
+{
+    if (hipOk && !declined) return DeviceBuildOutcome::Installed;
+    return deviceFault ? DeviceBuildOutcome::Failed : DeviceBuildOutcome::HostBuild;
 }
 
 } // namespace ark

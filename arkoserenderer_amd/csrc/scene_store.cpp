@@ -14,90 +14,52 @@
 #include "../../include/ark_ddgi_debug.h"
 #include "ark_fmath.h"
 #include "bvh_builder.h"
+#include "lbvh_device_build.h"
 
 // (every function here that can fail has an ErrorSink* err in scope)
 #define ARK_HIP(expr) ARK_HIP_TO(err, expr)
 
 namespace ark {
 
-// `nodes` and `tris` into b.buf (allocated here; b's offset and counts set). s == nullptr:
-// synchronous copies; else stream-ordered on `s` and complete on return.
-static hipError_t uploadBvh(const std::vector<GpuBvh8Node>& nodes, std::vector<GpuTriangle>& tris, hipStream_t s, DeviceBvh& b)
-{
-    b.triOffset = DeviceBvh::triOffsetFor(nodes.size());
-    b.nodeCount = nodes.size();
-    b.records = tris.size();
-    auto copy = [s](void* dst, const void* src, size_t n) { return s ? hipMemcpyAsync(dst, src, n, hipMemcpyHostToDevice, s) : hipMemcpy(dst, src, n, hipMemcpyHostToDevice); };
-    tris.push_back(GpuTriangle {}); // the padding record
-    hipError_t e = b.buf.alloc(DeviceBvh::bytesFor(b.nodeCount, b.records));
-    if (e == hipSuccess) e = copy(b.buf.ptr, nodes.data(), nodes.size() * sizeof(GpuBvh8Node));
-    if (e == hipSuccess) e = copy(b.tris(b.buf), tris.data(), tris.size() * sizeof(GpuTriangle));
-    if (e == hipSuccess && s) e = hipStreamSynchronize(s);
-    tris.pop_back();
-    return e;
-}
-
-// A background rebuild of the sun's light-space BVH (sunCollect / sunStart): a host thread
-// waits for a device snapshot of the world BVHs' triangle records (taken in stream
-// order behind the refits, `snap` / `evSnap`), builds the BVH for `dir` and uploads it
-// into `bvh`; `done` set last (release).
-struct SunJob {
+// A background rebuild (runRebuildJob), of the world BVHs after refits (worldCollect /
+// worldStart; the reference rebuilds its TLAS in full every 60 frames, GpuScene.cpp:998-1010)
+// or of the sun's light-space BVH for `dir` (sunCollect / sunStart). A host thread takes a
+// device snapshot of the refitted triangle records, taken in stream order behind the refits
+// (`snap` / `evSnap`), builds from them and uploads the result into `bvh`, level order
+// included; `done` is set last (release).
+//  - world: the three hit-mask classes' BVHs anew (set_scene's builder, or the device's),
+//    every record's words kept as they were (so hits stay bit-identical), and the new record
+//    order's source indices (perm, for the shading records).
+//  - sun: the light-space BVH8 over every class's records in `frame`.
+struct RebuildJob {
+    enum Kind { World, Sun } kind = World;
     std::thread t;
     std::atomic<bool> done { false };
-    float dir[3] {};
-    uint32_t version = 0; // SceneStore::version of the snapshot
+    uint32_t version = 0;  // SceneStore::version of the snapshot
     uint32_t refitsAt = 0; // SceneStore::refitCount of the snapshot (later refits: refitted forward at install)
-    DeviceBuffer snap;    // the records it builds from
-    hipEvent_t evSnap = nullptr;
-    DeviceBvh bvh;        // the result (its level order still on the host: levelOrder)
-    std::vector<uint32_t> levelOrder;
-    double frame[9] {};
-    float ms = 0.0f;
-    bool ok = false;
-    // runSunJobGpu: the device built the result; or it handed the job to the host build
-    // (t0: the job's start, so that ms stays the whole job's wall time)
-    bool gpu = false, gpuFallback = false, gpuFallbackCounted = false;
-    uint32_t instances = 0; // of the scene (the device build checks the records' against it)
-    std::chrono::steady_clock::time_point t0 {};
-    ~SunJob()
-    {
-        if (t.joinable()) t.join();
-        bvh.release(); // not installed (an installed one was moved to the scene)
-        snap.release();
-        if (evSnap) (void)hipEventDestroy(evSnap);
-    }
-};
-
-// A background rebuild of the world BVHs after refits (worldCollect / worldStart; the reference
-// rebuilds its TLAS in full every 60 frames, GpuScene.cpp:998-1010): a host thread takes
-// a device snapshot of the refitted triangle records, builds the three hit-mask classes'
-// BVHs anew from them (set_scene's builder), keeps every record's words as they were
-// (so hits stay bit-identical) and uploads nodes + records, the new record order's
-// source indices (perm, for the shading records) and the refit's level order.
-struct WorldJob {
-    std::thread t;
-    std::atomic<bool> done { false };
-    uint32_t version = 0, refitsAt = 0;
-    DeviceBuffer snap;
+    DeviceBuffer snap;     // the records it builds from
     hipEvent_t evSnap = nullptr;
     uint64_t snapRecords = 0;
+    DeviceBvh bvh;         // the result
+    float ms = 0.0f;       // the whole job's wall time (a device attempt that fell back included)
+    bool ok = false;
+    // the device built the result; or it handed the job to the host build (until counted)
+    bool gpu = false, gpuFallback = false;
+    // world
     std::vector<int> classOf; // instance -> hit-mask class (0 opaque, 1 masked, 2 blend)
-    DeviceBvh bvh;            // the result, its level order uploaded
     DeviceBuffer perm;
     int32_t roots[3] { -1, -1, -1 };
     uint32_t opaqueNodes = 0, maxLeaf = 0;
     float sah = 0.0f;
-    float ms = 0.0f;
-    bool ok = false;
-    // runWorldJobGpu: the device built the result; or it handed the job to the host build
-    // (t0: the job's start, so that ms stays the whole job's wall time)
-    bool gpu = false, gpuFallback = false;
-    std::chrono::steady_clock::time_point t0 {};
     std::string error;
-    ~WorldJob()
+    // sun
+    float dir[3] {};
+    double frame[9] {};     // sun_frame(dir)
+    uint32_t instances = 0; // of the scene (the device build checks the records' against it)
+    ~RebuildJob()
     {
         if (t.joinable()) t.join();
-        bvh.release();
+        bvh.release(); // not installed (an installed one was moved to the scene)
         for (DeviceBuffer* b : { &perm, &snap }) b->release();
         if (evSnap) (void)hipEventDestroy(evSnap);
     }
@@ -387,544 +349,206 @@ hipError_t snapshotRecords(SceneStore& st, DeviceBuffer& snap, hipEvent_t& ev, h
     return e;
 }
 
-// The sun rebuild's thread: the snapshot of the world records, the light-space BVH of
-// job->dir on the host (as set_scene builds it), uploaded into job->bvh.
-void runSunJob(SunJob* job, int device, uint64_t count, int threads)
-{
-    const auto t0 = job->gpuFallback ? job->t0 : std::chrono::steady_clock::now();
-    bool ok = hipSetDevice(device) == hipSuccess;
-    hipStream_t s = nullptr;
-    ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventSynchronize(job->evSnap) == hipSuccess;
-    std::vector<GpuTriangle> rec(ok ? count : 0);
-    ok = ok && hipMemcpyAsync(rec.data(), job->snap.ptr, count * sizeof(GpuTriangle), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
-    Bvh8BuildResult r;
-    if (ok) {
-        SunBvhInput in;
-        sun_frame(job->dir, in.frame);
-        sun_add_records(in, rec, threads);
-        std::vector<GpuTriangle>().swap(rec);
-        BvhBuildOptions opt;
-        opt.threads = threads;
-        Bvh8CollapseOptions copt;
-        copt.threads = threads;
-        ok = build_sun_bvh(in, opt, copt, r) && !r.nodes.empty();
-        std::memcpy(job->frame, in.frame, sizeof(job->frame));
-        job->bvh.inflateAbs = in.inflateAbs;
-        job->bvh.depth = r.max_depth;
-        const int32_t root = 0;
-        ok = ok && bvhLevelOrder(r.nodes.data(), r.nodes.size(), &root, 1, job->levelOrder, job->bvh.levelOffsets);
-    }
-    ok = ok && uploadBvh(r.nodes, r.tris, s, job->bvh) == hipSuccess;
-    if (s) (void)hipStreamDestroy(s);
-    job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    job->ok = ok;
-    job->done.store(true, std::memory_order_release);
-}
+// What a host build hands to the upload (hostBuild)
+struct HostBvh {
+    std::vector<GpuBvh8Node> nodes;
+    std::vector<GpuTriangle> tris;
+    std::vector<uint32_t> perm, order;
+};
 
-// The world rebuild's thread: the three classes' BVHs from the snapshot's records (their
+// The world rebuild on the host: the three classes' BVHs from the snapshot's records (their
 // vertices v0, v0 + e1, v0 + e2; each leaf record then replaced by its source record,
 // bit for bit), the record order's source indices and the refit's level order.
-void runWorldJob(WorldJob* job, int device, int threads)
+bool hostBuildWorld(RebuildJob* job, const std::vector<GpuTriangle>& rec, int threads, HostBvh& out)
 {
-    const auto t0 = job->gpuFallback ? job->t0 : std::chrono::steady_clock::now();
-    bool ok = hipSetDevice(device) == hipSuccess;
-    hipStream_t s = nullptr;
-    ok = ok && hipStreamCreateWithFlags(&s, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipEventSynchronize(job->evSnap) == hipSuccess;
+    std::vector<BuildTriangle> cls[3];
+    for (size_t i = 0; i < rec.size(); ++i) {
+        const GpuTriangle& g = rec[i];
+        if (isHoleTriangle(g)) continue;
+        uint32_t inst, flip;
+        std::memcpy(&inst, &g.t2[1], 4);
+        std::memcpy(&flip, &g.t2[3], 4);
+        if (inst >= job->classOf.size()) {
+            job->error = "record of an unknown instance";
+            return false;
+        }
+        BuildTriangle t;
+        const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
+        for (int a = 0; a < 3; ++a) {
+            t.v0[a] = g.t0[a];
+            t.v1[a] = g.t0[a] + e1[a];
+            t.v2[a] = g.t0[a] + e2[a];
+        }
+        t.instance = inst;
+        t.primitive = static_cast<uint32_t>(i); // the source record (replaced below)
+        t.flip_facing = flip;
+        cls[job->classOf[inst]].push_back(t);
+    }
+    WorldBvh8 w;
+    BvhBuildOptions opt;
+    opt.threads = threads;
+    Bvh8CollapseOptions copt;
+    copt.threads = threads;
+    const bool ok = build_world_bvh8(cls, opt, copt, w, job->error);
+    if (w.maxLeaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) job->error = "BVH2 leaf over the leaf size";
+    if (!ok) return false;
+    out.perm.assign(w.tris.size(), 0xffffffffu);
+    for (size_t i = 0; i < w.tris.size(); ++i) {
+        GpuTriangle& g = w.tris[i];
+        if (isHoleTriangle(g)) continue;
+        uint32_t src;
+        std::memcpy(&src, &g.t2[2], 4);
+        out.perm[i] = src;
+        g = rec[src];
+    }
+    std::copy(w.roots, w.roots + 3, job->roots);
+    job->opaqueNodes = w.opaqueNodes;
+    job->maxLeaf = w.maxLeaf;
+    job->sah = w.sah;
+    job->bvh.depth = w.depth;
+    out.nodes.swap(w.nodes);
+    out.tris.swap(w.tris);
+    return bvhLevelOrder(out.nodes.data(), out.nodes.size(), job->roots, 3, out.order, job->bvh.levelOffsets);
+}
+
+// The sun rebuild on the host: the light-space BVH of job->dir from the snapshot's records
+// (as set_scene builds it; `rec` freed once the builder has its input) and its level order.
+bool hostBuildSun(RebuildJob* job, std::vector<GpuTriangle>& rec, int threads, HostBvh& out)
+{
+    SunBvhInput in;
+    std::memcpy(in.frame, job->frame, sizeof(in.frame));
+    sun_add_records(in, rec, threads);
+    std::vector<GpuTriangle>().swap(rec);
+    BvhBuildOptions opt;
+    opt.threads = threads;
+    Bvh8CollapseOptions copt;
+    copt.threads = threads;
+    Bvh8BuildResult r;
+    const bool ok = build_sun_bvh(in, opt, copt, r) && !r.nodes.empty();
+    job->bvh.inflateAbs = in.inflateAbs;
+    job->bvh.depth = r.max_depth;
+    out.nodes.swap(r.nodes);
+    out.tris.swap(r.tris);
+    const int32_t root = 0;
+    return ok && bvhLevelOrder(out.nodes.data(), out.nodes.size(), &root, 1, out.order, job->bvh.levelOffsets);
+}
+
+// A job's host build on `s`: the snapshot downloaded, the kind's builder, the result
+// uploaded into job->bvh (the world's perm with it).
+bool hostBuild(RebuildJob* job, hipStream_t s, int threads)
+{
+    const bool world = job->kind == RebuildJob::World;
+    bool ok = s && hipEventSynchronize(job->evSnap) == hipSuccess; // (no stream: the job's device could not be used)
     std::vector<GpuTriangle> rec(ok ? job->snapRecords : 0);
     ok = ok && hipMemcpyAsync(rec.data(), job->snap.ptr, rec.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost, s) == hipSuccess && hipStreamSynchronize(s) == hipSuccess;
     if (!ok) job->error = "snapshot download failed";
-    std::vector<BuildTriangle> cls[3];
+    HostBvh h;
+    ok = ok && (world ? hostBuildWorld(job, rec, threads, h) : hostBuildSun(job, rec, threads, h));
     if (ok) {
-        for (size_t i = 0; i < rec.size(); ++i) {
-            const GpuTriangle& g = rec[i];
-            if (isHoleTriangle(g)) continue;
-            uint32_t inst, flip;
-            std::memcpy(&inst, &g.t2[1], 4);
-            std::memcpy(&flip, &g.t2[3], 4);
-            if (inst >= job->classOf.size()) {
-                ok = false;
-                job->error = "record of an unknown instance";
-                break;
-            }
-            BuildTriangle t;
-            const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-            for (int a = 0; a < 3; ++a) {
-                t.v0[a] = g.t0[a];
-                t.v1[a] = g.t0[a] + e1[a];
-                t.v2[a] = g.t0[a] + e2[a];
-            }
-            t.instance = inst;
-            t.primitive = static_cast<uint32_t>(i); // the source record (replaced below)
-            t.flip_facing = flip;
-            cls[job->classOf[inst]].push_back(t);
-        }
-    }
-    WorldBvh8 w;
-    std::vector<uint32_t> perm, order;
-    if (ok) {
-        BvhBuildOptions opt;
-        opt.threads = threads;
-        Bvh8CollapseOptions copt;
-        copt.threads = threads;
-        ok = build_world_bvh8(cls, opt, copt, w, job->error);
-        if (w.maxLeaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) job->error = "BVH2 leaf over the leaf size";
-    }
-    if (ok) {
-        perm.assign(w.tris.size(), 0xffffffffu);
-        for (size_t i = 0; i < w.tris.size(); ++i) {
-            GpuTriangle& g = w.tris[i];
-            if (isHoleTriangle(g)) continue;
-            uint32_t src;
-            std::memcpy(&src, &g.t2[2], 4);
-            perm[i] = src;
-            g = rec[src];
-        }
-        std::copy(w.roots, w.roots + 3, job->roots);
-        job->opaqueNodes = w.opaqueNodes;
-        job->maxLeaf = w.maxLeaf;
-        job->sah = w.sah;
-        job->bvh.depth = w.depth;
-        ok = bvhLevelOrder(w.nodes.data(), w.nodes.size(), w.roots, 3, order, job->bvh.levelOffsets);
-    }
-    if (ok) {
-        ok = DeviceBvh::bytesFor(w.nodes.size(), w.tris.size()) < (1ull << 32) && job->perm.alloc(std::max<size_t>(16, perm.size() * 4)) == hipSuccess &&
-             job->bvh.order.alloc(std::max<size_t>(16, order.size() * 4)) == hipSuccess &&
-             hipMemcpyAsync(job->perm.ptr, perm.data(), perm.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess &&
-             hipMemcpyAsync(job->bvh.order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess && uploadBvh(w.nodes, w.tris, s, job->bvh) == hipSuccess;
+        ok = (!world || (DeviceBvh::bytesFor(h.nodes.size(), h.tris.size()) < (1ull << 32) && job->perm.alloc(std::max<size_t>(16, h.perm.size() * 4)) == hipSuccess)) &&
+             job->bvh.order.alloc(std::max<size_t>(16, h.order.size() * 4)) == hipSuccess &&
+             (!world || hipMemcpyAsync(job->perm.ptr, h.perm.data(), h.perm.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess) &&
+             hipMemcpyAsync(job->bvh.order.ptr, h.order.data(), h.order.size() * 4, hipMemcpyHostToDevice, s) == hipSuccess && uploadBvh(h.nodes, h.tris, s, job->bvh) == hipSuccess;
         if (!ok && job->error.empty()) job->error = "upload failed";
     }
-    if (s) (void)hipStreamDestroy(s);
-    job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    job->ok = ok;
-    job->done.store(true, std::memory_order_release);
+    return ok;
 }
 
-// The deepest BVH8 the device build installs. The traversal's spill area is sized from the
-// installed depth (ensureSpill: depth + 2 - kStackLds entries per lane, DeviceBvh::depth),
-// and the deepest tree the host builds hand it is bounded by the BVH2 builder's depth cap
-// (BvhBuildOptions::max_depth, 60); a radix tree over coincident centroids can be
-// deeper, and such a scene is left to the host build.
-constexpr uint32_t kGpuBuildMaxDepth = 60;
-
-// Errors after which the device is not used again by the job (no host fallback)
-bool isDeviceFault(hipError_t e)
+// What the two device builds differ in (LbvhGpuBuild): the world's three class ranges and
+// its perm; the sun's one LBVH over every class's records, keyed and boxed in the sun's
+// frame, its slots in ascending w.
+void deviceBuildWorld(RebuildJob* job, LbvhGpuBuild& g)
 {
-    return e == hipErrorIllegalAddress || e == hipErrorLaunchFailure || e == hipErrorLaunchTimeOut || e == hipErrorECCNotCorrectable || e == hipErrorAssert ||
-           e == hipErrorNoDevice || e == hipErrorInvalidDevice;
+    g.classHost.assign(job->classOf.begin(), job->classOf.end());
+    g.perm = &job->perm;
 }
 
-// What a traced device build keeps on the host (ark_ddgi_debug_lbvh_device_parity): every
-// stage's result, downloaded before buildLbvhGpu returns (the stages after a fallback: empty)
-struct LbvhGpuTrace {
-    LbvhHeader hdr {};                            // as the build uses it (the light build's classCount[0] = prims)
-    std::vector<uint32_t> idx, idxSorted, split;  // hdr.prims each (split: set at the internal indices of each class range)
-    std::vector<uint64_t> keysSorted;
-    std::vector<GpuBvh8Node> nodes;
-    std::vector<GpuTriangle> tris;                // the rows, then the padding record
-    std::vector<uint32_t> perm, order, levelOffsets;
-    int32_t roots[3] { -1, -1, -1 };
-    uint32_t opaqueNodes = 0, depth = 0;
-    float inflateAbs = 0.0f;
-    bool built = false;
-    std::string why;                              // the fallback reason
-};
-
-// What the device builds of the world BVH8s and of the sun's light-space BVH8 differ in
-// (buildLbvhGpu): the class ranges, the key kernels, the slot rule and the refit's boxes.
-struct LbvhGpuBuild {
-    // in
-    const GpuTriangle* snap = nullptr; // the snapshot's records, ready once evSnap has completed
-    hipEvent_t evSnap = nullptr;
-    uint32_t records = 0;
-    std::vector<uint32_t> classHost;   // instance -> class (its size: the instances)
-    bool light = false;                // the sun's: one range over every class, keys and boxes in `frame`
-    double frame[9] {};
-    int slotRule = lbvh::kSlotsOctant, wBits = lbvh::kMortonBits;
-    DeviceBvh* bvh = nullptr;          // out: buffer, level order (device and offsets), counts, depth, inflateAbs
-    DeviceBuffer* perm = nullptr;      // out: the record order's source indices (null: not wanted)
-    LbvhGpuTrace* trace = nullptr;     // out: the stages' results (null in the product paths: nothing more is enqueued)
-    // out
-    int32_t roots[3] { -1, -1, -1 };
-    uint32_t opaqueNodes = 0, prims = 0;
-    std::vector<uint32_t> order;       // the level order on the host
-};
-
-// The device build on `s`: hipSuccess and `why` empty when g.bvh holds the result; `why`
-// set when the host has to build this scene.
-hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
+void deviceBuildSun(RebuildJob* job, LbvhGpuBuild& g)
 {
-    // Scratch in two allocations (one sized from the snapshot, one from the count of
-    // triangles read back): a free waits for the device's streams, frames in flight included
-    struct Arena {
-        DeviceBuffer buf;
-        size_t used = 0;
-        static size_t pad(size_t n) { return (n + 255) & ~static_cast<size_t>(255); }
-        DeviceBuffer take(size_t n)
-        {
-            DeviceBuffer b;
-            b.ptr = static_cast<char*>(buf.ptr) + used;
-            b.bytes = n;
-            used += pad(n);
-            return b; // a view: never released
-        }
-        ~Arena() { buf.release(); }
-    } arenaA, arenaB;
-    struct {
-        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes;
-    } w;
-    hipError_t e = hipSuccess;
-    struct KeepWhy {
-        LbvhGpuTrace* trace;
-        const std::string& why;
-        ~KeepWhy()
-        {
-            if (trace) trace->why = why;
-        }
-    } keepWhy { g.trace, why };
-#define ARK_GB(expr)                          \
-    do {                                      \
-        if ((e = (expr)) != hipSuccess) return e; \
-    } while (0)
-    if (g.records == 0 || g.classHost.empty()) {
-        why = "no records";
-        return hipSuccess;
-    }
-    const uint32_t records = g.records, instances = static_cast<uint32_t>(g.classHost.size());
-    const GpuTriangle* snap = g.snap;
-    const std::vector<uint32_t>& classHost = g.classHost;
-    ARK_GB(arenaA.buf.alloc(Arena::pad(instances * 4ull) + Arena::pad(sizeof(LbvhHeader)) + Arena::pad(records * 4ull) + Arena::pad(records * 8ull)));
-    w.classOf = arenaA.take(instances * 4ull);
-    w.hdr = arenaA.take(sizeof(LbvhHeader));
-    w.idx = arenaA.take(records * 4ull);
-    w.keys = arenaA.take(records * 8ull);
-    ARK_GB(hipMemcpyAsync(w.classOf.ptr, classHost.data(), instances * 4ull, hipMemcpyHostToDevice, s));
-    ARK_GB(hipStreamWaitEvent(s, g.evSnap, 0));
-    if (g.light) {
-        LbvhFrame fr;
-        std::memcpy(fr.m, g.frame, sizeof(fr.m));
-        ARK_GB(launch_lbvh_prims_light(snap, records, instances, fr, g.wBits, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
-    } else {
-        ARK_GB(launch_lbvh_prims(snap, records, w.classOf.as<uint32_t>(), instances, w.idx.as<uint32_t>(), w.keys.as<uint64_t>(), w.hdr.as<LbvhHeader>(), s));
-    }
-    LbvhHeader hdr {};
-    ARK_GB(hipMemcpyAsync(&hdr, w.hdr.ptr, sizeof(hdr), hipMemcpyDeviceToHost, s));
-    ARK_GB(hipStreamSynchronize(s));
-    if (g.light && !hdr.error) hdr.classCount[0] = hdr.prims; // one range [0, n): the keys' class bits are 0
-    if (g.trace) g.trace->hdr = hdr;
-    if (hdr.error || hdr.prims == 0 || hdr.prims > records || hdr.classCount[0] + hdr.classCount[1] + hdr.classCount[2] != hdr.prims) {
-        why = hdr.error ? "record of an unknown instance" : "no triangles";
-        return hipSuccess;
-    }
-    const uint32_t n = hdr.prims;
-    // sort the (key, record index) pairs
-    size_t tempBytes = 0;
-    ARK_GB(launch_lbvh_sort(nullptr, tempBytes, w.keys.as<uint64_t>(), nullptr, w.idx.as<uint32_t>(), nullptr, n, s));
-    // (the collapse's bound on the nodes: below)
-    const uint32_t nodeCap = n / 2u + 8u;
-    {
-        const size_t sizes[] = { tempBytes, n * 8ull, n * 4ull, n * 4ull, nodeCap * sizeof(GpuBvh8Node), nodeCap * sizeof(lbvh::Member), nodeCap * sizeof(lbvh::Member),
-                                 n * 4ull, kLbvhCounters * 4ull, nodeCap * 8ull, instances * sizeof(RefitInstance), nodeCap * 6ull * sizeof(float) };
-        size_t total = 0;
-        for (size_t b : sizes) total += Arena::pad(b);
-        ARK_GB(arenaB.buf.alloc(total));
-        w.sortTemp = arenaB.take(sizes[0]);
-        w.keysSorted = arenaB.take(sizes[1]);
-        w.idxSorted = arenaB.take(sizes[2]);
-        w.split = arenaB.take(sizes[3]);
-        w.nodes = arenaB.take(sizes[4]);
-        w.items[0] = arenaB.take(sizes[5]);
-        w.items[1] = arenaB.take(sizes[6]);
-        w.position = arenaB.take(sizes[7]);
-        w.counters = arenaB.take(sizes[8]);
-        w.masks = arenaB.take(sizes[9]);
-        w.inst = arenaB.take(sizes[10]);
-        w.boxes = arenaB.take(sizes[11]);
-    }
-    ARK_GB(launch_lbvh_sort(w.sortTemp.ptr, tempBytes, w.keys.as<uint64_t>(), w.keysSorted.as<uint64_t>(), w.idx.as<uint32_t>(), w.idxSorted.as<uint32_t>(), n, s));
-    // the radix trees, class by class
-    uint32_t classLo[3], first = 0;
-    for (int c = 0; c < 3; ++c) {
-        classLo[c] = first;
-        first += hdr.classCount[c];
-        ARK_GB(launch_lbvh_hierarchy(w.keysSorted.as<uint64_t>(), classLo[c], classLo[c] + hdr.classCount[c], w.split.as<uint32_t>(), s));
-    }
-    // the collapse. Every BVH8 node but a class's root is a BVH2 node of at least 4
-    // triangles, and one with an internal child has 8 members. With L nodes without an
-    // internal child (4 triangles of their own each), C with one (7 members of their
-    // own) and fewer than L with more, 4 L + 7 C <= n bounds 2 L + C by n / 2: fewer than
-    // n / 2 + 3 nodes (the kernel checks, and the job falls back beyond).
-    ARK_GB(hipMemsetAsync(w.counters.ptr, 0, kLbvhCounters * 4, s));
-    float lo[3], hi[3];
-    LbvhCollapseArgs a {};
-    for (int k = 0; k < 3; ++k) {
-        lo[k] = lbvhOrderedFloat(hdr.lo[k]);
-        hi[k] = lbvhOrderedFloat(hdr.hi[k]);
-        a.extent[k] = hi[k] - lo[k];
-    }
-    a.keys = w.keysSorted.as<uint64_t>();
-    a.split = w.split.as<uint32_t>();
-    a.nodes = w.nodes.as<GpuBvh8Node>();
-    a.position = w.position.as<uint32_t>();
-    a.counters = w.counters.as<uint32_t>();
-    a.criterion = lbvh::kDefaultCriterion;
-    a.slotRule = g.slotRule;
-    a.wBits = g.wBits;
-    std::vector<std::array<uint32_t, 3>> levels; // node counts [depth][class]
-    uint32_t nodeTotal = 0, counters[kLbvhCounters] = {};
-    for (int c = 0; c < 3; ++c) {
-        if (!hdr.classCount[c]) continue;
-        g.roots[c] = static_cast<int32_t>(nodeTotal);
-        a.items = nullptr;
-        a.root.r.first = classLo[c];
-        a.root.r.last = classLo[c] + hdr.classCount[c] - 1u;
-        a.root.node = classLo[c];
-        a.count = 1;
-        a.levelBase = nodeTotal;
-        int pong = 0;
-        for (uint32_t depth = 0; a.count; ++depth) {
-            if (depth >= kGpuBuildMaxDepth || a.levelBase + a.count > nodeCap) {
-                why = depth >= kGpuBuildMaxDepth ? "BVH8 deeper than the device build installs" : "more nodes than the device build's scratch";
-                return hipSuccess;
-            }
-            a.nextBase = a.levelBase + a.count;
-            a.nextCapacity = nodeCap - a.nextBase;
-            a.next = w.items[pong].as<lbvh::Member>();
-            ARK_GB(hipMemsetAsync(w.counters.as<uint32_t>() + kLbvhNextCount, 0, 4, s));
-            ARK_GB(launch_lbvh_collapse(a, s));
-            // the level's count, before the next level is launched
-            ARK_GB(hipMemcpyAsync(counters, w.counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, s));
-            ARK_GB(hipStreamSynchronize(s));
-            if (counters[kLbvhOverflow]) {
-                why = "more nodes than the device build's scratch";
-                return hipSuccess;
-            }
-            if (levels.size() <= depth) levels.push_back({ 0u, 0u, 0u });
-            levels[depth][c] = a.count;
-            a.items = a.next;
-            a.levelBase = a.nextBase;
-            a.count = counters[kLbvhNextCount];
-            pong ^= 1;
-        }
-        nodeTotal = a.levelBase;
-        if (c == 0) g.opaqueNodes = nodeTotal;
-    }
-    const uint32_t outRecords = counters[kLbvhRecords];
-    if (!(DeviceBvh::bytesFor(nodeTotal, outRecords) < (1ull << 32))) {
-        why = "nodes and records of 4 GiB or more";
-        return hipSuccess;
-    }
-    // the installed buffers, sized from the counts read back
-    DeviceBvh& b = *g.bvh;
-    b.triOffset = DeviceBvh::triOffsetFor(nodeTotal);
-    ARK_GB(b.buf.alloc(DeviceBvh::bytesFor(nodeTotal, outRecords)));
-    if (g.perm) ARK_GB(g.perm->alloc(std::max<size_t>(16, outRecords * 4ull)));
-    GpuBvh8Node* nodes = b.nodes(b.buf);
-    GpuTriangle* tris = b.tris(b.buf);
-    ARK_GB(hipMemcpyAsync(nodes, w.nodes.ptr, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToDevice, s));
-    ARK_GB(launch_lbvh_scatter(snap, w.idxSorted.as<uint32_t>(), w.position.as<uint32_t>(), tris, g.perm ? g.perm->as<uint32_t>() : nullptr, n, outRecords, s));
-    // the refit's level order from the level counts (bvhLevelOrder's format: deepest level
-    // first, ascending node index within a level; each class one breadth-first range)
-    std::vector<uint32_t>& order = g.order;
-    order.clear();
-    order.reserve(nodeTotal);
-    b.levelOffsets.assign(1, 0u);
-    {
-        std::vector<std::array<uint32_t, 3>> base(levels.size());
-        uint32_t at[3];
-        for (int c = 0; c < 3; ++c) at[c] = g.roots[c] >= 0 ? static_cast<uint32_t>(g.roots[c]) : 0u;
-        for (size_t d = 0; d < levels.size(); ++d)
-            for (int c = 0; c < 3; ++c) {
-                base[d][c] = at[c];
-                at[c] += levels[d][c];
-            }
-        for (size_t d = levels.size(); d-- > 0;) {
-            for (int c = 0; c < 3; ++c)
-                for (uint32_t k = 0; k < levels[d][c]; ++k) order.push_back(base[d][c] + k);
-            b.levelOffsets.push_back(static_cast<uint32_t>(order.size()));
-        }
-    }
-    ARK_GB(b.order.alloc(std::max<size_t>(16, order.size() * 4)));
-    ARK_GB(hipMemcpyAsync(b.order.ptr, order.data(), order.size() * 4, hipMemcpyHostToDevice, s));
-    // boxes, grids and planes: the refit over every level, deepest first, every node live
-    // (all mask bits set, no instance dirty: no record is touched), the inflation runWorldJob's
-    // or, in light coordinates, build_sun_bvh's (the box and the largest |coordinate| are
-    // min / max reductions: the same bits whatever the order)
-    ARK_GB(hipMemsetAsync(w.masks.ptr, 0xff, nodeTotal * 8ull, s));
-    ARK_GB(hipMemsetAsync(w.inst.ptr, 0, instances * sizeof(RefitInstance), s));
-    RefitBoxArgs ra {};
-    ra.inflate = bvh8_inflation_box(lo, hi);
-    ra.light = 0;
-    if (g.light) {
-        float maxAbs;
-        std::memcpy(&maxAbs, &hdr.maxAbs, 4);
-        ra.inflate = 2.0f * bvh8_inflation_box(lo, hi) + 2e-6f * maxAbs;
-        ra.light = 1;
-        std::memcpy(ra.frame, g.frame, sizeof(ra.frame));
-    }
-    b.inflateAbs = ra.inflate;
-    ra.dirty = ~0ull;
-    for (size_t l = 0; l + 1 < b.levelOffsets.size(); ++l)
-        ARK_GB(launch_refit_nodes(nodes, tris, w.boxes.as<float>(), b.order.as<uint32_t>() + b.levelOffsets[l], b.levelOffsets[l + 1] - b.levelOffsets[l], ra,
-                                  w.masks.as<uint64_t>(), w.inst.as<RefitInstance>(), nullptr, nullptr, s));
-    ARK_GB(hipStreamSynchronize(s));
-    if (LbvhGpuTrace* t = g.trace) {
-        t->idx.resize(n);
-        t->idxSorted.resize(n);
-        t->split.resize(n);
-        t->keysSorted.resize(n);
-        t->nodes.resize(nodeTotal);
-        t->tris.resize(outRecords + 1ull);
-        t->perm.resize(g.perm ? outRecords : 0u);
-        ARK_GB(hipMemcpyAsync(t->idx.data(), w.idx.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
-        ARK_GB(hipMemcpyAsync(t->idxSorted.data(), w.idxSorted.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
-        ARK_GB(hipMemcpyAsync(t->split.data(), w.split.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
-        ARK_GB(hipMemcpyAsync(t->keysSorted.data(), w.keysSorted.ptr, n * 8ull, hipMemcpyDeviceToHost, s));
-        ARK_GB(hipMemcpyAsync(t->nodes.data(), nodes, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost, s));
-        ARK_GB(hipMemcpyAsync(t->tris.data(), tris, (outRecords + 1ull) * sizeof(GpuTriangle), hipMemcpyDeviceToHost, s));
-        if (!t->perm.empty()) ARK_GB(hipMemcpyAsync(t->perm.data(), g.perm->ptr, outRecords * 4ull, hipMemcpyDeviceToHost, s));
-        ARK_GB(hipStreamSynchronize(s));
-        t->order = order;
-        t->levelOffsets = b.levelOffsets;
-        std::copy(g.roots, g.roots + 3, t->roots);
-        t->opaqueNodes = g.opaqueNodes;
-        t->depth = static_cast<uint32_t>(levels.size());
-        t->inflateAbs = ra.inflate;
-        t->built = true;
-    }
-#undef ARK_GB
-    b.nodeCount = nodeTotal;
-    b.records = outRecords;
-    b.depth = static_cast<uint32_t>(levels.size());
-    g.prims = n;
-    return hipSuccess;
+    g.classHost.assign(job->instances, 0u); // one tree: only the instance count matters
+    g.light = true;
+    std::memcpy(g.frame, job->frame, sizeof(g.frame));
+    g.slotRule = lbvh::kSlotsAscendingW;
+    g.wBits = lbvh::kSunKeyBitsW;
 }
 
-// The device build of runWorldJobGpu: the three classes' BVH8s into job
-hipError_t buildWorldGpu(WorldJob* job, hipStream_t s, std::string& why)
+// A job's device build on `s` (lbvh_device_build.h; ARK_DDGI_FLAG_GPU_REBUILD / _SUN), which
+// waits for the snapshot on the device: buildLbvhGpu's result and `why` into the job.
+hipError_t deviceBuild(RebuildJob* job, hipStream_t s, std::string& why)
 {
     if (job->snapRecords > 0x7fffffffull) {
         why = "no records";
         return hipSuccess;
     }
+    const bool world = job->kind == RebuildJob::World;
     LbvhGpuBuild g;
     g.snap = job->snap.as<GpuTriangle>();
     g.evSnap = job->evSnap;
     g.records = static_cast<uint32_t>(job->snapRecords);
-    g.classHost.assign(job->classOf.begin(), job->classOf.end());
     g.bvh = &job->bvh;
-    g.perm = &job->perm;
-    const float inflateAbs = job->bvh.inflateAbs; // (worldCollect sets the installed one's)
+    world ? deviceBuildWorld(job, g) : deviceBuildSun(job, g);
     const hipError_t e = buildLbvhGpu(g, s, why);
-    job->bvh.inflateAbs = inflateAbs;
-    std::copy(g.roots, g.roots + 3, job->roots);
-    job->opaqueNodes = g.opaqueNodes;
-    job->maxLeaf = std::min<uint32_t>(g.prims, static_cast<uint32_t>(kBvh8MaxLeafSize));
-    job->sah = 0.0f; // not evaluated on the device
+    if (world) {
+        // (inflateAbs: worldCollect sets the installed one's)
+        std::copy(g.roots, g.roots + 3, job->roots);
+        job->opaqueNodes = g.opaqueNodes;
+        job->maxLeaf = std::min<uint32_t>(g.prims, static_cast<uint32_t>(kBvh8MaxLeafSize));
+        job->sah = 0.0f; // not evaluated on the device
+    } else {
+        job->bvh.inflateAbs = g.inflateAbs;
+    }
     return e;
 }
 
-
-// The sun rebuild's thread with ARK_DDGI_FLAG_GPU_REBUILD_SUN: the same inputs and outputs as
-// runSunJob (job->bvh, levelOrder, frame, inflateAbs, depth, ms), the light-space BVH8 built
-// on the device - one LBVH over every class's records, keyed and boxed in the sun's frame,
-// its slots in ascending w - on a stream of the lowest priority that waits for the snapshot
-// on the device. A scene the device build does not take (no records, 4 GiB, depth, node
-// scratch, an error that is not a device fault) is built by runSunJob within this job; a
-// device fault fails the job (a sun rebuild failure: not retried).
-void runSunJobGpu(SunJob* job, int device, uint64_t count, int threads)
+// A rebuild job's thread. tryDevice: the device build first, on a stream of the lowest
+// priority; what becomes of it is deviceBuildOutcome's (scene_rebuild_policy.h). A scene
+// the device build does not take (no records, 4 GiB, depth, node scratch, an error that is
+// not a device fault) is built by the host within this job, from the same snapshot; a
+// device fault fails the job (the world's: no more rebuilds of this scene; the sun's: not
+// retried for this direction and version).
+void runRebuildJob(RebuildJob* job, int device, int threads, bool tryDevice)
 {
-    job->t0 = std::chrono::steady_clock::now();
+    const auto t0 = std::chrono::steady_clock::now();
     hipStream_t s = nullptr;
-    std::string why;
-    hipError_t e = hipSetDevice(device);
-    int least = 0, greatest = 0;
-    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
-    if (e == hipSuccess) {
-        double frame[3][3];
-        sun_frame(job->dir, frame);
-        std::memcpy(job->frame, frame, sizeof(job->frame));
-        if (count > 0x7fffffffull) {
-            why = "no records";
-        } else {
-            LbvhGpuBuild g;
-            g.snap = job->snap.as<GpuTriangle>();
-            g.evSnap = job->evSnap;
-            g.records = static_cast<uint32_t>(count);
-            g.classHost.assign(job->instances, 0u); // one tree: only the instance count matters
-            g.light = true;
-            std::memcpy(g.frame, job->frame, sizeof(g.frame));
-            g.slotRule = lbvh::kSlotsAscendingW;
-            g.wBits = lbvh::kSunKeyBitsW;
-            g.bvh = &job->bvh;
-            e = buildLbvhGpu(g, s, why);
-            job->levelOrder = std::move(g.order);
-            // (installSunBvh uploads the level order from the host, as after a host build)
-            job->bvh.order.release();
+    auto openStream = [&](bool lowest) {
+        hipError_t e = hipSetDevice(device);
+        int least = 0, greatest = 0;
+        if (e == hipSuccess && lowest) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
+        if (e == hipSuccess) e = lowest ? hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least) : hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
+        return e;
+    };
+    auto closeStream = [&] {
+        if (s) (void)hipStreamDestroy(s);
+        s = nullptr;
+    };
+    DeviceBuildOutcome outcome = DeviceBuildOutcome::HostBuild;
+    if (tryDevice) {
+        std::string why;
+        hipError_t e = openStream(true);
+        if (e == hipSuccess) e = deviceBuild(job, s, why);
+        closeStream();
+        outcome = deviceBuildOutcome(e == hipSuccess, isDeviceFault(e), !why.empty());
+        if (outcome == DeviceBuildOutcome::Failed) job->error = std::string("device build: ") + hipGetErrorString(e);
+        if (outcome == DeviceBuildOutcome::HostBuild) {
+            // the partial result dropped
+            job->bvh.release();
+            job->bvh = DeviceBvh {};
+            job->perm.release();
+            job->roots[0] = job->roots[1] = job->roots[2] = -1;
+            job->opaqueNodes = 0;
+            job->gpuFallback = true;
         }
     }
-    if (s) (void)hipStreamDestroy(s);
-    if (e == hipSuccess && why.empty()) {
-        job->gpu = true;
-        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
-        job->ok = true;
-        job->done.store(true, std::memory_order_release);
-        return;
+    bool ok = outcome == DeviceBuildOutcome::Installed;
+    job->gpu = ok;
+    if (outcome == DeviceBuildOutcome::HostBuild) {
+        (void)openStream(false);
+        ok = hostBuild(job, s, threads);
+        closeStream();
     }
-    if (isDeviceFault(e)) {
-        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
-        job->ok = false;
-        job->done.store(true, std::memory_order_release);
-        return;
-    }
-    // the host build from the same snapshot
-    job->bvh.release();
-    job->bvh = DeviceBvh {};
-    job->levelOrder.clear();
-    job->gpuFallback = true;
-    runSunJob(job, device, count, threads);
-}
-
-// The world rebuild's thread with ARK_DDGI_FLAG_GPU_REBUILD: the same inputs and outputs as
-// runWorldJob, the three BVHs built on the device (ddgi_bvh_build.hip) on a stream of the
-// lowest priority that waits for the snapshot on the device. A scene the device build
-// does not take (4 GiB, depth, an error that is not a device fault) is built by
-// runWorldJob within this job.
-void runWorldJobGpu(WorldJob* job, int device, int threads)
-{
-    job->t0 = std::chrono::steady_clock::now();
-    hipStream_t s = nullptr;
-    std::string why;
-    hipError_t e = hipSetDevice(device);
-    int least = 0, greatest = 0;
-    if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&least, &greatest);
-    if (e == hipSuccess) e = hipStreamCreateWithPriority(&s, hipStreamNonBlocking, least);
-    if (e == hipSuccess) e = buildWorldGpu(job, s, why);
-    if (s) (void)hipStreamDestroy(s);
-    if (e == hipSuccess && why.empty()) {
-        job->gpu = true;
-        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
-        job->ok = true;
-        job->done.store(true, std::memory_order_release);
-        return;
-    }
-    if (isDeviceFault(e)) {
-        job->error = std::string("device build: ") + hipGetErrorString(e);
-        job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - job->t0).count();
-        job->ok = false;
-        job->done.store(true, std::memory_order_release);
-        return;
-    }
-    // the host build from the same snapshot
-    job->bvh.release();
-    job->bvh = DeviceBvh {};
-    job->perm.release();
-    job->roots[0] = job->roots[1] = job->roots[2] = -1;
-    job->opaqueNodes = 0;
-    job->gpuFallback = true;
-    runWorldJob(job, device, threads);
+    job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    job->ok = ok;
+    job->done.store(true, std::memory_order_release);
 }
 
 // A shared scene's refits and installs, kept synchronous for now: the frames in flight of
@@ -1002,16 +626,12 @@ hipError_t replaceBvh(SceneStore& st, DeviceBvh& cur, DeviceBvh& b, hipStream_t 
     return hipSuccess;
 }
 
-// The light-space BVH `b` (its level order on the host) built for the sun direction `dir`
-// in `frame` becomes the scene's: uploaded by the job (sunCollect: host null), or here from
-// `host` (set_scene, synchronously).
-int installSunBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, Bvh8BuildResult* host, const std::vector<uint32_t>& levelOrder, const double* frame, const float* dir,
-                  hipStream_t s)
+// The light-space BVH `b` (its level order on the device, whoever built it) built for the
+// sun direction `dir` in `frame` becomes the scene's: its nodes and records uploaded by the
+// job (sunCollect: host null), or here from `host` (set_scene, synchronously).
+int installSunBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, Bvh8BuildResult* host, const double* frame, const float* dir, hipStream_t s)
 {
     ARK_HIP(replaceBvh(st, st.sun, b, s));
-    ARK_HIP(st.sun.order.alloc(std::max<size_t>(16, levelOrder.size() * 4)));
-    ARK_HIP(hipMemcpy(st.sun.order.ptr, levelOrder.data(), levelOrder.size() * 4, hipMemcpyHostToDevice));
-    st.sun.nodeCount = levelOrder.size();
     ARK_HIP(growBoxes(st, st.sun, s));
     if (host) ARK_HIP(uploadBvh(host->nodes, host->tris, nullptr, st.sun));
     setSunArgs(st);
@@ -1023,12 +643,27 @@ int installSunBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, Bvh8BuildResult*
     return ARK_DDGI_OK;
 }
 
-// The end of an install on `s` (sunCollect, worldCollect): the new topology refitted
-// forward when refits came in while it was built (every instance re-transformed), the
-// spares dropped, the next traversal and refit ordered behind it, the scene's version bumped.
-int finishInstall(SceneStore& st, const SceneCall& c, uint32_t refitsSince, hipStream_t s)
+// Where an installed job's bookkeeping goes: the world's fields or the sun's
+struct InstallBook {
+    bool& gpuBuilt;        // SceneStore::worldGpuBuilt / sunGpuBuilt
+    uint32_t& refitsSince; // SceneStore::refitsSinceBuild / sunRefitsSinceBuild
+    uint32_t &installedBuilder, &gpuRebuilds, &builtRefitVersion; // ArkDdgiBvhStats, as is the build time
+    float& buildMs;
+};
+
+// The end of an install of `job`'s result on `s` (sunCollect, worldCollect): its builder,
+// time and snapshot noted, the new topology refitted forward when refits came in while it
+// was built (every instance re-transformed: its records follow them), the spares dropped,
+// the next traversal and refit ordered behind it, the scene's version bumped.
+int finishInstall(SceneStore& st, const SceneCall& c, const RebuildJob& job, InstallBook book, hipStream_t s)
 {
     ErrorSink* err = c.err;
+    book.buildMs = job.ms;
+    book.gpuBuilt = job.gpu;
+    book.installedBuilder = job.gpu ? 1u : 0u;
+    if (job.gpu) book.gpuRebuilds++;
+    const uint32_t refitsSince = book.refitsSince = st.refitCount - job.refitsAt; // refits since its snapshot
+    book.builtRefitVersion = job.refitsAt;
     markTopologyChanged(st);
     if (refitsSince) {
         if (const int rc = uploadRefitInstances(err, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
@@ -1064,10 +699,11 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
         }
     }
     if (st.sunJob && st.sunJob->done.load(std::memory_order_acquire)) {
-        SunJob& j = *st.sunJob;
-        if (j.gpuFallback && !j.gpuFallbackCounted) {
+        RebuildJob& j = *st.sunJob;
+        if (j.gpuFallback) {
+            // counted once, however many calls poll the job before the right one installs it
             st.bvhStats.sun_gpu_fallbacks++;
-            j.gpuFallbackCounted = true;
+            j.gpuFallback = false;
         }
         if (!j.ok) {
             // remembered: not started again for this direction and scene version
@@ -1082,24 +718,18 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
             j.t.join();
             st.sunJob.reset();
         } else if (mayEnqueue && c.hasSun && sameDir(j.dir, c.sunDir)) {
-            std::unique_ptr<SunJob> job = std::move(st.sunJob);
+            std::unique_ptr<RebuildJob> job = std::move(st.sunJob);
             job->t.join();
             ARK_HIP(sharedBegin(c));
-            if (const int rc = installSunBvh(err, st, job->bvh, nullptr, job->levelOrder, job->frame, job->dir, s)) return rc;
+            if (const int rc = installSunBvh(err, st, job->bvh, nullptr, job->frame, job->dir, s)) return rc;
             ARK_HIP(retireBuffer(st, job->snap, s));
             st.bvhMaxDepth = std::max(st.bvhMaxDepth, st.sun.depth);
             st.bvhStats.max_depth = st.bvhMaxDepth;
             st.bvhStats.sun_node_count = st.sun.nodeCount;
             st.bvhStats.sun_max_depth = st.sun.depth;
             st.bvhStats.sun_rebuilds = ++st.sunRebuilds;
-            st.bvhStats.sun_build_ms = job->ms;
-            st.sunGpuBuilt = job->gpu;
-            st.bvhStats.sun_installed_builder = job->gpu ? 1u : 0u;
-            if (job->gpu) st.bvhStats.sun_gpu_rebuilds++;
-            st.sunRefitsSinceBuild = st.refitCount - job->refitsAt;
-            st.bvhStats.sun_built_refit_version = job->refitsAt;
-            // (refits that came in while it was built: its records follow them)
-            if (const int rc = finishInstall(st, c, st.sunRefitsSinceBuild, s)) return rc;
+            ArkDdgiBvhStats& b = st.bvhStats;
+            return finishInstall(st, c, *job, { st.sunGpuBuilt, st.sunRefitsSinceBuild, b.sun_installed_builder, b.sun_gpu_rebuilds, b.sun_built_refit_version, b.sun_build_ms }, s);
         }
         // else: built for another context's sun, which installs it (or the caller has no
         // ordered stream now: its next call does)
@@ -1107,16 +737,29 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
     return ARK_DDGI_OK;
 }
 
+// A new job's shared part: the scene's version and refit count, the snapshot on `s`, the
+// thread - with half the host threads: the other half stays with the frames being
+// enqueued meanwhile.
+int launchJob(SceneStore& st, ErrorSink* err, RebuildJob& job, hipStream_t s, bool gpu)
+{
+    job.version = st.version;
+    job.refitsAt = st.refitCount;
+    job.snapRecords = st.world.records;
+    ARK_HIP(snapshotRecords(st, job.snap, job.evSnap, s));
+    job.t = std::thread(runRebuildJob, &job, st.device, std::max(1, st.buildThreads / 2), gpu);
+    return ARK_DDGI_OK;
+}
+
 int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
 {
-    ErrorSink* err = c.err;
-    auto job = std::make_unique<SunJob>();
+    auto job = std::make_unique<RebuildJob>();
+    job->kind = RebuildJob::Sun;
     std::memcpy(job->dir, c.sunDir, sizeof(job->dir));
-    job->version = st.version;
-    job->refitsAt = st.refitCount;
-    ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
+    double frame[3][3];
+    sun_frame(job->dir, frame);
+    std::memcpy(job->frame, frame, sizeof(job->frame));
     job->instances = static_cast<uint32_t>(st.instHost.size());
-    job->t = std::thread(gpu ? runSunJobGpu : runSunJob, job.get(), st.device, st.world.records, std::max(1, st.buildThreads / 2));
+    if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
     st.sunJob = std::move(job);
     st.lastBackground = kBackgroundSun;
     return ARK_DDGI_OK;
@@ -1132,7 +775,7 @@ int worldCollect(SceneStore& st, const SceneCall& c, hipStream_t s)
 {
     ErrorSink* err = c.err;
     if (st.worldJob && st.worldJob->done.load(std::memory_order_acquire)) {
-        std::unique_ptr<WorldJob> job = std::move(st.worldJob);
+        std::unique_ptr<RebuildJob> job = std::move(st.worldJob);
         job->t.join();
         if (job->gpuFallback) st.bvhStats.bvh_gpu_fallbacks++;
         if (!job->ok) {
@@ -1167,28 +810,18 @@ int worldCollect(SceneStore& st, const SceneCall& c, hipStream_t s)
         st.bvhStats.node_bytes = st.world.nodeCount * sizeof(GpuBvh8Node);
         st.bvhStats.triangle_bytes = st.world.records * sizeof(GpuTriangle);
         st.bvhStats.bvh_rebuilds = ++st.worldRebuilds;
-        st.bvhStats.bvh_rebuild_ms = job->ms;
-        st.worldGpuBuilt = job->gpu;
-        st.bvhStats.bvh_installed_builder = job->gpu ? 1u : 0u;
-        if (job->gpu) st.bvhStats.bvh_gpu_rebuilds++;
-        st.refitsSinceBuild = st.refitCount - job->refitsAt; // refits since its snapshot
-        st.bvhStats.bvh_built_refit_version = job->refitsAt;
-        return finishInstall(st, c, st.refitsSinceBuild, s);
+        ArkDdgiBvhStats& b = st.bvhStats;
+        return finishInstall(st, c, *job, { st.worldGpuBuilt, st.refitsSinceBuild, b.bvh_installed_builder, b.bvh_gpu_rebuilds, b.bvh_built_refit_version, b.bvh_rebuild_ms }, s);
     }
     return ARK_DDGI_OK;
 }
 
 int worldStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
 {
-    ErrorSink* err = c.err;
-    auto job = std::make_unique<WorldJob>();
-    job->version = st.version;
-    job->refitsAt = st.refitCount;
-    job->snapRecords = st.world.records;
+    auto job = std::make_unique<RebuildJob>();
+    job->kind = RebuildJob::World;
     job->classOf = instanceClasses(st);
-    ARK_HIP(snapshotRecords(st, job->snap, job->evSnap, s));
-    // half the host threads: the other half stays with the frames being enqueued meanwhile
-    job->t = std::thread(gpu ? runWorldJobGpu : runWorldJob, job.get(), st.device, std::max(1, st.buildThreads / 2));
+    if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
     st.worldJob = std::move(job);
     st.lastBackground = kBackgroundWorld;
     st.refitsSinceBuild = 0;
@@ -1536,7 +1169,11 @@ int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThrea
         if (!bvhLevelOrder(r.nodes.data(), r.nodes.size(), &sroot, 1, order, sb.levelOffsets)) return err->fail(ARK_DDGI_E_DEVICE, "sun BVH: a node outside it");
         sb.depth = r.max_depth;
         sb.inflateAbs = sunIn.inflateAbs;
-        if ((rc = installSunBvh(err, *st, sb, &r, order, &sunIn.frame[0][0], s->directional_light.world_space_direction, nullptr)) != 0) return rc;
+        sb.nodeCount = r.nodes.size(); // (the install sizes the refit's boxes scratch from it, ahead of its upload)
+        rc = upload(err, sb.order, order.data(), order.size());
+        if (rc == 0) rc = installSunBvh(err, *st, sb, &r, &sunIn.frame[0][0], s->directional_light.world_space_direction, nullptr);
+        sb.order.release(); // (a failure before the install took it)
+        if (rc != 0) return rc;
     }
     sunBuildMs += std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - ts0).count();
     std::vector<GpuTriangle>().swap(sunIn.world);
@@ -1773,29 +1410,33 @@ int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out)
     return ARK_DDGI_OK;
 }
 
-int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
+namespace {
+
+// The check of an installed BVH8 set `b` (`name`: "world" / "sun"), its front copy's nodes
+// and records downloaded: check_bvh8_full (classOf: the instances' classes, or null: one
+// tree for every class; lightFrame: the boxes hold light coordinates), the structure, the
+// device build's breadth-first order, the refit's level order on the device against the
+// one recomputed from the downloaded nodes (levelOffsets null: none yet), the live
+// records' digest. `violations`: the caller's own, counted in.
+int installedBvhCheck(ErrorSink* err, const char* name, const DeviceBvh& b, const GpuBvh8Node* devNodes, const GpuTriangle* devTris, const std::vector<uint32_t>* levelOffsets,
+                      const int32_t* roots, int rootCount, const std::vector<int>* classOf, const double* lightFrame, bool deviceBuilt, uint64_t violations, uint64_t* out)
 {
-    std::vector<GpuBvh8Node> nodes(st.world.nodeCount);
-    std::vector<GpuTriangle> tris(st.world.records);
+    std::vector<GpuBvh8Node> nodes(b.nodeCount);
+    std::vector<GpuTriangle> tris(b.records);
     std::vector<uint32_t> order(nodes.size());
-    if (!nodes.empty()) ARK_HIP(hipMemcpy(nodes.data(), st.args.nodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
-    if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), st.args.tris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
-    if (!order.empty() && st.world.order.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.world.order.ptr, order.size() * 4, hipMemcpyDeviceToHost));
-    const std::vector<int> classOf = instanceClasses(st);
-    const int32_t roots[3] = { st.args.root_opaque, st.args.root_masked, st.args.root_blend };
-    Bvh8CheckResult c = check_bvh8_full(nodes, tris, roots, 3, &classOf, nullptr);
+    if (!nodes.empty()) ARK_HIP(hipMemcpy(nodes.data(), devNodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
+    if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), devTris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
+    if (!order.empty() && b.order.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), b.order.ptr, order.size() * 4, hipMemcpyDeviceToHost));
+    Bvh8CheckResult c = check_bvh8_full(nodes, tris, roots, rootCount, classOf, nullptr, lightFrame);
+    c.violations += violations;
     std::string why;
-    if (!checkBvh8Structure(nodes, tris, roots, 3, why)) c.violations++;
-    if (c.nodes != nodes.size()) c.violations++; // a node outside the classes' ranges
-    if (st.worldGpuBuilt) c.violations += c.notBreadthFirst; // the device build's order (the host collapse's: breadth first per subtree block)
-    if (roots[0] >= 0 && st.args.opaque_nodes != static_cast<uint32_t>((roots[1] >= 0 ? roots[1] : roots[2] >= 0 ? roots[2] : static_cast<int32_t>(nodes.size())) - roots[0]))
-        c.violations++;
-    // the refit's level order (none before the first refit after set_scene) against the
-    // one recomputed from the downloaded nodes
+    if (!checkBvh8Structure(nodes, tris, roots, rootCount, why)) c.violations++;
+    if (c.nodes != nodes.size()) c.violations++; // a node outside the roots' trees
+    if (deviceBuilt) c.violations += c.notBreadthFirst; // the device build's order (the host collapse's: breadth first per subtree block)
     std::vector<uint32_t> wantOrder, wantOffsets;
-    if (!bvhLevelOrder(nodes.data(), nodes.size(), roots, 3, wantOrder, wantOffsets)) {
+    if (!bvhLevelOrder(nodes.data(), nodes.size(), roots, rootCount, wantOrder, wantOffsets)) {
         c.violations++;
-    } else if (!st.world.levelOffsets.empty() && (wantOrder != order || wantOffsets != st.world.levelOffsets)) {
+    } else if (levelOffsets && (wantOrder != order || wantOffsets != *levelOffsets)) {
         c.violations++;
         why += " level order";
     }
@@ -1804,8 +1445,8 @@ int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
         if (isHoleTriangle(g)) continue;
         ++live;
         uint64_t h = 1469598103934665603ull;
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(&g);
-        for (size_t k = 0; k < sizeof(GpuTriangle); ++k) h = (h ^ b[k]) * 1099511628211ull;
+        const unsigned char* p = reinterpret_cast<const unsigned char*>(&g);
+        for (size_t k = 0; k < sizeof(GpuTriangle); ++k) h = (h ^ p[k]) * 1099511628211ull;
         digest += h;
     }
     if (live != c.triangles) c.violations++;
@@ -1816,228 +1457,31 @@ int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
     out[4] = live;
     out[5] = tris.size();
     out[6] = digest;
-    out[7] = st.worldGpuBuilt ? 1u : 0u;
-    if (c.violations) err->lastError = "world BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
+    out[7] = deviceBuilt ? 1u : 0u;
+    if (c.violations) err->lastError = std::string(name) + " BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
     return c.violations ? 1 : ARK_DDGI_OK;
+}
+
+} // namespace
+
+int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
+{
+    const std::vector<int> classOf = instanceClasses(st);
+    const int32_t roots[3] = { st.args.root_opaque, st.args.root_masked, st.args.root_blend };
+    const int32_t opaqueEnd = roots[1] >= 0 ? roots[1] : roots[2] >= 0 ? roots[2] : static_cast<int32_t>(st.world.nodeCount);
+    const uint64_t violations = roots[0] >= 0 && st.args.opaque_nodes != static_cast<uint32_t>(opaqueEnd - roots[0]) ? 1u : 0u;
+    // (no level order before the first refit after set_scene)
+    return installedBvhCheck(err, "world", st.world, st.args.nodes, st.args.tris, st.world.levelOffsets.empty() ? nullptr : &st.world.levelOffsets, roots, 3, &classOf, nullptr,
+                             st.worldGpuBuilt, violations, out);
 }
 
 int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
 {
     std::fill(out, out + 8, uint64_t(0));
     if (st.sunArgs.sun_root < 0 || !st.sun.nodeCount) return 1; // no light-space BVH
-    std::vector<GpuBvh8Node> nodes(st.sun.nodeCount);
-    std::vector<GpuTriangle> tris(st.sun.records);
-    std::vector<uint32_t> order(nodes.size());
-    ARK_HIP(hipMemcpy(nodes.data(), st.sunArgs.sun_nodes, nodes.size() * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost));
-    if (!tris.empty()) ARK_HIP(hipMemcpy(tris.data(), st.sunArgs.sun_tris, tris.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
-    if (st.sun.order.bytes >= order.size() * 4) ARK_HIP(hipMemcpy(order.data(), st.sun.order.ptr, order.size() * 4, hipMemcpyDeviceToHost));
     const int32_t root = 0;
-    // (one tree for every class: classOf unchecked; the boxes hold light coordinates)
-    Bvh8CheckResult c = check_bvh8_full(nodes, tris, &root, 1, nullptr, nullptr, st.sunFrameD);
-    std::string why;
-    if (!checkBvh8Structure(nodes, tris, &root, 1, why)) c.violations++;
-    if (c.nodes != nodes.size()) c.violations++; // a node outside the tree
-    if (st.sunGpuBuilt) c.violations += c.notBreadthFirst; // the device build's order
-    std::vector<uint32_t> wantOrder, wantOffsets;
-    if (!bvhLevelOrder(nodes.data(), nodes.size(), &root, 1, wantOrder, wantOffsets)) {
-        c.violations++;
-    } else if (wantOrder != order || wantOffsets != st.sun.levelOffsets) {
-        c.violations++;
-        why += " level order";
-    }
-    uint64_t live = 0, digest = 0;
-    for (const GpuTriangle& g : tris) {
-        if (isHoleTriangle(g)) continue;
-        ++live;
-        uint64_t h = 1469598103934665603ull;
-        const unsigned char* b = reinterpret_cast<const unsigned char*>(&g);
-        for (size_t k = 0; k < sizeof(GpuTriangle); ++k) h = (h ^ b[k]) * 1099511628211ull;
-        digest += h;
-    }
-    if (live != c.triangles) c.violations++;
-    out[0] = nodes.size();
-    out[1] = c.leafChildren;
-    out[2] = c.maxDepth;
-    out[3] = c.violations;
-    out[4] = live;
-    out[5] = tris.size();
-    out[6] = digest;
-    out[7] = st.sunGpuBuilt ? 1u : 0u;
-    if (c.violations) err->lastError = "sun BVH check: " + std::to_string(c.violations) + " violations" + (why.empty() ? "" : " (" + why + ")");
-    return c.violations ? 1 : ARK_DDGI_OK;
+    return installedBvhCheck(err, "sun", st.sun, st.sunArgs.sun_nodes, st.sunArgs.sun_tris, &st.sun.levelOffsets, &root, 1, nullptr, st.sunFrameD, st.sunGpuBuilt, 0, out);
 }
 
 } // namespace ark
 
-// ark_ddgi_debug.h: one traced device build (buildLbvhGpu, the product's kernels and
-// nothing else) of the given records on a stream of its own, without a context, against
-// build_lbvh_host of the same records in the device's compaction order, stage by stage.
-extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
-                                                  const float* sun_dir, int w_bits, uint64_t* out)
-{
-    using namespace ark;
-    if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
-    std::fill(out, out + 32, uint64_t(0));
-    for (uint32_t i = 0; i < n_instances; ++i)
-        if (class_of[i] < 0 || class_of[i] > 2) return -1; // (the kernels index the class counts by it)
-    int wBits = lbvh::kMortonBits;
-    if (sun_dir) {
-        wBits = w_bits < 0 ? lbvh::kSunKeyBitsW : w_bits;
-        if (wBits > lbvh::kMortonBits || (wBits & 1)) return -1;
-    }
-    const uint32_t n = static_cast<uint32_t>(n_records);
-    std::vector<GpuTriangle> rec(n);
-    std::memcpy(rec.data(), records, n * sizeof(GpuTriangle));
-
-    // the device build
-    struct Device {
-        hipStream_t s = nullptr;
-        hipEvent_t ev = nullptr;
-        DeviceBuffer snap, perm;
-        DeviceBvh bvh;
-        ~Device()
-        {
-            if (s) (void)hipStreamSynchronize(s);
-            bvh.release();
-            perm.release();
-            snap.release();
-            if (ev) (void)hipEventDestroy(ev);
-            if (s) (void)hipStreamDestroy(s);
-        }
-    } d;
-    LbvhGpuTrace trace;
-    LbvhGpuBuild g;
-    std::string why;
-    hipError_t e = hipSetDevice(device);
-    if (e == hipSuccess) e = hipStreamCreateWithFlags(&d.s, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&d.ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = d.snap.alloc(std::max<size_t>(16, n * sizeof(GpuTriangle)));
-    if (e == hipSuccess) e = hipMemcpyAsync(d.snap.ptr, rec.data(), n * sizeof(GpuTriangle), hipMemcpyHostToDevice, d.s);
-    if (e == hipSuccess) e = hipEventRecord(d.ev, d.s);
-    if (e == hipSuccess) {
-        g.snap = d.snap.as<GpuTriangle>();
-        g.evSnap = d.ev;
-        g.records = n;
-        g.classHost.assign(class_of, class_of + n_instances);
-        if (sun_dir) {
-            double frame[3][3];
-            sun_frame(sun_dir, frame);
-            g.light = true;
-            std::memcpy(g.frame, frame, sizeof(g.frame));
-            g.slotRule = lbvh::kSlotsAscendingW;
-            g.wBits = wBits;
-        }
-        g.bvh = &d.bvh;
-        g.perm = &d.perm;
-        g.trace = &trace;
-        e = buildLbvhGpu(g, d.s, why);
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(d.s);
-    out[26] = static_cast<uint64_t>(e);
-    if (e != hipSuccess) return -5;
-    static const char* const kWhy[] = { "", "no records", "no triangles", "record of an unknown instance", "BVH8 deeper than the device build installs",
-                                        "more nodes than the device build's scratch", "nodes and records of 4 GiB or more" };
-    out[4] = 7;
-    for (uint64_t k = 0; k < sizeof(kWhy) / sizeof(kWhy[0]); ++k)
-        if (trace.why == kWhy[k]) out[4] = k;
-    out[0] = trace.hdr.prims;
-    if (!trace.why.empty() || !trace.built) return 2; // the host's scene: nothing was built
-
-    // the compaction: a permutation of exactly the records that are not holes
-    std::vector<uint32_t> live;
-    for (uint32_t i = 0; i < n; ++i)
-        if (!isHoleTriangle(rec[i])) live.push_back(i);
-    {
-        std::vector<uint32_t> sorted = trace.idx;
-        std::sort(sorted.begin(), sorted.end());
-        out[5] = sorted.size() != live.size() ? 1u : 0u;
-        for (size_t j = 0; j < std::min(sorted.size(), live.size()); ++j) out[5] += sorted[j] != live[j] ? 1u : 0u;
-    }
-    if (sun_dir && !out[5] && !live.empty()) {
-        // k_lbvh_prims_light: a wave's survivors one run, ascending
-        uint64_t runs = 1, waves = 1;
-        for (size_t j = 0; j + 1 < trace.idx.size(); ++j) {
-            if ((trace.idx[j] >> 6) != (trace.idx[j + 1] >> 6)) runs++;
-            else if (trace.idx[j] >= trace.idx[j + 1]) out[6]++;
-            if ((live[j] >> 6) != (live[j + 1] >> 6)) waves++;
-        }
-        if (runs != waves) out[6]++;
-    }
-    std::vector<int> classOf(class_of, class_of + n_instances);
-    LbvhSunOptions so;
-    std::memcpy(so.frame, g.frame, sizeof(so.frame));
-    so.wBits = wBits;
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx);
-    auto bits = [](float f) {
-        uint32_t u;
-        std::memcpy(&u, &f, 4);
-        return u;
-    };
-    // the header
-    const uint32_t prims = static_cast<uint32_t>(live.size());
-    out[7] = (trace.hdr.prims != prims ? 1u : 0u) + (trace.hdr.error ? 1u : 0u);
-    for (int c = 0; c < 3; ++c) out[7] += trace.hdr.classCount[c] != r.classCount[c] ? 1u : 0u;
-    for (int k = 0; k < 3; ++k) {
-        // (== of floats: the ordered-bits atomics tell -0 from +0, std::min does not, and nothing later depends on a zero's sign)
-        out[8] += lbvhOrderedFloat(trace.hdr.lo[k]) == r.sceneLo[k] ? 0u : 1u;
-        out[8] += lbvhOrderedFloat(trace.hdr.hi[k]) == r.sceneHi[k] ? 0u : 1u;
-    }
-    out[9] = trace.hdr.maxAbs != bits(r.maxAbs) ? 1u : 0u;
-    out[10] = bits(trace.inflateAbs) != bits(r.inflateAbs) ? 1u : 0u;
-    // keys, sorted records, splits
-    if (trace.keysSorted.size() != prims || trace.idxSorted.size() != prims || trace.split.size() != prims || r.keysSorted.size() != prims) {
-        out[11] = out[12] = out[13] = 1;
-    } else {
-        for (uint32_t j = 0; j < prims; ++j) {
-            out[11] += trace.keysSorted[j] != r.keysSorted[j] ? 1u : 0u;
-            out[12] += trace.idxSorted[j] != r.idxSorted[j] ? 1u : 0u;
-        }
-        uint32_t first = 0;
-        for (int c = 0; c < 3; ++c) {
-            for (uint32_t i = first; i + 1u < first + r.classCount[c]; ++i) out[13] += trace.split[i] != r.split[i] ? 1u : 0u;
-            first += r.classCount[c];
-        }
-    }
-    // the tree
-    const GpuTriangle padding = trace.tris.back(); // (records + 1 entries)
-    trace.tris.pop_back();
-    Bvh8TreeView dv, hv;
-    dv.nodes = &trace.nodes;
-    dv.tris = &trace.tris;
-    dv.perm = &trace.perm;
-    dv.order = &trace.order;
-    dv.levelOffsets = &trace.levelOffsets;
-    dv.padding = &padding;
-    std::copy(trace.roots, trace.roots + 3, dv.roots);
-    dv.opaqueNodes = trace.opaqueNodes;
-    dv.depth = trace.depth;
-    hv.nodes = &r.nodes;
-    hv.tris = &r.tris;
-    hv.perm = &r.perm;
-    hv.order = &r.order;
-    hv.levelOffsets = &r.levelOffsets;
-    std::copy(r.roots, r.roots + 3, hv.roots);
-    hv.opaqueNodes = r.opaqueNodes;
-    hv.depth = r.depth;
-    const Bvh8CanonicalDiff diff = compare_bvh8_canonical(dv, hv);
-    out[1] = trace.nodes.size();
-    out[2] = trace.tris.size();
-    out[3] = trace.depth;
-    out[14] = diff.shape;
-    out[15] = diff.header;
-    out[16] = diff.grid;
-    out[17] = diff.planes;
-    out[18] = diff.children;
-    out[19] = diff.records;
-    out[20] = diff.perm;
-    out[21] = diff.holes;
-    out[22] = diff.levelOrder;
-    out[23] = diff.padding;
-    out[24] = static_cast<uint64_t>(diff.firstA);
-    out[25] = static_cast<uint64_t>(diff.firstB);
-    out[27] = diff.pairs;
-    out[28] = r.nodes.size();
-    uint64_t mismatches = 0;
-    for (int k = 5; k <= 23; ++k) mismatches += out[k];
-    return mismatches ? 1 : 0;
-}

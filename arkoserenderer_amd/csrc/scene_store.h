@@ -26,6 +26,7 @@
 
 #include "../../include/ark_ddgi.h"
 #include "ddgi_kernels.h"
+#include "device_bvh.h"
 #include "scene_rebuild_policy.h"
 
 namespace ark {
@@ -56,54 +57,7 @@ struct ErrorSink {
         if (_e != hipSuccess) return (sink)->hipFail(_e, #expr);        \
     } while (0)
 
-struct DeviceBuffer {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    hipError_t alloc(size_t n)
-    {
-        release();
-        bytes = n;
-        if (n == 0) return hipSuccess;
-        return hipMalloc(&ptr, n);
-    }
-    void release()
-    {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-    template<typename T> T* as() const { return static_cast<T*>(ptr); }
-};
-
-// One BVH8 set on the device - the world's three classes, or the sun's light-space BVH -
-// with what its refits need. One allocation: the nodes, then the triangle records at the
-// next 256-B boundary (the traversal addresses both through one buffer resource with a
-// 32-bit byte offset), then one padding record (a five-load fetch of the last record
-// stays in bounds, ARK_FETCH5).
-struct DeviceBvh {
-    DeviceBuffer buf; // the front copy: what the kernels read (SceneStore::Spare holds the others)
-    size_t triOffset = 0;
-    uint64_t nodeCount = 0, records = 0; // records: holes included, the padding record not
-    uint32_t depth = 0;
-    float inflateAbs = 0.0f; // the build's absolute box inflation (the refits' floor)
-    // the refit: order[levelOffsets[i] .. [i + 1]) on the device = the nodes of one depth,
-    // deepest first; its boxes scratch; the node masks (k_node_masks: per topology)
-    DeviceBuffer order, boxes, masks;
-    std::vector<uint32_t> levelOffsets;
-    bool masksValid = false;
-    static size_t triOffsetFor(uint64_t nodes) { return (nodes * sizeof(GpuBvh8Node) + 255) & ~static_cast<size_t>(255); }
-    static size_t bytesFor(uint64_t nodes, uint64_t records) { return triOffsetFor(nodes) + (records + 1) * sizeof(GpuTriangle); }
-    // nodes and records of a copy of it (the front one, or a spare)
-    GpuBvh8Node* nodes(const DeviceBuffer& copy) const { return copy.as<GpuBvh8Node>(); }
-    GpuTriangle* tris(const DeviceBuffer& copy) const { return reinterpret_cast<GpuTriangle*>(static_cast<char*>(copy.ptr) + triOffset); }
-    void release()
-    {
-        for (DeviceBuffer* b : { &buf, &order, &boxes, &masks }) b->release();
-    }
-};
-
-struct SunJob; // the background rebuilds (scene_store.cpp)
-struct WorldJob;
+struct RebuildJob; // a background rebuild (scene_store.cpp)
 
 // A buffer replaced while launches enqueued before may still read it: freed once `done`
 // (recorded behind them) has completed.
@@ -180,7 +134,7 @@ struct SceneStore {
     // sun-direction change it is rebuilt in the background (sceneSunStep)
     bool sunWanted = false;
     int buildThreads = 16;
-    std::unique_ptr<SunJob> sunJob;
+    std::unique_ptr<RebuildJob> sunJob;
     uint32_t sunRebuilds = 0;
     // rebuild requests (sceneSunStep): the sun direction the contexts sharing this scene
     // asked for last and how many calls in a row asked for it; a rebuild starts only on a
@@ -196,7 +150,7 @@ struct SceneStore {
     // the world BVHs' background rebuild (worldCollect / worldStart): refits since the installed
     // BVHs were built, the running job, rebuilds installed
     uint32_t refitsSinceBuild = 0, sunRefitsSinceBuild = 0;
-    std::unique_ptr<WorldJob> worldJob;
+    std::unique_ptr<RebuildJob> worldJob;
     uint32_t worldRebuilds = 0, refitCount = 0;
     bool worldRebuildFailed = false;
     // ARK_DDGI_FLAG_GPU_REBUILD: the installed world BVHs are a device build (an LBVH: once

@@ -3,7 +3,8 @@
 // the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check,
 // the three hit-mask classes' build (build_world_bvh8) and the refit's level order, the
 // LBVH restatement with the canonical tree comparison (compare_bvh8_canonical), and
-// the background rebuilds' scheduling (scene_rebuild_policy.h, a table of cases).
+// the background rebuilds' scheduling and what follows a job's device build
+// (scene_rebuild_policy.h, two tables of cases).
 // Built by tests/test_sanitizers.py with g++ -fsanitize=address,undefined
 // -fno-sanitize-recover=all; any report aborts with a non-zero status.
 #include <cstdio>
@@ -237,9 +238,42 @@ static int rebuildPolicyCases()
     return 0;
 }
 
+// How a rebuild job goes on after its device build (scene_rebuild_policy.h), all eight
+// inputs: installed only when every HIP call succeeded and the build declined nothing (a
+// fault flag beside a success cannot come from a hipError_t and changes nothing then);
+// else a device fault fails the job; everything else - a decline, a HIP error that is not
+// a device fault, both - is the host's.
+static int deviceBuildOutcomeCases()
+{
+    using namespace ark;
+    using O = DeviceBuildOutcome;
+    const struct {
+        bool hipOk, deviceFault, declined;
+        O want;
+    } cases[] = {
+        { true, false, false, O::Installed },
+        { true, false, true, O::HostBuild },  // no records, 4 GiB, depth, node scratch
+        { false, false, false, O::HostBuild }, // e.g. out of memory
+        { false, false, true, O::HostBuild },
+        { false, true, false, O::Failed },
+        { false, true, true, O::Failed },
+        { true, true, false, O::Installed },
+        { true, true, true, O::Failed },
+    };
+    int seen = 0;
+    for (const auto& c : cases) {
+        CHECK(deviceBuildOutcome(c.hipOk, c.deviceFault, c.declined) == c.want);
+        seen |= 1 << (c.hipOk * 4 + c.deviceFault * 2 + c.declined);
+    }
+    CHECK(seen == 0xff); // every combination once
+    std::printf("device build outcome: OK\n");
+    return 0;
+}
+
 int main()
 {
     CHECK(rebuildPolicyCases() == 0);
+    CHECK(deviceBuildOutcomeCases() == 0);
     ArkSoupParams sp;
     ark_soup_default_params(&sp);
     sp.triangle_count = 4096;

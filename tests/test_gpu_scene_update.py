@@ -330,6 +330,10 @@ def test_sun_bvh_rebuilt_in_background(cause):
     ctx = D.DDGIContext(grid, 10000.0, cfg)
     ctx.set_scene(sc)
     assert ctx.bvh_stats().sun_node_count > 0
+    # the installed tree downloaded, its level order on the device included: set_scene's here,
+    # the host job's below
+    chk = ctx.sun_bvh_installed_check()
+    assert chk["installed"] and chk["violations"] == 0 and chk["installed_builder"] == 0, (chk, ctx.last_error())
     orc = O.Oracle(ctx.desc)
     orc.set_scene(sc)
     exposure = dict(light_pre_exposure=1.0, environment_brightness=1.0)
@@ -358,6 +362,9 @@ def test_sun_bvh_rebuilt_in_background(cause):
             if installed_at is None and st.sun_rebuilds > 0:
                 installed_at = f
                 assert st.sun_node_count > 0 and st.max_depth >= st.sun_max_depth
+                chk = ctx.sun_bvh_installed_check()
+                assert chk["installed"] and chk["violations"] == 0 and chk["installed_builder"] == 0, (chk, ctx.last_error())
+                assert chk["nodes"] == st.sun_node_count
             f += 1
             assert time.time() - t0 < 90, "no light-space BVH rebuilt within 90 s"
             if installed_at is None:
