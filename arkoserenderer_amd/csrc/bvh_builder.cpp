@@ -5,6 +5,7 @@
 #include "../../include/ark_ddgi_debug.h"
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <cmath>
 #include <cstdint>
@@ -1858,10 +1859,87 @@ void recordVertices(const GpuTriangle& g, float v[3][3])
 }
 } // namespace
 
+namespace {
+// k_lbvh_treelet_sah, serially: the binary tree of one treelet T (4 .. kTreeletPrims
+// primitives) by a three-axis sweep SAH. box: 6 ordered words per sorted primitive, as the
+// sort left them. sorted and split are rewritten inside T's range, nbox and pbox filled.
+void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std::vector<uint32_t>& sorted, std::vector<uint32_t>& split, std::vector<float>& nbox,
+                    std::vector<float>& pbox)
+{
+    const uint32_t first = T.r.first, n = lbvh::count(T.r);
+    auto at = [&](uint32_t prim) { return &box[6ull * (first + prim)]; };
+    std::vector<uint32_t> ord[3];
+    for (int ax = 0; ax < 3; ++ax) {
+        std::vector<uint32_t> key(n);
+        for (uint32_t p = 0; p < n; ++p) key[p] = lbvh::sweepKey(lbvh::orderedFloat(at(p)[ax]), lbvh::orderedFloat(at(p)[3 + ax]));
+        ord[ax].resize(n);
+        for (uint32_t p = 0; p < n; ++p) ord[ax][p] = p;
+        std::stable_sort(ord[ax].begin(), ord[ax].end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
+    }
+    struct Segment {
+        uint32_t f, l, node; // positions and node index relative to `first`
+    };
+    std::vector<Segment> todo(1, Segment { 0u, n - 1u, T.node - first }), final;
+    std::vector<uint32_t> splitRel(n, 0xffffffffu);
+    std::vector<uint8_t> side(n, 0);
+    auto unite = [](uint32_t u[6], const uint32_t* b) {
+        for (int c = 0; c < 3; ++c) {
+            u[c] = std::min(u[c], b[c]);
+            u[3 + c] = std::max(u[3 + c], b[3 + c]);
+        }
+    };
+    while (!todo.empty()) {
+        const Segment sg = todo.back();
+        todo.pop_back();
+        const uint32_t cnt = sg.l - sg.f + 1u;
+        if (cnt <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+            final.push_back(sg);
+            continue;
+        }
+        uint64_t best = lbvh::kNoSplit;
+        for (int ax = 0; ax < 3; ++ax) {
+            std::vector<std::array<uint32_t, 6>> pre(cnt), suf(cnt);
+            uint32_t u[6] = { ~0u, ~0u, ~0u, 0u, 0u, 0u };
+            for (uint32_t i = 0; i < cnt; ++i) {
+                unite(u, at(ord[ax][sg.f + i]));
+                std::copy(u, u + 6, pre[i].begin());
+            }
+            uint32_t v[6] = { ~0u, ~0u, ~0u, 0u, 0u, 0u };
+            for (uint32_t i = cnt; i-- > 0;) {
+                unite(v, at(ord[ax][sg.f + i]));
+                std::copy(v, v + 6, suf[i].begin());
+            }
+            if (ax == 0)
+                for (int c = 0; c < 6; ++c) nbox[6ull * (first + sg.node) + c] = lbvh::orderedFloat(pre[cnt - 1u][c]);
+            for (uint32_t k = 1; k < cnt; ++k) best = std::min(best, lbvh::splitKey(lbvh::halfArea(pre[k - 1u].data()), lbvh::halfArea(suf[k].data()), k, cnt, static_cast<uint32_t>(ax)));
+        }
+        uint32_t axis, k;
+        lbvh::chosenSplit(best, cnt, axis, k);
+        for (uint32_t i = 0; i < cnt; ++i) side[ord[axis][sg.f + i]] = i >= k ? 1 : 0;
+        for (int b = 0; b < 3; ++b) std::stable_partition(ord[b].begin() + sg.f, ord[b].begin() + sg.l + 1u, [&](uint32_t p) { return side[p] == 0; });
+        splitRel[sg.node] = sg.f + k - 1u;
+        todo.push_back(Segment { sg.f, sg.f + k - 1u, sg.f + k - 1u });
+        todo.push_back(Segment { sg.f + k, sg.l, sg.f + k });
+    }
+    for (const Segment& sg : final)
+        for (uint32_t i = sg.f; i <= sg.l; ++i)
+            if (splitRel[i] == 0xffffffffu) splitRel[i] = sg.f;
+    std::vector<uint32_t> src(n);
+    for (uint32_t i = 0; i < n; ++i) src[i] = sorted[first + i];
+    for (uint32_t i = 0; i < n; ++i) {
+        const uint32_t prim = ord[0][i];
+        sorted[first + i] = src[prim];
+        for (int c = 0; c < 6; ++c) pbox[6ull * (first + i) + c] = lbvh::orderedFloat(at(prim)[c]);
+        if (first + i != lbvh::treeletSpareIndex(T)) split[first + i] = first + splitRel[i];
+    }
+}
+} // namespace
+
 LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun,
-                               const std::vector<uint32_t>* primOrder)
+                               const std::vector<uint32_t>* primOrder, bool sahPass)
 {
     LbvhHostResult R;
+    if (sahPass) criterion = lbvh::kOpenLargestBox;
     const lbvh::KeyLayout layout = { sun ? sun->wBits : lbvh::kMortonBits };
     const int slotRule = sun ? lbvh::kSlotsAscendingW : lbvh::kSlotsOctant;
     // the vertices a record is boxed by: the world ones, or their light coordinates
@@ -1921,6 +1999,29 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
     std::vector<uint64_t> keys(n);
     for (uint32_t j = 0; j < n; ++j) keys[j] = key[sorted[j]];
     std::vector<uint32_t> split(n, 0u), position(n, 0u);
+    // the record of each sorted primitive; the SAH pass permutes it inside its treelets
+    std::vector<uint32_t> sortedRec(n);
+    for (uint32_t j = 0; j < n; ++j) sortedRec[j] = idx[sorted[j]];
+    lbvh::SahBoxes boxes {};
+    std::vector<uint32_t> obox; // the sorted primitives' boxes as ordered words
+    if (sahPass) {
+        R.idxMorton = sortedRec;
+        R.nbox.assign(n * 6ull, 0.0f);
+        R.pbox.assign(n * 6ull, 0.0f);
+        obox.resize(n * 6ull);
+        for (uint32_t j = 0; j < n; ++j) {
+            float v[3][3];
+            boxVertices(rec[sortedRec[j]], v);
+            lbvh::primBox(v, &obox[6ull * j]);
+        }
+        boxes.nbox = R.nbox.data();
+        boxes.pbox = R.pbox.data();
+        for (int a = 0; a < 3; ++a) {
+            boxes.lo[a] = scene.lo[a];
+            boxes.hi[a] = scene.hi[a];
+        }
+    }
+    const lbvh::SahBoxes* sahBoxes = sahPass ? &boxes : nullptr;
     // hierarchy and collapse, class by class, level by level (the kernels' atomics: plain counters)
     uint32_t records = 0, first = 0;
     std::vector<std::vector<uint32_t>> levels; // node counts [depth][class]
@@ -1928,7 +2029,17 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
         const uint32_t lo = first, hi = first + classCount[c];
         first = hi;
         if (lo == hi) continue;
-        for (uint32_t i = lo; i + 1u < hi; ++i) split[i] = lbvh::findSplit(keys.data(), lo, hi, lbvh::nodeRange(keys.data(), lo, hi, i));
+        const size_t firstTreelet = R.treelets.size();
+        for (uint32_t i = lo; i + 1u < hi; ++i) {
+            const lbvh::Range r = lbvh::nodeRange(keys.data(), lo, hi, i);
+            split[i] = lbvh::findSplit(keys.data(), lo, hi, r);
+            if (!sahPass) continue;
+            // the SAH pass's work list (k_lbvh_hierarchy's appends; any order)
+            lbvh::Member m[2];
+            const int k = lbvh::treeletsOf(r, split[i], i == lo, m);
+            R.treelets.insert(R.treelets.end(), m, m + k);
+        }
+        for (size_t t = firstTreelet; t < R.treelets.size(); ++t) treeletSahHost(R.treelets[t], obox, sortedRec, split, R.nbox, R.pbox);
         R.roots[c] = static_cast<int32_t>(R.nodes.size());
         std::vector<lbvh::Member> level(1), next;
         level[0].r.first = lo;
@@ -1942,7 +2053,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
             const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
             for (size_t i = 0; i < level.size(); ++i) {
                 lbvh::WideNode w;
-                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout);
+                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout, sahBoxes);
                 const uint32_t slot0 = static_cast<uint32_t>(next.size());
                 const uint32_t triBase = w.rows.span ? records : 0u;
                 records += w.rows.span;
@@ -1962,11 +2073,9 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
                     const lbvh::Member& m = w.member[k];
                     if (sun) {
                         // the occupied slots' Morton cells ascend in their low w edge, without a gap
-                        int64_t clo[3];
-                        int cfree[3];
-                        lbvh::cellBounds(keys.data(), m.r, layout, clo, cfree);
-                        if (clo[2] < lastLow || s >= static_cast<uint32_t>(w.members)) R.slotOrderViolations++;
-                        lastLow = clo[2];
+                        const int64_t low = lbvh::memberLowW(keys.data(), m, layout, sahBoxes);
+                        if (low < lastLow || s >= static_cast<uint32_t>(w.members)) R.slotOrderViolations++;
+                        lastLow = low;
                     }
                     if ((w.imask >> s) & 1u) {
                         next.push_back(m);
@@ -1992,14 +2101,14 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
     }
     R.maxAbs = maxAbs;
     R.idxSorted.resize(n);
-    for (uint32_t j = 0; j < n; ++j) R.idxSorted[j] = idx[sorted[j]];
+    for (uint32_t j = 0; j < n; ++j) R.idxSorted[j] = sortedRec[j];
     R.keysSorted = keys;
     R.split = split;
     // scatter
     R.tris.assign(records, holeTriangle());
     R.perm.assign(records, 0xffffffffu);
     for (uint32_t j = 0; j < n; ++j) {
-        const uint32_t src = idx[sorted[j]];
+        const uint32_t src = sortedRec[j];
         R.tris[position[j]] = rec[src];
         R.perm[position[j]] = src;
     }
@@ -2526,7 +2635,8 @@ extern "C" int ark_ddgi_debug_bvh8_compare_selftest(const float* triangles, uint
     return rc;
 }
 
-extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out)
+namespace {
+int lbvhCheck(const float* triangles, uint64_t n, int criterion, bool sah, uint64_t* out, uint64_t* treelets)
 {
     using namespace ark;
     std::vector<GpuTriangle> rec(n);
@@ -2543,7 +2653,8 @@ extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n
         rec[i] = make_gpu_triangle(t);
     }
     const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion);
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion, nullptr, nullptr, sah);
+    if (treelets) *treelets = r.treelets.size();
     Bvh8CheckResult c = check_bvh8_full(r.nodes, r.tris, r.roots, 3, &classOf, triangles);
     // every input triangle in exactly one leaf, bit for bit
     std::vector<uint32_t> seen(n, 0);
@@ -2570,6 +2681,20 @@ extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n
     }
     return c.violations == 0 ? 0 : 1;
 }
+} // namespace
+
+extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out)
+{
+    return lbvhCheck(triangles, n, criterion, false, out, nullptr);
+}
+
+extern "C" int ark_ddgi_debug_lbvh_check_sah(const float* triangles, uint64_t n, int criterion, int sah, uint64_t* out)
+{
+    uint64_t treelets = 0;
+    const int rc = lbvhCheck(triangles, n, criterion, sah != 0, out, &treelets);
+    if (out) out[8] = treelets;
+    return rc;
+}
 
 extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out)
 {
@@ -2580,8 +2705,9 @@ extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uin
 // k_lbvh_prims_light, k_lbvh_keys_light, the collapse under lbvh::kSlotsAscendingW) restated
 // serially on the host with the same lbvh_build.h functions, over sun_frame's frame and
 // sunAddRecords' light triangles; then ark_ddgi_debug_sun_bvh_check's ray comparison.
-extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
-                                                   int w_bits, uint64_t* out)
+namespace {
+int sunLbvhCheck(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, int w_bits, bool sahPass, uint64_t* out,
+                 uint64_t* treelets)
 {
     using namespace ark;
     if (out) std::fill(out, out + 16, uint64_t(0));
@@ -2614,7 +2740,8 @@ extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64
     std::memcpy(so.frame, frame, sizeof(so.frame));
     so.wBits = w_bits;
     const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so);
+    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so, nullptr, sahPass);
+    if (treelets) *treelets = r.treelets.size();
     if (r.nodes.empty() || r.roots[0] != 0) return 1;
     // structure: one tree from node 0, each depth one range behind the depth above's, every
     // record the input's bit for bit (the light-space boxes are covered by the ray comparison:
@@ -2677,6 +2804,23 @@ extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64
     }
     if (violations || ia != ib) return 1;
     return mism == 0 ? 0 : 2;
+}
+} // namespace
+
+extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                                   int w_bits, uint64_t* out)
+{
+    return sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, false, out, nullptr);
+}
+
+extern "C" int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                                  int w_bits, int sah, uint64_t* out)
+{
+    uint64_t treelets = 0;
+    if (out) out[16] = 0;
+    const int rc = sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, sah != 0, out, &treelets);
+    if (out) out[16] = treelets;
+    return rc;
 }
 
 extern "C" int ark_ddgi_debug_sun_lbvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, uint64_t* out)

@@ -147,6 +147,12 @@ struct LbvhHostResult {
     float sceneLo[3] = { 0, 0, 0 }, sceneHi[3] = { 0, 0, 0 }, maxAbs = 0.0f;
     std::vector<uint64_t> keysSorted;
     std::vector<uint32_t> idxSorted, split;
+    // the SAH pass (sah: true): idxSorted and split above are as the pass leaves them,
+    // idxMorton as the sort left them; its work list (any order), a box per BVH2 node of a
+    // treelet (0 elsewhere) and per sorted primitive, 6 floats each
+    std::vector<uint32_t> idxMorton;
+    std::vector<lbvh::Member> treelets;
+    std::vector<float> nbox, pbox;
 };
 // sun: the light-space BVH8 of the sun's shadow rays instead (k_lbvh_prims_light /
 // k_lbvh_keys_light): one tree over every class (roots[0]), keys and boxes of the records'
@@ -159,8 +165,10 @@ struct LbvhSunOptions {
 // are not holes; null: ascending). The device's comes from atomics, and the stable sort
 // carries it into runs of equal keys: given the device's order, the result is the tree the
 // device has to build, ties included.
+// sah: the SAH pass over the treelets (k_lbvh_treelet_sah restated serially) between the
+// hierarchy and the collapse, which then opens by lbvh::kOpenLargestBox whatever `criterion`.
 LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun = nullptr,
-                               const std::vector<uint32_t>* primOrder = nullptr);
+                               const std::vector<uint32_t>* primOrder = nullptr, bool sah = false);
 
 // Two BVH8 sets of the same records compared in canonical form (ark_ddgi_debug_lbvh_device_parity:
 // the device build against build_lbvh_host). Node numbers within a level and tri_base come

@@ -15,7 +15,13 @@
 //                     coordinate|; the survivors compacted by one ballot and one atomic add
 //                     per wave
 //   (rocPRIM radix_sort_pairs over the 62 key bits)
-//   k_lbvh_hierarchy  one thread per BVH2 internal node of a class range: its split
+//   k_lbvh_hierarchy  one thread per BVH2 internal node of a class range: its split; under
+//                     ARK_DDGI_FLAG_GPU_REBUILD_SAH also the treelets it is the parent of,
+//                     appended to the SAH pass's work list (one atomic add each)
+//   k_lbvh_treelet_sah  (that flag only) one workgroup per treelet of at most
+//                     lbvh::kTreeletPrims primitives: its binary tree rebuilt by a
+//                     three-axis sweep SAH in LDS, its primitives reordered, a box per node
+//                     and primitive for the collapse's decisions (lbvh_build.h)
 //   k_lbvh_collapse   one level of one class, one thread per BVH8 node of the work
 //                     list: cut, slots and rows; the internal children's node indices
 //                     from one atomic add on the next level's counter, the rows' span
@@ -187,11 +193,197 @@ __global__ void __launch_bounds__(256) k_lbvh_keys_light(const GpuTriangle* __re
     keys[j] = lbvh::lightKey(c, lo, hi, layout);
 }
 
-__global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t* __restrict__ split)
+__global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t* __restrict__ split,
+                                                        lbvh::Member* __restrict__ treelets, uint32_t treeletCapacity, uint32_t* __restrict__ counters)
 {
     const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
     if (i + 1u >= hi) return; // internal nodes lo .. hi - 2
-    split[i] = lbvh::findSplit(keys, lo, hi, lbvh::nodeRange(keys, lo, hi, i));
+    const lbvh::Range r = lbvh::nodeRange(keys, lo, hi, i);
+    const uint32_t s = lbvh::findSplit(keys, lo, hi, r);
+    split[i] = s;
+    if (!treelets) return;
+    // the SAH pass's work list (its order does not matter: treelets are disjoint ranges)
+    lbvh::Member m[2];
+    const int n = lbvh::treeletsOf(r, s, i == lo, m);
+    for (int k = 0; k < n; ++k) {
+        const uint32_t at = atomicAdd(&counters[kLbvhTreelets], 1u);
+        if (at < treeletCapacity) treelets[at] = m[k];
+        else atomicOr(&counters[kLbvhOverflow], 1u); // (never: at most prims / 4 treelets)
+    }
+}
+
+// The SAH pass: one workgroup per treelet (4 .. 256 primitives), one primitive per thread,
+// the treelet's binary tree built top-down in LDS, every level inside the workgroup. The
+// primitives stand in three orders (by lo + hi of their boxes along each axis, ties to the
+// Morton order); the segments of a level are the same position ranges in all three.
+// Per level and axis: segmented prefix and suffix unions of the boxes in that axis's order
+// (shuffle scans within a wave, joined across the waves through LDS; unions of ordered
+// words, so exact in any order), every candidate's lbvh::splitKey, the segment's least by
+// one LDS atomic min; then all three orders stably partitioned by side (ballot ranks).
+// Out: sorted[] permuted inside the treelet (axis 0's final order), split[] of the
+// treelet's nodes under the radix tree's numbering (entries no node owns: the first of
+// their final segment; lbvh::treeletSpareIndex is an ancestor's and left alone), nbox[] of every node of more than kBvh8MaxLeafSize primitives,
+// pbox[] of every primitive at its new position. Nothing is read of or written to another
+// treelet's range, and no workgroup waits for another.
+__global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
+{
+    __shared__ uint32_t sBox[6][256];          // by primitive (Morton position in the treelet): lo xyz, hi xyz, ordered
+    __shared__ uint32_t sP[6][256], sS[6][256]; // a wave's prefix / suffix unions by position (hi complemented: all minima)
+    __shared__ unsigned long long sBest[256];  // at a segment's first position
+    __shared__ uint32_t sSrc[256];
+    __shared__ uint32_t sWave[4];
+    __shared__ uint16_t sCnt[256], sSplit[256];
+    __shared__ uint8_t sOrd[3][256], sF[256], sL[256], sN[256], sSide[256];
+
+    const uint32_t t = threadIdx.x, lane = t & 63u, wave = t >> 6;
+    const lbvh::Member T = a.list[blockIdx.x];
+    const uint32_t first = T.r.first, n = lbvh::count(T.r);
+    if (T.r.last < first || T.r.last >= a.prims || n > lbvh::kTreeletPrims || T.node < first || T.node > T.r.last) return; // (never: the list holds treelets only)
+    uint32_t box[6] = { ~0u, ~0u, ~0u, 0u, 0u, 0u };
+    if (t < n) {
+        const uint32_t src = a.sorted[first + t];
+        sSrc[t] = src;
+        const float4* q = reinterpret_cast<const float4*>(a.snap + src);
+        const float4 r0 = q[0], r1 = q[1], r2 = q[2];
+        const float v0[3] = { r0.x, r0.y, r0.z }, e1[3] = { r0.w, r1.x, r1.y }, e2[3] = { r1.z, r1.w, r2.x };
+        float v[3][3];
+        if (a.light) {
+            float unused;
+            lbvh::lightVertices(v0, e1, e2, a.frame.m, v, unused);
+        } else {
+            for (int k = 0; k < 3; ++k) {
+                v[0][k] = v0[k];
+                v[1][k] = v0[k] + e1[k];
+                v[2][k] = v0[k] + e2[k];
+            }
+        }
+        lbvh::primBox(v, box);
+    }
+    for (int c = 0; c < 6; ++c) sBox[c][t] = box[c];
+    // one segment, the treelet; the threads past it one segment each, never live
+    sF[t] = static_cast<uint8_t>(t < n ? 0u : t);
+    sL[t] = static_cast<uint8_t>(t < n ? n - 1u : t);
+    sN[t] = static_cast<uint8_t>(t < n ? T.node - first : t);
+    sSplit[t] = 0xffffu;
+    sSide[t] = 0;
+    for (int ax = 0; ax < 3; ++ax) sP[ax][t] = lbvh::sweepKey(lbvh::orderedFloat(box[ax]), lbvh::orderedFloat(box[3 + ax]));
+    __syncthreads();
+    for (int ax = 0; ax < 3; ++ax) {
+        uint32_t rank = t;
+        if (t < n) {
+            const uint32_t key = sP[ax][t];
+            rank = 0;
+            for (uint32_t q = 0; q < n; ++q) {
+                const uint32_t kq = sP[ax][q];
+                rank += (kq < key || (kq == key && q < t)) ? 1u : 0u;
+            }
+        }
+        sOrd[ax][rank] = static_cast<uint8_t>(t);
+    }
+    __syncthreads();
+    const uint32_t w0 = t & ~63u, w1 = w0 + 63u;
+    for (;;) {
+        const uint32_t f = sF[t], l = sL[t], cnt = l - f + 1u;
+        const bool live = cnt > static_cast<uint32_t>(kBvh8MaxLeafSize);
+        if (!__syncthreads_or(live ? 1 : 0)) break;
+        if (t == f) sBest[t] = lbvh::kNoSplit;
+        unsigned long long mine = lbvh::kNoSplit;
+        const uint32_t pLim = f > w0 ? f : w0, sLim = l < w1 ? l : w1;
+        for (int ax = 0; ax < 3; ++ax) {
+            const uint32_t prim = sOrd[ax][t];
+            uint32_t P[6], S[6];
+            for (int c = 0; c < 6; ++c) P[c] = S[c] = c < 3 ? sBox[c][prim] : ~sBox[c][prim];
+            for (uint32_t j = 1; j < 64u; j <<= 1)
+                for (int c = 0; c < 6; ++c) {
+                    const uint32_t up = __shfl_up(P[c], j, 64), dn = __shfl_down(S[c], j, 64);
+                    if (t >= pLim + j) P[c] = up < P[c] ? up : P[c];
+                    if (t + j <= sLim) S[c] = dn < S[c] ? dn : S[c];
+                }
+            for (int c = 0; c < 6; ++c) {
+                sP[c][t] = P[c];
+                sS[c][t] = S[c];
+            }
+            __syncthreads();
+            if (live) {
+                // the union of [f, t]: this wave's part, the first wave's from f on, whole waves between
+                if (f < w0) {
+                    for (int c = 0; c < 6; ++c) {
+                        const uint32_t o = sS[c][f];
+                        P[c] = o < P[c] ? o : P[c];
+                    }
+                    for (uint32_t w = (f >> 6) + 1u; w < wave; ++w)
+                        for (int c = 0; c < 6; ++c) {
+                            const uint32_t o = sP[c][64u * w + 63u];
+                            P[c] = o < P[c] ? o : P[c];
+                        }
+                }
+                for (int c = 3; c < 6; ++c) P[c] = ~P[c];
+                if (ax == 0 && t == l) {
+                    float* nb = a.nbox + 6ull * (first + sN[t]);
+                    for (int c = 0; c < 6; ++c) nb[c] = lbvh::orderedFloat(P[c]);
+                }
+                if (t < l) {
+                    // the union of [t + 1, l] the same way
+                    const uint32_t u = t + 1u, uw1 = (u & ~63u) + 63u;
+                    uint32_t R[6];
+                    for (int c = 0; c < 6; ++c) R[c] = sS[c][u];
+                    if (l > uw1) {
+                        for (int c = 0; c < 6; ++c) {
+                            const uint32_t o = sP[c][l];
+                            R[c] = o < R[c] ? o : R[c];
+                        }
+                        for (uint32_t w = (u >> 6) + 1u; w < (l >> 6); ++w)
+                            for (int c = 0; c < 6; ++c) {
+                                const uint32_t o = sP[c][64u * w + 63u];
+                                R[c] = o < R[c] ? o : R[c];
+                            }
+                    }
+                    for (int c = 3; c < 6; ++c) R[c] = ~R[c];
+                    const unsigned long long key = lbvh::splitKey(lbvh::halfArea(P), lbvh::halfArea(R), t - f + 1u, cnt, static_cast<uint32_t>(ax));
+                    mine = key < mine ? key : mine;
+                }
+            }
+            __syncthreads(); // sP / sS are the next axis's
+        }
+        if (live && t < l) atomicMin(&sBest[f], mine);
+        __syncthreads();
+        uint32_t axis = 0, k = cnt;
+        if (live) lbvh::chosenSplit(sBest[f], cnt, axis, k);
+        sSide[sOrd[axis][t]] = t - f >= k ? 1 : 0;
+        __syncthreads();
+        for (int b = 0; b < 3; ++b) {
+            const uint32_t prim = sOrd[b][t];
+            const bool right = sSide[prim] != 0;
+            const uint64_t lefts = __ballot(!right);
+            if (lane == 0u) sWave[wave] = static_cast<uint32_t>(__popcll(lefts));
+            __syncthreads();
+            uint32_t c = static_cast<uint32_t>(__popcll(lefts & ((uint64_t(1) << lane) - 1u)));
+            for (uint32_t w = 0; w < wave; ++w) c += sWave[w];
+            sCnt[t] = static_cast<uint16_t>(c); // lefts before position t
+            __syncthreads();
+            const uint32_t leftBefore = c - sCnt[f];
+            const uint32_t pos = right ? f + k + (t - f - leftBefore) : f + leftBefore;
+            sOrd[b][pos] = static_cast<uint8_t>(prim);
+            __syncthreads();
+        }
+        if (live) {
+            if (t == f) sSplit[sN[t]] = static_cast<uint16_t>(f + k - 1u);
+            if (t - f < k) {
+                sL[t] = static_cast<uint8_t>(f + k - 1u);
+                sN[t] = static_cast<uint8_t>(f + k - 1u);
+            } else {
+                sF[t] = static_cast<uint8_t>(f + k);
+                sN[t] = static_cast<uint8_t>(f + k);
+            }
+        }
+    }
+    if (t < n) {
+        const uint32_t prim = sOrd[0][t];
+        a.sorted[first + t] = sSrc[prim];
+        for (int c = 0; c < 6; ++c) a.pbox[6ull * (first + t) + c] = lbvh::orderedFloat(sBox[c][prim]);
+        const uint32_t sp = sSplit[t];
+        if (first + t != lbvh::treeletSpareIndex(T)) a.split[first + t] = first + (sp != 0xffffu ? sp : sF[t]);
+    }
 }
 
 __global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a)
@@ -201,7 +393,7 @@ __global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a)
     const lbvh::Member top = a.items ? a.items[i] : a.root;
     lbvh::WideNode w;
     const lbvh::KeyLayout layout = { a.wBits };
-    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w, a.slotRule, layout);
+    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w, a.slotRule, layout, a.useSah ? &a.sah : nullptr);
     uint32_t slot0 = 0;
     if (w.internal) {
         slot0 = atomicAdd(&a.counters[kLbvhNextCount], w.internal);
@@ -298,10 +490,18 @@ hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysI
     return rocprim::radix_sort_pairs(temp, tempBytes, keysIn, keysOut, valuesIn, valuesOut, count, 0u, static_cast<unsigned int>(lbvh::kKeyBits), s);
 }
 
-hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s)
+hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s, lbvh::Member* treelets, uint32_t treeletCapacity,
+                                 uint32_t* counters)
 {
     if (hi - lo < 2u) return hipSuccess;
-    hipLaunchKernelGGL(dev::k_lbvh_hierarchy, dim3((hi - lo - 1u + 255u) / 256u), dim3(256), 0, s, keys, lo, hi, split);
+    hipLaunchKernelGGL(dev::k_lbvh_hierarchy, dim3((hi - lo - 1u + 255u) / 256u), dim3(256), 0, s, keys, lo, hi, split, treelets, treeletCapacity, counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s)
+{
+    if (treelets == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_lbvh_treelet_sah, dim3(treelets), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -323,8 +323,12 @@ inline float lbvhOrderedFloat(uint32_t u)
     __builtin_memcpy(&f, &u, 4);
     return f;
 }
+// a light-space frame by value (rows u, v, w)
+struct LbvhFrame {
+    double m[9];
+};
 // the collapse's counters
-enum : uint32_t { kLbvhNextCount = 0, kLbvhRecords = 1, kLbvhOverflow = 2, kLbvhCounters = 4 };
+enum : uint32_t { kLbvhNextCount = 0, kLbvhRecords = 1, kLbvhOverflow = 2, kLbvhTreelets = 3, kLbvhCounters = 4 };
 // one level of one class (k_lbvh_collapse): node levelBase + i from items[i] (items null: the root)
 struct LbvhCollapseArgs {
     const uint64_t* keys;      // sorted
@@ -343,6 +347,8 @@ struct LbvhCollapseArgs {
     int criterion;             // lbvh::Criterion
     int slotRule;              // lbvh::SlotRule
     int wBits;                 // lbvh::KeyLayout of the keys
+    int useSah;                // the SAH pass ran: its boxes (criterion lbvh::kOpenLargestBox, the slots' centres and low w edges)
+    lbvh::SahBoxes sah;
 };
 // hdr zeroed, then the survivors' record indices (idx), counts and box, then their keys
 hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const uint32_t* classOf, uint32_t instances, uint32_t* idx, uint64_t* keys,
@@ -350,16 +356,28 @@ hipError_t launch_lbvh_prims(const GpuTriangle* snap, uint32_t records, const ui
 // The same for the sun's light-space BVH8 (one tree over every class): the box of the
 // records' light coordinates in `frame` (rows u, v, w; lbvh::lightVertices) and the largest
 // |world coordinate| (hdr->maxAbs), then the light-space keys (lbvh::lightKey, wBits)
-struct LbvhFrame {
-    double m[9];
-};
 hipError_t launch_lbvh_prims_light(const GpuTriangle* snap, uint32_t records, uint32_t instances, const LbvhFrame& frame, int wBits, uint32_t* idx, uint64_t* keys,
                                    LbvhHeader* hdr, hipStream_t s);
 // rocPRIM's radix sort of the (key, record index) pairs; temp null: tempBytes out
 hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn, uint32_t* valuesOut, uint32_t count,
                             hipStream_t s);
-// split[i] of the internal nodes lo .. hi - 2 of the class range [lo, hi)
-hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s);
+// split[i] of the internal nodes lo .. hi - 2 of the class range [lo, hi); treelets not null:
+// the SAH pass's work list (lbvh::treeletsOf), counted in counters[kLbvhTreelets]
+hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s, lbvh::Member* treelets = nullptr,
+                                 uint32_t treeletCapacity = 0, uint32_t* counters = nullptr);
+// The SAH pass (k_lbvh_treelet_sah): one workgroup per entry of list
+struct LbvhTreeletArgs {
+    const GpuTriangle* snap;
+    const lbvh::Member* list;
+    uint32_t prims;
+    uint32_t* sorted;  // permuted inside each treelet
+    uint32_t* split;   // rewritten inside each treelet
+    float* nbox;       // [prims][6], by BVH2 node
+    float* pbox;       // [prims][6], by sorted primitive
+    int light;         // boxes of the light coordinates in `frame`
+    LbvhFrame frame;
+};
+hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s);
 hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s);
 // tris[0 .. records]: holes and the zero padding record, then record sorted[j] of the snapshot at position[j]; perm
 hipError_t launch_lbvh_scatter(const GpuTriangle* snap, const uint32_t* sorted, const uint32_t* position, GpuTriangle* tris, uint32_t* perm, uint32_t prims,

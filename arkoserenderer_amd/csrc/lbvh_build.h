@@ -25,6 +25,18 @@
 // build_sun_bvh and the refit), lightKey (a Morton code of the light-space box's centre,
 // class bits 0, w given wBits of the 60 and u, v the rest: KeyLayout) and the slot rule
 // kSlotsAscendingW (every ray goes along +w and visits a node's children in slot order).
+//
+// The SAH pass (ARK_DDGI_FLAG_GPU_REBUILD_SAH, k_lbvh_treelet_sah and its host restatement):
+// every maximal range of the radix tree of at most kTreeletPrims primitives (a treelet) gets a
+// binary tree of its own by a full three-axis sweep SAH, its primitives reordered inside the
+// range. sorted[] is permuted inside a treelet; keys[] is NOT: it stays sorted and from then
+// on only describes the Morton cells of ranges that are unions of whole treelets. Inside a
+// treelet split[] keeps the numbering (left child [f, s]: node s, right child: node s + 1),
+// which is collision-free for any tree over contiguous ranges, so selectCut reads it as it
+// is. What the pass shares between the kernel and the host: ordered / orderedFloat (boxes are
+// min / max unions of ordered words: the same bits in any order, -0 below +0), sweepKey,
+// halfArea, splitKey; what the collapse reads of it: SahBoxes, kOpenLargestBox, rangeCentre,
+// memberLowW.
 #pragma once
 
 #include <stdint.h>
@@ -43,6 +55,7 @@ namespace lbvh {
 constexpr int kMortonBits = 20;         // per axis
 constexpr int kKeyBits = 62;            // 60 Morton bits + 2 class bits: the sort's end bit
 constexpr uint32_t kNoSlot = 0xffu;
+constexpr uint32_t kTreeletPrims = 256; // the SAH pass's subtree size: one workgroup, one primitive per thread
 
 // How the 60 Morton bits are split across the axes: w bits for axis 2, (60 - w) / 2 for
 // axes 0 and 1 each. From the top the key interleaves pairs of axes 0 and 1 (axis 0
@@ -98,6 +111,7 @@ ARK_LBVH_FN uint32_t count(const Range& r) { return r.last - r.first + 1u; }
 enum Criterion : int {
     kOpenLargestCount = 0, // most triangles
     kOpenLargestCell = 1,  // largest surface area of the range's Morton cell
+    kOpenLargestBox = 2,   // (the SAH pass) a member of at most kTreeletPrims by its stored box's half-area, a larger one by its cell
 };
 // The default (EXPERIMENTS.md "Device LBVH build"): the cell area, the nearest an LBVH
 // has to the host collapse's largest-box-area opening; by the host check's BVH8 SAH cost
@@ -107,6 +121,88 @@ constexpr int kDefaultCriterion = kOpenLargestCell;
 ARK_LBVH_FN int clz64(uint64_t x)
 {
     return x ? __builtin_clzll(x) : 64;
+}
+
+// fp32 as a word whose unsigned order is the numbers' (-0 below +0, a NaN above or below
+// everything by its sign), and back
+ARK_LBVH_FN uint32_t ordered(float f)
+{
+    union {
+        float f;
+        uint32_t u;
+    } s;
+    s.f = f;
+    return (s.u & 0x80000000u) ? ~s.u : (s.u | 0x80000000u);
+}
+ARK_LBVH_FN float orderedFloat(uint32_t u)
+{
+    union {
+        uint32_t u;
+        float f;
+    } s;
+    // the top bit cleared when it is set, every bit flipped otherwise
+    s.u = u ^ (0xffffffffu ^ (static_cast<uint32_t>(static_cast<int32_t>(u) >> 31) & 0x7fffffffu));
+    return s.f;
+}
+
+// The SAH pass -----------------------------------------------------------------------
+// What the pass leaves to the collapse: a box per BVH2 node of more than kBvh8MaxLeafSize
+// and at most kTreeletPrims primitives (nbox, 6 floats per node index: lo, hi), a box per
+// sorted primitive (pbox, 6 floats), and the scene box the keys were taken in
+struct SahBoxes {
+    const float* nbox;
+    const float* pbox;
+    float lo[3], hi[3];
+};
+
+// The word the primitives of a treelet are sorted by along one axis (ties: the lower
+// position in the Morton order): lo + hi of the primitive's box, in fp32
+ARK_LBVH_FN uint32_t sweepKey(float lo, float hi)
+{
+    const float s = lo + hi;
+    return s == s ? ordered(s) : 0xffffffffu; // (a NaN's sign and payload differ between host and device)
+}
+
+// Half the surface area of a box given as ordered words (lo xyz, hi xyz)
+ARK_LBVH_FN float halfArea(const uint32_t b[6])
+{
+    const float dx = orderedFloat(b[3]) - orderedFloat(b[0]), dy = orderedFloat(b[4]) - orderedFloat(b[1]), dz = orderedFloat(b[5]) - orderedFloat(b[2]);
+    return dx * dy + dy * dz + dz * dx;
+}
+ARK_LBVH_FN float halfArea(const float lo[3], const float hi[3])
+{
+    const float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
+    return dx * dy + dy * dz + dz * dx;
+}
+
+// A candidate split of a segment of n primitives (the first k of `axis`'s order to the
+// left), as a word whose minimum is the chosen one: the least cost areaL k + areaR (n - k)
+// (fp32, no contraction), ties to the k nearest n / 2, then the lower k, then the lower
+// axis. A cost that is not a finite number is no candidate (kNoSplit's upper word); a
+// segment without one splits at the middle of axis 0's order (chosenSplit). The tie rule
+// keeps coincident triangles from peeling 1 | n - 1, level after level.
+constexpr uint64_t kNoSplit = ~uint64_t(0);
+ARK_LBVH_FN uint64_t splitKey(float areaL, float areaR, uint32_t k, uint32_t n, uint32_t axis)
+{
+    const float c = areaL * static_cast<float>(k) + areaR * static_cast<float>(n - k);
+    if (!(c >= 0.0f && c < __builtin_inff())) return kNoSplit;
+    union {
+        float f;
+        uint32_t u;
+    } s;
+    s.f = c;
+    const uint32_t off = 2u * k > n ? 2u * k - n : n - 2u * k;
+    return static_cast<uint64_t>(s.u & 0x7fffffffu) << 32 | static_cast<uint64_t>(off) << 20 | static_cast<uint64_t>(k) << 8 | axis;
+}
+ARK_LBVH_FN void chosenSplit(uint64_t best, uint32_t n, uint32_t& axis, uint32_t& k)
+{
+    if ((best >> 32) == 0xffffffffu) {
+        axis = 0;
+        k = n / 2u;
+    } else {
+        axis = static_cast<uint32_t>(best & 0xffu);
+        k = static_cast<uint32_t>(best >> 8) & 0xfffu;
+    }
 }
 
 ARK_LBVH_FN uint64_t spread20(uint32_t v)
@@ -270,11 +366,85 @@ ARK_LBVH_FN float cellArea(const uint64_t* keys, const Range& r, const float ext
     return d[0] * d[1] + d[1] * d[2] + d[2] * d[0];
 }
 
+// The SAH pass's box of a range of at most kTreeletPrims primitives: its node's stored box,
+// or the union of a leaf member's primitive boxes
+ARK_LBVH_FN void memberBox(const SahBoxes& S, const Member& m, float lo[3], float hi[3])
+{
+    if (count(m.r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        for (int a = 0; a < 3; ++a) {
+            lo[a] = S.nbox[6ull * m.node + a];
+            hi[a] = S.nbox[6ull * m.node + 3 + a];
+        }
+        return;
+    }
+    uint32_t l[3], h[3];
+    for (int a = 0; a < 3; ++a) {
+        l[a] = 0xffffffffu;
+        h[a] = 0u;
+    }
+    for (uint32_t j = m.r.first; j <= m.r.last; ++j)
+        for (int a = 0; a < 3; ++a) {
+            const uint32_t pl = ordered(S.pbox[6ull * j + a]), ph = ordered(S.pbox[6ull * j + 3 + a]);
+            l[a] = pl < l[a] ? pl : l[a];
+            h[a] = ph > h[a] ? ph : h[a];
+        }
+    for (int a = 0; a < 3; ++a) {
+        lo[a] = orderedFloat(l[a]);
+        hi[a] = orderedFloat(h[a]);
+    }
+}
+
+// A primitive's box from its three vertices, as ordered words (lo xyz, hi xyz)
+ARK_LBVH_FN void primBox(const float v[3][3], uint32_t b[6])
+{
+    for (int a = 0; a < 3; ++a) {
+        uint32_t l = ordered(v[0][a]), h = l;
+        for (int k = 1; k < 3; ++k) {
+            const uint32_t o = ordered(v[k][a]);
+            l = o < l ? o : l;
+            h = o > h ? o : h;
+        }
+        b[a] = l;
+        b[3 + a] = h;
+    }
+}
+
+// The treelets that the BVH2 node over r with split s adds to the SAH pass's work list
+// (out[0 .. return)): each child of at most kTreeletPrims primitives of a node of more, and
+// a class's root of at most kTreeletPrims; none of kBvh8MaxLeafSize or fewer, which the
+// collapse never opens. Treelets are disjoint ranges of at least 4 primitives.
+ARK_LBVH_FN int treeletsOf(const Range& r, uint32_t s, bool isRoot, Member out[2])
+{
+    int n = 0;
+    if (count(r) > kTreeletPrims) {
+        Member a, b;
+        a.r.first = r.first;
+        a.r.last = s;
+        a.node = leftNode(a.r);
+        b.r.first = s + 1u;
+        b.r.last = r.last;
+        b.node = rightNode(b.r);
+        if (count(a.r) <= kTreeletPrims && count(a.r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) out[n++] = a;
+        if (count(b.r) <= kTreeletPrims && count(b.r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) out[n++] = b;
+    } else if (isRoot && count(r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        out[0].r = r;
+        out[0].node = r.first;
+        n = 1;
+    }
+    return n;
+}
+
+// A range of n primitives holds n - 1 nodes of its own under the numbering, its root
+// included: the index at the end its root's is not at belongs to an ancestor (a class's
+// root, whose index is its first, has none there: its last is no node's). The SAH pass
+// rewrites split[] at every index of a treelet but this one.
+ARK_LBVH_FN uint32_t treeletSpareIndex(const Member& T) { return T.node == T.r.first ? T.r.last : T.r.first; }
+
 // The members of the BVH8 node over `top` (top.node: its BVH2 node when it holds more
 // than one primitive): out[0 .. return). A node of at most kBvh8MaxLeafSize triangles
-// (only a class's root) is one leaf member.
+// (only a class's root) is one leaf member. S: the SAH pass's boxes (kOpenLargestBox).
 ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], Member out[8],
-                          const KeyLayout& L = kWorldLayout)
+                          const KeyLayout& L = kWorldLayout, const SahBoxes* S = nullptr)
 {
     if (count(top.r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
         out[0] = top;
@@ -304,7 +474,14 @@ ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Mem
         float best = -1.0f;
         for (int k = 0; k < n; ++k) {
             if (count(out[k].r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) continue;
-            const float v = criterion == kOpenLargestCell ? cellArea(keys, out[k].r, extent, L) : static_cast<float>(count(out[k].r));
+            float v;
+            if (criterion == kOpenLargestBox && S && count(out[k].r) <= kTreeletPrims) {
+                float lo[3], hi[3];
+                memberBox(*S, out[k], lo, hi);
+                v = halfArea(lo, hi);
+            } else {
+                v = criterion == kOpenLargestCell || (criterion == kOpenLargestBox && S) ? cellArea(keys, out[k].r, extent, L) : static_cast<float>(count(out[k].r));
+            }
             if (v > best) {
                 best = v;
                 open = k;
@@ -354,17 +531,38 @@ ARK_LBVH_FN void cellCentre(const uint64_t* keys, const Range& r, int64_t c[3], 
 // in slot order, as the host collapse's slot_sort_axis = 2): internal and leaf members
 // alike take slots 0, 1, ... in ascending order of the low w edge of their Morton cell,
 // ties to the lower first key; placeRows finds rows for any such assignment (stride 8).
+// Under the SAH pass (S, with parentNode the BVH2 node of `node`) a member or parent of at
+// most kTreeletPrims primitives is no whole Morton cell any more: its centre is that of its
+// stored box (rangeCentre), its low w edge that of its box (memberLowW; a leaf member's box
+// the union of its primitives'). Larger ranges keep their cells; all else is unchanged.
+ARK_LBVH_FN void rangeCentre(const uint64_t* keys, const Member& m, int64_t c[3], const SahBoxes* S)
+{
+    if (!S || count(m.r) > kTreeletPrims) return cellCentre(keys, m.r, c);
+    float lo[3], hi[3];
+    memberBox(*S, m, lo, hi);
+    for (int a = 0; a < 3; ++a) c[a] = 2 * static_cast<int64_t>(mortonCell(0.5f * lo[a] + 0.5f * hi[a], S->lo[a], mortonScale(S->lo[a], S->hi[a]))) + 1;
+}
+
+ARK_LBVH_FN int64_t memberLowW(const uint64_t* keys, const Member& m, const KeyLayout& L, const SahBoxes* S)
+{
+    if (!S || count(m.r) > kTreeletPrims) {
+        int64_t lo[3];
+        int free[3];
+        cellBounds(keys, m.r, L, lo, free);
+        return lo[2];
+    }
+    float lo[3], hi[3];
+    memberBox(*S, m, lo, hi);
+    const int bits = axisBits(L, 2);
+    return static_cast<int64_t>(layoutCell(lo[2], S->lo[2], layoutScale(S->lo[2], S->hi[2], bits), bits));
+}
+
 ARK_LBVH_FN void assignSlots(const uint64_t* keys, const Range& node, const Member* m, int n, uint32_t slotOf[8], int rule = kSlotsOctant,
-                             const KeyLayout& L = kWorldLayout)
+                             const KeyLayout& L = kWorldLayout, const SahBoxes* S = nullptr, uint32_t parentNode = 0)
 {
     if (rule == kSlotsAscendingW) {
         int64_t low[8];
-        for (int k = 0; k < n; ++k) {
-            int64_t lo[3];
-            int free[3];
-            cellBounds(keys, m[k].r, L, lo, free);
-            low[k] = lo[2];
-        }
+        for (int k = 0; k < n; ++k) low[k] = memberLowW(keys, m[k], L, S);
         for (int k = 0; k < n; ++k) {
             uint32_t rank = 0;
             for (int j = 0; j < n; ++j)
@@ -375,12 +573,15 @@ ARK_LBVH_FN void assignSlots(const uint64_t* keys, const Range& node, const Memb
     }
     uint32_t taken = 0;
     int64_t pc[3];
-    cellCentre(keys, node, pc);
+    Member parent;
+    parent.r = node;
+    parent.node = parentNode;
+    rangeCentre(keys, parent, pc, S);
     for (int k = 0; k < n; ++k) {
         slotOf[k] = kNoSlot;
         if (count(m[k].r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) continue;
         int64_t c[3];
-        cellCentre(keys, m[k].r, c);
+        rangeCentre(keys, m[k], c, S);
         const uint32_t want = (c[0] > pc[0] ? 1u : 0u) | (c[1] > pc[1] ? 2u : 0u) | (c[2] > pc[2] ? 4u : 0u);
         uint32_t bestSlot = 0, bestDist = 99;
         for (uint32_t s = 0; s < 8u; ++s) {
@@ -462,10 +663,10 @@ struct WideNode {
 };
 
 ARK_LBVH_FN void planNode(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], WideNode& w,
-                          int slotRule = kSlotsOctant, const KeyLayout& L = kWorldLayout)
+                          int slotRule = kSlotsOctant, const KeyLayout& L = kWorldLayout, const SahBoxes* S = nullptr)
 {
-    w.members = selectCut(keys, split, top, criterion, extent, w.member, L);
-    assignSlots(keys, top.r, w.member, w.members, w.slotOf, slotRule, L);
+    w.members = selectCut(keys, split, top, criterion, extent, w.member, L, S);
+    assignSlots(keys, top.r, w.member, w.members, w.slotOf, slotRule, L, S, top.node);
     uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     w.imask = 0;
     w.internal = 0;

@@ -29,6 +29,11 @@ bool isDeviceFault(hipError_t e)
 struct LbvhGpuTrace {
     LbvhHeader hdr {};                            // as the build uses it (the light build's classCount[0] = prims)
     std::vector<uint32_t> idx, idxSorted, split;  // hdr.prims each (split: set at the internal indices of each class range)
+    // the SAH pass (LbvhGpuBuild::sah): idxSorted as the sort left it (idxSorted above: as the
+    // pass left it), the work list, the boxes per BVH2 node and per sorted primitive
+    std::vector<uint32_t> idxMorton;
+    std::vector<lbvh::Member> treelets;
+    std::vector<float> nbox, pbox;
     std::vector<uint64_t> keysSorted;
     std::vector<GpuBvh8Node> nodes;
     std::vector<GpuTriangle> tris;                // the rows, then the padding record
@@ -59,7 +64,7 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         ~Arena() { buf.release(); }
     } arenaA, arenaB;
     struct {
-        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes;
+        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes, treelets, nbox, pbox;
     } w;
     hipError_t e = hipSuccess;
     struct KeepWhy {
@@ -110,9 +115,13 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
     ARK_GB(launch_lbvh_sort(nullptr, tempBytes, w.keys.as<uint64_t>(), nullptr, w.idx.as<uint32_t>(), nullptr, n, s));
     // (the collapse's bound on the nodes: below)
     const uint32_t nodeCap = n / 2u + 8u;
+    // (the SAH pass: treelets are disjoint ranges of at least 4 primitives; its list and boxes live in the same arena)
+    const uint32_t treeletCap = g.sah ? n / 4u + 1u : 0u;
+    const size_t sahBoxBytes = g.sah ? n * 6ull * sizeof(float) : 0;
     {
         const size_t sizes[] = { tempBytes, n * 8ull, n * 4ull, n * 4ull, nodeCap * sizeof(GpuBvh8Node), nodeCap * sizeof(lbvh::Member), nodeCap * sizeof(lbvh::Member),
-                                 n * 4ull, kLbvhCounters * 4ull, nodeCap * 8ull, instances * sizeof(RefitInstance), nodeCap * 6ull * sizeof(float) };
+                                 n * 4ull, kLbvhCounters * 4ull, nodeCap * 8ull, instances * sizeof(RefitInstance), nodeCap * 6ull * sizeof(float),
+                                 treeletCap * sizeof(lbvh::Member), sahBoxBytes, sahBoxBytes };
         size_t total = 0;
         for (size_t b : sizes) total += Arena::pad(b);
         ARK_GB(arenaB.buf.alloc(total));
@@ -128,21 +137,54 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         w.masks = arenaB.take(sizes[9]);
         w.inst = arenaB.take(sizes[10]);
         w.boxes = arenaB.take(sizes[11]);
+        w.treelets = arenaB.take(sizes[12]);
+        w.nbox = arenaB.take(sizes[13]);
+        w.pbox = arenaB.take(sizes[14]);
     }
     ARK_GB(launch_lbvh_sort(w.sortTemp.ptr, tempBytes, w.keys.as<uint64_t>(), w.keysSorted.as<uint64_t>(), w.idx.as<uint32_t>(), w.idxSorted.as<uint32_t>(), n, s));
     // the radix trees, class by class
+    ARK_GB(hipMemsetAsync(w.counters.ptr, 0, kLbvhCounters * 4, s));
     uint32_t classLo[3], first = 0;
     for (int c = 0; c < 3; ++c) {
         classLo[c] = first;
         first += hdr.classCount[c];
-        ARK_GB(launch_lbvh_hierarchy(w.keysSorted.as<uint64_t>(), classLo[c], classLo[c] + hdr.classCount[c], w.split.as<uint32_t>(), s));
+        ARK_GB(launch_lbvh_hierarchy(w.keysSorted.as<uint64_t>(), classLo[c], classLo[c] + hdr.classCount[c], w.split.as<uint32_t>(), s,
+                                     g.sah ? w.treelets.as<lbvh::Member>() : nullptr, treeletCap, w.counters.as<uint32_t>()));
+    }
+    uint32_t treelets = 0;
+    if (g.sah) {
+        // the SAH pass: one workgroup per treelet, the launch sized by the list's count read back
+        uint32_t counted[kLbvhCounters] = {};
+        if (g.trace) {
+            g.trace->idxMorton.resize(n);
+            ARK_GB(hipMemcpyAsync(g.trace->idxMorton.data(), w.idxSorted.ptr, n * 4ull, hipMemcpyDeviceToHost, s));
+        }
+        ARK_GB(hipMemsetAsync(w.nbox.ptr, 0, sahBoxBytes, s));
+        ARK_GB(hipMemsetAsync(w.pbox.ptr, 0, sahBoxBytes, s));
+        ARK_GB(hipMemcpyAsync(counted, w.counters.ptr, sizeof(counted), hipMemcpyDeviceToHost, s));
+        ARK_GB(hipStreamSynchronize(s));
+        treelets = counted[kLbvhTreelets];
+        if (counted[kLbvhOverflow] || treelets > treeletCap) {
+            why = "more nodes than the device build's scratch";
+            return hipSuccess;
+        }
+        LbvhTreeletArgs ta {};
+        ta.snap = snap;
+        ta.list = w.treelets.as<lbvh::Member>();
+        ta.prims = n;
+        ta.sorted = w.idxSorted.as<uint32_t>();
+        ta.split = w.split.as<uint32_t>();
+        ta.nbox = w.nbox.as<float>();
+        ta.pbox = w.pbox.as<float>();
+        ta.light = g.light ? 1 : 0;
+        std::memcpy(ta.frame.m, g.frame, sizeof(ta.frame.m));
+        ARK_GB(launch_lbvh_treelet_sah(ta, treelets, s));
     }
     // the collapse. Every BVH8 node but a class's root is a BVH2 node of at least 4
     // triangles, and one with an internal child has 8 members. With L nodes without an
     // internal child (4 triangles of their own each), C with one (7 members of their
     // own) and fewer than L with more, 4 L + 7 C <= n bounds 2 L + C by n / 2: fewer than
     // n / 2 + 3 nodes (the kernel checks, and the job falls back beyond).
-    ARK_GB(hipMemsetAsync(w.counters.ptr, 0, kLbvhCounters * 4, s));
     float lo[3], hi[3];
     LbvhCollapseArgs a {};
     for (int k = 0; k < 3; ++k) {
@@ -155,9 +197,16 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
     a.nodes = w.nodes.as<GpuBvh8Node>();
     a.position = w.position.as<uint32_t>();
     a.counters = w.counters.as<uint32_t>();
-    a.criterion = lbvh::kDefaultCriterion;
+    a.criterion = g.sah ? lbvh::kOpenLargestBox : lbvh::kDefaultCriterion;
     a.slotRule = g.slotRule;
     a.wBits = g.wBits;
+    a.useSah = g.sah ? 1 : 0;
+    a.sah.nbox = w.nbox.as<float>();
+    a.sah.pbox = w.pbox.as<float>();
+    for (int k = 0; k < 3; ++k) {
+        a.sah.lo[k] = lo[k];
+        a.sah.hi[k] = hi[k];
+    }
     std::vector<std::array<uint32_t, 3>> levels; // node counts [depth][class]
     uint32_t nodeTotal = 0, counters[kLbvhCounters] = {};
     for (int c = 0; c < 3; ++c) {
@@ -271,6 +320,14 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         ARK_GB(hipMemcpyAsync(t->nodes.data(), nodes, nodeTotal * sizeof(GpuBvh8Node), hipMemcpyDeviceToHost, s));
         ARK_GB(hipMemcpyAsync(t->tris.data(), tris, (outRecords + 1ull) * sizeof(GpuTriangle), hipMemcpyDeviceToHost, s));
         if (!t->perm.empty()) ARK_GB(hipMemcpyAsync(t->perm.data(), g.perm->ptr, outRecords * 4ull, hipMemcpyDeviceToHost, s));
+        if (g.sah) {
+            t->treelets.resize(treelets);
+            t->nbox.resize(n * 6ull);
+            t->pbox.resize(n * 6ull);
+            if (treelets) ARK_GB(hipMemcpyAsync(t->treelets.data(), w.treelets.ptr, treelets * sizeof(lbvh::Member), hipMemcpyDeviceToHost, s));
+            ARK_GB(hipMemcpyAsync(t->nbox.data(), w.nbox.ptr, sahBoxBytes, hipMemcpyDeviceToHost, s));
+            ARK_GB(hipMemcpyAsync(t->pbox.data(), w.pbox.ptr, sahBoxBytes, hipMemcpyDeviceToHost, s));
+        }
         ARK_GB(hipStreamSynchronize(s));
         t->order = order;
         t->levelOffsets = b.levelOffsets;
@@ -293,12 +350,14 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
 // ark_ddgi_debug.h: one traced device build (buildLbvhGpu, the product's kernels and
 // nothing else) of the given records on a stream of its own, without a context, against
 // build_lbvh_host of the same records in the device's compaction order, stage by stage.
-extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
-                                                  const float* sun_dir, int w_bits, uint64_t* out)
+namespace {
+// out: 40 words (ark_ddgi_debug_lbvh_device_parity_sah's)
+int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances, const float* sun_dir, int w_bits, bool sahPass,
+                     uint64_t* out)
 {
     using namespace ark;
     if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
-    std::fill(out, out + 32, uint64_t(0));
+    std::fill(out, out + 40, uint64_t(0));
     for (uint32_t i = 0; i < n_instances; ++i)
         if (class_of[i] < 0 || class_of[i] > 2) return -1; // (the kernels index the class counts by it)
     int wBits = lbvh::kMortonBits;
@@ -351,6 +410,7 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
         g.bvh = &d.bvh;
         g.perm = &d.perm;
         g.trace = &trace;
+        g.sah = sahPass;
         e = buildLbvhGpu(g, d.s, why);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(d.s);
@@ -388,7 +448,7 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
     LbvhSunOptions so;
     std::memcpy(so.frame, g.frame, sizeof(so.frame));
     so.wBits = wBits;
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx);
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx, sahPass);
     auto bits = [](float f) {
         uint32_t u;
         std::memcpy(&u, &f, 4);
@@ -411,13 +471,32 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
     } else {
         for (uint32_t j = 0; j < prims; ++j) {
             out[11] += trace.keysSorted[j] != r.keysSorted[j] ? 1u : 0u;
-            out[12] += trace.idxSorted[j] != r.idxSorted[j] ? 1u : 0u;
+            // (the SAH pass: [12] the order the sort left, [31] the order the pass left)
+            const std::vector<uint32_t>& dm = sahPass ? trace.idxMorton : trace.idxSorted;
+            const std::vector<uint32_t>& hm = sahPass ? r.idxMorton : r.idxSorted;
+            out[12] += j >= dm.size() || j >= hm.size() || dm[j] != hm[j] ? 1u : 0u;
+            if (sahPass) out[31] += trace.idxSorted[j] != r.idxSorted[j] ? 1u : 0u;
         }
         uint32_t first = 0;
         for (int c = 0; c < 3; ++c) {
             for (uint32_t i = first; i + 1u < first + r.classCount[c]; ++i) out[13] += trace.split[i] != r.split[i] ? 1u : 0u;
             first += r.classCount[c];
         }
+    }
+    if (sahPass) {
+        // the work list as a set, the boxes by bits
+        auto less = [](const lbvh::Member& a, const lbvh::Member& b) { return a.r.first < b.r.first; };
+        std::vector<lbvh::Member> dl = trace.treelets, hl = r.treelets;
+        std::sort(dl.begin(), dl.end(), less);
+        std::sort(hl.begin(), hl.end(), less);
+        out[29] = dl.size();
+        out[30] = dl.size() != hl.size() ? 1u : 0u;
+        for (size_t k = 0; k < std::min(dl.size(), hl.size()); ++k)
+            out[30] += dl[k].r.first != hl[k].r.first || dl[k].r.last != hl[k].r.last || dl[k].node != hl[k].node ? 1u : 0u;
+        out[32] = trace.nbox.size() != r.nbox.size() ? 1u : 0u;
+        out[33] = trace.pbox.size() != r.pbox.size() ? 1u : 0u;
+        for (size_t k = 0; k < std::min(trace.nbox.size(), r.nbox.size()); ++k) out[32] += bits(trace.nbox[k]) != bits(r.nbox[k]) ? 1u : 0u;
+        for (size_t k = 0; k < std::min(trace.pbox.size(), r.pbox.size()); ++k) out[33] += bits(trace.pbox[k]) != bits(r.pbox[k]) ? 1u : 0u;
     }
     // the tree
     const GpuTriangle padding = trace.tris.back(); // (records + 1 entries)
@@ -460,5 +539,23 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
     out[28] = r.nodes.size();
     uint64_t mismatches = 0;
     for (int k = 5; k <= 23; ++k) mismatches += out[k];
+    mismatches += out[30] + out[31] + out[32] + out[33];
     return mismatches ? 1 : 0;
+}
+} // namespace
+
+extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                                  const float* sun_dir, int w_bits, uint64_t* out)
+{
+    if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
+    uint64_t all[40];
+    const int rc = lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, false, all);
+    std::copy(all, all + 32, out);
+    return rc;
+}
+
+extern "C" int ark_ddgi_debug_lbvh_device_parity_sah(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                                      const float* sun_dir, int w_bits, int sah, uint64_t* out)
+{
+    return lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, sah != 0, out);
 }

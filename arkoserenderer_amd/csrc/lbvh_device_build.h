@@ -28,6 +28,9 @@ struct LbvhGpuBuild {
     bool light = false;                // the sun's: one range over every class, keys and boxes in `frame`
     double frame[9] {};
     int slotRule = lbvh::kSlotsOctant, wBits = lbvh::kMortonBits;
+    // ARK_DDGI_FLAG_GPU_REBUILD_SAH: the SAH pass over the radix tree's treelets
+    // (k_lbvh_treelet_sah) before the collapse, which then decides by the pass's boxes
+    bool sah = false;
     DeviceBvh* bvh = nullptr;          // out: buffer, level order (device and offsets), counts, depth
     DeviceBuffer* perm = nullptr;      // out: the record order's source indices (null: not wanted)
     LbvhGpuTrace* trace = nullptr;     // out: the stages' results (null in the product paths: nothing more is enqueued)

@@ -56,6 +56,7 @@ struct RebuildJob {
     float dir[3] {};
     double frame[9] {};     // sun_frame(dir)
     uint32_t instances = 0; // of the scene (the device build checks the records' against it)
+    bool sahPass = false;   // ARK_DDGI_FLAG_GPU_REBUILD_SAH: a device build runs the SAH pass
     ~RebuildJob()
     {
         if (t.joinable()) t.join();
@@ -461,6 +462,7 @@ void deviceBuildWorld(RebuildJob* job, LbvhGpuBuild& g)
 {
     g.classHost.assign(job->classOf.begin(), job->classOf.end());
     g.perm = &job->perm;
+    g.sah = job->sahPass;
 }
 
 void deviceBuildSun(RebuildJob* job, LbvhGpuBuild& g)
@@ -470,6 +472,7 @@ void deviceBuildSun(RebuildJob* job, LbvhGpuBuild& g)
     std::memcpy(g.frame, job->frame, sizeof(g.frame));
     g.slotRule = lbvh::kSlotsAscendingW;
     g.wBits = lbvh::kSunKeyBitsW;
+    g.sah = job->sahPass;
 }
 
 // A job's device build on `s` (lbvh_device_build.h; ARK_DDGI_FLAG_GPU_REBUILD / _SUN), which
@@ -759,6 +762,7 @@ int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     sun_frame(job->dir, frame);
     std::memcpy(job->frame, frame, sizeof(job->frame));
     job->instances = static_cast<uint32_t>(st.instHost.size());
+    job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
     if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
     st.sunJob = std::move(job);
     st.lastBackground = kBackgroundSun;
@@ -821,6 +825,7 @@ int worldStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     auto job = std::make_unique<RebuildJob>();
     job->kind = RebuildJob::World;
     job->classOf = instanceClasses(st);
+    job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
     if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
     st.worldJob = std::move(job);
     st.lastBackground = kBackgroundWorld;

@@ -78,6 +78,10 @@ class DDGIConfig:
     # on the device too (after a sun-direction change and after refits), one host rebuild once
     # no refit has come since; independent of gpu_rebuild
     gpu_rebuild_sun: bool = False
+    # ARK_DDGI_FLAG_GPU_REBUILD_SAH (experimental): the device builds that gpu_rebuild and
+    # gpu_rebuild_sun enable rebuild every subtree of at most 256 triangles by a sweep SAH
+    # before the 8-wide collapse; alone it does nothing
+    gpu_rebuild_sah: bool = False
     build_threads: int = 0
 
 
@@ -117,6 +121,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.flags = (abi.ARK_DDGI_FLAG_SERIAL_FRAMES if config.serial_frames else 0) | (0 if config.background_rebuild else abi.ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD)
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD if config.gpu_rebuild else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SUN if config.gpu_rebuild_sun else 0
+    d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SAH if config.gpu_rebuild_sah else 0
     d.build_threads = int(config.build_threads)
     return d
 
@@ -391,38 +396,50 @@ class DDGIContext:
 _BVH_CHECK_KEYS = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
 
 
-def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int | None = None) -> tuple:
+def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int | None = None, sah: bool | None = None) -> tuple:
     """ark_ddgi_debug_sun_lbvh_check: the device build of the sun's light-space BVH8 run
     serially on the host over world triangles (n x 9 floats), then a sun shadow ray from
     each origin (m x 3 floats) through it against brute force. Returns (rc, dict): rays,
     occluded_brute, occluded_bvh, mismatches, node_visits, triangle_tests, nodes,
     max_stack_depth, violations, inflation_differs, cost_lbvh, cost_host (any-hit steps per
     ray) and the tree's leaf_children, depth, records_with_holes, w_bits. w_bits: the
-    key's Morton bits given to w (None: the default). No GPU."""
+    key's Morton bits given to w (None: the default). sah not None:
+    ark_ddgi_debug_sun_lbvh_check_sah, with (True) or without the SAH pass of
+    gpu_rebuild_sah, and `treelets`. No GPU."""
     lib = abi.load_library()
     tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
     sd = np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
     org = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
-    out = (C.c_uint64 * 16)()
-    rc = lib.ark_ddgi_debug_sun_lbvh_check_opts(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
-                                                -1 if w_bits is None else int(w_bits), out)
     keys = ("rays", "occluded_brute", "occluded_bvh", "mismatches", "node_visits", "triangle_tests", "nodes", "max_stack_depth", "violations",
             "inflation_differs", "cost_lbvh", "cost_host", "leaf_children", "depth", "records_with_holes", "w_bits")
+    if sah is None:
+        out = (C.c_uint64 * 16)()
+        rc = lib.ark_ddgi_debug_sun_lbvh_check_opts(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
+                                                    -1 if w_bits is None else int(w_bits), out)
+    else:
+        out = (C.c_uint64 * 17)()
+        rc = lib.ark_ddgi_debug_sun_lbvh_check_sah(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
+                                                   -1 if w_bits is None else int(w_bits), 1 if sah else 0, out)
+        keys = keys + ("treelets",)
     r = dict(zip(keys, (int(v) for v in out)))
     r["cost_lbvh"] /= 1e6
     r["cost_host"] /= 1e6
     return rc, r
 
 
-def lbvh_check(triangles, criterion: int | None = None) -> tuple:
+def lbvh_check(triangles, criterion: int | None = None, sah: bool | None = None) -> tuple:
     """ark_ddgi_debug_lbvh_check: the device LBVH build's logic run serially on the host
     over world triangles (n x 9 floats). Returns (rc, out[8]) with out as
     ark_ddgi_debug_bvh8_check: nodes, leaf children, max depth, violations, triangles,
-    radix-tree nodes, internal children, BVH8 SAH cost x 1e6. No GPU."""
+    radix-tree nodes, internal children, BVH8 SAH cost x 1e6. sah not None:
+    ark_ddgi_debug_lbvh_check_sah, with (True) or without the SAH pass of gpu_rebuild_sah,
+    out[9] with the treelets last. No GPU."""
     lib = abi.load_library()
     tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
-    out = (C.c_uint64 * 8)()
-    if criterion is None:
+    out = (C.c_uint64 * (8 if sah is None else 9))()
+    if sah is not None:
+        rc = lib.ark_ddgi_debug_lbvh_check_sah(tris.ctypes.data, tris.shape[0], 1 if criterion is None else int(criterion), 1 if sah else 0, out)
+    elif criterion is None:
         rc = lib.ark_ddgi_debug_lbvh_check(tris.ctypes.data, tris.shape[0], out)
     else:
         rc = lib.ark_ddgi_debug_lbvh_check_opts(tris.ctypes.data, tris.shape[0], int(criterion), out)
@@ -453,23 +470,34 @@ _LBVH_PARITY_KEYS = ("prims", "nodes", "records_with_holes", "depth", "why", "co
                      "inflation", "keys", "sorted_indices", "splits", "shape", "node_header", "grid", "planes", "children", "records", "perm", "holes",
                      "level_order", "padding", "first_device_node", "first_host_node", "hip_error", "pairs", "host_nodes")
 LBVH_PARITY_MISMATCHES = _LBVH_PARITY_KEYS[5:24]
+# ark_ddgi_debug_lbvh_device_parity_sah's further words
+_LBVH_PARITY_SAH_KEYS = _LBVH_PARITY_KEYS + ("treelets", "treelet_list", "sorted_after_sah", "node_boxes", "prim_boxes")
+LBVH_PARITY_SAH_MISMATCHES = LBVH_PARITY_MISMATCHES + _LBVH_PARITY_SAH_KEYS[30:34]
 LBVH_WHY = ("", "no records", "no triangles", "record of an unknown instance", "too deep", "node scratch", "4 GiB", "other")
 
 
-def lbvh_device_parity(records, class_of, sun_dir=None, w_bits: int | None = None, device: int = 0) -> tuple:
+def lbvh_device_parity(records, class_of, sun_dir=None, w_bits: int | None = None, device: int = 0, sah: bool | None = None) -> tuple:
     """ark_ddgi_debug_lbvh_device_parity: the device LBVH build (the world's, or with sun_dir
     the sun's light-space one) run once over triangle records (triangle_records) and compared
     bit for bit, stage by stage, with its host restatement. class_of: instance -> hit-mask
     class. Returns (rc, dict): prims, nodes, records_with_holes, depth, why (LBVH_WHY's text)
-    and one mismatch count per stage (LBVH_PARITY_MISMATCHES). Needs a GPU."""
+    and one mismatch count per stage (LBVH_PARITY_MISMATCHES). sah not None:
+    ark_ddgi_debug_lbvh_device_parity_sah, both builds with (True) or without the SAH pass
+    of gpu_rebuild_sah; also treelets and LBVH_PARITY_SAH_MISMATCHES' counts. Needs a GPU."""
     lib = abi.load_library()
     rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 12)
     cls = np.ascontiguousarray(class_of, dtype=np.int32).reshape(-1)
     sd = None if sun_dir is None else np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
-    out = (C.c_uint64 * 32)()
-    rc = lib.ark_ddgi_debug_lbvh_device_parity(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
-                                               None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits), out)
-    r = dict(zip(_LBVH_PARITY_KEYS, (int(v) for v in out)))
+    if sah is None:
+        out = (C.c_uint64 * 32)()
+        rc = lib.ark_ddgi_debug_lbvh_device_parity(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
+                                                   None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits), out)
+        r = dict(zip(_LBVH_PARITY_KEYS, (int(v) for v in out)))
+    else:
+        out = (C.c_uint64 * 40)()
+        rc = lib.ark_ddgi_debug_lbvh_device_parity_sah(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
+                                                       None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits), 1 if sah else 0, out)
+        r = dict(zip(_LBVH_PARITY_SAH_KEYS, (int(v) for v in out)))
     r["why"] = LBVH_WHY[r["why"]] if rc >= 0 else "error"
     return rc, r
 

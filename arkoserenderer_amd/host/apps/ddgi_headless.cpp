@@ -26,6 +26,10 @@
 //                                                       checkpoint of the (unsharded) node after the
 //                                                       last frame / before the first; frame indices
 //                                                       start at F (DDGINode::saveState/loadState)
+//                 [--gpu-rebuild MASK]                  device rebuilds after moved instances: 1 the
+//                                                       world BVHs (DDGINode::setGpuRebuild), 2 the
+//                                                       sun's (setGpuRebuildSun), 4 their SAH pass
+//                                                       (setGpuRebuildSah); prints the rebuild counts
 //                 [--exchange-timeout SEC]              deadline of the exchange watchdog
 //                 [--exchange-deadline-test]            1-rank RCCL: stalls the exchange stream for
 //                                                       1.5 s under a 0.2 s deadline; the watchdog
@@ -332,7 +336,7 @@ int main(int argc, char** argv)
     std::string ncclIdPath, ncclNonce;
     double exchangeTimeout = 0.0;
     std::string saveStatePath, loadStatePath, frameScriptPath;
-    int firstFrame = 0;
+    int firstFrame = 0, gpuRebuild = 0;
     bool deadlineTest = false;
     const std::time_t startedAt = std::time(nullptr);
     float zFar = 10000.0f, exposure = 1.0f, env = 1.0f, ambient = 0.0f;
@@ -369,6 +373,7 @@ int main(int argc, char** argv)
         else if (a == "--load-state") loadStatePath = next();
         else if (a == "--first-frame") firstFrame = std::atoi(next());
         else if (a == "--frame-script") frameScriptPath = next();
+        else if (a == "--gpu-rebuild") gpuRebuild = std::atoi(next());
         else ARKOSE_LOG(Fatal, "unknown argument %s", a.c_str());
     }
     SceneFile file;
@@ -411,6 +416,9 @@ int main(int argc, char** argv)
         node.setProbeUpdatesPerFrame(updates);
         node.setComputeProbeOffsets(offsets != 0);
         node.setMaxProbeUpdates(updates);
+        node.setGpuRebuild((gpuRebuild & 1) != 0);
+        node.setGpuRebuildSun((gpuRebuild & 2) != 0);
+        node.setGpuRebuildSah((gpuRebuild & 4) != 0);
         if (slabCount > 1) node.setShard(shardRank, slabCount);
         return pipeline;
     };
@@ -543,6 +551,12 @@ int main(int argc, char** argv)
         ok = ok && dump(ctx, ARK_DDGI_PROBE_OFFSETS, out + ".off");
     }
     if (exchange) std::printf("ddgi_headless: %d Z-slab ranks, %s exchange\n", slabCount, exchange->name());
+    if (gpuRebuild) {
+        ArkDdgiBvhStats st {};
+        if (ark_ddgi_get_bvh_stats(ctx, &st) != ARK_DDGI_OK) ARKOSE_LOG(Error, "no BVH stats");
+        std::printf("ddgi_headless: gpu rebuild mask %d: device builds installed world %u, sun %u, fallbacks %u / %u, failures %u / %u\n", gpuRebuild, st.bvh_gpu_rebuilds,
+                    st.sun_gpu_rebuilds, st.bvh_gpu_fallbacks, st.sun_gpu_fallbacks, st.bvh_rebuild_failures, st.sun_rebuild_failures);
+    }
     pipelines.clear();
     exchange.reset();
     registries.clear();

@@ -79,7 +79,8 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
     desc.clear_overflow_mode = ARK_DDGI_CLEAR_OVERFLOW_INF;
     desc.shard_rank = m_shardRank;
     desc.shard_count = m_shardCount;
-    desc.flags = (m_gpuRebuild ? ARK_DDGI_FLAG_GPU_REBUILD : 0u) | (m_gpuRebuildSun ? ARK_DDGI_FLAG_GPU_REBUILD_SUN : 0u);
+    desc.flags = (m_gpuRebuild ? ARK_DDGI_FLAG_GPU_REBUILD : 0u) | (m_gpuRebuildSun ? ARK_DDGI_FLAG_GPU_REBUILD_SUN : 0u) |
+                 (m_gpuRebuildSah ? ARK_DDGI_FLAG_GPU_REBUILD_SAH : 0u);
     auto created = reg.createOrReuseDdgiContext("ddgi", desc);
     ArkDdgiCtx* ctx = created.first;
     if (!ctx) {

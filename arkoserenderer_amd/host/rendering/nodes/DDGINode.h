@@ -34,6 +34,9 @@ public:
     // ARK_DDGI_FLAG_GPU_REBUILD_SUN (before construct; experimental, off; either may be set
     // alone): the light-space sun BVH's background builds run on the device too
     void setGpuRebuildSun(bool on) { m_gpuRebuildSun = on; }
+    // ARK_DDGI_FLAG_GPU_REBUILD_SAH (before construct; experimental, off): those device builds
+    // rebuild every subtree of at most 256 triangles by a sweep SAH; alone it does nothing
+    void setGpuRebuildSah(bool on) { m_gpuRebuildSah = on; }
     // Z-slab ranks: the atlas exchange after each update (RCCL all-gather, or device
     // copies for contexts in one process); frame n+1's shading waits for frame n's.
     void setSlabExchange(SlabExchange* exchange) { m_exchange = exchange; }
@@ -74,6 +77,7 @@ private:
     int m_shardCount { 1 };
     bool m_gpuRebuild { false };
     bool m_gpuRebuildSun { false };
+    bool m_gpuRebuildSah { false };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     SlabExchange* m_exchange { nullptr };

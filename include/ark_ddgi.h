@@ -177,11 +177,18 @@ typedef struct ArkDdgiDesc {
  * too, one LBVH over all classes' records keyed and boxed in the sun's frame, its slots in
  * ascending w; once no refit has come since its snapshot one host rebuild replaces it. A
  * scene the device build cannot take is built by the host within the same job
- * (sun_gpu_fallbacks); results are the same. */
+ * (sun_gpu_fallbacks); results are the same. GPU_REBUILD_SAH (experimental, off by
+ * default): modifies the device builds that GPU_REBUILD and GPU_REBUILD_SUN enable; alone it
+ * is accepted and does nothing. Between the radix tree and the 8-wide collapse every subtree
+ * of at most 256 triangles is rebuilt by a full sweep SAH with its triangles reordered, and
+ * the collapse decides by the boxes that pass leaves. When a device build starts, what
+ * becomes of it and the host rebuild after the motion stops are unchanged; results are the
+ * same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
 #define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
 #define ARK_DDGI_FLAG_GPU_REBUILD_SUN 0x8u
+#define ARK_DDGI_FLAG_GPU_REBUILD_SAH 0x10u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {

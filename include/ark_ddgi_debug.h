@@ -89,6 +89,11 @@ int ark_ddgi_debug_scene_digest(struct ArkDdgiCtx* ctx, uint64_t* out);
  * Returns 0 when the check passes, 1 when it found violations. No GPU. */
 int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out);
 int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out);
+/* The same with the SAH pass of ARK_DDGI_FLAG_GPU_REBUILD_SAH restated serially between the
+ * radix tree and the cut (sah != 0; the cut then opens by the pass's boxes whatever
+ * `criterion`; sah = 0: _opts' result word for word). out[9]: _opts' eight, [8] the treelets
+ * the pass rebuilt. */
+int ark_ddgi_debug_lbvh_check_sah(const float* triangles, uint64_t n, int criterion, int sah, uint64_t* out);
 
 /* The device LBVH build itself (ARK_DDGI_FLAG_GPU_REBUILD, ARK_DDGI_FLAG_GPU_REBUILD_SUN: the
  * product's driver and kernels, nothing else) run once on `device`, synchronously and without
@@ -118,6 +123,14 @@ int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int crite
  * host ([4]; nothing built, nothing compared), negative on an invalid argument or a HIP error. */
 int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
                                       const float* sun_dir, int w_bits, uint64_t* out);
+/* The same of the device build with the SAH pass (ARK_DDGI_FLAG_GPU_REBUILD_SAH; sah != 0)
+ * against the host restatement with it; sah = 0: the entry above, word for word. out[40]:
+ * [0..28] as above ([12] the sorted record indices as the sort left them, [13] the splits as
+ * the pass left them), [29] the treelets, and the mismatch counts [30] the treelet list as a
+ * set, [31] the sorted record indices after the pass, [32] the boxes per BVH2 node and [33]
+ * per sorted primitive, by bits; they count towards the return value. */
+int ark_ddgi_debug_lbvh_device_parity_sah(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                          const float* sun_dir, int w_bits, int sah, uint64_t* out);
 
 /* compare_bvh8_canonical (the tree comparison of ark_ddgi_debug_lbvh_device_parity) tried on
  * the host: the LBVH restatement's tree of n triangles (9 floats each; triangle i of instance
@@ -167,6 +180,11 @@ int ark_ddgi_debug_sun_lbvh_check(const float* triangles, uint64_t n, const floa
                                   uint64_t* out);
 int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
                                        int w_bits, uint64_t* out);
+/* _opts with the SAH pass (sah != 0; [8] then counts slots that do not ascend in the low w
+ * edge of their members' boxes; sah = 0: _opts' result word for word). out[17]: _opts'
+ * sixteen, [16] the treelets the pass rebuilt. */
+int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                      int w_bits, int sah, uint64_t* out);
 
 /* ark_ddgi_debug_world_bvh_check for the installed light-space sun BVH. out[8] = {nodes,
  * leaf children, max depth, violations, records that are not holes, records with holes,

@@ -26,6 +26,11 @@ light-space sun BVH rebuilt on the device too. The trees then also tell the sun 
 builder and device builds; with --sun-turn each turn records the shadow phase on the world
 BVHs (while the build runs), on the device-built tree and on the host rebuild that settles
 it, and the time from set_lights to each install.
+
+--gpu-rebuild-sah (with either of the two): ARK_DDGI_FLAG_GPU_REBUILD_SAH, the device builds'
+SAH pass over subtrees of at most 256 triangles. Run it with and without in turn: the device
+builds' time (rebuild_ms, sun build_ms), the traversal and shadow phases on the tree traced
+right after the motion, the footprint and the rate while moving are the ones to compare.
 """
 import argparse
 import dataclasses
@@ -57,6 +62,7 @@ def main():
     ap.add_argument("--no-background", action="store_true", help="ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: refits only (isolates the rebuild threads' cost)")
     ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
     ap.add_argument("--gpu-rebuild-sun", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SUN: the light-space sun BVH's background builds on the device")
+    ap.add_argument("--gpu-rebuild-sah", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SAH: the device builds' SAH pass over subtrees of at most 256 triangles")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
     import torch
@@ -67,7 +73,8 @@ def main():
         sc, grid, R, zf = build(name)
         N = grid.probe_count()
         cfg = D.DDGIConfig(rays_per_probe=R, probe_updates_per_frame=N, max_rays_per_probe=R, max_probe_updates=N, compute_probe_offsets=True,
-                           background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild, gpu_rebuild_sun=args.gpu_rebuild_sun)
+                           background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild, gpu_rebuild_sun=args.gpu_rebuild_sun,
+                           gpu_rebuild_sah=args.gpu_rebuild_sah)
         node = D.DDGINode(cfg)
         node.construct(sc, grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
         app = [D.AppState(0)]
@@ -173,7 +180,8 @@ def main():
                 "ms_per_frame_moving": round(motion_s / args.frames * 1e3, 4),
                 "refit_device_ms": {"median": round(refit_dev[len(refit_dev) // 2], 4), "max": round(refit_dev[-1], 4)},
                 "refit_host_enqueue_ms": round(host_refit / args.frames * 1e3, 4), "background_rebuild": not args.no_background,
-                "gpu_rebuild": bool(args.gpu_rebuild), "gpu_rebuild_sun": bool(args.gpu_rebuild_sun), "trees": trees,
+                "gpu_rebuild": bool(args.gpu_rebuild), "gpu_rebuild_sun": bool(args.gpu_rebuild_sun), "gpu_rebuild_sah": bool(args.gpu_rebuild_sah),
+                "trees": trees,
                 "built_refit_version": {"world": int(st2.bvh_built_refit_version), "sun": int(st2.sun_built_refit_version), "refits": int(st2.refit_version)},
                 "installs_while_moving": {"world": int(st1.bvh_rebuilds - st0.bvh_rebuilds), "sun": int(st1.sun_rebuilds - st0.sun_rebuilds)},
                 "world_rebuild_ms": round(st2.bvh_rebuild_ms, 1), "sun_rebuild_ms": round(st2.sun_build_ms, 1),
