@@ -55,6 +55,7 @@ ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD = 0x2
 ARK_DDGI_FLAG_GPU_REBUILD = 0x4
 ARK_DDGI_FLAG_GPU_REBUILD_SUN = 0x8
 ARK_DDGI_FLAG_GPU_REBUILD_SAH = 0x10
+ARK_DDGI_FLAG_NO_SUN_COVER_MAP = 0x20
 
 ARK_TEX_RGBA8_UNORM = 0
 ARK_TEX_RGBA8_SRGB = 1
@@ -524,6 +525,10 @@ EXPORTS = {
     "ark_ddgi_debug_sun_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_bvh_installed_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_cover_map_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_cover_map_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_cover_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_cover_counts_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
 }
 
 _lib = None

@@ -21,8 +21,10 @@
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
 #include "ark_fmath.h"
+#include "bvh_builder.h"
 #include "ddgi_kernels.h"
 #include "scene_store.h"
+#include "sun_cover_build.h"
 
 using namespace ark;
 
@@ -211,6 +213,8 @@ struct ArkDdgiCtx : ErrorSink {
     uint32_t bvhMaxDepth = 0;
     // instrumentation
     bool counting = false;
+    bool coverCountsValid = false; // the last update was a counting one (ark_ddgi_debug_sun_cover_counts) ...
+    FrameArgs coverFrame {};       // ... and its shading arguments
     bool timing = false;
     hipEvent_t ev[6] = {};
     float lastMs[5] = {};
@@ -365,6 +369,20 @@ void deriveSceneArgs(ArkDdgiCtx* ctx)
     sc.sun_tris = sunOk ? st.sunArgs.sun_tris : nullptr;
     sc.sun_root = sunOk ? st.sunArgs.sun_root : -1;
     std::memcpy(sc.sun_frame, st.sunArgs.sun_frame, sizeof(sc.sun_frame));
+    // The sun's cover map only while it is the map of what this context traces: the front
+    // copy's geometry (valid), this sun direction bit for bit, and shadow rays long enough
+    // to reach every covering triangle (tmax = 2 zFar, shadowRayOf). Its frame is
+    // sun_frame(dir): the light-space BVH's when that one is used too.
+    const SceneStore::CoverMap& cm = st.coverMap;
+    const bool mapOk = ctx->hasSun && !(ctx->desc.flags & ARK_DDGI_FLAG_NO_SUN_COVER_MAP) && cm.valid && cm.buf.ptr &&
+                       std::memcmp(ctx->sunDir, cm.dir, sizeof(ctx->sunDir)) == 0 && 2.0f * ctx->desc.z_far >= cm.grid.wExtent;
+    sc.sun_map = mapOk ? cm.buf.as<float2>() : nullptr;
+    if (mapOk) {
+        sc.sun_grid = cm.grid;
+        sc.map_lift = cover::kTmin + cm.grid.margin;
+        sc.map_reach = cover::kTmin - cm.grid.margin;
+        std::memcpy(sc.sun_frame, cm.frame, sizeof(sc.sun_frame));
+    }
     ctx->scene = sc;
     ctx->lightCount = (ctx->hasSun ? 1u : 0u) + static_cast<uint32_t>(ctx->spotHost.size());
     ctx->bvhStats = st.bvhStats;
@@ -460,7 +478,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     ctx->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     const int shards = desc->shard_count > 0 ? desc->shard_count : 1;
     if (ctx->Rmax > ARK_DDGI_MAX_RAYS_PER_PROBE || ctx->Z % shards != 0 || desc->shard_rank < 0 || desc->shard_rank >= shards ||
-        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH)) ||
+        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_NO_SUN_COVER_MAP)) ||
         desc->build_threads < 0) {
         delete ctx;
         return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -521,7 +539,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     if ((e = ctx->hits.alloc(2 * K * R * sizeof(GpuHit))) != hipSuccess) return bad(e, "alloc hits");
     if ((e = ctx->surfels.alloc(K * R * 8)) != hipSuccess) return bad(e, "alloc surfels");
     if ((e = ctx->rayCounter.alloc(2 * kRayCounterWords * 4)) != hipSuccess) return bad(e, "alloc counter");
-    if ((e = ctx->counters.alloc(8 * sizeof(unsigned long long))) != hipSuccess) return bad(e, "alloc counters");
+    if ((e = ctx->counters.alloc(10 * sizeof(unsigned long long))) != hipSuccess) return bad(e, "alloc counters");
     if ((e = ctx->seqWords.alloc(128 * 4)) != hipSuccess) return bad(e, "alloc sequence words");
     if ((e = hipMemset(ctx->seqWords.ptr, 0, ctx->seqWords.bytes)) != hipSuccess) return bad(e, "clear sequence words");
     {
@@ -599,7 +617,7 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
     ctx->hasScene = false;
     ctx->sceneStore.reset();
     std::shared_ptr<SceneStore> st;
-    if (const int rc = buildScene(ctx, s, ctx->device, ctx->desc.build_threads, ctx->sunBvh, st)) return rc;
+    if (const int rc = buildScene(ctx, s, ctx->device, ctx->desc.build_threads, ctx->sunBvh, (ctx->desc.flags & ARK_DDGI_FLAG_NO_SUN_COVER_MAP) == 0, st)) return rc;
     return adoptScene(ctx, std::move(st));
 }
 
@@ -719,6 +737,80 @@ int ark_ddgi_debug_sun_bvh_installed_check(ArkDdgiCtx* ctx, uint64_t* out)
     ARK_HIP(hipSetDevice(ctx->device));
     ARK_HIP(hipDeviceSynchronize());
     return sceneSunBvhCheck(*ctx->sceneStore, ctx, out);
+}
+
+static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement);
+int ark_ddgi_debug_sun_cover_counts(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, true); }
+int ark_ddgi_debug_sun_cover_counts_device(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, false); }
+
+static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "cover counts before ark_ddgi_set_scene");
+    if (!ctx->coverCountsValid) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "cover counts: the last update was not a counting one (ark_ddgi_set_counting)");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    std::fill(out, out + 12, 0ull);
+    const SceneStore& st = *ctx->sceneStore;
+    const FrameArgs& f = ctx->coverFrame;
+    uint32_t dc[3] = { 0, 0, 0 };
+    ARK_HIP(hipMemcpy(dc, f.cover_counts, sizeof(dc), hipMemcpyDeviceToHost));
+    const bool inUse = ctx->scene.sun_map != nullptr;
+    for (int k = 0; k < 3; ++k) out[k] = dc[k];
+    out[3] = inUse ? 1 : 0;
+    if (inUse) {
+        out[4] = st.coverMap.grid.nx;
+        out[5] = st.coverMap.grid.ny;
+        out[6] = st.coverMap.buf.bytes;
+        out[7] = static_cast<uint64_t>(st.coverMap.buildMs * 1000.0f);
+    }
+    if (!hostRestatement || !ctx->hasSun || f.window_rays == 0) return ARK_DDGI_OK;
+    // the host restatement: the update's sun-ray origins, the map of the installed records
+    DeviceBuffer pts;
+    ARK_HIP(pts.alloc(static_cast<size_t>(f.window_rays) * sizeof(float4)));
+    hipError_t e = launch_sun_points(f, pts.as<float4>(), nullptr);
+    std::vector<float> P(static_cast<size_t>(f.window_rays) * 4u);
+    if (e == hipSuccess) e = hipMemcpy(P.data(), pts.ptr, P.size() * 4u, hipMemcpyDeviceToHost);
+    pts.release();
+    ARK_HIP(e);
+    cover::Grid grid {};
+    std::vector<float> map;
+    bool ok = false;
+    float F[9] {};
+    if (inUse) {
+        std::vector<GpuTriangle> rec(st.world.records);
+        ARK_HIP(hipMemcpy(rec.data(), st.world.tris(st.world.buf), rec.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
+        double frame[3][3];
+        sun_frame(ctx->sunDir, frame);
+        float L[3];
+        sunRayDirection(ctx->sunDir, L);
+        ok = hostBuildCoverMap(rec.data(), rec.size(), &frame[0][0], L, cover::kDefaultBudget, grid, map) && 2.0f * ctx->desc.z_far >= grid.wExtent;
+        for (int k = 0; k < 9; ++k) F[k] = static_cast<float>((&frame[0][0])[k]);
+        if (ok) {
+            if (std::memcmp(&grid, &st.coverMap.grid, sizeof(grid)) != 0) {
+                out[11] = ~0ull;
+            } else {
+                std::vector<float> dmap(map.size());
+                ARK_HIP(hipMemcpy(dmap.data(), st.coverMap.buf.ptr, dmap.size() * 4u, hipMemcpyDeviceToHost));
+                for (size_t i = 0; i < map.size(); ++i) out[11] += cover::floatBits(map[i]) != cover::floatBits(dmap[i]);
+            }
+        }
+    }
+    const float lift = cover::kTmin + grid.margin, reach = cover::kTmin - grid.margin;
+    for (uint32_t i = 0; i < f.window_rays; ++i) {
+        const float* o = &P[4u * i];
+        if (o[3] == 0.0f) continue;
+        int vd = cover::kUndecided;
+        if (ok) {
+            // sunCoords
+            const float pl[3] = { std::fma(o[0], F[0], std::fma(o[1], F[1], o[2] * F[2])), std::fma(o[0], F[3], std::fma(o[1], F[4], o[2] * F[5])),
+                                  std::fma(o[0], F[6], std::fma(o[1], F[7], o[2] * F[8])) };
+            const int64_t c = cover::cellIndex(grid, pl[0], pl[1]);
+            if (c >= 0) vd = cover::verdict(pl[2], lift, reach, map[2 * c], map[2 * c + 1]);
+        }
+        out[vd == cover::kOccluded ? 8 : vd == cover::kLit ? 9 : 10]++;
+    }
+    return ARK_DDGI_OK;
 }
 
 int ark_ddgi_set_instances(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count)
@@ -993,6 +1085,9 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
     f.ray_counter = ctx->rayCounter.as<uint32_t>() + b * kRayCounterWords;
     f.counters = ctx->counters.as<unsigned long long>();
     f.ray_steps = count ? ctx->raySteps.as<uint16_t>() : nullptr;
+    // (counters.ptr is cleared below when counting: the cover map's counts are its last three words)
+    f.cover_counts = count ? ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 3u : nullptr;
+    ctx->coverCountsValid = count;
     // shading work set (ensureShadeWork): per-ray light bits | shadow-ray list
     {
         const ShadeWorkLayout l = shadeWorkLayout(ctx);
@@ -1050,8 +1145,11 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
         if (timing) ARK_HIP(hipEventRecord(ctx->ev[1], s));
         FrameArgs fs = f;
         fs.spill = ctx->spill.as<uint32_t>(); // region 0
+        if (count) ctx->coverFrame = fs;
         if (f.light_count > 0) {
             ARK_HIP(launch_shadow_gen(ctx->scene, fs, s));
+            // (the grid stays sized by the window although the cover map leaves a few percent of
+            // the sun's rays on the list: an eighth of it measured the same, EXPERIMENTS.md)
             ARK_HIP(launch_trace_shadow(ctx->scene, fs, count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays), count, s));
         }
         if (timing) ARK_HIP(hipEventRecord(ctx->ev[5], s));

@@ -8,6 +8,7 @@
 #include "../../include/ark_ddgi.h"
 #include "ddgi_types.h"
 #include "lbvh_build.h"
+#include "sun_cover_map.h"
 
 namespace ark {
 
@@ -172,6 +173,13 @@ struct SceneArgs {
     const GpuTriangle* sun_tris;
     int32_t sun_root = -1; // (a zero-initialised SceneArgs must not mean "sun BVH at node 0")
     float sun_frame[9]; // rows u, v, w
+    // the sun's cover map (sun_cover_map.h): [ny][nx] texels (wCover, wTop) over sun_frame's
+    // (u, v), with which k_shadow_gen resolves most of the sun's shadow rays. Null: none -
+    // set by the host only while the map matches the geometry, the sun and z_far it was
+    // built and checked for (ark_ddgi.cpp deriveSceneArgs); sun_frame is then the map's.
+    const float2* sun_map;
+    cover::Grid sun_grid;
+    float map_lift, map_reach; // tmin + the margin, tmin - the margin (cover::verdict)
 
     __device__ __forceinline__ int resolveTexture(int idx) const
     {
@@ -232,6 +240,7 @@ struct FrameArgs {
     uint32_t* sun_heads;     // = ray_counter + kSunHeadWord
     uint32_t* ray_counter;
     unsigned long long* counters; // [0] nodes [1] tris [2] hits [3] shadow rays
+    uint32_t* cover_counts;  // counting updates: the sun's rays [0] resolved occluded [1] resolved lit [2] listed (k_shadow_gen); else null
     uint16_t* ray_steps;     // counting updates: traversal iterations of each probe ray (both passes) at its hit-record index
     // ray-list traversals (RT reflections): {origin, tmax}, {direction, pixel} per ray
     const float4* ray_list;
@@ -415,6 +424,8 @@ hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks
 hipError_t launch_shade(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
 hipError_t launch_trace_shadow(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
 hipError_t launch_shadow_gen(const SceneArgs& sc, const FrameArgs& f, hipStream_t s);
+// ark_ddgi_debug_sun_cover_counts: out[window_rays] = the sun shadow rays' origins of update f (w = 1; zeros: none)
+hipError_t launch_sun_points(const FrameArgs& f, float4* out, hipStream_t s);
 hipError_t launch_probe_update(const FrameArgs& f, hipStream_t s);
 hipError_t launch_probe_offsets(const FrameArgs& f, hipStream_t s);
 hipError_t launch_fill_u32(void* p, uint64_t count, uint32_t value, hipStream_t s);

@@ -11,7 +11,9 @@
 //                       kStackLds entries) and wave64 ballot refill of finished
 //                       lanes from a wave-private LDS pool of staged ray records
 //                       (raygen.rgen:35-92).
-//   3. k_shadow_gen     lit lights of every front hit -> shadow-ray list
+//   3. k_shadow_gen     lit lights of every front hit -> shadow-ray list; the sun's ray
+//                       resolved from the sun's cover map where its cell decides it
+//                       (sun_cover_map.h) and not listed then
 //      k_trace_shadow   persistent any-hit traversal of that list (opaque.rchit:35-54).
 //   4. k_shade          closest-hit shading (opaque.rchit:105-176) with the shadow
 //                       bits, environment on miss (raygen.rgen:71-80), indirect from
@@ -1959,6 +1961,33 @@ __device__ __forceinline__ uint32_t waveInclusiveScan(uint32_t x)
     return x;
 }
 
+// The hit point of ray `ray` (hit distance t as recorded: negative for a back face): the
+// origin of its shadow rays
+template<bool REFL>
+__device__ __forceinline__ V3 genHitPoint(const FrameArgs& f, uint32_t ray, float t)
+{
+    if (REFL) {
+        const float4 a = f.ray_list[2u * ray], b = f.ray_list[2u * ray + 1u];
+        const V3 origin = v3(a.x, a.y, a.z), dir = v3(b.x, b.y, b.z);
+        return origin + fabsf_(t) * dir; // rt_RayHitT of a front or back face
+    }
+    V3 origin, dir;
+    rayOf(f, ray, &origin, &dir);
+    return origin + t * dir;
+}
+
+// The sun's shadow ray from X by the cover map (sun_cover_map.h): occluded, lit, or
+// undecided - then it is listed and traced. Exact verdicts: every output stays what the
+// traversal would give.
+__device__ __forceinline__ int sunMapVerdict(const SceneArgs& sc, V3 X)
+{
+    const V3 pl = sunCoords(sc, X);
+    const int64_t c = cover::cellIndex(sc.sun_grid, pl.x, pl.y);
+    if (c < 0) return cover::kUndecided;
+    const float2 t = sc.sun_map[c];
+    return cover::verdict(pl.z, sc.map_lift, sc.map_reach, t.x, t.y);
+}
+
 // REFL: the reflection ray list (rt-reflections/raygen.rgen:122): queue position =
 // list index, and the closest hit shades back faces too, with the normal flipped
 // (opaque.rchit:121-125): N = -(shading normal), as negation commutes exactly with
@@ -1996,16 +2025,38 @@ __global__ void __launch_bounds__(256) k_shadow_gen(SceneArgs sc, FrameArgs f)
         hits[k] = rays[k] != kNoHit ? f.hits[rays[k]] : GpuHit { 0.0f, 0.0f, 0.0f, kNoHit };
         if (!REFL && hits[k].t < 0.0f) hits[k].tri = kNoHit; // backface: no shading, no shadow ray
     }
+    const bool useMap = sc.sun_map != nullptr; // (wave-uniform; set only with a sun: light 0)
+    uint32_t nOccluded = 0, nLit = 0, nListed = 0;
 #pragma unroll
     for (uint32_t k = 0; k < kGenSteps; ++k) {
         uint32_t bits = 0;
+        int vd = cover::kUndecided;
         if (hits[k].tri != kNoHit) {
             V3 N = hitShadingNormal(sc, hits[k].tri, hits[k].u, hits[k].v);
             if (REFL && hits[k].t < 0.0f) N = -N;
             bits = litLightMask(sc, N);
-            f.shadow_bits[rays[k]] = bits;
+            // the sun's ray (light 0) resolved from the cover map where its cell decides it:
+            // occluded - bit 16 set here, as k_trace_shadow would - or lit; not listed then
+            if (useMap && (bits & 1u)) {
+                vd = sunMapVerdict(sc, genHitPoint<REFL>(f, rays[k], hits[k].t));
+                f.shadow_bits[rays[k]] = bits | (vd == cover::kOccluded ? 1u << 16 : 0u);
+                if (vd != cover::kUndecided) bits &= ~1u;
+            } else {
+                f.shadow_bits[rays[k]] = bits;
+            }
         }
         bitsL[k * 256u + threadIdx.x] = bits;
+        if (f.cover_counts && useMap) {
+            nOccluded += static_cast<uint32_t>(__popcll(__ballot(vd == cover::kOccluded)));
+            nLit += static_cast<uint32_t>(__popcll(__ballot(vd == cover::kLit)));
+        }
+        if (f.cover_counts) nListed += static_cast<uint32_t>(__popcll(__ballot(sc.has_sun && (bits & 1u))));
+    }
+    // counting updates (ark_ddgi_debug_sun_cover_counts): the sun's rays resolved and listed
+    if (f.cover_counts && __lane_id() == 0u) {
+        atomicAdd(&f.cover_counts[0], nOccluded);
+        atomicAdd(&f.cover_counts[1], nLit);
+        atomicAdd(&f.cover_counts[2], nListed);
     }
     // counts packed: world-list rays in bits 0-15, sun-list rays in bits 16-31 (a
     // block has at most kGenSpan x kMaxLights = 11,264 of either, no carry)
@@ -2040,21 +2091,13 @@ __global__ void __launch_bounds__(256) k_shadow_gen(SceneArgs sc, FrameArgs f)
         if (bits == 0) continue;
         const uint32_t pos = first + k * 256u + threadIdx.x;
         uint32_t ray;
-        V3 hitPoint;
         if (REFL) {
             ray = pos;
-            const float4 a = f.ray_list[2u * pos], b = f.ray_list[2u * pos + 1u];
-            const V3 origin = v3(a.x, a.y, a.z), dir = v3(b.x, b.y, b.z);
-            const float t = fabsf_(f.hits[ray].t); // rt_RayHitT of a front or back face
-            hitPoint = origin + t * dir;
         } else {
             const uint32_t q = pos / f.R;
             ray = slotAt(f, q) * f.R + (pos - q * f.R);
-            const float t = f.hits[ray].t;
-            V3 origin, dir;
-            rayOf(f, ray, &origin, &dir);
-            hitPoint = origin + t * dir;
         }
+        const V3 hitPoint = genHitPoint<REFL>(f, ray, f.hits[ray].t);
         for (uint32_t b = bits; b; b &= b - 1) {
             const uint32_t l = static_cast<uint32_t>(__builtin_ctz(b));
             V3 ld;
@@ -2065,6 +2108,23 @@ __global__ void __launch_bounds__(256) k_shadow_gen(SceneArgs sc, FrameArgs f)
             else f.shadow_rays[sj++] = sr;
         }
     }
+}
+
+// ark_ddgi_debug_sun_cover_counts: the origin of every sun shadow ray of the update `f`
+// was (queue position order; w = 1, else zeros: no front hit, or the sun not lit there)
+__global__ void __launch_bounds__(256) k_sun_points(FrameArgs f, float4* __restrict__ out)
+{
+    const uint32_t pos = blockIdx.x * 256u + threadIdx.x;
+    if (pos >= f.window_rays) return;
+    const uint32_t q = pos / f.R;
+    const uint32_t ray = slotAt(f, q) * f.R + (pos - q * f.R);
+    const GpuHit h = f.hits[ray];
+    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (h.tri != kNoHit && !(h.t < 0.0f) && (f.shadow_bits[ray] & 1u)) {
+        const V3 X = genHitPoint<false>(f, ray, h.t);
+        o = make_float4(X.x, X.y, X.z, 1.0f);
+    }
+    out[pos] = o;
 }
 
 // Frame sequencing between a context's two streams (ark_ddgi.cpp updateImpl): the
@@ -2464,6 +2524,13 @@ hipError_t launch_shadow_gen(const SceneArgs& sc, const FrameArgs& f, hipStream_
     const uint32_t blocks = (f.window_rays + dev::kGenSpan - 1u) / dev::kGenSpan;
     if (blocks == 0) return hipSuccess;
     hipLaunchKernelGGL(dev::k_shadow_gen<false>, dim3(blocks), dim3(256), 0, s, sc, f);
+    return hipGetLastError();
+}
+
+hipError_t launch_sun_points(const FrameArgs& f, float4* out, hipStream_t s)
+{
+    if (f.window_rays == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_sun_points, dim3((f.window_rays + 255u) / 256u), dim3(256), 0, s, f, out);
     return hipGetLastError();
 }
 

@@ -15,6 +15,7 @@
 #include "ark_fmath.h"
 #include "bvh_builder.h"
 #include "lbvh_device_build.h"
+#include "sun_cover_build.h"
 
 // (every function here that can fail has an ErrorSink* err in scope)
 #define ARK_HIP(expr) ARK_HIP_TO(err, expr)
@@ -57,11 +58,20 @@ struct RebuildJob {
     double frame[9] {};     // sun_frame(dir)
     uint32_t instances = 0; // of the scene (the device build checks the records' against it)
     bool sahPass = false;   // ARK_DDGI_FLAG_GPU_REBUILD_SAH: a device build runs the SAH pass
+    // the sun's cover map of the snapshot (either kind, when the scene keeps one and the
+    // caller has a sun): built on the device after the BVH, installed with it when no refit
+    // came in since the snapshot
+    bool coverWanted = false, coverOk = false;
+    float coverDir[3] {};
+    double coverFrame[9] {};
+    cover::Grid coverGrid {};
+    DeviceBuffer coverBuf;
+    float coverMs = 0.0f;
     ~RebuildJob()
     {
         if (t.joinable()) t.join();
         bvh.release(); // not installed (an installed one was moved to the scene)
-        for (DeviceBuffer* b : { &perm, &snap }) b->release();
+        for (DeviceBuffer* b : { &perm, &snap, &coverBuf }) b->release();
         if (evSnap) (void)hipEventDestroy(evSnap);
     }
 };
@@ -549,6 +559,19 @@ void runRebuildJob(RebuildJob* job, int device, int threads, bool tryDevice)
         ok = hostBuild(job, s, threads);
         closeStream();
     }
+    if (ok && job->coverWanted) {
+        // the cover map of the same snapshot, on the device whoever built the BVH (a
+        // failure leaves the scene without a map: the sun's rays are all traced)
+        const auto tc = std::chrono::steady_clock::now();
+        float L[3];
+        sunRayDirection(job->coverDir, L);
+        if (openStream(true) == hipSuccess && hipEventSynchronize(job->evSnap) == hipSuccess &&
+            deviceBuildCoverMap(job->snap.as<GpuTriangle>(), job->snapRecords, job->coverFrame, L, cover::kDefaultBudget, s, job->coverGrid, job->coverBuf,
+                                job->coverOk) != hipSuccess)
+            job->coverOk = false;
+        closeStream();
+        job->coverMs = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tc).count();
+    }
     job->ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
     job->ok = ok;
     job->done.store(true, std::memory_order_release);
@@ -646,6 +669,30 @@ int installSunBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, Bvh8BuildResult*
     return ARK_DDGI_OK;
 }
 
+// The cover map no longer describes the front copy (a refit, an install): contexts stop
+// using it at their next refreshScene (the version moves with every such change), the
+// buffer is retired behind the launches that may still read it.
+hipError_t clearCoverMap(SceneStore& st, hipStream_t s)
+{
+    // (the version moves here too: a call that fails further on must not leave a context
+    // with the retired buffer's pointer in its kernel view)
+    if (st.coverMap.buf.ptr) ++st.version;
+    st.coverMap.valid = false;
+    return retireBuffer(st, st.coverMap.buf, s);
+}
+
+void setCoverMap(SceneStore& st, DeviceBuffer& buf, const cover::Grid& grid, const float* dir, const double* frame, float ms)
+{
+    SceneStore::CoverMap& cm = st.coverMap;
+    cm.buf = buf;
+    buf = DeviceBuffer {};
+    cm.grid = grid;
+    std::memcpy(cm.dir, dir, sizeof(cm.dir));
+    for (int k = 0; k < 9; ++k) cm.frame[k] = static_cast<float>(frame[k]);
+    cm.valid = true;
+    cm.buildMs = ms;
+}
+
 // Where an installed job's bookkeeping goes: the world's fields or the sun's
 struct InstallBook {
     bool& gpuBuilt;        // SceneStore::worldGpuBuilt / sunGpuBuilt
@@ -658,7 +705,7 @@ struct InstallBook {
 // time and snapshot noted, the new topology refitted forward when refits came in while it
 // was built (every instance re-transformed: its records follow them), the spares dropped,
 // the next traversal and refit ordered behind it, the scene's version bumped.
-int finishInstall(SceneStore& st, const SceneCall& c, const RebuildJob& job, InstallBook book, hipStream_t s)
+int finishInstall(SceneStore& st, const SceneCall& c, RebuildJob& job, InstallBook book, hipStream_t s)
 {
     ErrorSink* err = c.err;
     book.buildMs = job.ms;
@@ -668,6 +715,14 @@ int finishInstall(SceneStore& st, const SceneCall& c, const RebuildJob& job, Ins
     const uint32_t refitsSince = book.refitsSince = st.refitCount - job.refitsAt; // refits since its snapshot
     book.builtRefitVersion = job.refitsAt;
     markTopologyChanged(st);
+    // the job's cover map is the front copy's when no refit came in since its snapshot (the
+    // records it was built from are the ones installed or kept); an older one goes
+    if (job.coverOk && refitsSince == 0) {
+        ARK_HIP(clearCoverMap(st, s));
+        setCoverMap(st, job.coverBuf, job.coverGrid, job.coverDir, job.coverFrame, job.coverMs);
+    } else if (refitsSince != 0) {
+        ARK_HIP(clearCoverMap(st, s));
+    }
     if (refitsSince) {
         if (const int rc = uploadRefitInstances(err, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
         if (const int rc = enqueueRefit(err, st, s, st.world.buf, st.sun.buf, st.front)) return rc;
@@ -743,12 +798,19 @@ int sunCollect(SceneStore& st, const SceneCall& c, hipStream_t s, bool mayEnqueu
 // A new job's shared part: the scene's version and refit count, the snapshot on `s`, the
 // thread - with half the host threads: the other half stays with the frames being
 // enqueued meanwhile.
-int launchJob(SceneStore& st, ErrorSink* err, RebuildJob& job, hipStream_t s, bool gpu)
+int launchJob(SceneStore& st, ErrorSink* err, RebuildJob& job, hipStream_t s, bool gpu, bool hasSun, const float* sunDir)
 {
     job.version = st.version;
     job.refitsAt = st.refitCount;
     job.snapRecords = st.world.records;
     ARK_HIP(snapshotRecords(st, job.snap, job.evSnap, s));
+    job.coverWanted = st.coverWanted && hasSun;
+    if (job.coverWanted) {
+        std::memcpy(job.coverDir, sunDir, sizeof(job.coverDir));
+        double frame[3][3];
+        sun_frame(sunDir, frame);
+        std::memcpy(job.coverFrame, frame, sizeof(job.coverFrame));
+    }
     job.t = std::thread(runRebuildJob, &job, st.device, std::max(1, st.buildThreads / 2), gpu);
     return ARK_DDGI_OK;
 }
@@ -763,7 +825,7 @@ int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     std::memcpy(job->frame, frame, sizeof(job->frame));
     job->instances = static_cast<uint32_t>(st.instHost.size());
     job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
-    if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
+    if (const int rc = launchJob(st, c.err, *job, s, gpu, c.hasSun, c.sunDir)) return rc;
     st.sunJob = std::move(job);
     st.lastBackground = kBackgroundSun;
     return ARK_DDGI_OK;
@@ -826,7 +888,7 @@ int worldStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     job->kind = RebuildJob::World;
     job->classOf = instanceClasses(st);
     job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
-    if (const int rc = launchJob(st, c.err, *job, s, gpu)) return rc;
+    if (const int rc = launchJob(st, c.err, *job, s, gpu, c.hasSun, c.sunDir)) return rc;
     st.worldJob = std::move(job);
     st.lastBackground = kBackgroundWorld;
     st.refitsSinceBuild = 0;
@@ -1087,12 +1149,13 @@ SceneStore::~SceneStore()
     if (refitStream) (void)hipStreamDestroy(refitStream);
     world.release();
     sun.release();
+    coverMap.buf.release();
     for (DeviceBuffer* b : { &triNormals, &indices, &vertices, &positions, &meshes, &materials, &instances, &texInfos, &texels, &refitInst, &spare[0].world,
                              &spare[0].sun, &spare[0].instances, &spare[1].world, &spare[1].sun, &spare[1].instances })
         b->release();
 }
 
-int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThreads, int sunBvh, std::shared_ptr<SceneStore>& out)
+int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThreads, int sunBvh, bool coverMap, std::shared_ptr<SceneStore>& out)
 {
     auto st = std::make_shared<SceneStore>();
     st->device = device;
@@ -1224,6 +1287,21 @@ int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThrea
     st->spotsScene = std::move(gspots);
     st->sunWanted = st->sun.nodeCount > 0;
     st->buildThreads = opt.threads;
+    // the sun's cover map, on the device from the records just uploaded (no map: a scene
+    // it does not take, sun_cover_map.h; every sun ray is then traced)
+    st->coverWanted = coverMap;
+    if (coverMap && s->has_directional_light && st->world.records > 0) {
+        const auto tc = std::chrono::steady_clock::now();
+        double frame[3][3];
+        sun_frame(s->directional_light.world_space_direction, frame);
+        float L[3];
+        sunRayDirection(s->directional_light.world_space_direction, L);
+        cover::Grid grid {};
+        DeviceBuffer buf;
+        bool ok = false;
+        ARK_HIP(deviceBuildCoverMap(st->world.tris(st->world.buf), st->world.records, &frame[0][0], L, cover::kDefaultBudget, nullptr, grid, buf, ok));
+        if (ok) setCoverMap(*st, buf, grid, s->directional_light.world_space_direction, &frame[0][0], std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - tc).count());
+    }
     // the sun's traversal pushes onto the same spill area (its depth counts)
     st->bvhMaxDepth = std::max(st->world.depth, st->sun.depth);
     const auto t1 = std::chrono::steady_clock::now();
@@ -1339,6 +1417,8 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
             if (!std::isfinite(v)) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "set_instances: instance %u: non-finite transform", i);
     }
     ARK_HIP(sharedBegin(c));
+    // the cover map is of the geometry before this refit
+    ARK_HIP(clearCoverMap(st, s));
     int rc;
     if (st.world.levelOffsets.empty() && (rc = prepareRefit(err, st)) != 0) return rc;
     // Everything the calling context enqueued so far ends on `s` (the precondition): the

@@ -83,6 +83,22 @@ struct SceneStore {
     SceneArgs args {};    // the world BVHs, pools, materials, textures (lights: per context, deriveSceneArgs)
     SceneArgs sunArgs {}; // sun_nodes / sun_tris / sun_root / sun_frame of the light-space BVH (sun_root -1: none)
     float sunDirBuilt[3] { 0, 0, 0 }; // the sun direction the light-space BVH was built for
+    // The sun's cover map (sun_cover_map.h), a sibling product of the sun BVH whichever BVH
+    // the sun's rays traverse: built on the device from the world records at set_scene and
+    // by every background rebuild job (from its snapshot), for the sun direction `dir`.
+    // A stale map is wrong, not slow: `valid` is cleared and the buffer retired the moment
+    // the geometry it was built from changes (a refit, an install whose job saw refits come
+    // in); a context uses it only while valid, for exactly this direction, with a tmax the
+    // grid was checked for (ark_ddgi.cpp deriveSceneArgs).
+    struct CoverMap {
+        DeviceBuffer buf;
+        cover::Grid grid {};
+        float dir[3] { 0, 0, 0 };
+        float frame[9] {}; // sun_frame(dir) in fp32: sunCoords' rows
+        bool valid = false;
+        float buildMs = 0.0f;
+    } coverMap;
+    bool coverWanted = false; // set_scene: not disabled by ARK_DDGI_FLAG_NO_SUN_COVER_MAP
     // the scene's lights as set_scene got them: a context's lights until ark_ddgi_set_lights
     int32_t hasSunScene = 0;
     ArkDirectionalLight sunScene {};
@@ -195,7 +211,8 @@ struct SceneCall {
 // ark_ddgi_set_scene: the device scene of `s` built on `device` (the world BVHs, the
 // light-space sun BVH when it pays or sunBvh forces it: 0 never, 1 always, -1 by cost).
 // buildThreads: ArkDdgiDesc.build_threads. Synchronous; the device is idle.
-int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThreads, int sunBvh, std::shared_ptr<SceneStore>& out);
+// coverMap: the sun's cover map too, when the scene has a sun.
+int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThreads, int sunBvh, bool coverMap, std::shared_ptr<SceneStore>& out);
 
 // Everything an operation on `s` does to the scene first: buffers retired by earlier
 // installs freed, finished rebuilds installed on `s`, new ones started (scene_rebuild_policy.h).

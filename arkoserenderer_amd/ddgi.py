@@ -82,6 +82,9 @@ class DDGIConfig:
     # gpu_rebuild_sun enable rebuild every subtree of at most 256 triangles by a sweep SAH
     # before the 8-wide collapse; alone it does nothing
     gpu_rebuild_sah: bool = False
+    # the sun's cover map (on by default; False: ARK_DDGI_FLAG_NO_SUN_COVER_MAP, every sun
+    # shadow ray is traced - same results)
+    sun_cover_map: bool = True
     build_threads: int = 0
 
 
@@ -122,6 +125,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD if config.gpu_rebuild else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SUN if config.gpu_rebuild_sun else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SAH if config.gpu_rebuild_sah else 0
+    d.flags |= 0 if config.sun_cover_map else abi.ARK_DDGI_FLAG_NO_SUN_COVER_MAP
     d.build_threads = int(config.build_threads)
     return d
 
@@ -379,6 +383,15 @@ class DDGIContext:
         if rc < 0:
             self.check(rc, "ark_ddgi_debug_world_bvh_check")
         return dict(zip(_BVH_CHECK_KEYS, (int(v) for v in out)))
+
+    def sun_cover_counts(self, host_restatement: bool = True) -> dict:
+        """ark_ddgi_debug_sun_cover_counts after a counting update: the sun's rays resolved
+        by the cover map and listed, on the device and (host_restatement) by the host."""
+        out = (C.c_uint64 * 12)()
+        fn = self.lib.ark_ddgi_debug_sun_cover_counts if host_restatement else self.lib.ark_ddgi_debug_sun_cover_counts_device
+        self.check(fn(self.h, out), "ark_ddgi_debug_sun_cover_counts")
+        keys = ("occluded", "lit", "listed", "in_use", "nx", "ny", "bytes", "build_us", "host_occluded", "host_lit", "host_listed", "map_diff")
+        return dict(zip(keys, (int(v) for v in out)))
 
     def sun_bvh_installed_check(self) -> dict:
         """ark_ddgi_debug_sun_bvh_installed_check: the light-space sun BVH8 the kernels read

@@ -183,12 +183,17 @@ typedef struct ArkDdgiDesc {
  * of at most 256 triangles is rebuilt by a full sweep SAH with its triangles reordered, and
  * the collapse decides by the boxes that pass leaves. When a device build starts, what
  * becomes of it and the host rebuild after the motion stops are unchanged; results are the
- * same. */
+ * same. NO_SUN_COVER_MAP: by default a scene with a sun keeps the sun's cover map, a
+ * conservative light-space depth map built on the device at set_scene and by the background
+ * rebuilds, with which most of the sun's shadow rays are resolved exactly - occluded or lit -
+ * before they are listed for traversal; it is dropped the moment the geometry or the sun it
+ * was built for changes. The flag disables it (A/B runs, tests); results are the same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
 #define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
 #define ARK_DDGI_FLAG_GPU_REBUILD_SUN 0x8u
 #define ARK_DDGI_FLAG_GPU_REBUILD_SAH 0x10u
+#define ARK_DDGI_FLAG_NO_SUN_COVER_MAP 0x20u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {

@@ -197,6 +197,34 @@ int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const 
  * no light-space BVH is installed (out all zero). Synchronous. */
 int ark_ddgi_debug_sun_bvh_installed_check(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* The sun's cover map (csrc/sun_cover_map.h) built on the host (no GPU) from n triangles
+ * (9 floats each) for sun_dir, and its verdicts for n_rays origins (3 floats each) against a
+ * brute-force any-hit over every triangle with the kernels' fp32 Moller-Trumbore
+ * ([0.025, tmax]). budget_bytes: the map's byte budget (0: the default, 64 MB). out[13] =
+ * {rays, occluded (brute force), resolved occluded, resolved lit, wrong verdicts, cells in u,
+ * cells in v, map valid (0: no map for this scene or tmax - every ray undecided), cells with a
+ * cover, undecided, and the fp32 bits of the grid's lower corner u0, v0 and of its cells per
+ * unit length}. A wrong verdict: resolved occluded but not hit, or resolved lit but hit. */
+int ark_ddgi_debug_cover_map_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                   uint64_t budget_bytes, uint64_t* out);
+
+/* The device build of the same map against the host restatement. out[6] = {differing words
+ * (all ones: the grids differ), cells in u, cells in v, host built a map, device built a
+ * map, device build microseconds}. Synchronous. */
+int ark_ddgi_debug_cover_map_device(int device, const float* triangles, uint64_t n, const float* sun_dir, uint64_t budget_bytes, uint64_t* out);
+
+/* The sun's cover map as the context's last update used it. The update must have been a
+ * counting one (ark_ddgi_set_counting). out[12] = {sun rays resolved occluded, resolved lit,
+ * listed (k_shadow_gen's counts), map in use (0: none valid for this context - then the
+ * first two are 0), cells in u, cells in v, map bytes, map build microseconds, and the host
+ * restatement for the same rays - the update's hit points read back, the map rebuilt on the
+ * host from the installed records: resolved occluded, resolved lit, listed, words in which
+ * the installed map differs from the host's}. With no valid map the last four are computed
+ * for no map (0, 0, listed, 0). Synchronous. */
+int ark_ddgi_debug_sun_cover_counts(struct ArkDdgiCtx* ctx, uint64_t* out);
+/* The same without the host restatement (a large scene's takes long): out[8..11] stay 0. */
+int ark_ddgi_debug_sun_cover_counts_device(struct ArkDdgiCtx* ctx, uint64_t* out);
+
 #ifdef __cplusplus
 }
 #endif
