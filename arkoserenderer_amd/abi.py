@@ -56,6 +56,7 @@ ARK_DDGI_FLAG_GPU_REBUILD = 0x4
 ARK_DDGI_FLAG_GPU_REBUILD_SUN = 0x8
 ARK_DDGI_FLAG_GPU_REBUILD_SAH = 0x10
 ARK_DDGI_FLAG_NO_SUN_COVER_MAP = 0x20
+ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE = 0x40
 
 ARK_TEX_RGBA8_UNORM = 0
 ARK_TEX_RGBA8_SRGB = 1
@@ -529,6 +530,8 @@ EXPORTS = {
     "ark_ddgi_debug_cover_map_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_cover_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_cover_counts_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_shade_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_set_sun_only_small_windows": (C.c_int, [C.c_void_p, C.c_int]),
 }
 
 _lib = None

@@ -24,6 +24,7 @@
 #include "bvh_builder.h"
 #include "ddgi_kernels.h"
 #include "scene_store.h"
+#include "shade_schedule.h"
 #include "sun_cover_build.h"
 
 using namespace ark;
@@ -213,6 +214,9 @@ struct ArkDdgiCtx : ErrorSink {
     uint32_t bvhMaxDepth = 0;
     // instrumentation
     bool counting = false;
+    bool lastSunOnly = false;          // the last update ran the sun-only shading schedule (shade_schedule.h) ...
+    const uint32_t* lastDeferredCount = nullptr; // ... and this device word holds the rays it deferred
+    bool sunOnlySmallWindows = false;  // ark_ddgi_debug_set_sun_only_small_windows
     bool coverCountsValid = false; // the last update was a counting one (ark_ddgi_debug_sun_cover_counts) ...
     FrameArgs coverFrame {};       // ... and its shading arguments
     bool timing = false;
@@ -478,7 +482,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     ctx->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     const int shards = desc->shard_count > 0 ? desc->shard_count : 1;
     if (ctx->Rmax > ARK_DDGI_MAX_RAYS_PER_PROBE || ctx->Z % shards != 0 || desc->shard_rank < 0 || desc->shard_rank >= shards ||
-        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_NO_SUN_COVER_MAP)) ||
+        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_NO_SUN_COVER_MAP | ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE)) ||
         desc->build_threads < 0) {
         delete ctx;
         return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -810,6 +814,27 @@ static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement)
         }
         out[vd == cover::kOccluded ? 8 : vd == cover::kLit ? 9 : 10]++;
     }
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_set_sun_only_small_windows(ArkDdgiCtx* ctx, int enabled)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    ctx->sunOnlySmallWindows = enabled != 0;
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_shade_schedule(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    out[0] = out[1] = 0;
+    if (!ctx->lastSunOnly) return ARK_DDGI_OK;
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    uint32_t n = 0;
+    ARK_HIP(hipMemcpy(&n, ctx->lastDeferredCount, sizeof(n), hipMemcpyDeviceToHost));
+    out[0] = 1;
+    out[1] = n;
     return ARK_DDGI_OK;
 }
 
@@ -1146,7 +1171,14 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
         FrameArgs fs = f;
         fs.spill = ctx->spill.as<uint32_t>(); // region 0
         if (count) ctx->coverFrame = fs;
-        if (f.light_count > 0) {
+        // the sun alone, with its cover map: shading resolves the sun's rays itself, and
+        // only what the map leaves undecided is listed, traced and shaded in a second pass
+        // (not beside a half-occupancy traversal: shade_schedule.h)
+        const bool sunOnly = shadeScheduleOf({ f.light_count, ctx->scene.has_sun != 0, ctx->scene.sun_map != nullptr, ctx->desc.flags, half,
+                                               ctx->sunOnlySmallWindows }) == ShadeSchedule::SunOnly;
+        ctx->lastSunOnly = sunOnly;
+        ctx->lastDeferredCount = fs.sun_rays ? fs.sun_count : fs.shadow_count;
+        if (f.light_count > 0 && !sunOnly) {
             ARK_HIP(launch_shadow_gen(ctx->scene, fs, s));
             // (the grid stays sized by the window although the cover map leaves a few percent of
             // the sun's rays on the list: an eighth of it measured the same, EXPERIMENTS.md)
@@ -1157,8 +1189,13 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
         // rank it waits here for the previous exchange (the traversal above did not)
         if (shadeWaitEvent) ARK_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(shadeWaitEvent), 0));
         if (shadeWaitSeq) ARK_HIP(launch_seq_wait(seqTrace + 96, shadeWaitSeq, seqTimedOut, ctx->hostAbortDev, ctx->seqTimeoutTicks, s));
-        ARK_HIP(launch_shade(ctx->scene, fs, ctx->shadeBlocks, count, s));
+        ARK_HIP(launch_shade(ctx->scene, fs, ctx->shadeBlocks, count, s, sunOnly));
         if (timing) ARK_HIP(hipEventRecord(ctx->ev[2], s));
+        if (sunOnly) {
+            // (timings: "shade" is pass 1, "shadow" the traversal and the deferred pass)
+            ARK_HIP(launch_trace_shadow(ctx->scene, fs, count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays), count, s));
+            ARK_HIP(launch_shade_deferred(ctx->scene, fs, s));
+        }
         if (timing) ARK_HIP(hipEventRecord(ctx->ev[4], s));
         traceZone.end();
         // probeUpdateOffset (serial frames), probeUpdateIrradiance/Visibility + border
@@ -1167,6 +1204,7 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
         if (!pipe) ARK_HIP(launch_probe_offsets(fs, s));
         ARK_HIP(launch_probe_update(fs, s));
     } else {
+        ctx->lastSunOnly = false;
         if (pipe) ARK_HIP(tracedSync(ctx, seq, seqN, ts, s));
         if (shadeWaitEvent) ARK_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(shadeWaitEvent), 0));
         if (shadeWaitSeq) ARK_HIP(launch_seq_wait(seqTrace + 96, shadeWaitSeq, seqTimedOut, ctx->hostAbortDev, ctx->seqTimeoutTicks, s));

@@ -421,7 +421,10 @@ hipError_t launch_rt_reflections(const SceneArgs& sc, const FrameArgs& f, const 
                                  hipStream_t s);
 hipError_t launch_probe_debug(const FrameArgs& f, const ArkProbeDebugDesc& d, hipStream_t s);
 hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
-hipError_t launch_shade(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
+// sunFused: the sun-only schedule (shade_schedule.h) - no launch_shadow_gen before it;
+// launch_trace_shadow and launch_shade_deferred after it
+hipError_t launch_shade(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s, bool sunFused = false);
+hipError_t launch_shade_deferred(const SceneArgs& sc, const FrameArgs& f, hipStream_t s);
 hipError_t launch_trace_shadow(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
 hipError_t launch_shadow_gen(const SceneArgs& sc, const FrameArgs& f, hipStream_t s);
 // ark_ddgi_debug_sun_cover_counts: out[window_rays] = the sun shadow rays' origins of update f (w = 1; zeros: none)

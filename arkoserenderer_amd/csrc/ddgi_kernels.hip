@@ -19,7 +19,12 @@
 //                       bits, environment on miss (raygen.rgen:71-80), indirect from
 //                       the previous frame's atlases (probeSampling.glsl:64-163)
 //                       -> fp16 surfels.
-//   5. k_probe_update   (ddgi_update.hip) irradiance + visibility blend,
+//      The sun-only schedule (shade_schedule.h: the sun is the only light and its cover
+//      map is in use) has no k_shadow_gen: k_shade resolves the sun's ray itself and
+//      shades; the rays the map leaves undecided it lists, k_trace_shadow traces them,
+//      and a deferred k_shade instance shades those (3'. k_shade, k_trace_shadow,
+//      4'. k_shade<kShadeDeferred>).
+//   5. k_probe_update  (ddgi_update.hip) irradiance + visibility blend,
 //                       tile border copy, probe offsets.
 // No MFMA: the path is traversal/gather, latency/issue bound.
 
@@ -1463,7 +1468,8 @@ __device__ V3 sampleDDGI(const FrameArgs& f, V3 P, V3 N, V3 Vw)
 // k_shade takes chunks of kShadeChunk consecutive probe rays. Misses and backface
 // hits are finished in a classify pass; front hits are compacted into an LDS list
 // and shaded densely (material, textures, BRDF per lit light, DDGI indirect). The
-// shadow rays were traced before (k_shadow_gen + k_trace_shadow), and their per-ray light bits say
+// shadow rays were traced before (k_shadow_gen + k_trace_shadow; the sun-only schedule's
+// instances below resolve or defer the sun's ray themselves), and their per-ray light bits say
 // which lit lights are occluded: base (+ T or Z per lit light, in light order) +
 // indirect, the IEEE sequence of the single-pass closest-hit shader
 // (opaque.rchit:105-176 with traceShadowRay's shadowFactor 1 or 0).
@@ -1485,23 +1491,205 @@ __device__ __forceinline__ void rayOf(const FrameArgs& f, uint32_t ray, V3* orig
     *dir = rotate(v3(fb.x, fb.y, fb.z), v3(ps.axis[0], ps.axis[1], ps.axis[2]), ps.angle_sin, ps.angle_cos);
 }
 
-template<bool COUNT, int WPE>
+// The hit point of ray `ray` (hit distance t as recorded: negative for a back face): the
+// origin of its shadow rays
+template<bool REFL>
+__device__ __forceinline__ V3 genHitPoint(const FrameArgs& f, uint32_t ray, float t)
+{
+    if (REFL) {
+        const float4 a = f.ray_list[2u * ray], b = f.ray_list[2u * ray + 1u];
+        const V3 origin = v3(a.x, a.y, a.z), dir = v3(b.x, b.y, b.z);
+        return origin + fabsf_(t) * dir; // rt_RayHitT of a front or back face
+    }
+    V3 origin, dir;
+    rayOf(f, ray, &origin, &dir);
+    return origin + t * dir;
+}
+
+// The sun's shadow ray from X by the cover map (sun_cover_map.h): occluded, lit, or
+// undecided - then it is listed and traced. Exact verdicts: every output stays what the
+// traversal would give.
+__device__ __forceinline__ int sunMapVerdict(const SceneArgs& sc, V3 X)
+{
+    const V3 pl = sunCoords(sc, X);
+    const int64_t c = cover::cellIndex(sc.sun_grid, pl.x, pl.y);
+    if (c < 0) return cover::kUndecided;
+    const float2 t = sc.sun_map[c];
+    return cover::verdict(pl.z, sc.map_lift, sc.map_reach, t.x, t.y);
+}
+
+// A front hit's surface (opaque.rchit:105-131) and its lit lights: what the light loop and
+// the indirect term of shadeFront need.
+struct FrontSurface {
+    V3 origin, dir, N, baseColor, base;
+    float T, metallic, roughness, clearcoat, ccRough;
+    uint32_t need; // lit lights (LdotN > 0), bit l: the sun first, then the spots in order
+};
+
+// SPOTS = false: the scene has no spot light (the sun-only schedule), their loops are left out.
+template<bool SPOTS>
+__device__ __forceinline__ void frontSurface(const SceneArgs& sc, const FrameArgs& f, const GpuSpotLight* spotsL, uint32_t ray, FrontSurface& sf)
+{
+    const GpuHit hit = f.hits[ray];
+    rayOf(f, ray, &sf.origin, &sf.dir);
+    sf.T = hit.t;
+    // the triangle's shading record: vertex normals, instance, UVs
+    const float4* rec = sc.tri_normals + 4u * static_cast<size_t>(hit.tri);
+    const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
+    const GpuInstance gi = sc.instances[__float_as_uint(rc.y)];
+    const ArkShaderMaterial& mat = sc.materials[gi.material_index];
+    const float bx = 1.0f - hit.u - hit.v, by = hit.u, bz = hit.v;
+    // opaque.rchit:118-131 (front face: no flip)
+    V3 N = normalize(v3(ra.x, ra.y, ra.z) * bx + v3(ra.w, rb.x, rb.y) * by + v3(rb.z, rb.w, rc.x) * bz);
+    const float* M = gi.normal_matrix;
+    V3 Nw = { M[0] * N.x + M[1] * N.y + M[2] * N.z, M[4] * N.x + M[5] * N.y + M[6] * N.z, M[8] * N.x + M[9] * N.y + M[10] * N.z };
+    sf.N = N = normalize(Nw);
+    const float uvx = rc.z * bx + rd.x * by + rd.z * bz;
+    const float uvy = rc.w * bx + rd.y * by + rd.w * bz;
+    float4 c = sc.sample(mat.base_color, uvx, uvy);
+    sf.baseColor = v3(c.x, c.y, c.z) * v3(mat.color_tint[0], mat.color_tint[1], mat.color_tint[2]);
+    c = sc.sample(mat.emissive, uvx, uvy);
+    const V3 emissive = v3(c.x, c.y, c.z) * v3(mat.emissive_factor[0], mat.emissive_factor[1], mat.emissive_factor[2]);
+    c = sc.sample(mat.metallic_roughness, uvx, uvy);
+    sf.metallic = c.z * mat.metallic_factor;
+    sf.roughness = c.y * mat.roughness_factor;
+    sf.clearcoat = mat.clearcoat;
+    sf.ccRough = mat.clearcoat_roughness;
+    const V3 ambient = f.ambient_amount * sf.baseColor;
+    sf.base = emissive + ambient;
+    // lit lights (LdotN > 0): one shadow ray each (opaque.rchit:56-103)
+    uint32_t need = 0, l = 0;
+    if (sc.has_sun) {
+        const V3 Ld = -normalize(v3(sc.sun_dir[0], sc.sun_dir[1], sc.sun_dir[2]));
+        if (dot(Ld, N) > 0.0f) need |= 1u;
+        l++;
+    }
+    for (int li = 0; SPOTS && li < sc.spot_count; ++li, ++l) {
+        const V3 Ld = -normalize(v3(spotsL[li].direction[0], spotsL[li].direction[1], spotsL[li].direction[2]));
+        if (dot(Ld, N) > 0.0f) need |= 1u << l;
+    }
+    sf.need = need;
+}
+
+// The lit lights' terms (occ: bit l set - light l is occluded), the indirect term and the
+// surfel of a front hit: phase B of k_shade and its deferred pass run this one sequence.
+template<bool SPOTS>
+__device__ __forceinline__ void shadeFront(const SceneArgs& sc, const FrameArgs& f, const GpuSpotLight* spotsL, uint32_t ray, const FrontSurface& sf, uint32_t occ)
+{
+    const V3 origin = sf.origin, dir = sf.dir, N = sf.N, baseColor = sf.baseColor;
+    const float T = sf.T, metallic = sf.metallic, roughness = sf.roughness, clearcoat = sf.clearcoat, ccRough = sf.ccRough;
+    const uint32_t need = sf.need;
+    V3 color = sf.base;
+    const V3 V = -dir;
+    const V3 hitPoint = origin + T * dir;
+    uint32_t l = 0;
+    if (sc.has_sun) { // opaque.rchit:56-73
+        if (need & 1u) {
+            const V3 Ld = -normalize(v3(sc.sun_dir[0], sc.sun_dir[1], sc.sun_dir[2]));
+            const float LdotN = dot(Ld, N);
+            const V3 brdf = evaluateDefaultBRDF(Ld, V, N, baseColor, roughness, metallic, clearcoat, ccRough);
+            const V3 lc = v3(sc.sun_color[0], sc.sun_color[1], sc.sun_color[2]);
+            const V3 tT = brdf * LdotN * (lc * 1.0f);
+            const V3 tZ = brdf * LdotN * (lc * 0.0f);
+            color = color + ((occ >> l) & 1u ? tZ : tT);
+        }
+        l++;
+    }
+    for (int li = 0; SPOTS && li < sc.spot_count; ++li, ++l) { // opaque.rchit:75-103
+        if (!((need >> l) & 1u)) continue;
+        const GpuSpotLight sl = spotsL[li];
+        V3 sdir = v3(sl.direction[0], sl.direction[1], sl.direction[2]);
+        V3 Ld = -normalize(sdir);
+        float LdotN = dot(Ld, N);
+        {
+                V3 toLight = v3(sl.position[0], sl.position[1], sl.position[2]) - hitPoint;
+                float distanceToLight = length(toLight);
+                V3 normalizedToLight = toLight / distanceToLight;
+                float distanceAttenuation = 1.0f / square(distanceToLight);
+                // evaluateIESLookupTable (lighting.glsl:20-39)
+                V3 lrd = -normalizedToLight;
+                float iesValue = 0.0f;
+                float angleV = dot(lrd, sdir);
+                if (!(angleV <= 0.0f)) {
+                    float hx = dot(lrd, v3(sl.right[0], sl.right[1], sl.right[2]));
+                    float hy = dot(lrd, v3(sl.up[0], sl.up[1], sl.up[2]));
+                    float angleH = atan2f_(hy, hx) + kPi;
+                    float lx = acosf_(angleV) / (2.0f * sl.position[3]);
+                    float ly = clampf(angleH / kTwoPi, 0.0f, 1.0f);
+                    iesValue = sc.sample(sl.ies_texture, lx, ly).x;
+                }
+                V3 brdf = evaluateDefaultBRDF(Ld, V, N, baseColor, roughness, metallic, clearcoat, ccRough);
+                V3 lc = v3(sl.color[0], sl.color[1], sl.color[2]);
+                V3 tT = brdf * LdotN * (lc * 1.0f * distanceAttenuation * iesValue);
+                V3 tZ = brdf * LdotN * (lc * 0.0f * distanceAttenuation * iesValue);
+            color = color + ((occ >> l) & 1u ? tZ : tT);
+        }
+    }
+    // raygen.rgen:125-127 + evaluateIndirectLightFromPreviousFrame (:94-106)
+    const V3 Vi = -dir;
+    const V3 F0 = mix3(splat(kDielectricReflectance), baseColor, metallic);
+    const V3 F = F_Schlick3(fmaxf_(0.0f, dot(Vi, N)), F0);
+    const V3 irradiance = sampleDDGI<kGatherBatch>(f, hitPoint, N, Vi);
+    const V3 indirect = splat(1.0f - metallic) * (splat(1.0f) - F) * irradiance;
+    const V3 bi = baseColor * indirect;
+    storeSurfel(f, ray, color + bi, T);
+}
+
+// MODE, the schedule (shade_schedule.h):
+//  kShadeListed    every lit light's shadow ray was listed by k_shadow_gen and traced before
+//                  this launch; shadow_bits holds the occluded bits.
+//  kShadeSunFused  pass 1 of the sun-only schedule (one light, the sun, with its cover map;
+//                  no k_shadow_gen): phase B resolves the sun's ray of a front hit itself,
+//                  with the generator's functions and operand order (genHitPoint<false>:
+//                  origin + T * dir, sunMapVerdict), so the verdict is the same bits.
+//                  Occluded or lit: shaded at once, shadow_bits untouched. Undecided: the
+//                  surfel is left to the deferred pass - shadow_bits[ray] = the lit mask and
+//                  the ray joins an LDS list, which the block appends to the shadow-ray list
+//                  (the sun's own with a light-space BVH) after one global atomic per chunk
+//                  (a per-wave atomic on that counter serialises at L2, see k_shadow_gen).
+//                  List order is free: any-hit bits are ORed, surfels are independent.
+//                  The cover-map gather sits late, after the surface's texture fetches: issued
+//                  beside them it held the light-space coordinates and the texel across the
+//                  fetches, and the kernel has no register to spare at 4 waves per SIMD.
+//  kShadeDeferred  pass 2, after k_trace_shadow: a fixed grid strides over that list (count
+//                  read here) and shades each owner ray with its traced bit.
+// The counting variant of pass 1 keeps k_shadow_gen's cover_counts and writes shadow_bits of
+// every front hit as the generator did (k_sun_points reads them back).
+constexpr int kShadeListed = 0, kShadeSunFused = 1, kShadeDeferred = 2;
+
+template<bool COUNT, int WPE, int MODE = kShadeListed>
 __global__ void __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_eu(WPE))) k_shade(SceneArgs sc, FrameArgs f)
 {
     if (frameAborted(f.abort_word)) return;
     // compacted front hits (ray index) from the start, misses from the end
     __shared__ uint32_t listA[kShadeChunk];
-    __shared__ uint32_t counts[4];          // [0] front hits, [1] misses, [2,3] chunk
-    uint32_t cFront = 0;
+    // kShadeSunFused: the chunk's undecided front hits (ray index)
+    __shared__ uint32_t listD[MODE == kShadeSunFused ? kShadeChunk : 1];
+    __shared__ uint32_t counts[6];          // [0] front hits, [1] misses, [2,3] chunk, [4] deferred, [5] their list base
+    uint32_t cFront = 0, cOccluded = 0, cLit = 0, cListed = 0;
+    (void)listD; (void)cOccluded; (void)cLit; (void)cListed;
     // the spot lights, read once per workgroup: per front hit and lit spot they were a
     // dependent 96-B read ahead of the IES lookup (C5: k_shade 2.06 -> 1.97 ms, +1.2 %;
     // profiles/r04_s_shade_spots_lds.log)
-    __shared__ GpuSpotLight spotsL[kMaxLights - 1];
-    {
+    constexpr bool kSpots = MODE == kShadeListed; // (the sun-only schedule: the sun is the only light)
+    __shared__ GpuSpotLight spotsL[kSpots ? kMaxLights - 1 : 1];
+    if constexpr (kSpots) {
         const uint32_t words = static_cast<uint32_t>(sc.spot_count) * static_cast<uint32_t>(sizeof(GpuSpotLight) / 4u);
         for (uint32_t i = threadIdx.x; i < words; i += kShadeBlock)
             reinterpret_cast<uint32_t*>(spotsL)[i] = reinterpret_cast<const uint32_t*>(sc.spots)[i];
         __syncthreads();
+    }
+
+    if constexpr (MODE == kShadeDeferred) {
+        const uint32_t total = f.sun_rays ? *f.sun_count : *f.shadow_count;
+        const ShadowRay* const list = f.sun_rays ? f.sun_rays : f.shadow_rays;
+        for (uint32_t i = blockIdx.x * kShadeBlock + threadIdx.x; i < total; i += gridDim.x * kShadeBlock) {
+            const uint32_t ray = __float_as_uint(list[i].dir_owner.w) >> 4;
+            FrontSurface sf;
+            frontSurface<kSpots>(sc, f, spotsL, ray, sf);
+            shadeFront<kSpots>(sc, f, spotsL, ray, sf, f.shadow_bits[ray] >> 16);
+        }
+        return;
     }
 
     // chunks come from the second set of per-XCD partition heads (see grabRays)
@@ -1516,6 +1704,7 @@ __global__ void __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_e
             counts[1] = 0;
             counts[2] = b;
             counts[3] = e;
+            if (MODE == kShadeSunFused) counts[4] = 0;
         }
         __syncthreads();
         const uint32_t chunk = counts[2], chunkEnd = counts[3];
@@ -1547,107 +1736,34 @@ __global__ void __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_e
             const uint32_t kk = k0 + threadIdx.x;
             const bool valid = kk < nA;
             const uint32_t ray = valid ? listA[kk] : 0u;
-            // surface (opaque.rchit:105-131)
-            V3 origin = splat(0.0f), dir = splat(0.0f), N = splat(0.0f), baseColor = splat(0.0f), base = splat(0.0f);
-            float T = 0.0f, metallic = 0.0f, roughness = 0.0f, clearcoat = 0.0f, ccRough = 0.0f;
-            uint32_t need = 0;
+            FrontSurface sf { splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), splat(0.0f), 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0u };
             if (valid) {
                 if (COUNT) cFront++;
-                const GpuHit hit = f.hits[ray];
-                rayOf(f, ray, &origin, &dir);
-                T = hit.t;
-                // the triangle's shading record: vertex normals, instance, UVs
-                const float4* rec = sc.tri_normals + 4u * static_cast<size_t>(hit.tri);
-                const float4 ra = rec[0], rb = rec[1], rc = rec[2], rd = rec[3];
-                const GpuInstance gi = sc.instances[__float_as_uint(rc.y)];
-                const ArkShaderMaterial& mat = sc.materials[gi.material_index];
-                const float bx = 1.0f - hit.u - hit.v, by = hit.u, bz = hit.v;
-                // opaque.rchit:118-131 (front face: no flip)
-                N = normalize(v3(ra.x, ra.y, ra.z) * bx + v3(ra.w, rb.x, rb.y) * by + v3(rb.z, rb.w, rc.x) * bz);
-                const float* M = gi.normal_matrix;
-                V3 Nw = { M[0] * N.x + M[1] * N.y + M[2] * N.z, M[4] * N.x + M[5] * N.y + M[6] * N.z, M[8] * N.x + M[9] * N.y + M[10] * N.z };
-                N = normalize(Nw);
-                const float uvx = rc.z * bx + rd.x * by + rd.z * bz;
-                const float uvy = rc.w * bx + rd.y * by + rd.w * bz;
-                float4 c = sc.sample(mat.base_color, uvx, uvy);
-                baseColor = v3(c.x, c.y, c.z) * v3(mat.color_tint[0], mat.color_tint[1], mat.color_tint[2]);
-                c = sc.sample(mat.emissive, uvx, uvy);
-                const V3 emissive = v3(c.x, c.y, c.z) * v3(mat.emissive_factor[0], mat.emissive_factor[1], mat.emissive_factor[2]);
-                c = sc.sample(mat.metallic_roughness, uvx, uvy);
-                metallic = c.z * mat.metallic_factor;
-                roughness = c.y * mat.roughness_factor;
-                clearcoat = mat.clearcoat;
-                ccRough = mat.clearcoat_roughness;
-                const V3 ambient = f.ambient_amount * baseColor;
-                base = emissive + ambient;
-                // lit lights (LdotN > 0): one shadow ray each (opaque.rchit:56-103)
-                uint32_t l = 0;
-                if (sc.has_sun) {
-                    const V3 Ld = -normalize(v3(sc.sun_dir[0], sc.sun_dir[1], sc.sun_dir[2]));
-                    if (dot(Ld, N) > 0.0f) need |= 1u;
-                    l++;
-                }
-                for (int li = 0; li < sc.spot_count; ++li, ++l) {
-                    const V3 Ld = -normalize(v3(spotsL[li].direction[0], spotsL[li].direction[1], spotsL[li].direction[2]));
-                    if (dot(Ld, N) > 0.0f) need |= 1u << l;
-                }
+                frontSurface<kSpots>(sc, f, spotsL, ray, sf);
             }
             if (!valid) continue;
-            const uint32_t occ = need ? f.shadow_bits[ray] >> 16 : 0u;
-            V3 color = base;
-            const V3 V = -dir;
-            const V3 hitPoint = origin + T * dir;
-            uint32_t l = 0;
-            if (sc.has_sun) { // opaque.rchit:56-73
-                if (need & 1u) {
-                    const V3 Ld = -normalize(v3(sc.sun_dir[0], sc.sun_dir[1], sc.sun_dir[2]));
-                    const float LdotN = dot(Ld, N);
-                    const V3 brdf = evaluateDefaultBRDF(Ld, V, N, baseColor, roughness, metallic, clearcoat, ccRough);
-                    const V3 lc = v3(sc.sun_color[0], sc.sun_color[1], sc.sun_color[2]);
-                    const V3 tT = brdf * LdotN * (lc * 1.0f);
-                    const V3 tZ = brdf * LdotN * (lc * 0.0f);
-                    color = color + ((occ >> l) & 1u ? tZ : tT);
+            uint32_t occ = 0u;
+            if constexpr (MODE == kShadeSunFused) {
+                // the sun (the only light, bit 0) by its cover map
+                int vd = cover::kLit;
+                if (sf.need) {
+                    vd = sunMapVerdict(sc, sf.origin + sf.T * sf.dir);
+                    if (COUNT) {
+                        cOccluded += vd == cover::kOccluded;
+                        cLit += vd == cover::kLit;
+                        cListed += vd == cover::kUndecided;
+                    }
                 }
-                l++;
-            }
-            for (int li = 0; li < sc.spot_count; ++li, ++l) { // opaque.rchit:75-103
-                if (!((need >> l) & 1u)) continue;
-                const GpuSpotLight sl = spotsL[li];
-                V3 sdir = v3(sl.direction[0], sl.direction[1], sl.direction[2]);
-                V3 Ld = -normalize(sdir);
-                float LdotN = dot(Ld, N);
-                {
-                        V3 toLight = v3(sl.position[0], sl.position[1], sl.position[2]) - hitPoint;
-                        float distanceToLight = length(toLight);
-                        V3 normalizedToLight = toLight / distanceToLight;
-                        float distanceAttenuation = 1.0f / square(distanceToLight);
-                        // evaluateIESLookupTable (lighting.glsl:20-39)
-                        V3 lrd = -normalizedToLight;
-                        float iesValue = 0.0f;
-                        float angleV = dot(lrd, sdir);
-                        if (!(angleV <= 0.0f)) {
-                            float hx = dot(lrd, v3(sl.right[0], sl.right[1], sl.right[2]));
-                            float hy = dot(lrd, v3(sl.up[0], sl.up[1], sl.up[2]));
-                            float angleH = atan2f_(hy, hx) + kPi;
-                            float lx = acosf_(angleV) / (2.0f * sl.position[3]);
-                            float ly = clampf(angleH / kTwoPi, 0.0f, 1.0f);
-                            iesValue = sc.sample(sl.ies_texture, lx, ly).x;
-                        }
-                        V3 brdf = evaluateDefaultBRDF(Ld, V, N, baseColor, roughness, metallic, clearcoat, ccRough);
-                        V3 lc = v3(sl.color[0], sl.color[1], sl.color[2]);
-                        V3 tT = brdf * LdotN * (lc * 1.0f * distanceAttenuation * iesValue);
-                        V3 tZ = brdf * LdotN * (lc * 0.0f * distanceAttenuation * iesValue);
-                    color = color + ((occ >> l) & 1u ? tZ : tT);
+                if (COUNT || vd == cover::kUndecided) f.shadow_bits[ray] = sf.need | (vd == cover::kOccluded ? 1u << 16 : 0u);
+                if (vd == cover::kUndecided) {
+                    listD[atomicAdd(&counts[4], 1u)] = ray;
+                    continue;
                 }
+                occ = vd == cover::kOccluded ? 1u : 0u;
+            } else {
+                occ = sf.need ? f.shadow_bits[ray] >> 16 : 0u;
             }
-            // raygen.rgen:125-127 + evaluateIndirectLightFromPreviousFrame (:94-106)
-            const V3 Vi = -dir;
-            const V3 F0 = mix3(splat(kDielectricReflectance), baseColor, metallic);
-            const V3 F = F_Schlick3(fmaxf_(0.0f, dot(Vi, N)), F0);
-            const V3 irradiance = sampleDDGI<kGatherBatch>(f, hitPoint, N, Vi);
-            const V3 indirect = splat(1.0f - metallic) * (splat(1.0f) - F) * irradiance;
-            const V3 bi = baseColor * indirect;
-            storeSurfel(f, ray, color + bi, T);
+            shadeFront<kSpots>(sc, f, spotsL, ray, sf, occ);
         }
         // ---- C. misses (raygen.rgen:70-79) ------------------------------------------
         const uint32_t nM = counts[1];
@@ -1661,8 +1777,31 @@ __global__ void __launch_bounds__(kShadeBlock) __attribute__((amdgpu_waves_per_e
             storeSurfel(f, ray, f.environment_multiplier * v3(c.x, c.y, c.z), f.z_far);
         }
         __syncthreads();
+        if constexpr (MODE == kShadeSunFused) {
+            // the chunk's undecided rays to the shadow-ray list, as k_shadow_gen built them
+            const uint32_t nD = counts[4];
+            if (nD != 0) {
+                if (threadIdx.x == 0) counts[5] = atomicAdd(f.sun_rays ? f.sun_count : f.shadow_count, nD);
+                __syncthreads();
+                ShadowRay* const list = (f.sun_rays ? f.sun_rays : f.shadow_rays) + counts[5];
+                for (uint32_t i = threadIdx.x; i < nD; i += kShadeBlock) {
+                    const uint32_t ray = listD[i];
+                    const V3 hitPoint = genHitPoint<false>(f, ray, f.hits[ray].t);
+                    V3 ld;
+                    float tmax;
+                    shadowRayOf(sc, f.z_far, 0u, hitPoint, &ld, &tmax);
+                    list[i] = ShadowRay { make_float4(hitPoint.x, hitPoint.y, hitPoint.z, tmax), make_float4(ld.x, ld.y, ld.z, __uint_as_float((ray << 4) | 0u)) };
+                }
+                __syncthreads(); // before thread 0 resets the counts
+            }
+        }
     }
     if (COUNT) atomicAdd(&f.counters[6], static_cast<unsigned long long>(cFront));
+    if (COUNT && MODE == kShadeSunFused && f.cover_counts) {
+        atomicAdd(&f.cover_counts[0], cOccluded);
+        atomicAdd(&f.cover_counts[1], cLit);
+        atomicAdd(&f.cover_counts[2], cListed);
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1934,7 +2073,9 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     }
 }
 
-// Shadow-ray list: one thread per window ray in
+// Shadow-ray list (the generator schedule: spots, no valid cover map, the reflections -
+// shade_schedule.h; the sun-only schedule does this work inside k_shade and does not
+// launch the generator): one thread per window ray in
 // slot order; a front hit (raygen.rgen:121-127) stores its lit-light mask
 // (opaque.rchit:56-103, LdotN > 0 with the shading normal) in shadow_bits[ray] and
 // appends one shadow ray per lit light, owner = (ray << 4) | light. k_trace_shadow
@@ -1961,33 +2102,8 @@ __device__ __forceinline__ uint32_t waveInclusiveScan(uint32_t x)
     return x;
 }
 
-// The hit point of ray `ray` (hit distance t as recorded: negative for a back face): the
-// origin of its shadow rays
-template<bool REFL>
-__device__ __forceinline__ V3 genHitPoint(const FrameArgs& f, uint32_t ray, float t)
-{
-    if (REFL) {
-        const float4 a = f.ray_list[2u * ray], b = f.ray_list[2u * ray + 1u];
-        const V3 origin = v3(a.x, a.y, a.z), dir = v3(b.x, b.y, b.z);
-        return origin + fabsf_(t) * dir; // rt_RayHitT of a front or back face
-    }
-    V3 origin, dir;
-    rayOf(f, ray, &origin, &dir);
-    return origin + t * dir;
-}
-
-// The sun's shadow ray from X by the cover map (sun_cover_map.h): occluded, lit, or
-// undecided - then it is listed and traced. Exact verdicts: every output stays what the
-// traversal would give.
-__device__ __forceinline__ int sunMapVerdict(const SceneArgs& sc, V3 X)
-{
-    const V3 pl = sunCoords(sc, X);
-    const int64_t c = cover::cellIndex(sc.sun_grid, pl.x, pl.y);
-    if (c < 0) return cover::kUndecided;
-    const float2 t = sc.sun_map[c];
-    return cover::verdict(pl.z, sc.map_lift, sc.map_reach, t.x, t.y);
-}
-
+// (genHitPoint and sunMapVerdict: with k_shade, which resolves the sun's ray itself in the
+// sun-only schedule)
 // REFL: the reflection ray list (rt-reflections/raygen.rgen:122): queue position =
 // list index, and the closest hit shades back faces too, with the normal flipped
 // (opaque.rchit:121-125): N = -(shading normal), as negation commutes exactly with
@@ -2492,14 +2608,29 @@ static uint32_t persistentBlocks(const void* fn, int block, uint32_t fallback)
 // at C4 against the compiler's 133 VGPRs, 3 waves). Round 3: 5 waves (96 VGPRs)
 // spills 30 and shades in 0.525 instead of 0.469 ms (profiles/r03_ak).
 constexpr int kShadeWpe = 4;
-hipError_t launch_shade(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s)
+// sunFused: pass 1 of the sun-only schedule (shade_schedule.h), which resolves the sun's ray
+// itself and lists the undecided ones; launch_shade_deferred follows their traversal.
+hipError_t launch_shade(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s, bool sunFused)
 {
+    if (sunFused && (f.light_count != 1u || !sc.has_sun || sc.sun_map == nullptr)) return hipErrorInvalidValue;
+    void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
+    const void* fn;
     if (count) {
-        hipLaunchKernelGGL((dev::k_shade<true, 1>), dim3(blocks), dim3(kShadeBlock), 0, s, sc, f);
+        fn = sunFused ? reinterpret_cast<const void*>(&dev::k_shade<true, 1, dev::kShadeSunFused>) : reinterpret_cast<const void*>(&dev::k_shade<true, 1>);
     } else {
-        const void* fn = reinterpret_cast<const void*>(&dev::k_shade<false, kShadeWpe>);
-        hipLaunchKernelGGL((dev::k_shade<false, kShadeWpe>), dim3(persistentBlocks(fn, kShadeBlock, blocks)), dim3(kShadeBlock), 0, s, sc, f);
+        fn = sunFused ? reinterpret_cast<const void*>(&dev::k_shade<false, kShadeWpe, dev::kShadeSunFused>)
+                      : reinterpret_cast<const void*>(&dev::k_shade<false, kShadeWpe>);
+        blocks = persistentBlocks(fn, kShadeBlock, blocks);
     }
+    return hipLaunchKernel(fn, dim3(blocks), dim3(kShadeBlock), args, 0, s);
+}
+
+// Pass 2 of the sun-only schedule: the listed rays' surfels, a fixed grid striding over
+// the list (its count is read on the device; C4 lists ~97 K of 8.4 M rays).
+constexpr uint32_t kDeferredBlocks = 512;
+hipError_t launch_shade_deferred(const SceneArgs& sc, const FrameArgs& f, hipStream_t s)
+{
+    hipLaunchKernelGGL((dev::k_shade<false, kShadeWpe, dev::kShadeDeferred>), dim3(kDeferredBlocks), dim3(kShadeBlock), 0, s, sc, f);
     return hipGetLastError();
 }
 

@@ -85,6 +85,9 @@ class DDGIConfig:
     # the sun's cover map (on by default; False: ARK_DDGI_FLAG_NO_SUN_COVER_MAP, every sun
     # shadow ray is traced - same results)
     sun_cover_map: bool = True
+    # the sun-only shading schedule (on by default; False: ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE,
+    # the shadow-ray generator runs as for every other scene - same results)
+    fused_sun_shade: bool = True
     build_threads: int = 0
 
 
@@ -126,6 +129,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SUN if config.gpu_rebuild_sun else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SAH if config.gpu_rebuild_sah else 0
     d.flags |= 0 if config.sun_cover_map else abi.ARK_DDGI_FLAG_NO_SUN_COVER_MAP
+    d.flags |= 0 if config.fused_sun_shade else abi.ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE
     d.build_threads = int(config.build_threads)
     return d
 
@@ -392,6 +396,18 @@ class DDGIContext:
         self.check(fn(self.h, out), "ark_ddgi_debug_sun_cover_counts")
         keys = ("occluded", "lit", "listed", "in_use", "nx", "ny", "bytes", "build_us", "host_occluded", "host_lit", "host_listed", "map_diff")
         return dict(zip(keys, (int(v) for v in out)))
+
+    def shade_schedule(self) -> dict:
+        """ark_ddgi_debug_shade_schedule: whether the last update ran the sun-only shading
+        schedule, and the rays it deferred to its second shading pass."""
+        out = (C.c_uint64 * 2)()
+        self.check(self.lib.ark_ddgi_debug_shade_schedule(self.h, out), "ark_ddgi_debug_shade_schedule")
+        return {"sun_only": bool(out[0]), "deferred": int(out[1])}
+
+    def set_sun_only_small_windows(self, on: bool):
+        """ark_ddgi_debug_set_sun_only_small_windows: pipelined half-occupancy windows, which keep
+        the generator schedule by default, run the sun-only schedule too (tests)."""
+        self.check(self.lib.ark_ddgi_debug_set_sun_only_small_windows(self.h, int(on)), "ark_ddgi_debug_set_sun_only_small_windows")
 
     def sun_bvh_installed_check(self) -> dict:
         """ark_ddgi_debug_sun_bvh_installed_check: the light-space sun BVH8 the kernels read

@@ -187,13 +187,20 @@ typedef struct ArkDdgiDesc {
  * conservative light-space depth map built on the device at set_scene and by the background
  * rebuilds, with which most of the sun's shadow rays are resolved exactly - occluded or lit -
  * before they are listed for traversal; it is dropped the moment the geometry or the sun it
- * was built for changes. The flag disables it (A/B runs, tests); results are the same. */
+ * was built for changes. The flag disables it (A/B runs, tests); results are the same.
+ * NO_FUSED_SUN_SHADE: by default an update whose only light is the sun, with the cover map
+ * in use (and not a pipelined window of fewer than 5 Mi rays, where the generator is hidden
+ * beside the next frame's traversal), runs no shadow-ray generator: the shading kernel looks the map up itself, shades
+ * the resolved rays at once, lists the undecided ones, and shades those in a second pass
+ * after their traversal. The flag keeps the generator schedule that every other scene runs
+ * (A/B runs, tests); results are the same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
 #define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
 #define ARK_DDGI_FLAG_GPU_REBUILD_SUN 0x8u
 #define ARK_DDGI_FLAG_GPU_REBUILD_SAH 0x10u
 #define ARK_DDGI_FLAG_NO_SUN_COVER_MAP 0x20u
+#define ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE 0x40u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {

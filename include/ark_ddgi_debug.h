@@ -225,6 +225,17 @@ int ark_ddgi_debug_sun_cover_counts(struct ArkDdgiCtx* ctx, uint64_t* out);
 /* The same without the host restatement (a large scene's takes long): out[8..11] stay 0. */
 int ark_ddgi_debug_sun_cover_counts_device(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* The shading schedule of the context's last update (csrc/shade_schedule.h). out[2] = {1: the
+ * sun-only schedule ran (k_shade resolved the sun's rays from the cover map; no k_shadow_gen) -
+ * 0: the generator schedule, the rays that update deferred to its second shading pass (the
+ * undecided ones it listed; 0 under the generator schedule)}. Synchronous. */
+int ark_ddgi_debug_shade_schedule(struct ArkDdgiCtx* ctx, uint64_t* out);
+/* By default a pipelined window whose traversal runs the half-occupancy grid (fewer than 5 Mi
+ * rays with frames in flight) keeps the generator schedule, which is faster there. enabled != 0:
+ * such windows run the sun-only schedule too when the other conditions hold (tests: the
+ * schedule's chunk and list edge cases at sizes a test can afford). Results are the same. */
+int ark_ddgi_debug_set_sun_only_small_windows(struct ArkDdgiCtx* ctx, int enabled);
+
 #ifdef __cplusplus
 }
 #endif

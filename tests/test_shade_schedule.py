@@ -1,0 +1,24 @@
+"""Which shading schedule an update runs (csrc/shade_schedule.h: the sun-only schedule or the
+generator's), as a stand-alone program (tests/cpp/shade_schedule_test.cpp) built with g++
+under AddressSanitizer + UndefinedBehaviorSanitizer and run as a program, as
+test_lbvh_sah_sanitizers.py does. CPU only."""
+import os
+import subprocess
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SOURCES = [os.path.join(ROOT, "tests", "cpp", "shade_schedule_test.cpp")]
+
+
+def test_shade_schedule_under_sanitizers(tmp_path):
+    exe = str(tmp_path / "shade_schedule_test")
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fno-omit-frame-pointer", "-ffp-contract=off",
+           "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", os.path.join(ROOT, "arkoserenderer_amd", "csrc")] + SOURCES + ["-o", exe]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-4000:]
+    env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=1")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300, env=env)
+    print(r.stdout)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-4000:]
+    assert "table: OK" in r.stdout and r.stdout.rstrip().endswith("sweep: OK")
+    assert "ERROR: " not in r.stderr and "runtime error" not in r.stderr

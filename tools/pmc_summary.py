@@ -36,7 +36,51 @@ def short(name: str) -> str:
         return "k_refl_trace"
     if base == "k_shadow_gen":
         return "k_refl_shadow_gen" if m.group(3) == "true" else base
+    if base == "k_shade" and m.group(2) and m.group(2).rstrip(">").split(",")[-1].strip() == "2" and m.group(2).count(",") == 2:
+        return DEFERRED  # <COUNT, WPE, 2>: the sun-only schedule's second pass, folded into k_shade below
     return base + "_counting" if m.group(3) == "true" else base
+
+
+# The sun-only schedule shades in two launches per update, k_shade<.., 1> and k_shade<.., 2>
+# (csrc/shade_schedule.h). They are kept apart while rows are averaged per launch, then the
+# second is folded into "k_shade": times and bytes per update add up.
+DEFERRED = "k_shade#deferred"
+# every kernel of one probe-path update that bench.py's whole-update HBM figure sums; one the
+# profiled schedule did not launch (k_shadow_gen in the sun-only schedule) gets an entry of
+# no calls, no time and no bytes, so that the figure stays computed
+PATH_KERNELS = ("k_probe_slots", "k_trace", "k_probe_offsets", "k_shadow_gen", "k_shade", "k_probe_update")
+
+
+def fold_deferred(kernels):
+    d = kernels.pop(DEFERRED, None)
+    if d is None:
+        return
+    e = kernels.get("k_shade")
+    if e is None:
+        kernels["k_shade"] = d
+        return
+    e["passes"] = {"first": {k: e[k] for k in ("calls", "avg_ms", "hbm_bytes_per_launch") if k in e},
+                   "deferred": {k: d[k] for k in ("calls", "avg_ms", "hbm_bytes_per_launch") if k in d}}
+    e["avg_ms"] += d["avg_ms"]
+    if "pct" in e and "pct" in d:
+        e["pct"] += d["pct"]
+    keys = ("fetch_kib_raw", "write_kib", "hbm_bytes_per_launch", "hbm_bytes_per_launch_uncorrected")
+    if all(k in e and k in d for k in keys):
+        for k in keys:
+            e[k] += d[k]
+        e["hbm_gbs"] = round(e["hbm_bytes_per_launch"] / (e["avg_ms"] * 1e-3) / 1e9, 1)
+    else:
+        for k in keys + ("hbm_gbs",):
+            e.pop(k, None)
+
+
+def add_unlaunched(kernels):
+    if "k_trace" not in kernels:  # not a probe-path profile
+        return
+    for k in PATH_KERNELS:
+        if k not in kernels:
+            kernels[k] = {"calls": 0, "avg_ms": 0.0, "pct": 0.0, "fetch_kib_raw": 0.0, "write_kib": 0.0, "hbm_bytes_per_launch": 0,
+                          "hbm_bytes_per_launch_uncorrected": 0, "hbm_gbs": 0.0, "note": "not launched by the profiled schedule"}
 
 
 def main():
@@ -82,6 +126,8 @@ def main():
             e["hbm_bytes_per_launch_uncorrected"] = int((f + w) * 1024)
             e["hbm_gbs"] = round(e["hbm_bytes_per_launch"] / (st["avg_ms"] * 1e-3) / 1e9, 1)
         kernels[k] = e
+    fold_deferred(kernels)
+    add_unlaunched(kernels)
     cfg = {}
     log = os.path.join(src, "trace.log")
     if os.path.exists(log):

@@ -33,6 +33,8 @@ def base_name(name):
         mode = m.group(2).rstrip(">").split(",")[-1].strip()
         # <.., .., MODE>: 1 the sun's light-space traversal, 2 the sun's then the other lights'
         return {"1": "k_trace_shadow_sun", "2": "k_trace_shadow_sunw"}.get(mode, m.group(1))
+    if m.group(1) == "k_shade" and m.group(2) and m.group(2).count(",") == 2 and m.group(2).rstrip(">").split(",")[-1].strip() == "2":
+        return "k_shade_deferred"  # <.., .., 2>: the sun-only schedule's second pass (csrc/shade_schedule.h)
     return m.group(1)
 
 
