@@ -526,6 +526,7 @@ EXPORTS = {
     "ark_ddgi_debug_sun_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_bvh_installed_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_refit_reach": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_cover_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

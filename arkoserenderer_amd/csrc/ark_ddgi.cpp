@@ -743,6 +743,15 @@ int ark_ddgi_debug_sun_bvh_installed_check(ArkDdgiCtx* ctx, uint64_t* out)
     return sceneSunBvhCheck(*ctx->sceneStore, ctx, out);
 }
 
+int ark_ddgi_debug_refit_reach(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "refit reach before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    return sceneRefitReach(*ctx->sceneStore, ctx, out);
+}
+
 static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement);
 int ark_ddgi_debug_sun_cover_counts(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, true); }
 int ark_ddgi_debug_sun_cover_counts_device(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, false); }

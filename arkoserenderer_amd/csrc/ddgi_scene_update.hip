@@ -148,8 +148,12 @@ __global__ void __launch_bounds__(128) k_refit_nodes(GpuBvh8Node* __restrict__ n
     const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
     const uint32_t i = t >> 3, s = t & 7u;
     const uint32_t n0 = i < count ? order[i] : 0u;
-    // a node none of whose instances moved keeps its planes and its box (boxes[]) from
-    // the last refit that reached it (the same transforms and inflation: RefitBoxArgs.dirty)
+    // a node with no dirty instance below it keeps its planes (this copy's, of the transforms
+    // the copy holds) and its box (boxes[], one scratch for every copy, of the refit before
+    // this one, whichever copy that wrote). Both are of the new transforms and this
+    // inflation because the host's dirty set (RefitBoxArgs.dirty) holds every instance whose
+    // transform differs from this copy's or from the refit before's, and is all ones when
+    // the inflation differs from this copy's or from the scratch's (scene_store.cpp)
     const bool live = i < count && (masks[n0] & ra.dirty) != 0; // a node's eight lanes alike
     if (!__any(live)) return;
     const uint32_t n = live ? n0 : 0u;

@@ -43,11 +43,18 @@ struct DeviceBvh {
     uint32_t depth = 0;
     float inflateAbs = 0.0f; // the build's absolute box inflation (the refits' floor)
     // the refit: order[levelOffsets[i] .. [i + 1]) on the device = the nodes of one depth,
-    // deepest first (uploaded by whoever built the BVH, before it is installed); its boxes
-    // scratch; the node masks (k_node_masks: per topology)
+    // deepest first (uploaded by whoever built the BVH, before it is installed); the node
+    // masks (k_node_masks: per topology); its boxes scratch, one for the three geometry
+    // copies: after every refit boxes[n] is the box of the latest transforms of the
+    // instances below n at the inflation boxesInflate, whichever copy that refit wrote (a
+    // refit's dirty set holds every instance that changed since the refit before it, and
+    // a refit at another inflation reaches every node: scene_store.cpp)
     DeviceBuffer order, boxes, masks;
     std::vector<uint32_t> levelOffsets;
     bool masksValid = false;
+    float boxesInflate = 0.0f;
+    // the dirty word of the last refit (ark_ddgi_debug_refit_reach, while masksValid)
+    uint64_t refitDirty = 0;
     static size_t triOffsetFor(uint64_t nodes) { return (nodes * sizeof(GpuBvh8Node) + 255) & ~static_cast<size_t>(255); }
     static size_t bytesFor(uint64_t nodes, uint64_t records) { return triOffsetFor(nodes) + (records + 1) * sizeof(GpuTriangle); }
     // nodes and records of a copy of it (the front one, or a spare)

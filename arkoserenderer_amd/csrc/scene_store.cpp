@@ -236,7 +236,8 @@ float inflationStep(float x) { return x > 0.0f ? std::ldexp(1.0f, static_cast<in
 // The refit of one BVH's copy `copy` on `s`, level by level: the nodes with an instance of
 // `dirty` below them (the node masks, k_node_masks, computed first when the topology is
 // new), or every node (refitFull, or an inflation other than the one the copy's boxes
-// hold, `held`: updated).
+// hold, `held`: updated - or other than the one the boxes scratch holds, which the refit
+// before left there for another copy: a live node reads its skipped children's boxes from it).
 int refitBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, const DeviceBuffer& copy, RefitBoxArgs args, uint64_t dirty, float& held, hipStream_t s)
 {
     GpuBvh8Node* nodes = b.nodes(copy);
@@ -251,17 +252,19 @@ int refitBvh(ErrorSink* err, SceneStore& st, DeviceBvh& b, const DeviceBuffer& c
         for (size_t l = 0; l + 1 < lv.size(); ++l) ARK_HIP(launch_node_masks(nodes, tris, b.masks.as<uint64_t>(), order + lv[l], lv[l + 1] - lv[l], s));
         b.masksValid = true;
     }
-    args.dirty = (st.refitFull || args.inflate != held) ? ~0ull : dirty;
+    args.dirty = (st.refitFull || args.inflate != held || args.inflate != b.boxesInflate) ? ~0ull : dirty;
+    b.refitDirty = args.dirty;
     for (size_t l = 0; l + 1 < lv.size(); ++l)
         ARK_HIP(launch_refit_nodes(nodes, tris, b.boxes.as<float>(), order + lv[l], lv[l + 1] - lv[l], args, b.masks.as<uint64_t>(), st.refitInst.as<RefitInstance>(),
                                    st.indices.as<uint32_t>(), st.positions.as<float>(), s));
     held = args.inflate;
+    b.boxesInflate = args.inflate;
     return ARK_DDGI_OK;
 }
 
 // The refit of the copy (`world`, `sun`; slot: the transforms and inflations it holds) of
 // every BVH of the scene on `s`: the records of the moved instances (st.refitInst's dirty
-// flags: those whose transform differs from the copy's) re-transformed, the boxes and
+// flags: those whose transform differs from the copy's or the refit before's) re-transformed, the boxes and
 // planes above them recomputed - the world BVHs, then the light-space sun BVH (its boxes
 // of the records' light coordinates). The boxes' inflations from the instances' bounds
 // (refitInflations, host).
@@ -288,7 +291,12 @@ int enqueueRefit(ErrorSink* err, SceneStore& st, hipStream_t s, const DeviceBuff
 
 // The refit's transforms of `instances` on the device (stream-ordered), every one dirty
 // (have = nullptr: the records are of an older version, an installed rebuild) or those
-// whose transform differs from the one the target copy's records hold (`have`).
+// whose transform differs from the one the target copy's records hold (`have`) or from
+// the refit before's (st.instHost). The second keeps the boxes scratch, which the three
+// copies share, current: a node is skipped only when nothing below it changed since the
+// scratch last saw it, whichever copy that refit wrote. An instance back at the pose the
+// target copy holds (a nudge and return, a loop of period 3) is re-transformed to the
+// same bits.
 int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* instances, uint32_t count, const std::vector<std::array<float, 12>>* have,
                          hipStream_t s)
 {
@@ -300,7 +308,7 @@ int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* in
         const float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
         const ArkRTTriangleMesh& mesh = st.meshHost[instances[ii].rt_mesh_index];
         RefitInstance& q = st.refitHost[ii];
-        const bool moved = allDirty || std::memcmp((*have)[ii].data(), M, sizeof(q.m)) != 0;
+        const bool moved = allDirty || std::memcmp((*have)[ii].data(), M, sizeof(q.m)) != 0 || std::memcmp(st.instHost[ii].object_to_world, M, sizeof(q.m)) != 0;
         std::memcpy(q.m, M, sizeof(q.m));
         q.first_vertex = mesh.first_vertex;
         q.first_index = static_cast<uint32_t>(mesh.first_index);
@@ -1566,6 +1574,24 @@ int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
     if (st.sunArgs.sun_root < 0 || !st.sun.nodeCount) return 1; // no light-space BVH
     const int32_t root = 0;
     return installedBvhCheck(err, "sun", st.sun, st.sunArgs.sun_nodes, st.sunArgs.sun_tris, &st.sun.levelOffsets, &root, 1, nullptr, st.sunFrameD, st.sunGpuBuilt, 0, out);
+}
+
+int sceneRefitReach(const SceneStore& st, ErrorSink* err, uint64_t* out)
+{
+    std::fill(out, out + 4, uint64_t(0));
+    // the nodes k_refit_nodes found live: masks[n] & dirty (masks of this topology only
+    // once a refit has computed them)
+    auto reach = [&](const DeviceBvh& b, uint64_t* o) -> int {
+        if (!b.masksValid || !b.nodeCount || b.masks.bytes < b.nodeCount * 8) return ARK_DDGI_OK;
+        std::vector<uint64_t> m(b.nodeCount);
+        ARK_HIP(hipMemcpy(m.data(), b.masks.ptr, m.size() * 8, hipMemcpyDeviceToHost));
+        o[0] = b.nodeCount;
+        for (uint64_t v : m) o[1] += (v & b.refitDirty) != 0;
+        return ARK_DDGI_OK;
+    };
+    if (const int rc = reach(st.world, out)) return rc;
+    if (st.sunArgs.sun_root >= 0 && st.sun.records) return reach(st.sun, out + 2);
+    return ARK_DDGI_OK;
 }
 
 } // namespace ark

@@ -110,8 +110,8 @@ struct SceneStore {
     uint32_t version = 0;
     DeviceBuffer refitInst;
     double sunFrameD[9] {};
-    // the refit's transforms: the last ones uploaded (dirty = changed since the records
-    // were written); pinned staging of the stream-ordered uploads, two sets in turn
+    // the refit's transforms: the last ones uploaded (dirty = changed since the target
+    // copy's records were written, or since the refit before); pinned staging of the stream-ordered uploads, two sets in turn
     std::vector<RefitInstance> refitHost;
     // pinned staging of the per-frame uploads, a ring: a slot is reused once its copy (a
     // few calls back) has run, so the host runs up to kStageSlots / 2 frames of
@@ -140,8 +140,11 @@ struct SceneStore {
         int slot = 0;
     };
     Spare spare[2]; // spare[0]: the next refit's target
-    // the inflations each copy's boxes hold ([slot][0 world, 1 sun]); refitFull: the next
-    // refit reaches every node (a new topology, or boxes scratch not of this one)
+    // the inflations each copy's boxes hold ([slot][0 world, 1 sun]; 0: set_scene's own,
+    // so the first refit of that copy reaches every node); refitFull: the next refit reaches
+    // every node (a new topology, or boxes scratch not of this one). The boxes scratch
+    // (DeviceBvh::boxes) is one for the three copies: after every refit it holds, for every
+    // node, the box of the latest transforms at DeviceBvh::boxesInflate
     bool refitFull = true;
     float inflCopy[3][2] {};
     int front = 0; // slot of the front copy (xf index)
@@ -235,6 +238,9 @@ int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out);
 int sceneWorldBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
 // ark_ddgi_debug_sun_bvh_installed_check over the front copy (1 with out zeroed: none installed)
 int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
+// ark_ddgi_debug_refit_reach: the nodes of the world and the light-space BVHs and those the
+// last refit reached (the node masks downloaded; the device is idle)
+int sceneRefitReach(const SceneStore& st, ErrorSink* err, uint64_t* out);
 
 // SpotLightData as the closest hit reads it
 GpuSpotLight gpuSpotLight(const ArkSpotLight& sl);

@@ -421,6 +421,13 @@ class DDGIContext:
         r["installed"] = r["nodes"] > 0
         return r
 
+    def refit_reach(self) -> dict:
+        """ark_ddgi_debug_refit_reach: the nodes of the world BVHs and of the light-space
+        sun BVH, and how many of each the last refit reached (all 0 before the first)."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.lib.ark_ddgi_debug_refit_reach(self.h, out), "ark_ddgi_debug_refit_reach")
+        return dict(zip(("world_nodes", "world_reached", "sun_nodes", "sun_reached"), (int(v) for v in out)))
+
 
 _BVH_CHECK_KEYS = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
 

@@ -197,6 +197,14 @@ int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const 
  * no light-space BVH is installed (out all zero). Synchronous. */
 int ark_ddgi_debug_sun_bvh_installed_check(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* How far the last refit (ark_ddgi_set_instances[_async]) went. out[4] = {world BVH nodes,
+ * world nodes it reached, light-space sun BVH nodes, sun nodes it reached}: a node is
+ * reached when an instance of the refit's dirty set lies below it by the node masks (bit
+ * instance id mod 64, so instances 64 apart count as one); every other node kept its
+ * planes. The last two are 0 without a light-space BVH, all four before the first refit
+ * (and a BVH's two after a rebuild was installed, until the next refit). Synchronous. */
+int ark_ddgi_debug_refit_reach(struct ArkDdgiCtx* ctx, uint64_t* out);
+
 /* The sun's cover map (csrc/sun_cover_map.h) built on the host (no GPU) from n triangles
  * (9 floats each) for sun_dir, and its verdicts for n_rays origins (3 floats each) against a
  * brute-force any-hit over every triangle with the kernels' fp32 Moller-Trumbore

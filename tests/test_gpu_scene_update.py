@@ -473,7 +473,8 @@ def test_partial_refits_equal_full_refit():
     instance, then another, one back, a mirrored one, and a pause - the geometry the
     kernels read (world and light-space BVH nodes and records) is byte-identical to a
     context that refits every node once to the final transforms (no background rebuilds:
-    the topology stays)."""
+    the topology stays). Checks after every step, in a scene whose refits really skip
+    nodes: test_gpu_refit_sequences.py."""
     sc = S.soup(64_000, extent=7.0)
     grid = D.ProbeGrid((4, 4, 4), (2.0, 2.0, 2.0), (0.0, 0.0, 0.0))
     cfg = D.DDGIConfig(rays_per_probe=32, probe_updates_per_frame=64, max_rays_per_probe=32, max_probe_updates=64,
