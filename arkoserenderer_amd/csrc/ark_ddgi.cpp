@@ -21,10 +21,10 @@
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
 #include "ark_fmath.h"
-#include "bvh_builder.h"
 #include "ddgi_kernels.h"
 #include "scene_store.h"
 #include "shade_schedule.h"
+#include "sun_bvh.h"
 #include "sun_cover_build.h"
 
 using namespace ark;

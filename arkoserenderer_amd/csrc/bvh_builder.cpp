@@ -1,8 +1,10 @@
-// bvh_builder.cpp — binned SAH BVH2 over world-space triangles (host, C++ threads).
+// bvh_builder.cpp — the host build of the world BVHs (C++ threads): the binned-SAH BVH2
+// over world-space triangles, its collapse into the 8-wide quantized layout and the
+// structural checks every build passes before it reaches the GPU.
 #include "bvh_builder.h"
 
 #include "../../include/ark_ddgi.h"
-#include "../../include/ark_ddgi_debug.h"
+#include "bvh_internal.h"
 
 #include <algorithm>
 #include <array>
@@ -18,40 +20,6 @@
 
 namespace ark {
 namespace {
-
-struct Aabb {
-    float lo[3] = { INFINITY, INFINITY, INFINITY };
-    float hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    void grow(const float p[3])
-    {
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = std::min(lo[a], p[a]);
-            hi[a] = std::max(hi[a], p[a]);
-        }
-    }
-    void grow(const Aabb& b)
-    {
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = std::min(lo[a], b.lo[a]);
-            hi[a] = std::max(hi[a], b.hi[a]);
-        }
-    }
-    float area() const
-    {
-        float d0 = hi[0] - lo[0], d1 = hi[1] - lo[1], d2 = hi[2] - lo[2];
-        if (!(d0 >= 0.0f)) return 0.0f;
-        return 2.0f * (d0 * d1 + d1 * d2 + d2 * d0);
-    }
-    // SAH surface with per-face weights w = {xy, yz, zx} (BvhBuildOptions::area_w):
-    // {1, 1, 1} is the surface area; rays parallel to z (the light-space BVH of the
-    // sun's shadow rays) cross a box with a probability proportional to its xy face
-    float area(const float* w) const
-    {
-        float d0 = hi[0] - lo[0], d1 = hi[1] - lo[1], d2 = hi[2] - lo[2];
-        if (!(d0 >= 0.0f)) return 0.0f;
-        return 2.0f * (w[0] * d0 * d1 + w[1] * d1 * d2 + w[2] * d2 * d0);
-    }
-};
 
 struct Ref {
     Aabb box;
@@ -248,18 +216,8 @@ private:
         GpuBvhNode& nd = m_nodes[local];
         Aabb bb[2] = { b0, b1 };
         for (int c = 0; c < 2; ++c) {
-            Aabb& b = bb[c];
-            if (b.lo[0] > 1e29f) continue; // far sentinel stays exact
-            float m = 0.0f, e = 0.0f;
-            for (int a = 0; a < 3; ++a) {
-                m = std::max(m, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
-                e = std::max(e, b.hi[a] - b.lo[a]);
-            }
-            const float eps = m * 2e-6f + e * 1e-5f + 1e-7f + m_opt.inflate_abs;
-            for (int a = 0; a < 3; ++a) {
-                b.lo[a] -= eps;
-                b.hi[a] += eps;
-            }
+            if (bb[c].lo[0] > 1e29f) continue; // far sentinel stays exact
+            inflateChildBox(bb[c], m_opt.inflate_abs);
         }
         nd.n0[0] = bb[0].lo[0]; nd.n0[1] = bb[0].hi[0]; nd.n0[2] = bb[0].lo[1]; nd.n0[3] = bb[0].hi[1];
         nd.n1[0] = bb[1].lo[0]; nd.n1[1] = bb[1].hi[0]; nd.n1[2] = bb[1].lo[1]; nd.n1[3] = bb[1].hi[1];
@@ -572,35 +530,6 @@ void quantGrid(float L, float H, int& e, double& p)
     }
 }
 
-// The node writer: the quantization grid of a node over `box` (p, e) and the
-// outward-rounded planes of its slots' boxes (null: an unused slot, left as it is)
-void writeNodePlanes(GpuBvh8Node& nd, const Aabb& box, const Aabb* const slotBox[8])
-{
-    double step[3], p[3];
-    for (int a = 0; a < 3; ++a) {
-        int e;
-        quantGrid(box.lo[a], box.hi[a], e, p[a]);
-        step[a] = std::ldexp(1.0, e);
-        nd.p[a] = static_cast<float>(p[a]);
-        nd.e[a] = static_cast<uint8_t>(e + 127);
-    }
-    for (int s = 0; s < 8; ++s) {
-        if (!slotBox[s]) continue;
-        const Aabb& b = *slotBox[s];
-        for (int a = 0; a < 3; ++a) {
-            double ql = std::floor((static_cast<double>(b.lo[a]) - p[a]) / step[a]);
-            double qh = std::ceil((static_cast<double>(b.hi[a]) - p[a]) / step[a]);
-            ql = std::min(255.0, std::max(0.0, ql));
-            qh = std::min(255.0, std::max(0.0, qh));
-            // outward rounding, checked on the exact fp32 decode
-            while (ql > 0.0 && static_cast<double>(static_cast<float>(p[a] + ql * step[a])) > b.lo[a]) ql -= 1.0;
-            while (qh < 255.0 && static_cast<double>(static_cast<float>(p[a] + qh * step[a])) < b.hi[a]) qh += 1.0;
-            nd.qlo[a][s] = static_cast<uint8_t>(ql);
-            nd.qhi[a][s] = static_cast<uint8_t>(qh);
-        }
-    }
-}
-
 // First-fit placement of a node's leaf-triangle rows (a 24-bit pattern over
 // positions base + 0..23) into the triangle array: the lowest base, at most
 // kRowWindow below the end of the array, whose positions are all free. The search
@@ -677,6 +606,49 @@ uint32_t leafRowStride(const uint32_t cnt[8])
 
 } // namespace
 
+// bvh_internal.h: the node writer
+void writeNodePlanes(GpuBvh8Node& nd, const Aabb& box, const Aabb* const slotBox[8])
+{
+    double step[3], p[3];
+    for (int a = 0; a < 3; ++a) {
+        int e;
+        quantGrid(box.lo[a], box.hi[a], e, p[a]);
+        step[a] = std::ldexp(1.0, e);
+        nd.p[a] = static_cast<float>(p[a]);
+        nd.e[a] = static_cast<uint8_t>(e + 127);
+    }
+    for (int s = 0; s < 8; ++s) {
+        if (!slotBox[s]) continue;
+        const Aabb& b = *slotBox[s];
+        for (int a = 0; a < 3; ++a) {
+            double ql = std::floor((static_cast<double>(b.lo[a]) - p[a]) / step[a]);
+            double qh = std::ceil((static_cast<double>(b.hi[a]) - p[a]) / step[a]);
+            ql = std::min(255.0, std::max(0.0, ql));
+            qh = std::min(255.0, std::max(0.0, qh));
+            // outward rounding, checked on the exact fp32 decode
+            while (ql > 0.0 && static_cast<double>(static_cast<float>(p[a] + ql * step[a])) > b.lo[a]) ql -= 1.0;
+            while (qh < 255.0 && static_cast<double>(static_cast<float>(p[a] + qh * step[a])) < b.hi[a]) qh += 1.0;
+            nd.qlo[a][s] = static_cast<uint8_t>(ql);
+            nd.qhi[a][s] = static_cast<uint8_t>(qh);
+        }
+    }
+}
+
+// bvh_internal.h: Builder::writeNode's inflation of a child box
+void inflateChildBox(Aabb& b, float inflateAbs)
+{
+    float m = 0.0f, e = 0.0f;
+    for (int a = 0; a < 3; ++a) {
+        m = std::max(m, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
+        e = std::max(e, b.hi[a] - b.lo[a]);
+    }
+    const float eps = m * 2e-6f + e * 1e-5f + 1e-7f + inflateAbs;
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] -= eps;
+        b.hi[a] += eps;
+    }
+}
+
 GpuTriangle make_gpu_triangle(const BuildTriangle& t)
 {
     GpuTriangle g;
@@ -724,6 +696,34 @@ int bvh8SlotTriangles(const GpuBvh8Node& nd, int s, uint32_t out[kBvh8MaxLeafSiz
         else out[n++] = nd.tri_base + pos;
     }
     return n > 0 ? n : -1;
+}
+
+bool decodeSlotBox(const GpuBvh8Node& nd, int slot, float lo[3], float hi[3])
+{
+    bool exact = true;
+    for (int a = 0; a < 3; ++a) {
+        const float step = std::ldexp(1.0f, static_cast<int>(nd.e[a]) - 127);
+        lo[a] = std::fma(static_cast<float>(nd.qlo[a][slot]), step, nd.p[a]);
+        hi[a] = std::fma(static_cast<float>(nd.qhi[a][slot]), step, nd.p[a]);
+        if (static_cast<double>(lo[a]) != static_cast<double>(nd.p[a]) + nd.qlo[a][slot] * static_cast<double>(step)) exact = false;
+        if (static_cast<double>(hi[a]) != static_cast<double>(nd.p[a]) + nd.qhi[a][slot] * static_cast<double>(step)) exact = false;
+    }
+    return exact;
+}
+
+std::vector<BuildTriangle> soupTriangles(const float* triangles, uint64_t n)
+{
+    std::vector<BuildTriangle> tris(n);
+    for (uint64_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) {
+            tris[i].v0[a] = triangles[9 * i + a];
+            tris[i].v1[a] = triangles[9 * i + 3 + a];
+            tris[i].v2[a] = triangles[9 * i + 6 + a];
+        }
+        tris[i].instance = tris[i].flip_facing = 0;
+        tris[i].primitive = static_cast<uint32_t>(i);
+    }
+    return tris;
 }
 
 float bvh8_inflation(const float* xyz, uint64_t nTriangles)
@@ -938,7 +938,6 @@ void collapseQueue(const BvhBuildResult& bvh2, const CollapsePlan& plan, const B
             if (m == 1) {
                 emitChildren(bvh2, plan, two[0], 8, ch, n);
             } else {
-                const uint32_t src = it.src;
                 int kk = 1;
                 float best = INFINITY;
                 for (int k = 1; k < 8; ++k) {
@@ -948,7 +947,6 @@ void collapseQueue(const BvhBuildResult& bvh2, const CollapsePlan& plan, const B
                         kk = k;
                     }
                 }
-                (void)src;
                 emitChildren(bvh2, plan, two[0], kk, ch, n);
                 emitChildren(bvh2, plan, two[1], 8 - kk, ch, n);
             }
@@ -1298,1535 +1296,3 @@ bool build_world_bvh8(std::vector<BuildTriangle> cls[3], BvhBuildOptions opt, co
 }
 
 } // namespace ark
-
-// ark_ddgi_debug.h: host-side structural check of the BVH8 (see the header).
-extern "C" int ark_ddgi_debug_bvh8_check(const float* triangles, uint64_t n, uint64_t* out)
-{
-    return ark_ddgi_debug_bvh8_check_opts(triangles, n, 1, 0.0f, out);
-}
-
-extern "C" int ark_ddgi_debug_bvh8_check_opts(const float* triangles, uint64_t n, int sah_optimal, float tri_cost, uint64_t* out)
-{
-    using namespace ark;
-    std::vector<BuildTriangle> tris(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) {
-            tris[i].v0[a] = triangles[9 * i + a];
-            tris[i].v1[a] = triangles[9 * i + 3 + a];
-            tris[i].v2[a] = triangles[9 * i + 6 + a];
-        }
-        tris[i].instance = 0;
-        tris[i].primitive = static_cast<uint32_t>(i);
-        tris[i].flip_facing = 0;
-    }
-    BvhBuildOptions opt;
-    opt.max_leaf_size = kBvh8MaxLeafSize;
-    opt.inflate_abs = bvh8_inflation(triangles, n);
-    const BvhBuildResult r2 = build_bvh(tris, opt, 0u, 0u);
-    Bvh8CollapseOptions copt;
-    copt.sah_optimal = sah_optimal != 0;
-    if (tri_cost > 0.0f) copt.tri_cost = std::max(0.01f, tri_cost);
-    const Bvh8BuildResult r8 = collapse_bvh8(r2, 0u, 0u, copt);
-    uint64_t violations = 0, internalChildren = 0;
-    std::vector<uint32_t> seen(n, 0);
-    struct Box {
-        float lo[3], hi[3];
-    };
-    struct Item {
-        uint32_t node;
-        std::vector<Box> anc;
-    };
-    std::vector<Item> work;
-    if (!r8.nodes.empty()) work.push_back({ 0u, {} });
-    while (!work.empty()) {
-        Item it = std::move(work.back());
-        work.pop_back();
-        if (it.node >= r8.nodes.size()) {
-            violations++;
-            continue;
-        }
-        const GpuBvh8Node& nd = r8.nodes[it.node];
-        uint32_t internal = 0;
-        for (int s = 0; s < 8; ++s) {
-            const bool in = (nd.imask >> s) & 1u;
-            uint32_t slotTris[kBvh8MaxLeafSize];
-            const int cnt = bvh8SlotTriangles(nd, s, slotTris);
-            if (cnt < 0) {
-                violations++;
-                continue;
-            }
-            if (!in && cnt == 0) continue;
-            Box b;
-            for (int a = 0; a < 3; ++a) {
-                const float step = std::ldexp(1.0f, static_cast<int>(nd.e[a]) - 127);
-                b.lo[a] = std::fma(static_cast<float>(nd.qlo[a][s]), step, nd.p[a]);
-                b.hi[a] = std::fma(static_cast<float>(nd.qhi[a][s]), step, nd.p[a]);
-                if (static_cast<double>(b.lo[a]) != static_cast<double>(nd.p[a]) + nd.qlo[a][s] * static_cast<double>(step)) violations++;
-                if (static_cast<double>(b.hi[a]) != static_cast<double>(nd.p[a]) + nd.qhi[a][s] * static_cast<double>(step)) violations++;
-            }
-            std::vector<Box> anc = it.anc;
-            anc.push_back(b);
-            if (in) {
-                internalChildren++;
-                work.push_back({ nd.child_base + internal++, std::move(anc) });
-                continue;
-            }
-            for (int ti = 0; ti < cnt; ++ti) {
-                const uint32_t t = slotTris[ti];
-                if (t >= r8.tris.size() || isHoleTriangle(r8.tris[t])) {
-                    violations++;
-                    continue;
-                }
-                const GpuTriangle& g = r8.tris[t];
-                uint32_t prim;
-                std::memcpy(&prim, &g.t2[2], 4);
-                if (prim < n) seen[prim]++;
-                if (prim >= n) continue;
-                const float* verts[3] = { tris[prim].v0, tris[prim].v1, tris[prim].v2 };
-                for (int k = 0; k < 3; ++k)
-                    for (int a = 0; a < 3; ++a)
-                        for (const Box& bx : anc)
-                            if (verts[k][a] < bx.lo[a] || verts[k][a] > bx.hi[a]) violations++;
-            }
-        }
-    }
-    for (uint64_t i = 0; i < n; ++i)
-        if (seen[i] != 1) violations++;
-    if (out) {
-        out[0] = r8.nodes.size();
-        out[1] = r8.leaf_children;
-        out[2] = r8.max_depth;
-        out[3] = violations;
-        out[4] = r8.triangles;
-        out[5] = r2.nodes.size();
-        out[6] = internalChildren;
-        out[7] = static_cast<uint64_t>(static_cast<double>(r8.sah_cost) * 1e6); // BVH8 SAH cost x 1e6
-    }
-    return violations == 0 ? 0 : 1;
-}
-
-namespace ark {
-
-// The sun's shadow rays (opaque.rchit:35-54, the sun branch :56-73) all travel along
-// L = -normalize(sun direction) - the fp32 value k_shadow_gen gives them. In the
-// orthonormal frame (u, v, w = L / |L|) they are rays along +w: a child box is crossed
-// iff the ray's (u, v) lies in the box's u-v rectangle and the box reaches above its
-// origin, a containment test in the node's quantized grid with no division and no
-// per-child multiply (k_trace_shadow<SUN>, visitNodeSun). The light-space BVH holds
-// every triangle of every hit-mask class (shadow rays test all three with the Opaque
-// flag, no alpha test) with the world-space triangle records, so the any-hit tests and
-// their results are those of the world BVHs.
-void sun_frame(const float sunDir[3], double frame[3][3])
-{
-    // L = -normalize(dir) in fp32, the operation order of normalize() in the kernels
-    // (v * (1 / sqrt(dot(v, v))), dot left to right)
-    const float dd = sunDir[0] * sunDir[0] + sunDir[1] * sunDir[1] + sunDir[2] * sunDir[2];
-    const float sc = 1.0f / std::sqrt(dd);
-    const float L[3] = { -(sunDir[0] * sc), -(sunDir[1] * sc), -(sunDir[2] * sc) };
-    double w[3] = { L[0], L[1], L[2] };
-    const double wl = std::sqrt(w[0] * w[0] + w[1] * w[1] + w[2] * w[2]);
-    for (double& x : w) x /= wl;
-    const double h[3] = { std::fabs(w[0]) < 0.9 ? 1.0 : 0.0, std::fabs(w[0]) < 0.9 ? 0.0 : 1.0, 0.0 };
-    double u[3] = { h[1] * w[2] - h[2] * w[1], h[2] * w[0] - h[0] * w[2], h[0] * w[1] - h[1] * w[0] };
-    const double ul = std::sqrt(u[0] * u[0] + u[1] * u[1] + u[2] * u[2]);
-    for (double& x : u) x /= ul;
-    const double v[3] = { w[1] * u[2] - w[2] * u[1], w[2] * u[0] - w[0] * u[2], w[0] * u[1] - w[1] * u[0] };
-    for (int k = 0; k < 3; ++k) {
-        frame[0][k] = u[k];
-        frame[1][k] = v[k];
-        frame[2][k] = w[k];
-    }
-}
-
-// Light-space build triangles of world-space records: rec(i) gives triangle i's record.
-template<class RecordOf>
-static void sunAddRecords(SunBvhInput& in, size_t n, RecordOf rec, int threads)
-{
-    const size_t base = in.world.size();
-    in.tris.resize(base + n);
-    in.world.resize(base + n);
-    // independent per triangle: in chunks on `threads` threads, the largest |coordinate|
-    // reduced at the end (a max does not depend on the order)
-    const int T = std::max(1, std::min<int>(threads > 0 ? threads : static_cast<int>(std::thread::hardware_concurrency()), static_cast<int>(n >> 16) + 1));
-    std::vector<float> maxAbs(T, 0.0f);
-    auto work = [&](int t) {
-        const size_t b = n * t / T, e = n * (t + 1) / T;
-        for (size_t i = b; i < e; ++i) {
-            const GpuTriangle rc = rec(i);
-            // the triangle Möller–Trumbore tests: v0, v0 + e1, v0 + e2 (exact, from the record)
-            // (lbvh_build.h: the refit and the device build box the same light coordinates)
-            const float e1[3] = { rc.t0[3], rc.t1[0], rc.t1[1] }, e2[3] = { rc.t1[2], rc.t1[3], rc.t2[0] };
-            float Lv[3][3], m;
-            lbvh::lightVertices(rc.t0, e1, e2, &in.frame[0][0], Lv, m);
-            maxAbs[t] = std::max(maxAbs[t], m);
-            BuildTriangle& l = in.tris[base + i];
-            float* dst[3] = { l.v0, l.v1, l.v2 };
-            for (int k = 0; k < 3; ++k)
-                for (int r = 0; r < 3; ++r) dst[k][r] = Lv[k][r];
-            l.instance = 0;
-            l.primitive = static_cast<uint32_t>(base + i);
-            l.flip_facing = 0;
-            in.world[base + i] = rc;
-        }
-    };
-    std::vector<std::thread> pool;
-    for (int t = 1; t < T; ++t) pool.emplace_back(work, t);
-    work(0);
-    for (std::thread& th : pool) th.join();
-    for (float m : maxAbs) in.maxAbs = std::max(in.maxAbs, m);
-}
-
-void sun_add_triangles(SunBvhInput& in, const std::vector<BuildTriangle>& tris, int threads)
-{
-    sunAddRecords(in, tris.size(), [&](size_t i) { return make_gpu_triangle(tris[i]); }, threads);
-}
-
-void sun_add_records(SunBvhInput& in, const std::vector<GpuTriangle>& records, int threads)
-{
-    std::vector<uint32_t> live;
-    live.reserve(records.size());
-    for (size_t i = 0; i < records.size(); ++i)
-        if (!isHoleTriangle(records[i])) live.push_back(static_cast<uint32_t>(i));
-    sunAddRecords(in, live.size(), [&](size_t i) { return records[live[i]]; }, threads);
-}
-
-bool build_sun_bvh(SunBvhInput& in, const BvhBuildOptions& opt, const Bvh8CollapseOptions& copt, Bvh8BuildResult& out)
-{
-    // light-space box inflation: the rounding of the light coordinates to fp32 here and
-    // of the origin's (u, v, w) in the kernel (a 3-term fp32 dot product, about 3 ulp of
-    // |P|), Möller–Trumbore's acceptance margin (as the world BVHs: bvh8_inflation_box,
-    // 1e-6 of the diagonal) - each covered twice over
-    float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
-    for (const BuildTriangle& t : in.tris)
-        for (const float* v : { t.v0, t.v1, t.v2 })
-            for (int a = 0; a < 3; ++a) {
-                lo[a] = std::min(lo[a], v[a]);
-                hi[a] = std::max(hi[a], v[a]);
-            }
-    BvhBuildOptions lopt = opt;
-    lopt.max_leaf_size = kBvh8MaxLeafSize;
-    lopt.inflate_abs = 2.0f * bvh8_inflation_box(lo, hi) + 2e-6f * in.maxAbs;
-    in.inflateAbs = lopt.inflate_abs;
-    BvhBuildResult r2 = build_bvh(in.tris, lopt, 0u, 0u);
-    std::vector<BuildTriangle>().swap(in.tris);
-    if (r2.max_leaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) return false;
-    Bvh8CollapseOptions lc = copt;
-    lc.slot_sort_axis = 2; // every ray goes along +w
-    out = collapse_bvh8(r2, 0u, 0u, lc);
-    // the leaves' records become the world-space ones (primitive = world index)
-    for (GpuTriangle& g : out.tris) {
-        if (isHoleTriangle(g)) continue;
-        uint32_t idx;
-        std::memcpy(&idx, &g.t2[2], 4);
-        g = in.world[idx];
-    }
-    std::vector<GpuTriangle>().swap(in.world);
-    return true;
-}
-
-void sun_sample_origins(const std::vector<GpuTriangle>& tris, const float L[3], uint32_t n, std::vector<float>& out)
-{
-    out.clear();
-    if (tris.empty() || n == 0) return;
-    uint64_t x = 0x9E3779B97F4A7C15ull; // xorshift64: the same samples every build
-    auto next = [&]() {
-        x ^= x << 13;
-        x ^= x >> 7;
-        x ^= x << 17;
-        return x;
-    };
-    for (uint64_t tries = 0; out.size() < 3ull * n && tries < 32ull * n; ++tries) {
-        const GpuTriangle& g = tris[next() % tris.size()];
-        if (isHoleTriangle(g)) continue;
-        const double e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-        const double nrm[3] = { e1[1] * e2[2] - e1[2] * e2[1], e1[2] * e2[0] - e1[0] * e2[2], e1[0] * e2[1] - e1[1] * e2[0] };
-        uint32_t flip;
-        std::memcpy(&flip, &g.t2[3], 4);
-        const double dn = (nrm[0] * L[0] + nrm[1] * L[1] + nrm[2] * L[2]) * (flip ? -1.0 : 1.0);
-        if (!(dn > 0.0)) continue; // the front face (CCW, mirrored instances flipped) must face the sun
-        const double r1 = static_cast<double>(next() >> 11) * 0x1p-53, r2 = static_cast<double>(next() >> 11) * 0x1p-53;
-        const double sq = std::sqrt(r1), b1 = sq * (1.0 - r2), b2 = sq * r2;
-        for (int a = 0; a < 3; ++a) out.push_back(static_cast<float>(g.t0[a] + b1 * e1[a] + b2 * e2[a]));
-    }
-}
-
-double sun_shadow_cost(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
-                       const double (*frame)[3], const float L[3], const std::vector<float>& origins)
-{
-    const size_t n = origins.size() / 3;
-    if (n == 0) return 0.0;
-    const float tmin = 0.025f, tmax = 1e30f;
-    uint64_t steps = 0;
-    std::vector<uint32_t> stack;
-    for (size_t r = 0; r < n; ++r) {
-        const float* P = &origins[3 * r];
-        float ob[3], db[3];
-        for (int a = 0; a < 3; ++a) {
-            ob[a] = frame ? static_cast<float>(frame[a][0] * P[0] + frame[a][1] * P[1] + frame[a][2] * P[2]) : P[a];
-            db[a] = frame ? (a == 2 ? 1.0f : 0.0f) : L[a];
-        }
-        float idir[3];
-        for (int a = 0; a < 3; ++a) idir[a] = 1.0f / (std::fabs(db[a]) < 1e-20f ? std::copysign(1e-20f, db[a]) : db[a]);
-        bool hit = false;
-        for (int k = 0; k < nRoots && !hit; ++k) {
-            if (roots[k] < 0) continue;
-            stack.assign(1, static_cast<uint32_t>(roots[k]));
-            while (!stack.empty() && !hit) {
-                const GpuBvh8Node& nd = nodes[stack.back()];
-                stack.pop_back();
-                steps++;
-                struct Cand { float tn; int s; } hc[8];
-                int nh = 0;
-                uint32_t before[8], cnt = 0;
-                for (int s = 0; s < 8; ++s) {
-                    before[s] = cnt;
-                    if ((nd.imask >> s) & 1u) cnt++;
-                    if (!((nd.imask >> s) & 1u) && !((nd.leaf_mask >> s) & 1u)) continue;
-                    float tn = tmin, tf = tmax;
-                    for (int a = 0; a < 3; ++a) {
-                        const float step = std::ldexp(1.0f, static_cast<int>(nd.e[a]) - 127);
-                        float t0 = (std::fma(static_cast<float>(nd.qlo[a][s]), step, nd.p[a]) - ob[a]) * idir[a];
-                        float t1 = (std::fma(static_cast<float>(nd.qhi[a][s]), step, nd.p[a]) - ob[a]) * idir[a];
-                        if (t0 > t1) std::swap(t0, t1);
-                        tn = std::max(tn, t0);
-                        tf = std::min(tf, t1);
-                    }
-                    if (tn <= tf * 1.00001f + 1e-7f) hc[nh++] = { tn, s };
-                }
-                std::sort(hc, hc + nh, [](const Cand& p, const Cand& q) { return p.tn < q.tn; });
-                // the node's leaf triangles first (the dual step), nearest leaf first
-                for (int i = 0; i < nh && !hit; ++i) {
-                    if ((nd.imask >> hc[i].s) & 1u) continue;
-                    uint32_t t[kBvh8MaxLeafSize];
-                    const int c = bvh8SlotTriangles(nd, hc[i].s, t);
-                    for (int j = 0; j < c && !hit; ++j) {
-                        steps++;
-                        const GpuTriangle& g = tris[t[j]];
-                        const float v0[3] = { g.t0[0], g.t0[1], g.t0[2] }, e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-                        const float pv[3] = { L[1] * e2[2] - L[2] * e2[1], L[2] * e2[0] - L[0] * e2[2], L[0] * e2[1] - L[1] * e2[0] };
-                        const float det = e1[0] * pv[0] + e1[1] * pv[1] + e1[2] * pv[2];
-                        if (det == 0.0f) continue;
-                        const float inv = 1.0f / det;
-                        const float sv[3] = { P[0] - v0[0], P[1] - v0[1], P[2] - v0[2] };
-                        const float u = (sv[0] * pv[0] + sv[1] * pv[1] + sv[2] * pv[2]) * inv;
-                        if (!(u >= 0.0f && u <= 1.0f)) continue;
-                        const float q[3] = { sv[1] * e1[2] - sv[2] * e1[1], sv[2] * e1[0] - sv[0] * e1[2], sv[0] * e1[1] - sv[1] * e1[0] };
-                        const float v = (L[0] * q[0] + L[1] * q[1] + L[2] * q[2]) * inv;
-                        if (!(v >= 0.0f && u + v <= 1.0f)) continue;
-                        const float tt = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) * inv;
-                        hit = tt >= tmin && tt <= tmax;
-                    }
-                }
-                for (int i = nh - 1; i >= 0 && !hit; --i)
-                    if ((nd.imask >> hc[i].s) & 1u) stack.push_back(nd.child_base + before[hc[i].s]);
-            }
-        }
-    }
-    return static_cast<double>(steps) / static_cast<double>(n);
-}
-
-} // namespace ark
-
-
-// ark_ddgi_debug.h: the sun's light-space BVH on the host (no GPU), checked against
-// brute force. Builds it as set_scene does (sun_frame, sun_add_triangles,
-// build_sun_bvh), then for every origin traces a sun shadow ray (L = -normalize(sun
-// dir) in fp32, [0.025, tmax]) twice: through the BVH with a host restatement of
-// k_trace_shadow<SUN>'s node test (visitNodeSun: the same fp32 quantized coordinate,
-// floor / ceil, integer plane compares) and against every triangle; both use the same
-// Möller–Trumbore (the kernels' operation order). out[8] = {rays, occluded (brute
-// force), occluded (BVH), mismatches, node visits, triangle tests, BVH8 nodes, max
-// stack depth}. A mismatch would be a culled occluder: the node test must be
-// conservative.
-namespace {
-// A sun shadow ray per origin traced through the light-space BVH (nodes, tris) by the host
-// restatement of visitNodeSun and against every record of `world`: out[0..7] as
-// ark_ddgi_debug_sun_bvh_check's; the mismatching rays returned
-uint64_t sunRayCompare(const std::vector<ark::GpuBvh8Node>& nodes, const std::vector<ark::GpuTriangle>& tris, const std::vector<ark::GpuTriangle>& world,
-                       const double frame[3][3], const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, uint64_t* out)
-{
-    using namespace ark;
-    float F[9];
-    for (int a = 0; a < 3; ++a)
-        for (int k = 0; k < 3; ++k) F[a * 3 + k] = static_cast<float>(frame[a][k]);
-    const float dd = sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2];
-    const float sc = 1.0f / std::sqrt(dd);
-    const float L[3] = { -(sun_dir[0] * sc), -(sun_dir[1] * sc), -(sun_dir[2] * sc) };
-    const float tmin = 0.025f;
-    // the kernels' Möller–Trumbore (intersectTri: crossFma / dotFma3, 1 / det)
-    auto mt = [&](const float o[3], const GpuTriangle& g) {
-        const float v0[3] = { g.t0[0], g.t0[1], g.t0[2] }, e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-        auto cr = [](const float* a, const float* b, float* c) {
-            c[0] = std::fma(a[1], b[2], -(a[2] * b[1]));
-            c[1] = std::fma(a[2], b[0], -(a[0] * b[2]));
-            c[2] = std::fma(a[0], b[1], -(a[1] * b[0]));
-        };
-        auto dt = [](const float* a, const float* b) { return std::fma(a[0], b[0], std::fma(a[1], b[1], a[2] * b[2])); };
-        float p[3], q[3];
-        cr(L, e2, p);
-        const float det = dt(e1, p);
-        const float inv = 1.0f / det;
-        const float s[3] = { o[0] - v0[0], o[1] - v0[1], o[2] - v0[2] };
-        const float u = dt(s, p) * inv;
-        cr(s, e1, q);
-        const float v = dt(L, q) * inv;
-        const float t = dt(e2, q) * inv;
-        return (u >= 0.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (t >= tmin) & (t <= tmax);
-    };
-    std::atomic<uint64_t> occB { 0 }, occV { 0 }, mism { 0 }, visits { 0 }, tests { 0 }, maxDepth { 0 };
-    auto worker = [&](uint64_t r0, uint64_t r1) {
-        for (uint64_t ri = r0; ri < r1; ++ri) {
-            const float* o = origins + 3 * ri;
-            bool brute = false;
-            for (const GpuTriangle& g : world)
-                if (mt(o, g)) {
-                    brute = true;
-                    break;
-                }
-            // light-space traversal (visitNodeSun)
-            const float pl[3] = { std::fma(o[0], F[0], std::fma(o[1], F[1], o[2] * F[2])), std::fma(o[0], F[3], std::fma(o[1], F[4], o[2] * F[5])),
-                                  std::fma(o[0], F[6], std::fma(o[1], F[7], o[2] * F[8])) };
-            std::vector<uint32_t> stack { 0u };
-            bool bvh = false;
-            uint64_t nv = 0, nt = 0, md = 0;
-            while (!stack.empty() && !bvh) {
-                const GpuBvh8Node& nd = nodes[stack.back()];
-                stack.pop_back();
-                nv++;
-                int F_[2], C_[3];
-                float Q[3];
-                for (int a = 0; a < 3; ++a) {
-                    const float q = std::ldexp(pl[a] - nd.p[a], 127 - static_cast<int>(nd.e[a]));
-                    Q[a] = std::min(258.0f, std::max(-2.0f, q));
-                }
-                F_[0] = static_cast<int>(std::floor(Q[0]));
-                F_[1] = static_cast<int>(std::floor(Q[1]));
-                for (int a = 0; a < 3; ++a) C_[a] = static_cast<int>(std::ceil(Q[a]));
-                uint32_t internalBefore = 0;
-                std::vector<uint32_t> push;
-                for (int sl = 0; sl < 8; ++sl) {
-                    const bool internal = (nd.imask >> sl) & 1u;
-                    const bool hitc = nd.qlo[0][sl] <= F_[0] && nd.qhi[0][sl] >= C_[0] && nd.qlo[1][sl] <= F_[1] && nd.qhi[1][sl] >= C_[1] &&
-                                      nd.qhi[2][sl] >= C_[2];
-                    if (internal) {
-                        if (hitc) push.push_back(nd.child_base + internalBefore);
-                        internalBefore++;
-                        continue;
-                    }
-                    if (!hitc || !((nd.leaf_mask >> sl) & 1u)) continue;
-                    uint32_t st[kBvh8MaxLeafSize];
-                    const int cnt = bvh8SlotTriangles(nd, sl, st);
-                    for (int i = 0; i < cnt && !bvh; ++i) {
-                        nt++;
-                        bvh = mt(o, tris[st[i]]);
-                    }
-                }
-                for (size_t i = push.size(); i-- > 0;) stack.push_back(push[i]);
-                md = std::max<uint64_t>(md, stack.size());
-            }
-            occB += brute ? 1 : 0;
-            occV += bvh ? 1 : 0;
-            mism += brute != bvh ? 1 : 0;
-            visits += nv;
-            tests += nt;
-            uint64_t m = maxDepth.load();
-            while (md > m && !maxDepth.compare_exchange_weak(m, md)) {}
-        }
-    };
-    const int T = 8;
-    std::vector<std::thread> pool;
-    for (int t = 0; t < T; ++t) pool.emplace_back(worker, n_rays * t / T, n_rays * (t + 1) / T);
-    for (auto& th : pool) th.join();
-    if (out) {
-        out[0] = n_rays;
-        out[1] = occB.load();
-        out[2] = occV.load();
-        out[3] = mism.load();
-        out[4] = visits.load();
-        out[5] = tests.load();
-        out[6] = nodes.size();
-        out[7] = maxDepth.load();
-    }
-    return mism.load();
-}
-} // namespace
-
-
-
-
-extern "C" int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
-                                             uint64_t* out)
-{
-    using namespace ark;
-    std::vector<BuildTriangle> tris(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) {
-            tris[i].v0[a] = triangles[9 * i + a];
-            tris[i].v1[a] = triangles[9 * i + 3 + a];
-            tris[i].v2[a] = triangles[9 * i + 6 + a];
-        }
-        tris[i].instance = 0;
-        tris[i].primitive = static_cast<uint32_t>(i);
-        tris[i].flip_facing = 0;
-    }
-    SunBvhInput in;
-    sun_frame(sun_dir, in.frame);
-    sun_add_triangles(in, tris);
-    std::vector<GpuTriangle> world = in.world;
-    BvhBuildOptions opt;
-    opt.threads = 8;
-    Bvh8CollapseOptions copt;
-    Bvh8BuildResult r;
-    if (n == 0 || !build_sun_bvh(in, opt, copt, r)) return 1;
-    return sunRayCompare(r.nodes, r.tris, world, in.frame, sun_dir, origins, n_rays, tmax, out) == 0 ? 0 : 2;
-}
-
-
-// ark_ddgi_debug.h: set_scene's choice between the light-space BVH and the world BVH
-// for the sun's shadow rays, on a triangle soup (one hit-mask class).
-extern "C" int ark_ddgi_debug_sun_choice(const float* triangles, uint64_t n, const float* sun_dir, uint32_t n_samples, double* out)
-{
-    using namespace ark;
-    if (n == 0 || !out) return 1;
-    std::vector<BuildTriangle> tris(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) {
-            tris[i].v0[a] = triangles[9 * i + a];
-            tris[i].v1[a] = triangles[9 * i + 3 + a];
-            tris[i].v2[a] = triangles[9 * i + 6 + a];
-        }
-        tris[i].instance = 0;
-        tris[i].primitive = static_cast<uint32_t>(i);
-        tris[i].flip_facing = 0;
-    }
-    SunBvhInput in;
-    sun_frame(sun_dir, in.frame);
-    sun_add_triangles(in, tris);
-    double frame[3][3];
-    std::memcpy(frame, in.frame, sizeof(frame));
-    BvhBuildOptions opt;
-    opt.max_leaf_size = kBvh8MaxLeafSize;
-    opt.inflate_abs = bvh8_inflation(triangles, n);
-    opt.threads = 8;
-    Bvh8CollapseOptions copt;
-    const BvhBuildResult r2 = build_bvh(tris, opt, 0u, 0u);
-    if (r2.max_leaf > static_cast<uint32_t>(kBvh8MaxLeafSize)) return 1;
-    const Bvh8BuildResult w8 = collapse_bvh8(r2, 0u, 0u, copt);
-    Bvh8BuildResult s8;
-    if (!build_sun_bvh(in, opt, copt, s8)) return 1;
-    const float dd = sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2];
-    const float sc = 1.0f / std::sqrt(dd);
-    const float L[3] = { -(sun_dir[0] * sc), -(sun_dir[1] * sc), -(sun_dir[2] * sc) };
-    std::vector<float> origins;
-    sun_sample_origins(w8.tris, L, n_samples, origins);
-    const int32_t root = 0;
-    out[0] = sun_shadow_cost(w8.nodes, w8.tris, &root, 1, nullptr, L, origins);
-    out[1] = sun_shadow_cost(s8.nodes, s8.tris, &root, 1, frame, L, origins);
-    out[2] = sun_bvh_pays(out[0], out[1]) ? 1.0 : 0.0;
-    out[3] = static_cast<double>(origins.size() / 3);
-    return 0;
-}
-
-// --- the device LBVH's build logic on the host (lbvh_build.h) and the checks shared by
-// ark_ddgi_debug_lbvh_check and ark_ddgi_debug_world_bvh_check ------------------------
-namespace ark {
-
-namespace {
-// writeNode's inflation of a child box (k_refit_nodes inflateBox)
-void inflateChildBox(Aabb& b, float inflateAbs)
-{
-    float m = 0.0f, e = 0.0f;
-    for (int a = 0; a < 3; ++a) {
-        m = std::max(m, std::max(std::fabs(b.lo[a]), std::fabs(b.hi[a])));
-        e = std::max(e, b.hi[a] - b.lo[a]);
-    }
-    const float eps = m * 2e-6f + e * 1e-5f + 1e-7f + inflateAbs;
-    for (int a = 0; a < 3; ++a) {
-        b.lo[a] -= eps;
-        b.hi[a] += eps;
-    }
-}
-
-// the vertices Möller-Trumbore tests: v0, v0 + e1, v0 + e2
-void recordVertices(const GpuTriangle& g, float v[3][3])
-{
-    const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-    for (int a = 0; a < 3; ++a) {
-        v[0][a] = g.t0[a];
-        v[1][a] = g.t0[a] + e1[a];
-        v[2][a] = g.t0[a] + e2[a];
-    }
-}
-} // namespace
-
-namespace {
-// k_lbvh_treelet_sah, serially: the binary tree of one treelet T (4 .. kTreeletPrims
-// primitives) by a three-axis sweep SAH. box: 6 ordered words per sorted primitive, as the
-// sort left them. sorted and split are rewritten inside T's range, nbox and pbox filled.
-void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std::vector<uint32_t>& sorted, std::vector<uint32_t>& split, std::vector<float>& nbox,
-                    std::vector<float>& pbox)
-{
-    const uint32_t first = T.r.first, n = lbvh::count(T.r);
-    auto at = [&](uint32_t prim) { return &box[6ull * (first + prim)]; };
-    std::vector<uint32_t> ord[3];
-    for (int ax = 0; ax < 3; ++ax) {
-        std::vector<uint32_t> key(n);
-        for (uint32_t p = 0; p < n; ++p) key[p] = lbvh::sweepKey(lbvh::orderedFloat(at(p)[ax]), lbvh::orderedFloat(at(p)[3 + ax]));
-        ord[ax].resize(n);
-        for (uint32_t p = 0; p < n; ++p) ord[ax][p] = p;
-        std::stable_sort(ord[ax].begin(), ord[ax].end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-    }
-    struct Segment {
-        uint32_t f, l, node; // positions and node index relative to `first`
-    };
-    std::vector<Segment> todo(1, Segment { 0u, n - 1u, T.node - first }), final;
-    std::vector<uint32_t> splitRel(n, 0xffffffffu);
-    std::vector<uint8_t> side(n, 0);
-    auto unite = [](uint32_t u[6], const uint32_t* b) {
-        for (int c = 0; c < 3; ++c) {
-            u[c] = std::min(u[c], b[c]);
-            u[3 + c] = std::max(u[3 + c], b[3 + c]);
-        }
-    };
-    while (!todo.empty()) {
-        const Segment sg = todo.back();
-        todo.pop_back();
-        const uint32_t cnt = sg.l - sg.f + 1u;
-        if (cnt <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
-            final.push_back(sg);
-            continue;
-        }
-        uint64_t best = lbvh::kNoSplit;
-        for (int ax = 0; ax < 3; ++ax) {
-            std::vector<std::array<uint32_t, 6>> pre(cnt), suf(cnt);
-            uint32_t u[6] = { ~0u, ~0u, ~0u, 0u, 0u, 0u };
-            for (uint32_t i = 0; i < cnt; ++i) {
-                unite(u, at(ord[ax][sg.f + i]));
-                std::copy(u, u + 6, pre[i].begin());
-            }
-            uint32_t v[6] = { ~0u, ~0u, ~0u, 0u, 0u, 0u };
-            for (uint32_t i = cnt; i-- > 0;) {
-                unite(v, at(ord[ax][sg.f + i]));
-                std::copy(v, v + 6, suf[i].begin());
-            }
-            if (ax == 0)
-                for (int c = 0; c < 6; ++c) nbox[6ull * (first + sg.node) + c] = lbvh::orderedFloat(pre[cnt - 1u][c]);
-            for (uint32_t k = 1; k < cnt; ++k) best = std::min(best, lbvh::splitKey(lbvh::halfArea(pre[k - 1u].data()), lbvh::halfArea(suf[k].data()), k, cnt, static_cast<uint32_t>(ax)));
-        }
-        uint32_t axis, k;
-        lbvh::chosenSplit(best, cnt, axis, k);
-        for (uint32_t i = 0; i < cnt; ++i) side[ord[axis][sg.f + i]] = i >= k ? 1 : 0;
-        for (int b = 0; b < 3; ++b) std::stable_partition(ord[b].begin() + sg.f, ord[b].begin() + sg.l + 1u, [&](uint32_t p) { return side[p] == 0; });
-        splitRel[sg.node] = sg.f + k - 1u;
-        todo.push_back(Segment { sg.f, sg.f + k - 1u, sg.f + k - 1u });
-        todo.push_back(Segment { sg.f + k, sg.l, sg.f + k });
-    }
-    for (const Segment& sg : final)
-        for (uint32_t i = sg.f; i <= sg.l; ++i)
-            if (splitRel[i] == 0xffffffffu) splitRel[i] = sg.f;
-    std::vector<uint32_t> src(n);
-    for (uint32_t i = 0; i < n; ++i) src[i] = sorted[first + i];
-    for (uint32_t i = 0; i < n; ++i) {
-        const uint32_t prim = ord[0][i];
-        sorted[first + i] = src[prim];
-        for (int c = 0; c < 6; ++c) pbox[6ull * (first + i) + c] = lbvh::orderedFloat(at(prim)[c]);
-        if (first + i != lbvh::treeletSpareIndex(T)) split[first + i] = first + splitRel[i];
-    }
-}
-} // namespace
-
-LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun,
-                               const std::vector<uint32_t>* primOrder, bool sahPass)
-{
-    LbvhHostResult R;
-    if (sahPass) criterion = lbvh::kOpenLargestBox;
-    const lbvh::KeyLayout layout = { sun ? sun->wBits : lbvh::kMortonBits };
-    const int slotRule = sun ? lbvh::kSlotsAscendingW : lbvh::kSlotsOctant;
-    // the vertices a record is boxed by: the world ones, or their light coordinates
-    float maxAbs = 0.0f;
-    auto boxVertices = [&](const GpuTriangle& g, float v[3][3]) {
-        if (!sun) return recordVertices(g, v);
-        const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-        float m;
-        lbvh::lightVertices(g.t0, e1, e2, sun->frame, v, m);
-        maxAbs = std::max(maxAbs, m);
-    };
-    // primitives: the records that are not holes, their boxes, the scene box
-    std::vector<uint32_t> idx;
-    std::vector<Aabb> pbox;
-    Aabb scene;
-    if (primOrder) {
-        idx = *primOrder;
-    } else {
-        for (size_t i = 0; i < rec.size(); ++i)
-            if (!isHoleTriangle(rec[i])) idx.push_back(static_cast<uint32_t>(i));
-    }
-    for (uint32_t i : idx) {
-        float v[3][3];
-        boxVertices(rec[i], v);
-        Aabb b;
-        for (int k = 0; k < 3; ++k) b.grow(v[k]);
-        scene.grow(b);
-        pbox.push_back(b);
-    }
-    const uint32_t n = static_cast<uint32_t>(idx.size());
-    // (the light-space inflation: build_sun_bvh's expression)
-    const float inflateAbs = !n ? 0.0f : sun ? 2.0f * bvh8_inflation_box(scene.lo, scene.hi) + 2e-6f * maxAbs : bvh8_inflation_box(scene.lo, scene.hi);
-    R.inflateAbs = inflateAbs;
-    float scale[3], extent[3];
-    for (int a = 0; a < 3; ++a) {
-        scale[a] = n ? lbvh::mortonScale(scene.lo[a], scene.hi[a]) : 0.0f;
-        extent[a] = n ? scene.hi[a] - scene.lo[a] : 0.0f;
-    }
-    auto instanceOf = [&](uint32_t record) {
-        uint32_t inst;
-        std::memcpy(&inst, &rec[record].t2[1], 4);
-        return inst;
-    };
-    std::vector<uint64_t> key(n);
-    uint32_t classCount[3] = { 0, 0, 0 };
-    for (uint32_t j = 0; j < n; ++j) {
-        float c[3];
-        for (int a = 0; a < 3; ++a) c[a] = 0.5f * pbox[j].lo[a] + 0.5f * pbox[j].hi[a];
-        const uint32_t inst = instanceOf(idx[j]);
-        const int cls = sun ? 0 : inst < classOf.size() ? classOf[inst] : 0; // the sun's: one tree for all classes
-        classCount[cls]++;
-        key[j] = sun ? lbvh::lightKey(c, scene.lo, scene.hi, layout) : lbvh::mortonKey(c, scene.lo, scale, static_cast<uint32_t>(cls));
-    }
-    std::vector<uint32_t> sorted(n);
-    for (uint32_t j = 0; j < n; ++j) sorted[j] = j;
-    std::stable_sort(sorted.begin(), sorted.end(), [&](uint32_t a, uint32_t b) { return key[a] < key[b]; });
-    std::vector<uint64_t> keys(n);
-    for (uint32_t j = 0; j < n; ++j) keys[j] = key[sorted[j]];
-    std::vector<uint32_t> split(n, 0u), position(n, 0u);
-    // the record of each sorted primitive; the SAH pass permutes it inside its treelets
-    std::vector<uint32_t> sortedRec(n);
-    for (uint32_t j = 0; j < n; ++j) sortedRec[j] = idx[sorted[j]];
-    lbvh::SahBoxes boxes {};
-    std::vector<uint32_t> obox; // the sorted primitives' boxes as ordered words
-    if (sahPass) {
-        R.idxMorton = sortedRec;
-        R.nbox.assign(n * 6ull, 0.0f);
-        R.pbox.assign(n * 6ull, 0.0f);
-        obox.resize(n * 6ull);
-        for (uint32_t j = 0; j < n; ++j) {
-            float v[3][3];
-            boxVertices(rec[sortedRec[j]], v);
-            lbvh::primBox(v, &obox[6ull * j]);
-        }
-        boxes.nbox = R.nbox.data();
-        boxes.pbox = R.pbox.data();
-        for (int a = 0; a < 3; ++a) {
-            boxes.lo[a] = scene.lo[a];
-            boxes.hi[a] = scene.hi[a];
-        }
-    }
-    const lbvh::SahBoxes* sahBoxes = sahPass ? &boxes : nullptr;
-    // hierarchy and collapse, class by class, level by level (the kernels' atomics: plain counters)
-    uint32_t records = 0, first = 0;
-    std::vector<std::vector<uint32_t>> levels; // node counts [depth][class]
-    for (int c = 0; c < 3; ++c) {
-        const uint32_t lo = first, hi = first + classCount[c];
-        first = hi;
-        if (lo == hi) continue;
-        const size_t firstTreelet = R.treelets.size();
-        for (uint32_t i = lo; i + 1u < hi; ++i) {
-            const lbvh::Range r = lbvh::nodeRange(keys.data(), lo, hi, i);
-            split[i] = lbvh::findSplit(keys.data(), lo, hi, r);
-            if (!sahPass) continue;
-            // the SAH pass's work list (k_lbvh_hierarchy's appends; any order)
-            lbvh::Member m[2];
-            const int k = lbvh::treeletsOf(r, split[i], i == lo, m);
-            R.treelets.insert(R.treelets.end(), m, m + k);
-        }
-        for (size_t t = firstTreelet; t < R.treelets.size(); ++t) treeletSahHost(R.treelets[t], obox, sortedRec, split, R.nbox, R.pbox);
-        R.roots[c] = static_cast<int32_t>(R.nodes.size());
-        std::vector<lbvh::Member> level(1), next;
-        level[0].r.first = lo;
-        level[0].r.last = hi - 1u;
-        level[0].node = lo;
-        R.nodes.resize(R.nodes.size() + 1);
-        uint32_t levelBase = static_cast<uint32_t>(R.roots[c]), depth = 0;
-        while (!level.empty()) {
-            ++depth;
-            next.clear();
-            const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
-            for (size_t i = 0; i < level.size(); ++i) {
-                lbvh::WideNode w;
-                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout, sahBoxes);
-                const uint32_t slot0 = static_cast<uint32_t>(next.size());
-                const uint32_t triBase = w.rows.span ? records : 0u;
-                records += w.rows.span;
-                GpuBvh8Node nd;
-                std::memset(&nd, 0, sizeof(nd));
-                nd.imask = static_cast<uint8_t>(w.imask);
-                nd.child_base = nextBase + slot0;
-                nd.tri_base = triBase;
-                nd.leaf_tris = w.rows.leaf_tris;
-                nd.tri_stride = static_cast<uint8_t>(w.rows.stride);
-                nd.leaf_mask = static_cast<uint8_t>(w.rows.leaf_mask);
-                R.nodes[levelBase + i] = nd;
-                int64_t lastLow = -1;
-                for (uint32_t s = 0; s < 8u; ++s) {
-                    const int k = lbvh::memberInSlot(w, s);
-                    if (k < 0) continue;
-                    const lbvh::Member& m = w.member[k];
-                    if (sun) {
-                        // the occupied slots' Morton cells ascend in their low w edge, without a gap
-                        const int64_t low = lbvh::memberLowW(keys.data(), m, layout, sahBoxes);
-                        if (low < lastLow || s >= static_cast<uint32_t>(w.members)) R.slotOrderViolations++;
-                        lastLow = low;
-                    }
-                    if ((w.imask >> s) & 1u) {
-                        next.push_back(m);
-                    } else {
-                        R.leafChildren++;
-                        for (uint32_t t = 0; t < lbvh::count(m.r); ++t) position[m.r.first + t] = triBase + s + w.rows.stride * t;
-                    }
-                }
-            }
-            R.nodes.resize(R.nodes.size() + next.size());
-            if (levels.size() < depth) levels.resize(depth, std::vector<uint32_t>(3, 0u));
-            levels[depth - 1][c] = static_cast<uint32_t>(level.size());
-            levelBase = nextBase;
-            level.swap(next);
-        }
-        if (c == 0) R.opaqueNodes = static_cast<uint32_t>(R.nodes.size());
-        R.depth = std::max(R.depth, depth);
-    }
-    for (int c = 0; c < 3; ++c) R.classCount[c] = classCount[c];
-    for (int a = 0; a < 3 && n; ++a) {
-        R.sceneLo[a] = scene.lo[a];
-        R.sceneHi[a] = scene.hi[a];
-    }
-    R.maxAbs = maxAbs;
-    R.idxSorted.resize(n);
-    for (uint32_t j = 0; j < n; ++j) R.idxSorted[j] = sortedRec[j];
-    R.keysSorted = keys;
-    R.split = split;
-    // scatter
-    R.tris.assign(records, holeTriangle());
-    R.perm.assign(records, 0xffffffffu);
-    for (uint32_t j = 0; j < n; ++j) {
-        const uint32_t src = sortedRec[j];
-        R.tris[position[j]] = rec[src];
-        R.perm[position[j]] = src;
-    }
-    R.triangles = n;
-    // level order: deepest first, ascending node index within a level (bvhLevelOrder's format)
-    {
-        std::vector<uint32_t> classBase(3, 0u);
-        for (int c = 0; c < 3; ++c) classBase[c] = R.roots[c] >= 0 ? static_cast<uint32_t>(R.roots[c]) : 0u;
-        std::vector<std::vector<uint32_t>> byDepth(levels.size());
-        for (size_t d = 0; d < levels.size(); ++d)
-            for (int c = 0; c < 3; ++c) {
-                for (uint32_t k = 0; k < levels[d][c]; ++k) byDepth[d].push_back(classBase[c] + k);
-                classBase[c] += levels[d][c];
-            }
-        R.levelOffsets.assign(1, 0u);
-        for (size_t d = byDepth.size(); d-- > 0;) {
-            R.order.insert(R.order.end(), byDepth[d].begin(), byDepth[d].end());
-            R.levelOffsets.push_back(static_cast<uint32_t>(R.order.size()));
-        }
-    }
-    // boxes from the records upward, the planes by the node writer (what k_refit_nodes
-    // does on the device): children have higher indices than their parent
-    std::vector<Aabb> nodeBox(R.nodes.size());
-    double sah = 0.0;
-    std::vector<double> childArea(R.nodes.size(), 0.0); // sum over a node's children of area x cost
-    std::vector<double> unionArea(R.nodes.size(), 0.0); // area of the union of a node's child boxes
-    for (size_t k = R.nodes.size(); k-- > 0;) {
-        GpuBvh8Node& nd = R.nodes[k];
-        Aabb slot[8], box;
-        const Aabb* slotBox[8];
-        uint32_t internal = 0;
-        for (int s = 0; s < 8; ++s) {
-            slotBox[s] = nullptr;
-            double cost = 1.0;
-            if ((nd.imask >> s) & 1u) {
-                slot[s] = nodeBox[nd.child_base + internal++];
-            } else if ((nd.leaf_mask >> s) & 1u) {
-                uint32_t t[kBvh8MaxLeafSize];
-                const int cnt = bvh8SlotTriangles(nd, s, t);
-                for (int i = 0; i < cnt; ++i) {
-                    float v[3][3];
-                    boxVertices(R.tris[t[i]], v);
-                    for (int q = 0; q < 3; ++q) slot[s].grow(v[q]);
-                }
-                inflateChildBox(slot[s], inflateAbs);
-                cost = std::max(cnt, 0);
-            } else {
-                continue;
-            }
-            slotBox[s] = &slot[s];
-            box.grow(slot[s]);
-            childArea[k] += static_cast<double>(slot[s].area()) * cost;
-        }
-        writeNodePlanes(nd, box, slotBox);
-        nodeBox[k] = box;
-        unionArea[k] = box.area();
-        inflateChildBox(nodeBox[k], inflateAbs);
-    }
-    // BVH8 SAH cost of the opaque class relative to its root's box (node 1, triangle 1: collapseQueue's)
-    if (R.roots[0] >= 0) {
-        const uint32_t r0 = static_cast<uint32_t>(R.roots[0]);
-        const double rootArea = std::max(1e-30, unionArea[r0]);
-        sah = 1.0;
-        for (uint32_t k = r0; k < r0 + R.opaqueNodes; ++k) sah += childArea[k] / rootArea;
-    }
-    R.sah = sah;
-    return R;
-}
-
-Bvh8CheckResult check_bvh8_full(const std::vector<GpuBvh8Node>& nodes, const std::vector<GpuTriangle>& tris, const int32_t* roots, int nRoots,
-                                const std::vector<int>* classOf, const float* vertices, const double* lightFrame)
-{
-    Bvh8CheckResult R;
-    struct Box {
-        float lo[3], hi[3];
-    };
-    struct Item {
-        uint32_t node;
-        int32_t parent; // item of the parent's slot box (-1: a root)
-        Box box;        // this node's box as its parent decodes it
-        uint32_t depth;
-    };
-    std::vector<uint8_t> seenTri(tris.size(), 0), seenNode(nodes.size(), 0);
-    for (int c = 0; c < nRoots; ++c) {
-        if (roots[c] < 0) continue;
-        // breadth first: the class's nodes must be roots[c], roots[c] + 1, ... in this order
-        std::vector<Item> items;
-        items.push_back({ static_cast<uint32_t>(roots[c]), -1, {}, 1u });
-        uint32_t lowest = 0xffffffffu, highest = 0u;
-        uint64_t classNodes = 0;
-        std::vector<uint32_t> levelLo, levelHi, levelCount; // of the nodes of each depth
-        for (size_t qi = 0; qi < items.size(); ++qi) {
-            const Item it = items[qi];
-            if (it.node >= nodes.size() || seenNode[it.node]) {
-                R.violations++;
-                continue;
-            }
-            seenNode[it.node] = 1;
-            R.nodes++;
-            if (levelLo.size() < it.depth) {
-                levelLo.resize(it.depth, 0xffffffffu);
-                levelHi.resize(it.depth, 0u);
-                levelCount.resize(it.depth, 0u);
-            }
-            levelLo[it.depth - 1] = std::min(levelLo[it.depth - 1], it.node);
-            levelHi[it.depth - 1] = std::max(levelHi[it.depth - 1], it.node);
-            levelCount[it.depth - 1]++;
-            lowest = std::min(lowest, it.node);
-            highest = std::max(highest, it.node);
-            classNodes++;
-            R.maxDepth = std::max<uint64_t>(R.maxDepth, it.depth);
-            const GpuBvh8Node& nd = nodes[it.node];
-            if ((nd.leaf_tris >> 24) || (nd.leaf_mask & nd.imask)) R.violations++;
-            uint32_t internal = 0;
-            for (int s = 0; s < 8; ++s) {
-                const bool in = (nd.imask >> s) & 1u;
-                uint32_t slotTris[kBvh8MaxLeafSize];
-                const int cnt = bvh8SlotTriangles(nd, s, slotTris);
-                if (cnt < 0) {
-                    R.violations++;
-                    continue;
-                }
-                if (!in && cnt == 0) continue;
-                Box b;
-                for (int a = 0; a < 3; ++a) {
-                    const float step = std::ldexp(1.0f, static_cast<int>(nd.e[a]) - 127);
-                    b.lo[a] = std::fma(static_cast<float>(nd.qlo[a][s]), step, nd.p[a]);
-                    b.hi[a] = std::fma(static_cast<float>(nd.qhi[a][s]), step, nd.p[a]);
-                    if (static_cast<double>(b.lo[a]) != static_cast<double>(nd.p[a]) + nd.qlo[a][s] * static_cast<double>(step)) R.violations++;
-                    if (static_cast<double>(b.hi[a]) != static_cast<double>(nd.p[a]) + nd.qhi[a][s] * static_cast<double>(step)) R.violations++;
-                }
-                if (in) {
-                    R.internalChildren++;
-                    items.push_back({ nd.child_base + internal++, static_cast<int32_t>(qi), b, it.depth + 1u });
-                    continue;
-                }
-                R.leafChildren++;
-                for (int ti = 0; ti < cnt; ++ti) {
-                    const uint32_t t = slotTris[ti];
-                    if (t >= tris.size() || isHoleTriangle(tris[t]) || seenTri[t]) {
-                        R.violations++;
-                        continue;
-                    }
-                    seenTri[t] = 1;
-                    R.triangles++;
-                    const GpuTriangle& g = tris[t];
-                    uint32_t inst, prim;
-                    std::memcpy(&inst, &g.t2[1], 4);
-                    std::memcpy(&prim, &g.t2[2], 4);
-                    if (classOf && (inst >= classOf->size() || (*classOf)[inst] != c)) R.violations++; // under the wrong class's root
-                    float v[6][3];
-                    recordVertices(g, v);
-                    if (lightFrame) {
-                        const float e1[3] = { g.t0[3], g.t1[0], g.t1[1] }, e2[3] = { g.t1[2], g.t1[3], g.t2[0] };
-                        float m;
-                        lbvh::lightVertices(g.t0, e1, e2, lightFrame, v, m);
-                    }
-                    int nv = 3;
-                    if (vertices) {
-                        std::memcpy(v[3], vertices + 9ull * prim, 9 * sizeof(float));
-                        nv = 6;
-                    }
-                    // inside the leaf slot's box and every ancestor's
-                    const Box* bx = &b;
-                    for (int32_t up = static_cast<int32_t>(qi);; up = items[up].parent) {
-                        for (int k = 0; k < nv; ++k)
-                            for (int a = 0; a < 3; ++a)
-                                if (!(v[k][a] >= bx->lo[a] && v[k][a] <= bx->hi[a])) R.violations++;
-                        if (items[up].parent < 0) break;
-                        bx = &items[up].box;
-                    }
-                }
-            }
-        }
-        // the class's nodes are the range [root, root + count)
-        if (classNodes && (lowest != static_cast<uint32_t>(roots[c]) || highest - lowest + 1u != classNodes)) R.notContiguous++;
-        // breadth first: each depth's nodes one range behind the depth above's
-        uint32_t at = static_cast<uint32_t>(roots[c]);
-        for (size_t d = 0; d < levelCount.size(); ++d) {
-            if (levelLo[d] != at || levelHi[d] - levelLo[d] + 1u != levelCount[d]) R.notBreadthFirst++;
-            at += levelCount[d];
-        }
-    }
-    for (size_t t = 0; t < tris.size(); ++t)
-        if (!seenTri[t] && !isHoleTriangle(tris[t])) R.violations++; // unreachable
-    R.violations += R.notContiguous;
-    return R;
-}
-
-Bvh8CanonicalDiff compare_bvh8_canonical(const Bvh8TreeView& A, const Bvh8TreeView& B)
-{
-    Bvh8CanonicalDiff D;
-    const Bvh8TreeView* T[2] = { &A, &B };
-    const std::vector<GpuBvh8Node>& na = *A.nodes;
-    const std::vector<GpuBvh8Node>& nb = *B.nodes;
-    auto span = [](const GpuBvh8Node& nd) { return nd.leaf_tris ? 32u - static_cast<uint32_t>(__builtin_clz(nd.leaf_tris)) : 0u; };
-    // each tree on its own: the level order, the padding record, the rows exactly the records
-    std::vector<uint64_t> perDepth[2];
-    for (int t = 0; t < 2; ++t) {
-        const std::vector<GpuBvh8Node>& nodes = *T[t]->nodes;
-        std::vector<uint32_t> order, offsets;
-        const bool walked = bvhLevelOrder(nodes.data(), nodes.size(), T[t]->roots, 3, order, offsets);
-        if (!walked) D.children++;
-        if (T[t]->order && T[t]->levelOffsets && (!walked || order != *T[t]->order || offsets != *T[t]->levelOffsets)) D.levelOrder++;
-        for (size_t l = 0; walked && l + 1 < offsets.size(); ++l) perDepth[t].push_back(offsets[l + 1] - offsets[l]); // (deepest first)
-        if (walked && (order.size() != nodes.size() || offsets.size() != static_cast<size_t>(T[t]->depth) + 1u)) D.shape++;
-        uint64_t rows = 0;
-        for (const GpuBvh8Node& nd : nodes) rows += span(nd);
-        if (rows != T[t]->tris->size()) D.shape++;
-        if (T[t]->perm && T[t]->perm->size() != T[t]->tris->size()) D.shape++;
-        if (T[t]->padding) {
-            const GpuTriangle zero {};
-            if (std::memcmp(T[t]->padding, &zero, sizeof(zero)) != 0) D.padding++;
-        }
-    }
-    if (perDepth[0] != perDepth[1]) D.shape++;
-    if (na.size() != nb.size() || A.tris->size() != B.tris->size() || A.opaqueNodes != B.opaqueNodes || A.depth != B.depth) D.shape++;
-    const bool perms = A.perm && B.perm && A.perm->size() == A.tris->size() && B.perm->size() == B.tris->size();
-    std::vector<uint8_t> seenA(na.size(), 0), seenB(nb.size(), 0);
-    std::vector<std::pair<uint32_t, uint32_t>> work;
-    for (int c = 0; c < 3; ++c) {
-        if ((A.roots[c] >= 0) != (B.roots[c] >= 0)) D.shape++;
-        else if (A.roots[c] >= 0) work.push_back({ static_cast<uint32_t>(A.roots[c]), static_cast<uint32_t>(B.roots[c]) });
-    }
-    while (!work.empty()) {
-        const auto [ia, ib] = work.back();
-        work.pop_back();
-        const uint64_t before = D.total();
-        if (ia >= na.size() || ib >= nb.size() || seenA[ia] || seenB[ib]) {
-            D.children++;
-        } else {
-            seenA[ia] = seenB[ib] = 1;
-            D.pairs++;
-            const GpuBvh8Node& a = na[ia];
-            const GpuBvh8Node& b = nb[ib];
-            const bool sameHeader = a.imask == b.imask && a.leaf_mask == b.leaf_mask && a.leaf_tris == b.leaf_tris && a.tri_stride == b.tri_stride;
-            if (!sameHeader) D.header++;
-            if (std::memcmp(a.p, b.p, sizeof(a.p)) != 0 || std::memcmp(a.e, b.e, sizeof(a.e)) != 0) D.grid++;
-            if (sameHeader) {
-                for (int s = 0; s < 8; ++s) {
-                    if (!(((a.imask | a.leaf_mask) >> s) & 1u)) continue;
-                    for (int ax = 0; ax < 3; ++ax)
-                        if (a.qlo[ax][s] != b.qlo[ax][s] || a.qhi[ax][s] != b.qhi[ax][s]) D.planes++;
-                }
-                // the rows, position by position: a leaf slot's records, holes elsewhere
-                for (uint32_t pos = 0; pos < span(a); ++pos) {
-                    const uint64_t ra = static_cast<uint64_t>(a.tri_base) + pos, rb = static_cast<uint64_t>(b.tri_base) + pos;
-                    if (ra >= A.tris->size() || rb >= B.tris->size()) {
-                        D.records++;
-                        continue;
-                    }
-                    const GpuTriangle& ta = (*A.tris)[ra];
-                    const GpuTriangle& tb = (*B.tris)[rb];
-                    if ((a.leaf_tris >> pos) & 1u) {
-                        if (std::memcmp(&ta, &tb, sizeof(GpuTriangle)) != 0 || isHoleTriangle(ta)) D.records++;
-                        if (perms && (*A.perm)[ra] != (*B.perm)[rb]) D.perm++;
-                    } else {
-                        const GpuTriangle hole = holeTriangle();
-                        if (std::memcmp(&ta, &hole, sizeof(hole)) != 0 || std::memcmp(&tb, &hole, sizeof(hole)) != 0) D.holes++;
-                        if (perms && ((*A.perm)[ra] != 0xffffffffu || (*B.perm)[rb] != 0xffffffffu)) D.holes++;
-                    }
-                }
-            }
-            // internal children by rank (as far as both have them)
-            const uint32_t ka = static_cast<uint32_t>(__builtin_popcount(a.imask)), kb = static_cast<uint32_t>(__builtin_popcount(b.imask));
-            for (uint32_t k = std::min(ka, kb); k-- > 0;) work.push_back({ a.child_base + k, b.child_base + k });
-        }
-        if (D.total() != before && D.firstA < 0) {
-            D.firstA = ia;
-            D.firstB = ib;
-        }
-    }
-    return D;
-}
-
-} // namespace ark
-
-// ark_ddgi_debug.h: what compare_bvh8_canonical notices, without a GPU
-namespace {
-using namespace ark;
-
-struct HostTree {
-    std::vector<GpuBvh8Node> nodes;
-    std::vector<GpuTriangle> tris;
-    std::vector<uint32_t> perm, order, levelOffsets;
-    int32_t roots[3] = { -1, -1, -1 };
-    uint32_t opaqueNodes = 0, depth = 0;
-    Bvh8TreeView view() const
-    {
-        Bvh8TreeView v;
-        v.nodes = &nodes;
-        v.tris = &tris;
-        v.perm = &perm;
-        v.order = &order;
-        v.levelOffsets = &levelOffsets;
-        std::copy(roots, roots + 3, v.roots);
-        v.opaqueNodes = opaqueNodes;
-        v.depth = depth;
-        return v;
-    }
-};
-
-uint32_t rowSpan(const GpuBvh8Node& nd) { return nd.leaf_tris ? 32u - static_cast<uint32_t>(__builtin_clz(nd.leaf_tris)) : 0u; }
-
-// What the device's atomics do to a tree: within each level of each class, the blocks of
-// siblings (child_base) and the rows (tri_base) handed out in another order
-HostTree shuffledTwin(const LbvhHostResult& r, uint64_t seed)
-{
-    HostTree t;
-    const uint32_t N = static_cast<uint32_t>(r.nodes.size());
-    uint64_t state = seed * 0x9e3779b97f4a7c15ull + 1u;
-    auto rnd = [&](uint32_t n) { // xorshift64*
-        state ^= state >> 12;
-        state ^= state << 25;
-        state ^= state >> 27;
-        return static_cast<uint32_t>(((state * 0x2545f4914f6cdd1dull) >> 33) % n);
-    };
-    auto shuffle = [&](std::vector<uint32_t>& v) {
-        for (size_t i = v.size(); i > 1; --i) std::swap(v[i - 1], v[rnd(static_cast<uint32_t>(i))]);
-    };
-    t.nodes.resize(N);
-    t.tris.assign(r.tris.size(), holeTriangle());
-    t.perm.assign(r.perm.size(), 0xffffffffu);
-    uint32_t records = 0;
-    for (int c = 0; c < 3; ++c) {
-        t.roots[c] = r.roots[c];
-        if (r.roots[c] < 0) continue;
-        std::vector<uint32_t> level(1, static_cast<uint32_t>(r.roots[c])); // old indices, in new index order
-        uint32_t levelBase = level[0];
-        while (!level.empty()) {
-            const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
-            // the sibling blocks of the next level, parent by parent in a shuffled order
-            std::vector<uint32_t> parents(level.size()), next;
-            for (uint32_t i = 0; i < parents.size(); ++i) parents[i] = i;
-            shuffle(parents);
-            std::vector<uint32_t> childBase(level.size(), 0u);
-            for (uint32_t i : parents) {
-                const GpuBvh8Node& nd = r.nodes[level[i]];
-                childBase[i] = nextBase + static_cast<uint32_t>(next.size());
-                for (int k = 0; k < __builtin_popcount(nd.imask); ++k) {
-                    next.push_back(nd.child_base + k);
-                }
-            }
-            // this level's rows in another shuffled order
-            shuffle(parents);
-            for (uint32_t i : parents) {
-                const GpuBvh8Node& nd = r.nodes[level[i]];
-                GpuBvh8Node out = nd;
-                out.child_base = childBase[i];
-                out.tri_base = rowSpan(nd) ? records : 0u;
-                for (uint32_t pos = 0; pos < rowSpan(nd); ++pos) {
-                    t.tris[out.tri_base + pos] = r.tris[nd.tri_base + pos];
-                    t.perm[out.tri_base + pos] = r.perm[nd.tri_base + pos];
-                }
-                records += rowSpan(nd);
-                t.nodes[levelBase + i] = out;
-            }
-            levelBase = nextBase;
-            level.swap(next);
-        }
-    }
-    t.opaqueNodes = r.opaqueNodes;
-    t.depth = r.depth;
-    bvhLevelOrder(t.nodes.data(), t.nodes.size(), t.roots, 3, t.order, t.levelOffsets);
-    return t;
-}
-
-void swapSlotPlanes(GpuBvh8Node& nd, int s1, int s2)
-{
-    for (int a = 0; a < 3; ++a) {
-        std::swap(nd.qlo[a][s1], nd.qlo[a][s2]);
-        std::swap(nd.qhi[a][s1], nd.qhi[a][s2]);
-    }
-}
-
-// Applies mutation `which` (0 .. 5: ark_ddgi_debug.h's (a) .. (f)) to the first node that
-// allows it; false when none does
-bool mutateTree(HostTree& t, int which)
-{
-    if (which == 5) {
-        for (uint32_t& p : t.perm)
-            if (p != 0xffffffffu) {
-                p ^= 1u;
-                return true;
-            }
-        return false;
-    }
-    for (size_t k = 0; k < t.nodes.size(); ++k) {
-        GpuBvh8Node& nd = t.nodes[k];
-        const uint32_t occupied = nd.imask | nd.leaf_mask;
-        int in[8], nIn = 0, leaf[8], nLeaf = 0, cnt[8];
-        for (int s = 0; s < 8; ++s) {
-            uint32_t tri[kBvh8MaxLeafSize];
-            cnt[s] = std::max(0, bvh8SlotTriangles(nd, s, tri));
-            if ((nd.imask >> s) & 1u) in[nIn++] = s;
-            else if (cnt[s]) leaf[nLeaf++] = s;
-        }
-        if (which == 0) { // (a) one plane one quantum looser
-            for (int s = 0; s < 8; ++s) {
-                if (!((occupied >> s) & 1u)) continue;
-                if (nd.qlo[0][s] > 0) {
-                    nd.qlo[0][s]--;
-                    return true;
-                }
-                if (nd.qhi[0][s] < 255) {
-                    nd.qhi[0][s]++;
-                    return true;
-                }
-            }
-        } else if (which == 1) { // (b) one axis's grid one exponent coarser, the planes re-quantised outward
-            // (p stays: it is a multiple of the old step, and every plane stays exact in
-            // fp32 while |p / old step| + 512 < 2^24)
-            const int a = 1;
-            const double step = std::ldexp(1.0, static_cast<int>(nd.e[a]) - 127);
-            if (nd.e[a] >= 250 || std::fabs(nd.p[a] / step) + 512.0 >= 16777216.0) continue;
-            nd.e[a]++;
-            for (int s = 0; s < 8; ++s) {
-                if (!((occupied >> s) & 1u)) continue;
-                nd.qlo[a][s] = static_cast<uint8_t>(nd.qlo[a][s] / 2);       // floor
-                nd.qhi[a][s] = static_cast<uint8_t>((nd.qhi[a][s] + 1) / 2); // ceil
-            }
-            return true;
-        } else if (which == 2) { // (c) two internal children exchanged, with their planes
-            if (nIn < 2) continue;
-            std::swap(t.nodes[nd.child_base], t.nodes[nd.child_base + 1]);
-            swapSlotPlanes(nd, in[0], in[1]);
-            return true;
-        } else { // (d), (e): two leaf slots with as many triangles
-            for (int i = 0; i < nLeaf; ++i)
-                for (int j = i + 1; j < nLeaf; ++j) {
-                    if (cnt[leaf[i]] != cnt[leaf[j]]) continue;
-                    const int s1 = leaf[i], s2 = leaf[j];
-                    // (d) every member, the rows rewritten and the planes with them;
-                    // (e) one record each, both slots' planes widened to their union
-                    const int members = which == 3 ? cnt[s1] : 1;
-                    for (int m = 0; m < members; ++m) {
-                        const uint32_t p1 = nd.tri_base + s1 + nd.tri_stride * m, p2 = nd.tri_base + s2 + nd.tri_stride * m;
-                        std::swap(t.tris[p1], t.tris[p2]);
-                        std::swap(t.perm[p1], t.perm[p2]);
-                    }
-                    if (which == 3) {
-                        swapSlotPlanes(nd, s1, s2);
-                    } else {
-                        for (int a = 0; a < 3; ++a) {
-                            nd.qlo[a][s1] = nd.qlo[a][s2] = std::min(nd.qlo[a][s1], nd.qlo[a][s2]);
-                            nd.qhi[a][s1] = nd.qhi[a][s2] = std::max(nd.qhi[a][s1], nd.qhi[a][s2]);
-                        }
-                    }
-                    return true;
-                }
-        }
-    }
-    return false;
-}
-} // namespace
-
-extern "C" int ark_ddgi_debug_bvh8_compare_selftest(const float* triangles, uint64_t n, const float* sun_dir, uint64_t seed, uint64_t* out)
-{
-    using namespace ark;
-    if (!triangles || n == 0 || !out) return -1;
-    std::fill(out, out + 16, uint64_t(0));
-    std::vector<GpuTriangle> rec(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        BuildTriangle t;
-        for (int a = 0; a < 3; ++a) {
-            t.v0[a] = triangles[9 * i + a];
-            t.v1[a] = triangles[9 * i + 3 + a];
-            t.v2[a] = triangles[9 * i + 6 + a];
-        }
-        t.instance = static_cast<uint32_t>(i % 3u); // three instances, one of each class
-        t.primitive = static_cast<uint32_t>(i);
-        t.flip_facing = 0;
-        rec[i] = make_gpu_triangle(t);
-    }
-    const std::vector<int> classOf = { 0, 1, 2 };
-    LbvhSunOptions so;
-    if (sun_dir) {
-        double frame[3][3];
-        sun_frame(sun_dir, frame);
-        std::memcpy(so.frame, frame, sizeof(so.frame));
-    }
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr);
-    HostTree ref;
-    ref.nodes = r.nodes;
-    ref.tris = r.tris;
-    ref.perm = r.perm;
-    ref.order = r.order;
-    ref.levelOffsets = r.levelOffsets;
-    std::copy(r.roots, r.roots + 3, ref.roots);
-    ref.opaqueNodes = r.opaqueNodes;
-    ref.depth = r.depth;
-    const HostTree twin = shuffledTwin(r, seed);
-    uint64_t moved = 0;
-    for (size_t k = 0; k < ref.nodes.size(); ++k)
-        if (ref.nodes[k].child_base != twin.nodes[k].child_base || ref.nodes[k].tri_base != twin.nodes[k].tri_base) moved++;
-    const Bvh8CanonicalDiff same = compare_bvh8_canonical(ref.view(), twin.view());
-    out[0] = ref.nodes.size();
-    out[1] = moved;
-    out[2] = same.total();
-    out[3] = same.pairs;
-    const Bvh8CheckResult twinCheck = check_bvh8_full(twin.nodes, twin.tris, twin.roots, 3, sun_dir ? nullptr : &classOf, nullptr, sun_dir ? so.frame : nullptr);
-    out[4] = twinCheck.violations;
-    int rc = same.total() == 0 && same.pairs == ref.nodes.size() && twinCheck.violations == 0 && moved > 0 ? 0 : 1;
-    for (int which = 0; which < 6; ++which) {
-        HostTree m = twin;
-        if (!mutateTree(m, which)) {
-            rc = 1;
-            continue;
-        }
-        const Bvh8CanonicalDiff d = compare_bvh8_canonical(ref.view(), m.view());
-        // the kind of difference each mutation has to show: (a) planes, (b) grid, (c) the
-        // exchanged children's nodes or planes, (d), (e) records, (f) perm and nothing else
-        const uint64_t kind[6] = { d.planes, d.grid, d.header + d.grid + d.planes + d.records, d.records, d.records, d.perm == d.total() ? d.perm : 0 };
-        out[5 + which] = kind[which];
-        if (kind[which] == 0 || d.firstA < 0) rc = 1;
-        if (which < 2) {
-            // (a) and (b) stay valid trees: what check_bvh8_full, the only check of a device
-            // build's boxes before, could not tell from the tree the design describes
-            const Bvh8CheckResult c = check_bvh8_full(m.nodes, m.tris, m.roots, 3, sun_dir ? nullptr : &classOf, nullptr, sun_dir ? so.frame : nullptr);
-            out[11 + which] = c.violations;
-            if (c.violations) rc = 1;
-        }
-    }
-    return rc;
-}
-
-namespace {
-int lbvhCheck(const float* triangles, uint64_t n, int criterion, bool sah, uint64_t* out, uint64_t* treelets)
-{
-    using namespace ark;
-    std::vector<GpuTriangle> rec(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        BuildTriangle t;
-        for (int a = 0; a < 3; ++a) {
-            t.v0[a] = triangles[9 * i + a];
-            t.v1[a] = triangles[9 * i + 3 + a];
-            t.v2[a] = triangles[9 * i + 6 + a];
-        }
-        t.instance = 0;
-        t.primitive = static_cast<uint32_t>(i);
-        t.flip_facing = 0;
-        rec[i] = make_gpu_triangle(t);
-    }
-    const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion, nullptr, nullptr, sah);
-    if (treelets) *treelets = r.treelets.size();
-    Bvh8CheckResult c = check_bvh8_full(r.nodes, r.tris, r.roots, 3, &classOf, triangles);
-    // every input triangle in exactly one leaf, bit for bit
-    std::vector<uint32_t> seen(n, 0);
-    for (size_t i = 0; i < r.tris.size(); ++i) {
-        if (isHoleTriangle(r.tris[i])) continue;
-        uint32_t prim;
-        std::memcpy(&prim, &r.tris[i].t2[2], 4);
-        if (prim >= n || r.perm[i] != prim || std::memcmp(&r.tris[i], &rec[prim], sizeof(GpuTriangle)) != 0) c.violations++;
-        else seen[prim]++;
-    }
-    for (uint64_t i = 0; i < n; ++i)
-        if (seen[i] != 1) c.violations++;
-    if (c.maxDepth != r.depth || c.nodes != r.nodes.size()) c.violations++;
-    c.violations += c.notBreadthFirst;
-    if (out) {
-        out[0] = r.nodes.size();
-        out[1] = c.leafChildren;
-        out[2] = r.depth;
-        out[3] = c.violations;
-        out[4] = c.triangles;
-        out[5] = n ? 2 * n - 1 : 0; // the radix tree's nodes
-        out[6] = c.internalChildren;
-        out[7] = static_cast<uint64_t>(r.sah * 1e6);
-    }
-    return c.violations == 0 ? 0 : 1;
-}
-} // namespace
-
-extern "C" int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int criterion, uint64_t* out)
-{
-    return lbvhCheck(triangles, n, criterion, false, out, nullptr);
-}
-
-extern "C" int ark_ddgi_debug_lbvh_check_sah(const float* triangles, uint64_t n, int criterion, int sah, uint64_t* out)
-{
-    uint64_t treelets = 0;
-    const int rc = lbvhCheck(triangles, n, criterion, sah != 0, out, &treelets);
-    if (out) out[8] = treelets;
-    return rc;
-}
-
-extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out)
-{
-    return ark_ddgi_debug_lbvh_check_opts(triangles, n, ark::lbvh::kDefaultCriterion, out);
-}
-
-// ark_ddgi_debug.h: the device build of the sun's light-space BVH8 (ddgi_bvh_build.hip:
-// k_lbvh_prims_light, k_lbvh_keys_light, the collapse under lbvh::kSlotsAscendingW) restated
-// serially on the host with the same lbvh_build.h functions, over sun_frame's frame and
-// sunAddRecords' light triangles; then ark_ddgi_debug_sun_bvh_check's ray comparison.
-namespace {
-int sunLbvhCheck(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, int w_bits, bool sahPass, uint64_t* out,
-                 uint64_t* treelets)
-{
-    using namespace ark;
-    if (out) std::fill(out, out + 16, uint64_t(0));
-    if (w_bits < 0) w_bits = lbvh::kSunKeyBitsW;
-    if (n == 0 || w_bits > lbvh::kMortonBits || (w_bits & 1)) return 1;
-    std::vector<BuildTriangle> tris(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        for (int a = 0; a < 3; ++a) {
-            tris[i].v0[a] = triangles[9 * i + a];
-            tris[i].v1[a] = triangles[9 * i + 3 + a];
-            tris[i].v2[a] = triangles[9 * i + 6 + a];
-        }
-        tris[i].instance = 0;
-        tris[i].primitive = static_cast<uint32_t>(i);
-        tris[i].flip_facing = 0;
-    }
-    SunBvhInput in;
-    sun_frame(sun_dir, in.frame);
-    sun_add_triangles(in, tris);
-    const std::vector<GpuTriangle> world = in.world;
-    double frame[3][3];
-    std::memcpy(frame, in.frame, sizeof(frame));
-    // the host's tree of the same triangles: its inflation and its cost
-    BvhBuildOptions opt;
-    opt.threads = 8;
-    Bvh8CollapseOptions copt;
-    Bvh8BuildResult sah;
-    if (!build_sun_bvh(in, opt, copt, sah)) return 1;
-    LbvhSunOptions so;
-    std::memcpy(so.frame, frame, sizeof(so.frame));
-    so.wBits = w_bits;
-    const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so, nullptr, sahPass);
-    if (treelets) *treelets = r.treelets.size();
-    if (r.nodes.empty() || r.roots[0] != 0) return 1;
-    // structure: one tree from node 0, each depth one range behind the depth above's, every
-    // record the input's bit for bit (the light-space boxes are covered by the ray comparison:
-    // check_bvh8_full's containment is of world coordinates)
-    uint64_t violations = r.slotOrderViolations;
-    std::string why;
-    const int32_t root = 0;
-    if (!checkBvh8Structure(r.nodes, r.tris, &root, 1, why)) violations++;
-    std::vector<uint32_t> order, offsets;
-    if (!bvhLevelOrder(r.nodes.data(), r.nodes.size(), &root, 1, order, offsets) || order != r.order || offsets != r.levelOffsets) violations++;
-    if (offsets.size() != static_cast<size_t>(r.depth) + 1u) violations++;
-    {
-        // bvhLevelOrder's levels, deepest first, must be consecutive ranges ending at the node count
-        uint32_t end = static_cast<uint32_t>(r.nodes.size());
-        for (size_t l = 0; l + 1 < offsets.size(); ++l) {
-            const uint32_t cnt = offsets[l + 1] - offsets[l];
-            for (uint32_t k = 0; k < cnt; ++k)
-                if (order[offsets[l] + k] != end - cnt + k) {
-                    violations++;
-                    break;
-                }
-            end -= cnt;
-        }
-        if (end != 0) violations++;
-    }
-    uint64_t leafChildren = 0;
-    for (const GpuBvh8Node& nd : r.nodes) {
-        if (nd.leaf_mask & nd.imask) violations++;
-        leafChildren += static_cast<uint64_t>(__builtin_popcount(nd.leaf_mask));
-    }
-    std::vector<uint32_t> seen(n, 0);
-    for (size_t i = 0; i < r.tris.size(); ++i) {
-        if (isHoleTriangle(r.tris[i])) continue;
-        uint32_t prim;
-        std::memcpy(&prim, &r.tris[i].t2[2], 4);
-        if (prim >= n || r.perm[i] != prim || std::memcmp(&r.tris[i], &world[prim], sizeof(GpuTriangle)) != 0) violations++;
-        else seen[prim]++;
-    }
-    for (uint64_t i = 0; i < n; ++i)
-        if (seen[i] != 1) violations++;
-    uint32_t ia, ib;
-    std::memcpy(&ia, &r.inflateAbs, 4);
-    std::memcpy(&ib, &in.inflateAbs, 4);
-    const uint64_t mism = sunRayCompare(r.nodes, r.tris, world, frame, sun_dir, origins, n_rays, tmax, out);
-    const float dd = sun_dir[0] * sun_dir[0] + sun_dir[1] * sun_dir[1] + sun_dir[2] * sun_dir[2];
-    const float sc = 1.0f / std::sqrt(dd);
-    const float L[3] = { -(sun_dir[0] * sc), -(sun_dir[1] * sc), -(sun_dir[2] * sc) };
-    const std::vector<float> o(origins, origins + 3 * n_rays);
-    if (out) {
-        out[6] = r.nodes.size();
-        out[8] = violations;
-        out[9] = ia != ib ? 1 : 0;
-        out[10] = static_cast<uint64_t>(sun_shadow_cost(r.nodes, r.tris, &root, 1, frame, L, o) * 1e6);
-        out[11] = static_cast<uint64_t>(sun_shadow_cost(sah.nodes, sah.tris, &root, 1, frame, L, o) * 1e6);
-        // the tree's shape (_opts only)
-        out[12] = leafChildren;
-        out[13] = r.depth;
-        out[14] = r.tris.size();
-        out[15] = static_cast<uint64_t>(w_bits);
-    }
-    if (violations || ia != ib) return 1;
-    return mism == 0 ? 0 : 2;
-}
-} // namespace
-
-extern "C" int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
-                                                   int w_bits, uint64_t* out)
-{
-    return sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, false, out, nullptr);
-}
-
-extern "C" int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
-                                                  int w_bits, int sah, uint64_t* out)
-{
-    uint64_t treelets = 0;
-    if (out) out[16] = 0;
-    const int rc = sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, sah != 0, out, &treelets);
-    if (out) out[16] = treelets;
-    return rc;
-}
-
-extern "C" int ark_ddgi_debug_sun_lbvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, uint64_t* out)
-{
-    uint64_t all[16];
-    const int rc = ark_ddgi_debug_sun_lbvh_check_opts(triangles, n, sun_dir, origins, n_rays, tmax, ark::lbvh::kSunKeyBitsW, all);
-    if (out) std::copy(all, all + 12, out);
-    return rc;
-}

@@ -311,7 +311,7 @@ __device__ __forceinline__ uint32_t nextChild(uint32_t base, uint32_t& bits, uin
 // where step * idir is exact (a power of two) and (p - o) * idir carries at most
 // about 2 ulp of |p - o| * |idir| (idir itself within 1 ulp of 1/d, safeInv); the
 // build inflates every box by 1e-6 of the
-// scene diagonal on top of its own relative margin (bvh_builder.cpp), which
+// scene diagonal on top of its own relative margin (bvh_builder.cpp inflateChildBox), which
 // covers that error, and the comparison keeps a relative margin for far boxes,
 // so a box holding an exact triangle hit is never culled. The near/far plane of
 // each axis is chosen by the ray octant. Scalar fp32, one slot at a time: a packed

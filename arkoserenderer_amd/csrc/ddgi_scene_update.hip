@@ -11,7 +11,7 @@
 //                    from the object-space pools in set_scene's fp32 operation order
 //                    (scene_store.cpp), each node's child boxes - leaf slots
 //                    from their triangle records, internal children from the level below
-//                    - inflated as the builder inflates them (bvh_builder.cpp writeNode),
+//                    - inflated as the builder inflates them (bvh_builder.cpp inflateChildBox),
 //                    the node's quantization grid and outward-rounded child planes
 //                    recomputed (quantGrid, collapse_bvh8). The world BVHs box world
 //                    coordinates; the sun's light-space BVH its records' light
@@ -90,7 +90,7 @@ __global__ void __launch_bounds__(256) k_node_masks(const GpuBvh8Node* __restric
 }
 
 // The light coordinates of a record's three vertices as build_sun_bvh computes them
-// (bvh_builder.cpp sunAddRecords: v0, v0 + e1, v0 + e2 in double, each rotated into the
+// (sun_bvh.cpp sunAddRecords: v0, v0 + e1, v0 + e2 in double, each rotated into the
 // frame in double and rounded to fp32), and the largest |world coordinate|.
 __device__ __forceinline__ void lightVertices(const float4 t0, const float4 t1, const float4 t2, const double* F, float L[3][3], float& maxAbs)
 {
@@ -98,7 +98,7 @@ __device__ __forceinline__ void lightVertices(const float4 t0, const float4 t1, 
     lbvh::lightVertices(v0, e1, e2, F, L, maxAbs);
 }
 
-// bvh_builder.cpp writeNode's inflation of a child box: relative to its magnitude and
+// bvh_builder.cpp inflateChildBox, the inflation of a child box: relative to its magnitude and
 // extent, plus the scene's absolute inflation
 __device__ __forceinline__ void inflateBox(float lo[3], float hi[3], float inflateAbs)
 {
@@ -232,7 +232,7 @@ __global__ void __launch_bounds__(128) k_refit_nodes(GpuBvh8Node* __restrict__ n
         nd->qhi[a][s] = static_cast<uint8_t>(qh);
     }
     if (s == 0) {
-        // this node's box as its parent's child box (inflated, as writeNode does per level)
+        // this node's box as its parent's child box (inflated, as the builder does per level)
         inflateBox(nlo, nhi, inflateAbs);
         float* b = boxes + 6u * static_cast<size_t>(n);
         for (int a = 0; a < 3; ++a) {

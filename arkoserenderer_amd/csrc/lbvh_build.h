@@ -1,6 +1,6 @@
 // lbvh_build.h — the build logic of the device-side LBVH of the world BVH8s
 // (ddgi_bvh_build.hip), shared with its serial host restatement
-// (ark_ddgi_debug_lbvh_check, bvh_builder.cpp). Plain inline functions over plain
+// (ark_ddgi_debug_lbvh_check, lbvh_host.cpp). Plain inline functions over plain
 // arrays, no HIP types: the host check and the kernels run the same code.
 //
 //   mortonKey      class << 60 | 60-bit Morton code (20 bits per axis, x highest) of a

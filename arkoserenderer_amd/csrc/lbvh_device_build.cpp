@@ -7,7 +7,10 @@
 #include <cstring>
 
 #include "../../include/ark_ddgi_debug.h"
+#include "bvh8_check.h"
 #include "bvh_builder.h"
+#include "lbvh_host.h"
+#include "sun_bvh.h"
 
 namespace ark {
 

@@ -13,8 +13,10 @@
 
 #include "../../include/ark_ddgi_debug.h"
 #include "ark_fmath.h"
+#include "bvh8_check.h"
 #include "bvh_builder.h"
 #include "lbvh_device_build.h"
+#include "sun_bvh.h"
 #include "sun_cover_build.h"
 
 // (every function here that can fail has an ErrorSink* err in scope)

@@ -10,17 +10,14 @@
 
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"
-#include "bvh_builder.h"
+#include "sun_bvh.h"
 #include "sun_cover_build.h"
 
 namespace ark {
 
 void sunRayDirection(const float sunDir[3], float L[3])
 {
-    // normalize() of the kernels: v * (1 / sqrt(dot(v, v))), dot left to right (sun_frame)
-    const float dd = sunDir[0] * sunDir[0] + sunDir[1] * sunDir[1] + sunDir[2] * sunDir[2];
-    const float sc = 1.0f / std::sqrt(dd);
-    for (int k = 0; k < 3; ++k) L[k] = -(sunDir[k] * sc);
+    sun_ray_dir(sunDir, L); // normalize() of the kernels, as sun_frame's w
 }
 
 bool hostBuildCoverMap(const GpuTriangle* rec, uint64_t records, const double* frame, const float* dir, uint64_t budgetBytes, cover::Grid& grid,
@@ -103,19 +100,8 @@ namespace {
 
 void recordsOf(const float* triangles, uint64_t n, std::vector<ark::GpuTriangle>& rec)
 {
-    rec.resize(n);
-    for (uint64_t i = 0; i < n; ++i) {
-        ark::BuildTriangle t;
-        for (int a = 0; a < 3; ++a) {
-            t.v0[a] = triangles[9 * i + a];
-            t.v1[a] = triangles[9 * i + 3 + a];
-            t.v2[a] = triangles[9 * i + 6 + a];
-        }
-        t.instance = 0;
-        t.primitive = static_cast<uint32_t>(i);
-        t.flip_facing = 0;
-        rec[i] = ark::make_gpu_triangle(t);
-    }
+    rec.clear();
+    for (const ark::BuildTriangle& t : ark::soupTriangles(triangles, n)) rec.push_back(ark::make_gpu_triangle(t));
 }
 
 } // namespace

@@ -1,8 +1,8 @@
 // lbvh_sah_test.cpp — the serial restatement of the SAH pass of the device BVH builds
-// (ARK_DDGI_FLAG_GPU_REBUILD_SAH; bvh_builder.cpp build_lbvh_host with the pass, through
+// (ARK_DDGI_FLAG_GPU_REBUILD_SAH; lbvh_host.cpp build_lbvh_host with the pass, through
 // ark_ddgi_debug_lbvh_check_sah and ark_ddgi_debug_sun_lbvh_check_sah) on 257 and 4,099
 // triangles of a soup (two treelets under one upper node; many) and on 300 coincident
-// triangles (equal boxes: the tie rule). Stand-alone: built with bvh_builder.cpp under
+// triangles (equal boxes: the tie rule). Stand-alone: built with the host BVH sources under
 // AddressSanitizer + UndefinedBehaviorSanitizer and run as a program
 // (tests/test_lbvh_sah_sanitizers.py). No GPU.
 #include <cstdint>

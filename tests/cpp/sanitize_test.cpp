@@ -12,6 +12,7 @@
 #include <string>
 #include <vector>
 
+#include "bvh8_check.h"
 #include "bvh_builder.h"
 #include "scene_rebuild_policy.h"
 #include "../../include/ark_ddgi.h"

@@ -9,7 +9,6 @@
 #include <cstdio>
 #include <vector>
 
-#include "bvh_builder.h"
 #include "scene_rebuild_policy.h"
 #include "../../include/ark_ddgi.h"
 #include "../../include/ark_ddgi_debug.h"

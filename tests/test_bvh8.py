@@ -1,5 +1,5 @@
 """Host-side check of the 8-wide quantized BVH that ark_ddgi_set_scene uploads
-(bvh_builder.cpp): exact fp32 plane decode, conservative (outward) quantization,
+(bvh_builder.cpp, checked by bvh8_check.cpp): exact fp32 plane decode, conservative (outward) quantization,
 every triangle in exactly one leaf. No GPU."""
 import ctypes as C
 

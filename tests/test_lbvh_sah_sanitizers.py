@@ -9,6 +9,10 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SOURCES = [
     os.path.join(ROOT, "tests", "cpp", "lbvh_sah_test.cpp"),
     os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh_builder.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "sun_bvh.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "lbvh_host.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh8_check.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh_debug.cpp"),
 ]
 
 

@@ -14,6 +14,10 @@ SOURCES = [
     os.path.join(ROOT, "tests", "cpp", "sanitize_test.cpp"),
     os.path.join(ROOT, "oracle", "ddgi_oracle.cpp"),
     os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh_builder.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "sun_bvh.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "lbvh_host.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh8_check.cpp"),
+    os.path.join(ROOT, "arkoserenderer_amd", "csrc", "bvh_debug.cpp"),
     os.path.join(ROOT, "arkoserenderer_amd", "csrc", "scene_gen.cpp"),
 ]
 

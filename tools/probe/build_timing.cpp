@@ -1,14 +1,15 @@
 // Host timing of set_scene's BVH path on the C4 soup (no GPU): world BVH2 build,
 // BVH8 collapse, the sun's light-space BVH and its cost sampling.
 // g++ -O3 -std=c++17 -pthread -I../../include tools/probe/build_timing.cpp
-//     arkoserenderer_amd/csrc/bvh_builder.cpp arkoserenderer_amd/csrc/scene_gen.cpp
+//     arkoserenderer_amd/csrc/bvh_builder.cpp arkoserenderer_amd/csrc/sun_bvh.cpp
+//     arkoserenderer_amd/csrc/scene_gen.cpp
 #include <chrono>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <vector>
 
-#include "../../arkoserenderer_amd/csrc/bvh_builder.h"
+#include "../../arkoserenderer_amd/csrc/sun_bvh.h"
 #include "../../include/ark_scene.h"
 
 using namespace ark;
