@@ -55,6 +55,7 @@ ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD = 0x2
 ARK_DDGI_FLAG_GPU_REBUILD = 0x4
 ARK_DDGI_FLAG_GPU_REBUILD_SUN = 0x8
 ARK_DDGI_FLAG_GPU_REBUILD_SAH = 0x10
+ARK_DDGI_FLAG_GPU_REBUILD_PLAN = 0x80
 ARK_DDGI_FLAG_NO_SUN_COVER_MAP = 0x20
 ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE = 0x40
 
@@ -522,6 +523,9 @@ EXPORTS = {
     "ark_ddgi_debug_bvh8_compare_selftest": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_world_bvh_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_lbvh_check_sah": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_lbvh_check_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_sun_lbvh_check_plan": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_lbvh_device_parity_plan": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_lbvh_check_sah": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_lbvh_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint64)]),

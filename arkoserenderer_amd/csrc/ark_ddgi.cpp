@@ -482,7 +482,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     ctx->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     const int shards = desc->shard_count > 0 ? desc->shard_count : 1;
     if (ctx->Rmax > ARK_DDGI_MAX_RAYS_PER_PROBE || ctx->Z % shards != 0 || desc->shard_rank < 0 || desc->shard_rank >= shards ||
-        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_NO_SUN_COVER_MAP | ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE)) ||
+        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_GPU_REBUILD_PLAN | ARK_DDGI_FLAG_NO_SUN_COVER_MAP | ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE)) ||
         desc->build_threads < 0) {
         delete ctx;
         return ARK_DDGI_E_INVALID_ARGUMENT;

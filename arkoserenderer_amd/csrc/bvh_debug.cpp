@@ -464,14 +464,18 @@ extern "C" int ark_ddgi_debug_bvh8_compare_selftest(const float* triangles, uint
 }
 
 namespace {
-int lbvhCheck(const float* triangles, uint64_t n, int criterion, bool sah, uint64_t* out, uint64_t* treelets)
+int lbvhCheck(const float* triangles, uint64_t n, int criterion, bool sah, uint64_t* out, uint64_t* treelets, bool plan = false, uint64_t* planOut = nullptr)
 {
     using namespace ark;
     std::vector<GpuTriangle> rec;
     for (const BuildTriangle& t : soupTriangles(triangles, n)) rec.push_back(make_gpu_triangle(t));
     const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion, nullptr, nullptr, sah);
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, criterion, nullptr, nullptr, sah, plan);
     if (treelets) *treelets = r.treelets.size();
+    if (planOut) {
+        planOut[0] = r.planRootCost;
+        planOut[1] = r.smallInternal + (r.planStalled ? 1u : 0u);
+    }
     Bvh8CheckResult c = check_bvh8_full(r.nodes, r.tris, r.roots, 3, &classOf, triangles);
     // every input triangle in exactly one leaf, bit for bit
     c.violations += recordViolations(r.tris, r.perm, rec);
@@ -504,6 +508,19 @@ extern "C" int ark_ddgi_debug_lbvh_check_sah(const float* triangles, uint64_t n,
     return rc;
 }
 
+extern "C" int ark_ddgi_debug_lbvh_check_plan(const float* triangles, uint64_t n, int criterion, int sah, int plan, uint64_t* out)
+{
+    uint64_t treelets = 0, planWords[2] = { 0, 0 };
+    int rc = lbvhCheck(triangles, n, criterion, sah != 0, out, &treelets, plan != 0, planWords);
+    if (out) {
+        out[8] = treelets;
+        out[9] = planWords[0];
+        out[10] = planWords[1];
+    }
+    if (plan && sah && planWords[1]) rc = 1;
+    return rc;
+}
+
 extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uint64_t* out)
 {
     return ark_ddgi_debug_lbvh_check_opts(triangles, n, ark::lbvh::kDefaultCriterion, out);
@@ -515,7 +532,7 @@ extern "C" int ark_ddgi_debug_lbvh_check(const float* triangles, uint64_t n, uin
 // sunAddRecords' light triangles; then ark_ddgi_debug_sun_bvh_check's ray comparison.
 namespace {
 int sunLbvhCheck(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax, int w_bits, bool sahPass, uint64_t* out,
-                 uint64_t* treelets)
+                 uint64_t* treelets, bool plan = false, uint64_t* planOut = nullptr)
 {
     using namespace ark;
     if (out) std::fill(out, out + 16, uint64_t(0));
@@ -537,8 +554,12 @@ int sunLbvhCheck(const float* triangles, uint64_t n, const float* sun_dir, const
     std::memcpy(so.frame, frame, sizeof(so.frame));
     so.wBits = w_bits;
     const std::vector<int> classOf(1, 0);
-    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so, nullptr, sahPass);
+    const LbvhHostResult r = build_lbvh_host(world, classOf, lbvh::kDefaultCriterion, &so, nullptr, sahPass, plan);
     if (treelets) *treelets = r.treelets.size();
+    if (planOut) {
+        planOut[0] = r.planRootCost;
+        planOut[1] = r.smallInternal + (r.planStalled ? 1u : 0u);
+    }
     if (r.nodes.empty() || r.roots[0] != 0) return 1;
     // structure: one tree from node 0, each depth one range behind the depth above's, every
     // record the input's bit for bit (the light-space boxes are covered by the ray comparison:
@@ -607,6 +628,21 @@ extern "C" int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_
     if (out) out[16] = 0;
     const int rc = sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, sah != 0, out, &treelets);
     if (out) out[16] = treelets;
+    return rc;
+}
+
+extern "C" int ark_ddgi_debug_sun_lbvh_check_plan(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                                   int w_bits, int sah, int plan, uint64_t* out)
+{
+    uint64_t treelets = 0, planWords[2] = { 0, 0 };
+    if (out) out[16] = out[17] = out[18] = 0;
+    int rc = sunLbvhCheck(triangles, n, sun_dir, origins, n_rays, tmax, w_bits, sah != 0, out, &treelets, plan != 0, planWords);
+    if (out) {
+        out[16] = treelets;
+        out[17] = planWords[0];
+        out[18] = planWords[1];
+    }
+    if (plan && sah && planWords[1] && rc == 0) rc = 1;
     return rc;
 }
 

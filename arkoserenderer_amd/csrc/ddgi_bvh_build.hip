@@ -22,6 +22,10 @@
 //                     lbvh::kTreeletPrims primitives: its binary tree rebuilt by a
 //                     three-axis sweep SAH in LDS, its primitives reordered, a box per node
 //                     and primitive for the collapse's decisions (lbvh_build.h)
+//   k_lbvh_upper_plan  (ARK_DDGI_FLAG_GPU_REBUILD_PLAN, with the SAH pass, whose plan instance
+//                     splits down to single primitives and plans the treelets' nodes) one
+//                     workgroup: boxes and collapse plans of the nodes above the treelets, in
+//                     rounds with a barrier between them; the collapse then cuts by the picks
 //   k_lbvh_collapse   one level of one class, one thread per BVH8 node of the work
 //                     list: cut, slots and rows; the internal children's node indices
 //                     from one atomic add on the next level's counter, the rows' span
@@ -193,8 +197,12 @@ __global__ void __launch_bounds__(256) k_lbvh_keys_light(const GpuTriangle* __re
     keys[j] = lbvh::lightKey(c, lo, hi, layout);
 }
 
+// kPlan (the collapse plan): ranges of 2 and 3 primitives are treelets too, and a node of more
+// than lbvh::kTreeletPrims is appended to the list of the nodes above the treelets
+template <bool kPlan>
 __global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restrict__ keys, uint32_t lo, uint32_t hi, uint32_t* __restrict__ split,
-                                                        lbvh::Member* __restrict__ treelets, uint32_t treeletCapacity, uint32_t* __restrict__ counters)
+                                                        lbvh::Member* __restrict__ treelets, uint32_t treeletCapacity, uint32_t* __restrict__ counters,
+                                                        lbvh::Member* __restrict__ upper, uint32_t upperCapacity)
 {
     const uint32_t i = lo + blockIdx.x * 256u + threadIdx.x;
     if (i + 1u >= hi) return; // internal nodes lo .. hi - 2
@@ -204,12 +212,37 @@ __global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restri
     if (!treelets) return;
     // the SAH pass's work list (its order does not matter: treelets are disjoint ranges)
     lbvh::Member m[2];
-    const int n = lbvh::treeletsOf(r, s, i == lo, m);
+    const int n = lbvh::treeletsOf(r, s, i == lo, m, kPlan);
     for (int k = 0; k < n; ++k) {
         const uint32_t at = atomicAdd(&counters[kLbvhTreelets], 1u);
         if (at < treeletCapacity) treelets[at] = m[k];
-        else atomicOr(&counters[kLbvhOverflow], 1u); // (never: at most prims / 4 treelets)
+        else atomicOr(&counters[kLbvhOverflow], 1u); // (never: at most prims / 4 treelets, prims / 2 under the plan)
     }
+    if (kPlan && lbvh::count(r) > lbvh::kTreeletPrims) {
+        const uint32_t at = atomicAdd(&counters[kLbvhUpper], 1u);
+        if (at < upperCapacity) {
+            lbvh::Member u;
+            u.r = r;
+            u.node = i;
+            upper[at] = u;
+        } else {
+            atomicOr(&counters[kLbvhOverflow], 1u); // (never: fewer than prims such nodes)
+        }
+    }
+}
+
+// What the plan instance of k_lbvh_treelet_sah keeps in LDS beside the pass's own: per node
+// of the treelet (by its index in the treelet) the eight costs, its box's half-area, its
+// range and its done flag
+struct PlanLds {
+    float cost[8][256];
+    float area[256];
+    uint8_t first[256], last[256], done[256];
+};
+__device__ __forceinline__ PlanLds& planLds()
+{
+    __shared__ PlanLds lds;
+    return lds;
 }
 
 // The SAH pass: one workgroup per treelet (4 .. 256 primitives), one primitive per thread,
@@ -225,8 +258,17 @@ __global__ void __launch_bounds__(256) k_lbvh_hierarchy(const uint64_t* __restri
 // their final segment; lbvh::treeletSpareIndex is an ancestor's and left alone), nbox[] of every node of more than kBvh8MaxLeafSize primitives,
 // pbox[] of every primitive at its new position. Nothing is read of or written to another
 // treelet's range, and no workgroup waits for another.
+// kPlan (the collapse plan; treelets of 2 primitives or more): the instance that keeps
+// splitting until every segment is one primitive - the same sweep, split key, tie rule and
+// numbering - writes nbox of every node, and then plans the treelet's nodes bottom-up inside
+// the workgroup (lbvh::planCosts): one thread per node, the costs and the done flags in LDS, a
+// barrier between rounds, until the root is done. A node's flag is raised in the round after
+// its costs were written, behind a barrier, so a parent never reads half a plan. Out: the
+// packed picks of every node (picks, lbvh::kPlanDone set), the root's eight costs (pcost).
+template <bool kPlan>
 __global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
 {
+    constexpr uint32_t kLeafMost = kPlan ? 1u : static_cast<uint32_t>(kBvh8MaxLeafSize);
     __shared__ uint32_t sBox[6][256];          // by primitive (Morton position in the treelet): lo xyz, hi xyz, ordered
     __shared__ uint32_t sP[6][256], sS[6][256]; // a wave's prefix / suffix unions by position (hi complemented: all minima)
     __shared__ unsigned long long sBest[256];  // at a segment's first position
@@ -266,6 +308,7 @@ __global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
     sN[t] = static_cast<uint8_t>(t < n ? T.node - first : t);
     sSplit[t] = 0xffffu;
     sSide[t] = 0;
+    if constexpr (kPlan) planLds().done[t] = 0;
     for (int ax = 0; ax < 3; ++ax) sP[ax][t] = lbvh::sweepKey(lbvh::orderedFloat(box[ax]), lbvh::orderedFloat(box[3 + ax]));
     __syncthreads();
     for (int ax = 0; ax < 3; ++ax) {
@@ -284,7 +327,7 @@ __global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
     const uint32_t w0 = t & ~63u, w1 = w0 + 63u;
     for (;;) {
         const uint32_t f = sF[t], l = sL[t], cnt = l - f + 1u;
-        const bool live = cnt > static_cast<uint32_t>(kBvh8MaxLeafSize);
+        const bool live = cnt > kLeafMost;
         if (!__syncthreads_or(live ? 1 : 0)) break;
         if (t == f) sBest[t] = lbvh::kNoSplit;
         unsigned long long mine = lbvh::kNoSplit;
@@ -321,6 +364,12 @@ __global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
                 if (ax == 0 && t == l) {
                     float* nb = a.nbox + 6ull * (first + sN[t]);
                     for (int c = 0; c < 6; ++c) nb[c] = lbvh::orderedFloat(P[c]);
+                    if constexpr (kPlan) {
+                        PlanLds& pl = planLds();
+                        pl.area[sN[t]] = lbvh::halfArea(P);
+                        pl.first[sN[t]] = static_cast<uint8_t>(f);
+                        pl.last[sN[t]] = static_cast<uint8_t>(l);
+                    }
                 }
                 if (t < l) {
                     // the union of [t + 1, l] the same way
@@ -384,16 +433,137 @@ __global__ void __launch_bounds__(256) k_lbvh_treelet_sah(LbvhTreeletArgs a)
         const uint32_t sp = sSplit[t];
         if (first + t != lbvh::treeletSpareIndex(T)) a.split[first + t] = first + (sp != 0xffffu ? sp : sF[t]);
     }
+    if constexpr (kPlan) {
+        // node t of the treelet (every index but the spare one): its range and split, relative
+        PlanLds& pl = planLds();
+        // (0 to do, 1 costs written, 2 flag raised; an index without a split - never: n - 1 nodes on n - 1 indices - is none)
+        int state = t < n && first + t != lbvh::treeletSpareIndex(T) && sSplit[t] != 0xffffu ? 0 : 2;
+        const uint32_t nf = pl.first[t], nl = pl.last[t], ns = sSplit[t];
+        for (uint32_t round = 0; round <= n; ++round) { // (a tree of n - 1 nodes is done within n - 1 rounds)
+            if (state == 1) {
+                pl.done[t] = 1;
+                state = 2;
+            }
+            if (!__syncthreads_or(state == 0 ? 1 : 0)) break;
+            if (state != 0) continue;
+            const bool leftSingle = ns == nf, rightSingle = ns + 1u == nl;
+            if (!(leftSingle || pl.done[ns]) || !(rightSingle || pl.done[ns + 1u])) continue;
+            float L[8], R[8], C[8];
+            if (leftSingle) {
+                uint32_t b[6];
+                for (int c = 0; c < 6; ++c) b[c] = sBox[c][sOrd[0][nf]];
+                lbvh::planLeafCosts(b, L);
+            } else {
+                for (int i = 0; i < 8; ++i) L[i] = pl.cost[i][ns];
+            }
+            if (rightSingle) {
+                uint32_t b[6];
+                for (int c = 0; c < 6; ++c) b[c] = sBox[c][sOrd[0][nl]];
+                lbvh::planLeafCosts(b, R);
+            } else {
+                for (int i = 0; i < 8; ++i) R[i] = pl.cost[i][ns + 1u];
+            }
+            const uint32_t word = lbvh::planCosts(pl.area[t], nl - nf + 1u, L, R, C);
+            for (int i = 0; i < 8; ++i) pl.cost[i][t] = C[i];
+            a.picks[first + t] = word | lbvh::kPlanDone;
+            if (first + t == T.node)
+                for (int i = 0; i < 8; ++i) a.pcost[8ull * T.node + i] = C[i];
+            state = 1;
+        }
+    }
 }
 
-__global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a)
+// The collapse plan above the treelets: one workgroup per build, in rounds. In a round every
+// thread strides over the list of the nodes of more than lbvh::kTreeletPrims primitives; a
+// node that is not done and whose two children are - a treelet's root (planned by the kernel
+// before), a single primitive outside every treelet (boxed here from its snapshot record, its
+// pbox written for the collapse), or an upper node marked done in an earlier round - gets its
+// box (nbox, the union of its children's ordered words), its costs (pcost) and its word
+// (picks) with lbvh::kPlanComputed; behind a barrier the words computed in this round get
+// lbvh::kPlanDone, and a second barrier ends the round. Nothing is read that this workgroup
+// wrote in the same phase, no other workgroup exists, and the result does not depend on the
+// schedule: unions of ordered words are exact in any order and a plan reads finished children
+// only. The tree's height bounds the rounds by the list's length; a round that computes
+// nothing while nodes are left sets counters[kLbvhPlanStalled] and ends the kernel.
+__device__ __forceinline__ bool upperChild(const LbvhUpperArgs& a, const lbvh::Member& m, uint32_t b[6], float C[8])
+{
+    const uint32_t cnt = lbvh::count(m.r);
+    if (cnt == 1u) {
+        const uint32_t src = a.sorted[m.r.first];
+        const float4* q = reinterpret_cast<const float4*>(a.snap + src);
+        const float4 r0 = q[0], r1 = q[1], r2 = q[2];
+        const float v0[3] = { r0.x, r0.y, r0.z }, e1[3] = { r0.w, r1.x, r1.y }, e2[3] = { r1.z, r1.w, r2.x };
+        float v[3][3];
+        if (a.light) {
+            float unused;
+            lbvh::lightVertices(v0, e1, e2, a.frame.m, v, unused);
+        } else {
+            for (int k = 0; k < 3; ++k) {
+                v[0][k] = v0[k];
+                v[1][k] = v0[k] + e1[k];
+                v[2][k] = v0[k] + e2[k];
+            }
+        }
+        lbvh::primBox(v, b);
+        for (int c = 0; c < 6; ++c) a.pbox[6ull * m.r.first + c] = lbvh::orderedFloat(b[c]);
+        lbvh::planLeafCosts(b, C);
+        return true;
+    }
+    if (cnt > lbvh::kTreeletPrims && !(a.picks[m.node] & lbvh::kPlanDone)) return false;
+    for (int c = 0; c < 6; ++c) b[c] = lbvh::ordered(a.nbox[6ull * m.node + c]);
+    for (int i = 0; i < 8; ++i) C[i] = a.pcost[8ull * m.node + i];
+    return true;
+}
+
+__global__ void __launch_bounds__(1024) k_lbvh_upper_plan(LbvhUpperArgs a)
+{
+    for (uint32_t round = 0; round < a.count; ++round) {
+        int left = 0, computed = 0;
+        for (uint32_t j = threadIdx.x; j < a.count; j += 1024u) {
+            const lbvh::Member m = a.list[j];
+            // (never: the list holds nodes of this build's ranges only)
+            if (m.r.last >= a.prims || m.r.first > m.r.last || m.node < m.r.first || m.node > m.r.last) continue;
+            if (a.picks[m.node] & lbvh::kPlanDone) continue;
+            left = 1;
+            lbvh::Member l, r;
+            lbvh::childrenOf(a.split, m, l, r);
+            if (l.r.last < m.r.first || l.r.last >= m.r.last) continue; // (never: a split inside the range)
+            uint32_t lb[6], rb[6], box[6];
+            float L[8], R[8], C[8];
+            if (!upperChild(a, l, lb, L) || !upperChild(a, r, rb, R)) continue;
+            const uint32_t word = lbvh::planUpperNode(lb, L, rb, R, lbvh::count(m.r), box, C);
+            for (int c = 0; c < 6; ++c) a.nbox[6ull * m.node + c] = lbvh::orderedFloat(box[c]);
+            for (int i = 0; i < 8; ++i) a.pcost[8ull * m.node + i] = C[i];
+            a.picks[m.node] = word | lbvh::kPlanComputed;
+            computed = 1;
+        }
+        const int anyLeft = __syncthreads_or(left);
+        const int anyComputed = __syncthreads_or(computed);
+        if (!anyLeft) return;
+        if (!anyComputed) {
+            if (threadIdx.x == 0u) atomicOr(&a.counters[kLbvhPlanStalled], 1u);
+            return;
+        }
+        // this round's words become final: from the next round on their nodes count as done
+        for (uint32_t j = threadIdx.x; j < a.count; j += 1024u) {
+            const lbvh::Member m = a.list[j];
+            if (m.node >= a.prims) continue;
+            const uint32_t word = a.picks[m.node];
+            if ((word & lbvh::kPlanComputed) && !(word & lbvh::kPlanDone)) a.picks[m.node] = word | lbvh::kPlanDone;
+        }
+        __syncthreads();
+    }
+}
+
+template <bool kPlan>
+__global__ void __launch_bounds__(128) k_lbvh_collapse(LbvhCollapseArgs a, const uint32_t* __restrict__ picks)
 {
     const uint32_t i = blockIdx.x * 128u + threadIdx.x;
     if (i >= a.count) return;
     const lbvh::Member top = a.items ? a.items[i] : a.root;
     lbvh::WideNode w;
     const lbvh::KeyLayout layout = { a.wBits };
-    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w, a.slotRule, layout, a.useSah ? &a.sah : nullptr);
+    lbvh::planNode(a.keys, a.split, top, a.criterion, a.extent, w, a.slotRule, layout, a.useSah ? &a.sah : nullptr, kPlan ? picks : nullptr);
     uint32_t slot0 = 0;
     if (w.internal) {
         slot0 = atomicAdd(&a.counters[kLbvhNextCount], w.internal);
@@ -491,24 +661,43 @@ hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysI
 }
 
 hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s, lbvh::Member* treelets, uint32_t treeletCapacity,
-                                 uint32_t* counters)
+                                 uint32_t* counters, lbvh::Member* upper, uint32_t upperCapacity)
 {
     if (hi - lo < 2u) return hipSuccess;
-    hipLaunchKernelGGL(dev::k_lbvh_hierarchy, dim3((hi - lo - 1u + 255u) / 256u), dim3(256), 0, s, keys, lo, hi, split, treelets, treeletCapacity, counters);
+    const dim3 grid((hi - lo - 1u + 255u) / 256u);
+    if (treelets && upper)
+        hipLaunchKernelGGL(dev::k_lbvh_hierarchy<true>, grid, dim3(256), 0, s, keys, lo, hi, split, treelets, treeletCapacity, counters, upper, upperCapacity);
+    else
+        hipLaunchKernelGGL(dev::k_lbvh_hierarchy<false>, grid, dim3(256), 0, s, keys, lo, hi, split, treelets, treeletCapacity, counters, nullptr, 0u);
     return hipGetLastError();
 }
 
-hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s)
+hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s, bool plan)
 {
     if (treelets == 0) return hipSuccess;
-    hipLaunchKernelGGL(dev::k_lbvh_treelet_sah, dim3(treelets), dim3(256), 0, s, a);
+    if (plan && (!a.picks || !a.pcost)) return hipErrorInvalidValue;
+    if (plan)
+        hipLaunchKernelGGL(dev::k_lbvh_treelet_sah<true>, dim3(treelets), dim3(256), 0, s, a);
+    else
+        hipLaunchKernelGGL(dev::k_lbvh_treelet_sah<false>, dim3(treelets), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 
-hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s)
+hipError_t launch_lbvh_upper_plan(const LbvhUpperArgs& a, hipStream_t s)
 {
     if (a.count == 0) return hipSuccess;
-    hipLaunchKernelGGL(dev::k_lbvh_collapse, dim3((a.count + 127u) / 128u), dim3(128), 0, s, a);
+    hipLaunchKernelGGL(dev::k_lbvh_upper_plan, dim3(1), dim3(1024), 0, s, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s, const uint32_t* picks)
+{
+    if (a.count == 0) return hipSuccess;
+    const dim3 grid((a.count + 127u) / 128u);
+    if (picks)
+        hipLaunchKernelGGL(dev::k_lbvh_collapse<true>, grid, dim3(128), 0, s, a, picks);
+    else
+        hipLaunchKernelGGL(dev::k_lbvh_collapse<false>, grid, dim3(128), 0, s, a, picks);
     return hipGetLastError();
 }
 

@@ -337,7 +337,9 @@ struct LbvhFrame {
     double m[9];
 };
 // the collapse's counters
-enum : uint32_t { kLbvhNextCount = 0, kLbvhRecords = 1, kLbvhOverflow = 2, kLbvhTreelets = 3, kLbvhCounters = 4 };
+// (kLbvhUpper: the nodes above the treelets, the collapse plan's second list; kLbvhPlanStalled:
+// k_lbvh_upper_plan ran a round that finished no node)
+enum : uint32_t { kLbvhNextCount = 0, kLbvhRecords = 1, kLbvhOverflow = 2, kLbvhTreelets = 3, kLbvhUpper = 4, kLbvhPlanStalled = 5, kLbvhCounters = 6 };
 // one level of one class (k_lbvh_collapse): node levelBase + i from items[i] (items null: the root)
 struct LbvhCollapseArgs {
     const uint64_t* keys;      // sorted
@@ -371,9 +373,11 @@ hipError_t launch_lbvh_prims_light(const GpuTriangle* snap, uint32_t records, ui
 hipError_t launch_lbvh_sort(void* temp, size_t& tempBytes, const uint64_t* keysIn, uint64_t* keysOut, const uint32_t* valuesIn, uint32_t* valuesOut, uint32_t count,
                             hipStream_t s);
 // split[i] of the internal nodes lo .. hi - 2 of the class range [lo, hi); treelets not null:
-// the SAH pass's work list (lbvh::treeletsOf), counted in counters[kLbvhTreelets]
+// the SAH pass's work list (lbvh::treeletsOf), counted in counters[kLbvhTreelets]; upper not
+// null (the collapse plan): ranges of 2 and 3 are treelets too, and the nodes of more than
+// lbvh::kTreeletPrims primitives are listed in upper, counted in counters[kLbvhUpper]
 hipError_t launch_lbvh_hierarchy(const uint64_t* keys, uint32_t lo, uint32_t hi, uint32_t* split, hipStream_t s, lbvh::Member* treelets = nullptr,
-                                 uint32_t treeletCapacity = 0, uint32_t* counters = nullptr);
+                                 uint32_t treeletCapacity = 0, uint32_t* counters = nullptr, lbvh::Member* upper = nullptr, uint32_t upperCapacity = 0);
 // The SAH pass (k_lbvh_treelet_sah): one workgroup per entry of list
 struct LbvhTreeletArgs {
     const GpuTriangle* snap;
@@ -385,9 +389,34 @@ struct LbvhTreeletArgs {
     float* pbox;       // [prims][6], by sorted primitive
     int light;         // boxes of the light coordinates in `frame`
     LbvhFrame frame;
+    // the collapse plan (launch_lbvh_treelet_sah's plan): the packed picks by BVH2 node
+    // [prims], the eight costs of each treelet's root at its node index [prims][8]
+    uint32_t* picks;
+    float* pcost;
 };
-hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s);
-hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s);
+// plan: the instance that splits down to single primitives and plans every node of the treelet
+hipError_t launch_lbvh_treelet_sah(const LbvhTreeletArgs& a, uint32_t treelets, hipStream_t s, bool plan = false);
+// The nodes above the treelets (k_lbvh_upper_plan, one workgroup): list[0 .. count), children
+// before parents in rounds; nbox, picks and pcost at each node's index, pbox of the single
+// primitives outside every treelet; counters[kLbvhPlanStalled] set if a round finishes no node
+struct LbvhUpperArgs {
+    const GpuTriangle* snap;
+    const lbvh::Member* list;
+    uint32_t count;
+    uint32_t prims;
+    const uint32_t* sorted;
+    const uint32_t* split;
+    float* nbox;
+    float* pbox;
+    uint32_t* picks;
+    float* pcost;
+    uint32_t* counters;
+    int light;
+    LbvhFrame frame;
+};
+hipError_t launch_lbvh_upper_plan(const LbvhUpperArgs& a, hipStream_t s);
+// picks: the collapse plan's words by BVH2 node (the instance that cuts by lbvh::planCut); null: the greedy cut
+hipError_t launch_lbvh_collapse(const LbvhCollapseArgs& a, hipStream_t s, const uint32_t* picks = nullptr);
 // tris[0 .. records]: holes and the zero padding record, then record sorted[j] of the snapshot at position[j]; perm
 hipError_t launch_lbvh_scatter(const GpuTriangle* snap, const uint32_t* sorted, const uint32_t* position, GpuTriangle* tris, uint32_t* perm, uint32_t prims,
                                uint32_t records, hipStream_t s);

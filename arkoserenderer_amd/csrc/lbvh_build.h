@@ -37,6 +37,17 @@
 // min / max unions of ordered words: the same bits in any order, -0 below +0), sweepKey,
 // halfArea, splitKey; what the collapse reads of it: SahBoxes, kOpenLargestBox, rangeCentre,
 // memberLowW.
+//
+// The collapse plan (ARK_DDGI_FLAG_GPU_REBUILD_PLAN, with the SAH pass): the treelets go down
+// to single primitives (treeletsOf lists ranges of 2 and 3 too, so only single primitives lie
+// outside a treelet), and every BVH2 node n gets cost[n][i], i = 1 .. 8 - the least SAH cost
+// of the subtree below n held in at most i slots of a BVH8 node (Ylitie, Karras, Laine 2017,
+// the host collapse's planNode) - and the picks that reach it (planCosts; one packed word per
+// node, kPlanDone set once it is final). Bottom-up: inside a treelet by its workgroup, above
+// the treelets by k_lbvh_upper_plan, which also boxes those nodes. The collapse then walks the
+// picks (planCut) where it chose greedily (selectCut); a range of at most kBvh8MaxLeafSize
+// primitives is never an internal member, so assignSlots, the rows and the scatter see what
+// they saw before.
 #pragma once
 
 #include <stdint.h>
@@ -412,9 +423,11 @@ ARK_LBVH_FN void primBox(const float v[3][3], uint32_t b[6])
 // The treelets that the BVH2 node over r with split s adds to the SAH pass's work list
 // (out[0 .. return)): each child of at most kTreeletPrims primitives of a node of more, and
 // a class's root of at most kTreeletPrims; none of kBvh8MaxLeafSize or fewer, which the
-// collapse never opens. Treelets are disjoint ranges of at least 4 primitives.
-ARK_LBVH_FN int treeletsOf(const Range& r, uint32_t s, bool isRoot, Member out[2])
+// collapse never opens. Treelets are disjoint ranges of at least 4 primitives. plan (the
+// collapse plan): ranges of 2 and 3 too - then only single primitives lie outside a treelet.
+ARK_LBVH_FN int treeletsOf(const Range& r, uint32_t s, bool isRoot, Member out[2], bool plan = false)
 {
+    const uint32_t least = plan ? 1u : static_cast<uint32_t>(kBvh8MaxLeafSize);
     int n = 0;
     if (count(r) > kTreeletPrims) {
         Member a, b;
@@ -424,9 +437,9 @@ ARK_LBVH_FN int treeletsOf(const Range& r, uint32_t s, bool isRoot, Member out[2
         b.r.first = s + 1u;
         b.r.last = r.last;
         b.node = rightNode(b.r);
-        if (count(a.r) <= kTreeletPrims && count(a.r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) out[n++] = a;
-        if (count(b.r) <= kTreeletPrims && count(b.r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) out[n++] = b;
-    } else if (isRoot && count(r) > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        if (count(a.r) <= kTreeletPrims && count(a.r) > least) out[n++] = a;
+        if (count(b.r) <= kTreeletPrims && count(b.r) > least) out[n++] = b;
+    } else if (isRoot && count(r) > least) {
         out[0].r = r;
         out[0].node = r.first;
         n = 1;
@@ -489,6 +502,150 @@ ARK_LBVH_FN int selectCut(const uint64_t* keys, const uint32_t* split, const Mem
         }
         if (open < 0) break;
         cur = out[open];
+    }
+    return n;
+}
+
+// The collapse plan -----------------------------------------------------------------
+// cost[n][i] (C[i - 1]) of a BVH2 node n over cnt primitives with box half-area `area`, from
+// its children's (L, R; a single primitive: planLeafCosts): with dist(j) the least
+// L[k] + R[j - k] over k = 1 .. j - 1 (the lowest k wins ties), cost[n][1] is
+// area kPlanNodeCost + dist(8) - n as a BVH8 node of its own - for more than kBvh8MaxLeafSize
+// primitives and area kPlanTriCost cnt - one leaf slot - otherwise (such a range is never an
+// internal member), cost[n][i] = min(dist(i), cost[n][i - 1]). fp32, no contraction, left
+// then right. Returns the picks, packed: the slots given to the left child at i = 2, 3 (two
+// bits each, from bit 0) and i = 4 .. 8 (three bits each, from bit 4), 0: as i - 1; from bit
+// 19 those of the node's own 8 (more than kBvh8MaxLeafSize primitives). 22 bits.
+constexpr float kPlanNodeCost = 1.0f, kPlanTriCost = 1.0f; // Bvh8CollapseOptions' defaults
+constexpr uint32_t kPlanPickBits = 0x3fffffu;
+constexpr uint32_t kPlanDone = 0x80000000u;     // the node's word is final
+constexpr uint32_t kPlanComputed = 0x40000000u; // (k_lbvh_upper_plan: written this round, final from the next)
+ARK_LBVH_FN uint32_t planPickShift(int i) { return i < 4 ? 2u * static_cast<uint32_t>(i - 2) : 4u + 3u * static_cast<uint32_t>(i - 4); }
+ARK_LBVH_FN uint32_t planPick(uint32_t word, int i) { return (word >> planPickShift(i)) & (i < 4 ? 3u : 7u); }
+ARK_LBVH_FN uint32_t planOwnPick(uint32_t word) { return (word >> 19) & 7u; }
+
+ARK_LBVH_FN void planLeafCosts(const uint32_t box[6], float C[8])
+{
+    const float c = halfArea(box) * kPlanTriCost;
+    for (int i = 0; i < 8; ++i) C[i] = c;
+}
+
+template <int J>
+ARK_LBVH_FN float planDist(const float L[8], const float R[8], uint32_t& bestK)
+{
+    float best = L[0] + R[J - 2];
+    bestK = 1u;
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int k = 2; k < J; ++k) {
+        const float v = L[k - 1] + R[J - k - 1];
+        if (v < best) {
+            best = v;
+            bestK = static_cast<uint32_t>(k);
+        }
+    }
+    return best;
+}
+
+template <int I>
+ARK_LBVH_FN void planStep(const float L[8], const float R[8], float C[8], uint32_t& word)
+{
+    uint32_t k;
+    const float d = planDist<I>(L, R, k);
+    if (d < C[I - 2]) {
+        C[I - 1] = d;
+        word |= k << planPickShift(I);
+    } else {
+        C[I - 1] = C[I - 2];
+    }
+}
+
+ARK_LBVH_FN uint32_t planCosts(float area, uint32_t cnt, const float L[8], const float R[8], float C[8])
+{
+    uint32_t word = 0;
+    if (cnt > static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        uint32_t k8;
+        const float d = planDist<8>(L, R, k8);
+        C[0] = area * kPlanNodeCost + d;
+        word = k8 << 19;
+    } else {
+        C[0] = area * kPlanTriCost * static_cast<float>(cnt);
+    }
+    planStep<2>(L, R, C, word);
+    planStep<3>(L, R, C, word);
+    planStep<4>(L, R, C, word);
+    planStep<5>(L, R, C, word);
+    planStep<6>(L, R, C, word);
+    planStep<7>(L, R, C, word);
+    planStep<8>(L, R, C, word);
+    return word;
+}
+
+// A node above the treelets: its box (ordered words) the union of its children's, its plan
+// from theirs
+ARK_LBVH_FN uint32_t planUpperNode(const uint32_t lb[6], const float L[8], const uint32_t rb[6], const float R[8], uint32_t cnt, uint32_t box[6], float C[8])
+{
+    for (int a = 0; a < 3; ++a) {
+        box[a] = lb[a] < rb[a] ? lb[a] : rb[a];
+        box[3 + a] = lb[3 + a] > rb[3 + a] ? lb[3 + a] : rb[3 + a];
+    }
+    return planCosts(halfArea(box), cnt, L, R, C);
+}
+
+// The two children of the BVH2 node of m (more than one primitive) under the numbering
+ARK_LBVH_FN void childrenOf(const uint32_t* split, const Member& m, Member& a, Member& b)
+{
+    const uint32_t sp = split[m.node];
+    a.r.first = m.r.first;
+    a.r.last = sp;
+    a.node = leftNode(a.r);
+    b.r.first = sp + 1u;
+    b.r.last = m.r.last;
+    b.node = rightNode(b.r);
+}
+
+// selectCut by the plan: the members of the BVH8 node over `top`, in left-to-right range
+// order. From top's own 8-way distribution down, with a stack of at most 8 (the slots on it
+// sum to at most 8): a range that reaches i = 1, or a single primitive, is a member - an
+// internal one if it holds more than kBvh8MaxLeafSize primitives; a pick of 0 is "as i - 1".
+// A pick outside 1 .. i - 1 (never: planCosts writes none) is taken as the nearest inside.
+ARK_LBVH_FN int planCut(const uint32_t* split, const uint32_t* picks, const Member& top, Member out[8])
+{
+    if (count(top.r) <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        out[0] = top;
+        return 1;
+    }
+    Member stack[8];
+    uint32_t slots[8];
+    int sp = 0, n = 0;
+    Member cur = top;
+    uint32_t i = 8u, k = planOwnPick(picks[top.node]);
+    for (;;) {
+        // `cur` shares its i slots between its children: k to the left one
+        k = k < 1u ? 1u : k > i - 1u ? i - 1u : k;
+        Member a, b;
+        childrenOf(split, cur, a, b);
+        stack[sp] = b;
+        slots[sp++] = i - k;
+        stack[sp] = a;
+        slots[sp++] = k;
+        bool opened = false;
+        while (sp > 0 && !opened) {
+            cur = stack[--sp];
+            i = slots[sp];
+            k = 0u;
+            if (count(cur.r) > 1u) {
+                const uint32_t word = picks[cur.node];
+                while (i >= 2u && (k = planPick(word, static_cast<int>(i))) == 0u) --i;
+            }
+            if (count(cur.r) > 1u && i >= 2u) {
+                opened = true;
+            } else if (n < 8) {
+                out[n++] = cur;
+            }
+        }
+        if (!opened) break;
     }
     return n;
 }
@@ -663,9 +820,9 @@ struct WideNode {
 };
 
 ARK_LBVH_FN void planNode(const uint64_t* keys, const uint32_t* split, const Member& top, int criterion, const float extent[3], WideNode& w,
-                          int slotRule = kSlotsOctant, const KeyLayout& L = kWorldLayout, const SahBoxes* S = nullptr)
+                          int slotRule = kSlotsOctant, const KeyLayout& L = kWorldLayout, const SahBoxes* S = nullptr, const uint32_t* picks = nullptr)
 {
-    w.members = selectCut(keys, split, top, criterion, extent, w.member, L, S);
+    w.members = picks ? planCut(split, picks, top, w.member) : selectCut(keys, split, top, criterion, extent, w.member, L, S);
     assignSlots(keys, top.r, w.member, w.members, w.slotOf, slotRule, L, S, top.node);
     uint32_t cnt[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     w.imask = 0;

@@ -37,6 +37,11 @@ struct LbvhGpuTrace {
     std::vector<uint32_t> idxMorton;
     std::vector<lbvh::Member> treelets;
     std::vector<float> nbox, pbox;
+    // the collapse plan (LbvhGpuBuild::plan): the nodes above the treelets, the packed picks
+    // per BVH2 node, the eight costs per node index (set at treelet roots and upper nodes)
+    std::vector<lbvh::Member> upper;
+    std::vector<uint32_t> picks;
+    std::vector<float> pcost;
     std::vector<uint64_t> keysSorted;
     std::vector<GpuBvh8Node> nodes;
     std::vector<GpuTriangle> tris;                // the rows, then the padding record
@@ -67,7 +72,7 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         ~Arena() { buf.release(); }
     } arenaA, arenaB;
     struct {
-        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes, treelets, nbox, pbox;
+        DeviceBuffer classOf, hdr, idx, idxSorted, keys, keysSorted, sortTemp, split, position, items[2], nodes, counters, masks, inst, boxes, treelets, nbox, pbox, upper, picks, pcost;
     } w;
     hipError_t e = hipSuccess;
     struct KeepWhy {
@@ -119,12 +124,16 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
     // (the collapse's bound on the nodes: below)
     const uint32_t nodeCap = n / 2u + 8u;
     // (the SAH pass: treelets are disjoint ranges of at least 4 primitives; its list and boxes live in the same arena)
-    const uint32_t treeletCap = g.sah ? n / 4u + 1u : 0u;
+    // (the collapse plan: treelets of at least 2, fewer than n nodes above them; a word and eight costs per node index)
+    const bool plan = g.sah && g.plan;
+    const uint32_t treeletCap = plan ? n / 2u + 1u : g.sah ? n / 4u + 1u : 0u;
+    const uint32_t upperCap = plan ? n : 0u;
     const size_t sahBoxBytes = g.sah ? n * 6ull * sizeof(float) : 0;
+    const size_t picksBytes = plan ? n * 4ull : 0, pcostBytes = plan ? n * 8ull * sizeof(float) : 0;
     {
         const size_t sizes[] = { tempBytes, n * 8ull, n * 4ull, n * 4ull, nodeCap * sizeof(GpuBvh8Node), nodeCap * sizeof(lbvh::Member), nodeCap * sizeof(lbvh::Member),
                                  n * 4ull, kLbvhCounters * 4ull, nodeCap * 8ull, instances * sizeof(RefitInstance), nodeCap * 6ull * sizeof(float),
-                                 treeletCap * sizeof(lbvh::Member), sahBoxBytes, sahBoxBytes };
+                                 treeletCap * sizeof(lbvh::Member), sahBoxBytes, sahBoxBytes, upperCap * sizeof(lbvh::Member), picksBytes, pcostBytes };
         size_t total = 0;
         for (size_t b : sizes) total += Arena::pad(b);
         ARK_GB(arenaB.buf.alloc(total));
@@ -143,6 +152,9 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         w.treelets = arenaB.take(sizes[12]);
         w.nbox = arenaB.take(sizes[13]);
         w.pbox = arenaB.take(sizes[14]);
+        w.upper = arenaB.take(sizes[15]);
+        w.picks = arenaB.take(sizes[16]);
+        w.pcost = arenaB.take(sizes[17]);
     }
     ARK_GB(launch_lbvh_sort(w.sortTemp.ptr, tempBytes, w.keys.as<uint64_t>(), w.keysSorted.as<uint64_t>(), w.idx.as<uint32_t>(), w.idxSorted.as<uint32_t>(), n, s));
     // the radix trees, class by class
@@ -152,9 +164,10 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         classLo[c] = first;
         first += hdr.classCount[c];
         ARK_GB(launch_lbvh_hierarchy(w.keysSorted.as<uint64_t>(), classLo[c], classLo[c] + hdr.classCount[c], w.split.as<uint32_t>(), s,
-                                     g.sah ? w.treelets.as<lbvh::Member>() : nullptr, treeletCap, w.counters.as<uint32_t>()));
+                                     g.sah ? w.treelets.as<lbvh::Member>() : nullptr, treeletCap, w.counters.as<uint32_t>(),
+                                     plan ? w.upper.as<lbvh::Member>() : nullptr, upperCap));
     }
-    uint32_t treelets = 0;
+    uint32_t treelets = 0, upperNodes = 0;
     if (g.sah) {
         // the SAH pass: one workgroup per treelet, the launch sized by the list's count read back
         uint32_t counted[kLbvhCounters] = {};
@@ -164,10 +177,15 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         }
         ARK_GB(hipMemsetAsync(w.nbox.ptr, 0, sahBoxBytes, s));
         ARK_GB(hipMemsetAsync(w.pbox.ptr, 0, sahBoxBytes, s));
+        if (plan) {
+            ARK_GB(hipMemsetAsync(w.picks.ptr, 0, picksBytes, s));
+            ARK_GB(hipMemsetAsync(w.pcost.ptr, 0, pcostBytes, s));
+        }
         ARK_GB(hipMemcpyAsync(counted, w.counters.ptr, sizeof(counted), hipMemcpyDeviceToHost, s));
         ARK_GB(hipStreamSynchronize(s));
         treelets = counted[kLbvhTreelets];
-        if (counted[kLbvhOverflow] || treelets > treeletCap) {
+        upperNodes = counted[kLbvhUpper];
+        if (counted[kLbvhOverflow] || treelets > treeletCap || upperNodes > upperCap) {
             why = "more nodes than the device build's scratch";
             return hipSuccess;
         }
@@ -181,7 +199,27 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         ta.pbox = w.pbox.as<float>();
         ta.light = g.light ? 1 : 0;
         std::memcpy(ta.frame.m, g.frame, sizeof(ta.frame.m));
-        ARK_GB(launch_lbvh_treelet_sah(ta, treelets, s));
+        ta.picks = plan ? w.picks.as<uint32_t>() : nullptr;
+        ta.pcost = plan ? w.pcost.as<float>() : nullptr;
+        ARK_GB(launch_lbvh_treelet_sah(ta, treelets, s, plan));
+        if (plan) {
+            // the nodes above the treelets, behind the treelets' kernel: one workgroup, in rounds
+            LbvhUpperArgs ua {};
+            ua.snap = snap;
+            ua.list = w.upper.as<lbvh::Member>();
+            ua.count = upperNodes;
+            ua.prims = n;
+            ua.sorted = w.idxSorted.as<uint32_t>();
+            ua.split = w.split.as<uint32_t>();
+            ua.nbox = w.nbox.as<float>();
+            ua.pbox = w.pbox.as<float>();
+            ua.picks = w.picks.as<uint32_t>();
+            ua.pcost = w.pcost.as<float>();
+            ua.counters = w.counters.as<uint32_t>();
+            ua.light = ta.light;
+            ua.frame = ta.frame;
+            ARK_GB(launch_lbvh_upper_plan(ua, s));
+        }
     }
     // the collapse. Every BVH8 node but a class's root is a BVH2 node of at least 4
     // triangles, and one with an internal child has 8 members. With L nodes without an
@@ -231,12 +269,16 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
             a.nextCapacity = nodeCap - a.nextBase;
             a.next = w.items[pong].as<lbvh::Member>();
             ARK_GB(hipMemsetAsync(w.counters.as<uint32_t>() + kLbvhNextCount, 0, 4, s));
-            ARK_GB(launch_lbvh_collapse(a, s));
+            ARK_GB(launch_lbvh_collapse(a, s, plan ? w.picks.as<uint32_t>() : nullptr));
             // the level's count, before the next level is launched
             ARK_GB(hipMemcpyAsync(counters, w.counters.ptr, sizeof(counters), hipMemcpyDeviceToHost, s));
             ARK_GB(hipStreamSynchronize(s));
             if (counters[kLbvhOverflow]) {
                 why = "more nodes than the device build's scratch";
+                return hipSuccess;
+            }
+            if (counters[kLbvhPlanStalled]) {
+                why = "the collapse plan did not finish";
                 return hipSuccess;
             }
             if (levels.size() <= depth) levels.push_back({ 0u, 0u, 0u });
@@ -331,6 +373,14 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
             ARK_GB(hipMemcpyAsync(t->nbox.data(), w.nbox.ptr, sahBoxBytes, hipMemcpyDeviceToHost, s));
             ARK_GB(hipMemcpyAsync(t->pbox.data(), w.pbox.ptr, sahBoxBytes, hipMemcpyDeviceToHost, s));
         }
+        if (plan) {
+            t->upper.resize(upperNodes);
+            t->picks.resize(n);
+            t->pcost.resize(n * 8ull);
+            if (upperNodes) ARK_GB(hipMemcpyAsync(t->upper.data(), w.upper.ptr, upperNodes * sizeof(lbvh::Member), hipMemcpyDeviceToHost, s));
+            ARK_GB(hipMemcpyAsync(t->picks.data(), w.picks.ptr, picksBytes, hipMemcpyDeviceToHost, s));
+            ARK_GB(hipMemcpyAsync(t->pcost.data(), w.pcost.ptr, pcostBytes, hipMemcpyDeviceToHost, s));
+        }
         ARK_GB(hipStreamSynchronize(s));
         t->order = order;
         t->levelOffsets = b.levelOffsets;
@@ -354,13 +404,14 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
 // nothing else) of the given records on a stream of its own, without a context, against
 // build_lbvh_host of the same records in the device's compaction order, stage by stage.
 namespace {
-// out: 40 words (ark_ddgi_debug_lbvh_device_parity_sah's)
+// out: 48 words (ark_ddgi_debug_lbvh_device_parity_plan's)
 int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances, const float* sun_dir, int w_bits, bool sahPass,
-                     uint64_t* out)
+                     bool planPass, uint64_t* out)
 {
+    planPass = planPass && sahPass;
     using namespace ark;
     if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
-    std::fill(out, out + 40, uint64_t(0));
+    std::fill(out, out + 48, uint64_t(0));
     for (uint32_t i = 0; i < n_instances; ++i)
         if (class_of[i] < 0 || class_of[i] > 2) return -1; // (the kernels index the class counts by it)
     int wBits = lbvh::kMortonBits;
@@ -414,13 +465,14 @@ int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const 
         g.perm = &d.perm;
         g.trace = &trace;
         g.sah = sahPass;
+        g.plan = planPass;
         e = buildLbvhGpu(g, d.s, why);
     }
     if (e == hipSuccess) e = hipStreamSynchronize(d.s);
     out[26] = static_cast<uint64_t>(e);
     if (e != hipSuccess) return -5;
     static const char* const kWhy[] = { "", "no records", "no triangles", "record of an unknown instance", "BVH8 deeper than the device build installs",
-                                        "more nodes than the device build's scratch", "nodes and records of 4 GiB or more" };
+                                        "more nodes than the device build's scratch", "nodes and records of 4 GiB or more" }; // (another, the plan's included: 7)
     out[4] = 7;
     for (uint64_t k = 0; k < sizeof(kWhy) / sizeof(kWhy[0]); ++k)
         if (trace.why == kWhy[k]) out[4] = k;
@@ -451,7 +503,7 @@ int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const 
     LbvhSunOptions so;
     std::memcpy(so.frame, g.frame, sizeof(so.frame));
     so.wBits = wBits;
-    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx, sahPass);
+    const LbvhHostResult r = build_lbvh_host(rec, classOf, lbvh::kDefaultCriterion, sun_dir ? &so : nullptr, out[5] ? nullptr : &trace.idx, sahPass, planPass);
     auto bits = [](float f) {
         uint32_t u;
         std::memcpy(&u, &f, 4);
@@ -501,6 +553,29 @@ int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const 
         for (size_t k = 0; k < std::min(trace.nbox.size(), r.nbox.size()); ++k) out[32] += bits(trace.nbox[k]) != bits(r.nbox[k]) ? 1u : 0u;
         for (size_t k = 0; k < std::min(trace.pbox.size(), r.pbox.size()); ++k) out[33] += bits(trace.pbox[k]) != bits(r.pbox[k]) ? 1u : 0u;
     }
+    if (planPass) {
+        // the upper list as a set; the picks at every node index, the costs of the treelet
+        // roots and upper nodes (all else 0 on both sides) and the upper nodes' boxes, by bits
+        auto less = [](const lbvh::Member& a, const lbvh::Member& b) { return a.node < b.node; };
+        std::vector<lbvh::Member> dl = trace.upper, hl = r.upper;
+        std::sort(dl.begin(), dl.end(), less);
+        std::sort(hl.begin(), hl.end(), less);
+        out[34] = dl.size();
+        out[38] = dl.size() != hl.size() ? 1u : 0u;
+        for (size_t k = 0; k < std::min(dl.size(), hl.size()); ++k)
+            out[38] += dl[k].r.first != hl[k].r.first || dl[k].r.last != hl[k].r.last || dl[k].node != hl[k].node ? 1u : 0u;
+        out[35] = trace.picks.size() != r.picks.size() ? 1u : 0u;
+        for (size_t k = 0; k < std::min(trace.picks.size(), r.picks.size()); ++k) out[35] += trace.picks[k] != r.picks[k] ? 1u : 0u;
+        out[36] = trace.pcost.size() != r.pcost.size() ? 1u : 0u;
+        for (size_t k = 0; k < std::min(trace.pcost.size(), r.pcost.size()); ++k) out[36] += bits(trace.pcost[k]) != bits(r.pcost[k]) ? 1u : 0u;
+        for (const lbvh::Member& m : hl)
+            for (int q = 0; q < 6; ++q) {
+                const size_t at = 6ull * m.node + static_cast<size_t>(q);
+                out[37] += at >= trace.nbox.size() || at >= r.nbox.size() || bits(trace.nbox[at]) != bits(r.nbox[at]) ? 1u : 0u;
+            }
+        out[39] = r.planRounds;
+        if (r.planStalled) out[35]++;
+    }
     // the tree
     const GpuTriangle padding = trace.tris.back(); // (records + 1 entries)
     trace.tris.pop_back();
@@ -542,7 +617,7 @@ int lbvhDeviceParity(int device, const void* records, uint64_t n_records, const 
     out[28] = r.nodes.size();
     uint64_t mismatches = 0;
     for (int k = 5; k <= 23; ++k) mismatches += out[k];
-    mismatches += out[30] + out[31] + out[32] + out[33];
+    mismatches += out[30] + out[31] + out[32] + out[33] + out[35] + out[36] + out[37] + out[38];
     return mismatches ? 1 : 0;
 }
 } // namespace
@@ -551,8 +626,8 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
                                                   const float* sun_dir, int w_bits, uint64_t* out)
 {
     if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
-    uint64_t all[40];
-    const int rc = lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, false, all);
+    uint64_t all[48];
+    const int rc = lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, false, false, all);
     std::copy(all, all + 32, out);
     return rc;
 }
@@ -560,5 +635,15 @@ extern "C" int ark_ddgi_debug_lbvh_device_parity(int device, const void* records
 extern "C" int ark_ddgi_debug_lbvh_device_parity_sah(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
                                                       const float* sun_dir, int w_bits, int sah, uint64_t* out)
 {
-    return lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, sah != 0, out);
+    if (!records || !class_of || !out || n_records == 0 || n_records > 0x7fffffffull || n_instances == 0) return -1;
+    uint64_t all[48];
+    const int rc = lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, sah != 0, false, all);
+    std::copy(all, all + 40, out);
+    return rc;
+}
+
+extern "C" int ark_ddgi_debug_lbvh_device_parity_plan(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                                       const float* sun_dir, int w_bits, int sah, int plan, uint64_t* out)
+{
+    return lbvhDeviceParity(device, records, n_records, class_of, n_instances, sun_dir, w_bits, sah != 0, plan != 0, out);
 }

@@ -31,6 +31,10 @@ struct LbvhGpuBuild {
     // ARK_DDGI_FLAG_GPU_REBUILD_SAH: the SAH pass over the radix tree's treelets
     // (k_lbvh_treelet_sah) before the collapse, which then decides by the pass's boxes
     bool sah = false;
+    // ARK_DDGI_FLAG_GPU_REBUILD_PLAN (with sah; alone it does nothing): the pass splits down to
+    // single primitives and plans its nodes, k_lbvh_upper_plan the nodes above the treelets,
+    // and the collapse follows the picks (lbvh::planCut)
+    bool plan = false;
     DeviceBvh* bvh = nullptr;          // out: buffer, level order (device and offsets), counts, depth
     DeviceBuffer* perm = nullptr;      // out: the record order's source indices (null: not wanted)
     LbvhGpuTrace* trace = nullptr;     // out: the stages' results (null in the product paths: nothing more is enqueued)

@@ -14,9 +14,12 @@ namespace {
 // k_lbvh_treelet_sah, serially: the binary tree of one treelet T (4 .. kTreeletPrims
 // primitives) by a three-axis sweep SAH. box: 6 ordered words per sorted primitive, as the
 // sort left them. sorted and split are rewritten inside T's range, nbox and pbox filled.
+// plan (the collapse plan; T of 2 primitives or more): split down to single primitives, nbox
+// of every node, then the nodes' plans bottom-up: their words in picks, the root's costs in pcost.
 void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std::vector<uint32_t>& sorted, std::vector<uint32_t>& split, std::vector<float>& nbox,
-                    std::vector<float>& pbox)
+                    std::vector<float>& pbox, bool plan, std::vector<uint32_t>& picks, std::vector<float>& pcost)
 {
+    const uint32_t leafMost = plan ? 1u : static_cast<uint32_t>(kBvh8MaxLeafSize);
     const uint32_t first = T.r.first, n = lbvh::count(T.r);
     auto at = [&](uint32_t prim) { return &box[6ull * (first + prim)]; };
     std::vector<uint32_t> ord[3];
@@ -30,7 +33,8 @@ void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std
     struct Segment {
         uint32_t f, l, node; // positions and node index relative to `first`
     };
-    std::vector<Segment> todo(1, Segment { 0u, n - 1u, T.node - first }), final;
+    std::vector<Segment> todo(1, Segment { 0u, n - 1u, T.node - first }), final, made;
+    std::vector<float> area(n, 0.0f);
     std::vector<uint32_t> splitRel(n, 0xffffffffu);
     std::vector<uint8_t> side(n, 0);
     auto unite = [](uint32_t u[6], const uint32_t* b) {
@@ -43,10 +47,11 @@ void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std
         const Segment sg = todo.back();
         todo.pop_back();
         const uint32_t cnt = sg.l - sg.f + 1u;
-        if (cnt <= static_cast<uint32_t>(kBvh8MaxLeafSize)) {
+        if (cnt <= leafMost) {
             final.push_back(sg);
             continue;
         }
+        made.push_back(sg);
         uint64_t best = lbvh::kNoSplit;
         for (int ax = 0; ax < 3; ++ax) {
             std::vector<std::array<uint32_t, 6>> pre(cnt), suf(cnt);
@@ -60,8 +65,10 @@ void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std
                 unite(v, at(ord[ax][sg.f + i]));
                 std::copy(v, v + 6, suf[i].begin());
             }
-            if (ax == 0)
+            if (ax == 0) {
                 for (int c = 0; c < 6; ++c) nbox[6ull * (first + sg.node) + c] = lbvh::orderedFloat(pre[cnt - 1u][c]);
+                area[sg.node] = lbvh::halfArea(pre[cnt - 1u].data());
+            }
             for (uint32_t k = 1; k < cnt; ++k) best = std::min(best, lbvh::splitKey(lbvh::halfArea(pre[k - 1u].data()), lbvh::halfArea(suf[k].data()), k, cnt, static_cast<uint32_t>(ax)));
         }
         uint32_t axis, k;
@@ -83,14 +90,31 @@ void treeletSahHost(const lbvh::Member& T, const std::vector<uint32_t>& box, std
         for (int c = 0; c < 6; ++c) pbox[6ull * (first + i) + c] = lbvh::orderedFloat(at(prim)[c]);
         if (first + i != lbvh::treeletSpareIndex(T)) split[first + i] = first + splitRel[i];
     }
+    if (!plan) return;
+    // the plans, children before parents (a child is made after its parent)
+    std::vector<std::array<float, 8>> cost(n);
+    auto childCosts = [&](uint32_t f, uint32_t l, uint32_t node, float C[8]) {
+        if (f == l) return lbvh::planLeafCosts(at(ord[0][f]), C);
+        std::copy(cost[node].begin(), cost[node].end(), C);
+    };
+    for (size_t k = made.size(); k-- > 0;) {
+        const Segment& sg = made[k];
+        const uint32_t sp = splitRel[sg.node];
+        float L[8], R[8];
+        childCosts(sg.f, sp, sp, L);
+        childCosts(sp + 1u, sg.l, sp + 1u, R);
+        picks[first + sg.node] = lbvh::planCosts(area[sg.node], sg.l - sg.f + 1u, L, R, cost[sg.node].data()) | lbvh::kPlanDone;
+    }
+    std::copy(cost[T.node - first].begin(), cost[T.node - first].end(), pcost.begin() + 8ull * T.node);
 }
 } // namespace
 
 LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun,
-                               const std::vector<uint32_t>* primOrder, bool sahPass)
+                               const std::vector<uint32_t>* primOrder, bool sahPass, bool plan)
 {
     LbvhHostResult R;
     if (sahPass) criterion = lbvh::kOpenLargestBox;
+    plan = plan && sahPass; // (the flag does nothing without the SAH pass)
     const lbvh::KeyLayout layout = { sun ? sun->wBits : lbvh::kMortonBits };
     const int slotRule = sun ? lbvh::kSlotsAscendingW : lbvh::kSlotsOctant;
     // the vertices a record is boxed by: the world ones, or their light coordinates
@@ -165,6 +189,10 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
             boxVertices(rec[sortedRec[j]], v);
             lbvh::primBox(v, &obox[6ull * j]);
         }
+        if (plan) {
+            R.picks.assign(n, 0u);
+            R.pcost.assign(n * 8ull, 0.0f);
+        }
         boxes.nbox = R.nbox.data();
         boxes.pbox = R.pbox.data();
         for (int a = 0; a < 3; ++a) {
@@ -180,17 +208,63 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
         const uint32_t lo = first, hi = first + classCount[c];
         first = hi;
         if (lo == hi) continue;
-        const size_t firstTreelet = R.treelets.size();
+        const size_t firstTreelet = R.treelets.size(), firstUpper = R.upper.size();
         for (uint32_t i = lo; i + 1u < hi; ++i) {
             const lbvh::Range r = lbvh::nodeRange(keys.data(), lo, hi, i);
             split[i] = lbvh::findSplit(keys.data(), lo, hi, r);
             if (!sahPass) continue;
             // the SAH pass's work list (k_lbvh_hierarchy's appends; any order)
             lbvh::Member m[2];
-            const int k = lbvh::treeletsOf(r, split[i], i == lo, m);
+            const int k = lbvh::treeletsOf(r, split[i], i == lo, m, plan);
             R.treelets.insert(R.treelets.end(), m, m + k);
+            // the nodes above the treelets (k_lbvh_hierarchy's second list)
+            if (plan && lbvh::count(r) > lbvh::kTreeletPrims) R.upper.push_back(lbvh::Member { r, i });
         }
-        for (size_t t = firstTreelet; t < R.treelets.size(); ++t) treeletSahHost(R.treelets[t], obox, sortedRec, split, R.nbox, R.pbox);
+        for (size_t t = firstTreelet; t < R.treelets.size(); ++t) treeletSahHost(R.treelets[t], obox, sortedRec, split, R.nbox, R.pbox, plan, R.picks, R.pcost);
+        if (plan) {
+            // k_lbvh_upper_plan: rounds over the class's upper nodes until none is left; a
+            // node whose children are done is boxed and planned (the device's schedule differs,
+            // the result does not: unions of ordered words, plans of finished children)
+            std::vector<lbvh::Member> todo(R.upper.begin() + static_cast<std::ptrdiff_t>(firstUpper), R.upper.end());
+            auto done = [&](const lbvh::Member& m) { return lbvh::count(m.r) <= lbvh::kTreeletPrims || (R.picks[m.node] & lbvh::kPlanDone) != 0u; };
+            auto childPlan = [&](const lbvh::Member& m, uint32_t b[6], float C[8]) {
+                if (lbvh::count(m.r) == 1u) {
+                    // a stray primitive: its box from its vertices, kept for the collapse too
+                    std::copy(&obox[6ull * m.r.first], &obox[6ull * m.r.first] + 6, b);
+                    for (int q = 0; q < 6; ++q) R.pbox[6ull * m.r.first + q] = lbvh::orderedFloat(b[q]);
+                    return lbvh::planLeafCosts(b, C);
+                }
+                for (int q = 0; q < 6; ++q) b[q] = lbvh::ordered(R.nbox[6ull * m.node + q]);
+                std::copy(&R.pcost[8ull * m.node], &R.pcost[8ull * m.node] + 8, C);
+            };
+            while (!todo.empty()) {
+                std::vector<lbvh::Member> later, now;
+                for (const lbvh::Member& m : todo) {
+                    lbvh::Member a, b;
+                    lbvh::childrenOf(split.data(), m, a, b);
+                    (done(a) && done(b) ? now : later).push_back(m);
+                }
+                if (now.empty()) {
+                    R.planStalled = true; // (never: the list is a tree's)
+                    break;
+                }
+                for (const lbvh::Member& m : now) {
+                    lbvh::Member a, b;
+                    lbvh::childrenOf(split.data(), m, a, b);
+                    uint32_t lb[6], rb[6], box[6];
+                    float L[8], Rc[8], Cn[8];
+                    childPlan(a, lb, L);
+                    childPlan(b, rb, Rc);
+                    const uint32_t word = lbvh::planUpperNode(lb, L, rb, Rc, lbvh::count(m.r), box, Cn);
+                    for (int q = 0; q < 6; ++q) R.nbox[6ull * m.node + q] = lbvh::orderedFloat(box[q]);
+                    std::copy(Cn, Cn + 8, &R.pcost[8ull * m.node]);
+                    R.picks[m.node] = word | lbvh::kPlanComputed | lbvh::kPlanDone;
+                }
+                todo.swap(later);
+                R.planRounds++;
+            }
+            if (c == 0 && hi - lo > static_cast<uint32_t>(kBvh8MaxLeafSize)) std::memcpy(&R.planRootCost, &R.pcost[8ull * lo], 4);
+        }
         R.roots[c] = static_cast<int32_t>(R.nodes.size());
         std::vector<lbvh::Member> level(1), next;
         level[0].r.first = lo;
@@ -204,7 +278,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
             const uint32_t nextBase = levelBase + static_cast<uint32_t>(level.size());
             for (size_t i = 0; i < level.size(); ++i) {
                 lbvh::WideNode w;
-                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout, sahBoxes);
+                lbvh::planNode(keys.data(), split.data(), level[i], criterion, extent, w, slotRule, layout, sahBoxes, plan ? R.picks.data() : nullptr);
                 const uint32_t slot0 = static_cast<uint32_t>(next.size());
                 const uint32_t triBase = w.rows.span ? records : 0u;
                 records += w.rows.span;
@@ -286,6 +360,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
     double sah = 0.0;
     std::vector<double> childArea(R.nodes.size(), 0.0); // sum over a node's children of area x cost
     std::vector<double> unionArea(R.nodes.size(), 0.0); // area of the union of a node's child boxes
+    std::vector<uint64_t> below(R.nodes.size(), 0u);    // triangles below a node
     for (size_t k = R.nodes.size(); k-- > 0;) {
         GpuBvh8Node& nd = R.nodes[k];
         Aabb slot[8], box;
@@ -295,6 +370,8 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
             slotBox[s] = nullptr;
             double cost = 1.0;
             if ((nd.imask >> s) & 1u) {
+                below[k] += below[nd.child_base + internal];
+                if (below[nd.child_base + internal] <= static_cast<uint64_t>(kBvh8MaxLeafSize)) R.smallInternal++;
                 slot[s] = nodeBox[nd.child_base + internal++];
             } else if ((nd.leaf_mask >> s) & 1u) {
                 uint32_t t[kBvh8MaxLeafSize];
@@ -306,6 +383,7 @@ LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& rec, const std::v
                 }
                 inflateChildBox(slot[s], inflateAbs);
                 cost = std::max(cnt, 0);
+                below[k] += static_cast<uint64_t>(std::max(cnt, 0));
             } else {
                 continue;
             }

@@ -38,6 +38,19 @@ struct LbvhHostResult {
     std::vector<uint32_t> idxMorton;
     std::vector<lbvh::Member> treelets;
     std::vector<float> nbox, pbox;
+    // the collapse plan (plan: true): treelets then lists ranges of 2 and 3 too and nbox holds
+    // every node's box, the upper nodes' included; the nodes above the treelets (any order),
+    // the packed picks per BVH2 node (lbvh::planCosts' word, kPlanDone set; 0 elsewhere), the
+    // eight costs of every treelet root and upper node (0 elsewhere), the opaque class's
+    // root's cost[1] as a word (0: a root of at most kBvh8MaxLeafSize triangles), the rounds
+    // the upper nodes took, and the BVH8 nodes but the roots with at most kBvh8MaxLeafSize
+    // triangles below them (the plan never makes one)
+    std::vector<lbvh::Member> upper;
+    std::vector<uint32_t> picks;
+    std::vector<float> pcost;
+    uint32_t planRootCost = 0, planRounds = 0;
+    bool planStalled = false;
+    uint64_t smallInternal = 0;
 };
 // sun: the light-space BVH8 of the sun's shadow rays instead (k_lbvh_prims_light /
 // k_lbvh_keys_light): one tree over every class (roots[0]), keys and boxes of the records'
@@ -52,7 +65,9 @@ struct LbvhSunOptions {
 // device has to build, ties included.
 // sah: the SAH pass over the treelets (k_lbvh_treelet_sah restated serially) between the
 // hierarchy and the collapse, which then opens by lbvh::kOpenLargestBox whatever `criterion`.
+// plan (with sah only): the collapse plan - the treelets down to single primitives, the plans
+// of their nodes and of the nodes above them, and the collapse by lbvh::planCut.
 LbvhHostResult build_lbvh_host(const std::vector<GpuTriangle>& records, const std::vector<int>& classOf, int criterion, const LbvhSunOptions* sun = nullptr,
-                               const std::vector<uint32_t>* primOrder = nullptr, bool sah = false);
+                               const std::vector<uint32_t>* primOrder = nullptr, bool sah = false, bool plan = false);
 
 } // namespace ark

@@ -60,6 +60,7 @@ struct RebuildJob {
     double frame[9] {};     // sun_frame(dir)
     uint32_t instances = 0; // of the scene (the device build checks the records' against it)
     bool sahPass = false;   // ARK_DDGI_FLAG_GPU_REBUILD_SAH: a device build runs the SAH pass
+    bool planPass = false;  // ARK_DDGI_FLAG_GPU_REBUILD_PLAN: and collapses by the plan
     // the sun's cover map of the snapshot (either kind, when the scene keeps one and the
     // caller has a sun): built on the device after the BVH, installed with it when no refit
     // came in since the snapshot
@@ -483,6 +484,7 @@ void deviceBuildWorld(RebuildJob* job, LbvhGpuBuild& g)
     g.classHost.assign(job->classOf.begin(), job->classOf.end());
     g.perm = &job->perm;
     g.sah = job->sahPass;
+    g.plan = job->planPass;
 }
 
 void deviceBuildSun(RebuildJob* job, LbvhGpuBuild& g)
@@ -493,6 +495,7 @@ void deviceBuildSun(RebuildJob* job, LbvhGpuBuild& g)
     g.slotRule = lbvh::kSlotsAscendingW;
     g.wBits = lbvh::kSunKeyBitsW;
     g.sah = job->sahPass;
+    g.plan = job->planPass;
 }
 
 // A job's device build on `s` (lbvh_device_build.h; ARK_DDGI_FLAG_GPU_REBUILD / _SUN), which
@@ -835,6 +838,7 @@ int sunStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     std::memcpy(job->frame, frame, sizeof(job->frame));
     job->instances = static_cast<uint32_t>(st.instHost.size());
     job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
+    job->planPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_PLAN) != 0;
     if (const int rc = launchJob(st, c.err, *job, s, gpu, c.hasSun, c.sunDir)) return rc;
     st.sunJob = std::move(job);
     st.lastBackground = kBackgroundSun;
@@ -898,6 +902,7 @@ int worldStart(SceneStore& st, const SceneCall& c, hipStream_t s, bool gpu)
     job->kind = RebuildJob::World;
     job->classOf = instanceClasses(st);
     job->sahPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_SAH) != 0;
+    job->planPass = (c.flags & ARK_DDGI_FLAG_GPU_REBUILD_PLAN) != 0;
     if (const int rc = launchJob(st, c.err, *job, s, gpu, c.hasSun, c.sunDir)) return rc;
     st.worldJob = std::move(job);
     st.lastBackground = kBackgroundWorld;

@@ -82,6 +82,10 @@ class DDGIConfig:
     # gpu_rebuild_sun enable rebuild every subtree of at most 256 triangles by a sweep SAH
     # before the 8-wide collapse; alone it does nothing
     gpu_rebuild_sah: bool = False
+    # ARK_DDGI_FLAG_GPU_REBUILD_PLAN (experimental): the device builds that run that SAH pass
+    # split down to single triangles and collapse by the SAH-optimal plan (the host build's)
+    # where they otherwise open members greedily; without the pass it does nothing
+    gpu_rebuild_plan: bool = False
     # the sun's cover map (on by default; False: ARK_DDGI_FLAG_NO_SUN_COVER_MAP, every sun
     # shadow ray is traced - same results)
     sun_cover_map: bool = True
@@ -128,6 +132,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD if config.gpu_rebuild else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SUN if config.gpu_rebuild_sun else 0
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_SAH if config.gpu_rebuild_sah else 0
+    d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_PLAN if config.gpu_rebuild_plan else 0
     d.flags |= 0 if config.sun_cover_map else abi.ARK_DDGI_FLAG_NO_SUN_COVER_MAP
     d.flags |= 0 if config.fused_sun_shade else abi.ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE
     d.build_threads = int(config.build_threads)
@@ -432,7 +437,7 @@ class DDGIContext:
 _BVH_CHECK_KEYS = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")
 
 
-def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int | None = None, sah: bool | None = None) -> tuple:
+def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int | None = None, sah: bool | None = None, plan: bool | None = None) -> tuple:
     """ark_ddgi_debug_sun_lbvh_check: the device build of the sun's light-space BVH8 run
     serially on the host over world triangles (n x 9 floats), then a sun shadow ray from
     each origin (m x 3 floats) through it against brute force. Returns (rc, dict): rays,
@@ -441,14 +446,21 @@ def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int 
     ray) and the tree's leaf_children, depth, records_with_holes, w_bits. w_bits: the
     key's Morton bits given to w (None: the default). sah not None:
     ark_ddgi_debug_sun_lbvh_check_sah, with (True) or without the SAH pass of
-    gpu_rebuild_sah, and `treelets`. No GPU."""
+    gpu_rebuild_sah, and `treelets`. plan not None: ark_ddgi_debug_sun_lbvh_check_plan, with
+    (True) or without the collapse plan of gpu_rebuild_plan on top of sah (None: True), and
+    `plan_root_cost` (an fp32 word), `small_internal`. No GPU."""
     lib = abi.load_library()
     tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
     sd = np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
     org = np.ascontiguousarray(origins, dtype=np.float32).reshape(-1, 3)
     keys = ("rays", "occluded_brute", "occluded_bvh", "mismatches", "node_visits", "triangle_tests", "nodes", "max_stack_depth", "violations",
             "inflation_differs", "cost_lbvh", "cost_host", "leaf_children", "depth", "records_with_holes", "w_bits")
-    if sah is None:
+    if plan is not None:
+        out = (C.c_uint64 * 19)()
+        rc = lib.ark_ddgi_debug_sun_lbvh_check_plan(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
+                                                    -1 if w_bits is None else int(w_bits), 0 if sah is False else 1, 1 if plan else 0, out)
+        keys = keys + ("treelets", "plan_root_cost", "small_internal")
+    elif sah is None:
         out = (C.c_uint64 * 16)()
         rc = lib.ark_ddgi_debug_sun_lbvh_check_opts(tris.ctypes.data, tris.shape[0], sd.ctypes.data, org.ctypes.data, org.shape[0], float(tmax),
                                                     -1 if w_bits is None else int(w_bits), out)
@@ -463,17 +475,22 @@ def sun_lbvh_check(triangles, sun_dir, origins, tmax: float = 1e30, w_bits: int 
     return rc, r
 
 
-def lbvh_check(triangles, criterion: int | None = None, sah: bool | None = None) -> tuple:
+def lbvh_check(triangles, criterion: int | None = None, sah: bool | None = None, plan: bool | None = None) -> tuple:
     """ark_ddgi_debug_lbvh_check: the device LBVH build's logic run serially on the host
     over world triangles (n x 9 floats). Returns (rc, out[8]) with out as
     ark_ddgi_debug_bvh8_check: nodes, leaf children, max depth, violations, triangles,
     radix-tree nodes, internal children, BVH8 SAH cost x 1e6. sah not None:
     ark_ddgi_debug_lbvh_check_sah, with (True) or without the SAH pass of gpu_rebuild_sah,
-    out[9] with the treelets last. No GPU."""
+    out[9] with the treelets last. plan not None: ark_ddgi_debug_lbvh_check_plan, with (True)
+    or without the collapse plan of gpu_rebuild_plan on top of sah (None: True), out[11] with
+    the plan's root cost word and the internal members of at most 3 triangles last. No GPU."""
     lib = abi.load_library()
     tris = np.ascontiguousarray(triangles, dtype=np.float32).reshape(-1, 9)
-    out = (C.c_uint64 * (8 if sah is None else 9))()
-    if sah is not None:
+    out = (C.c_uint64 * (11 if plan is not None else 8 if sah is None else 9))()
+    if plan is not None:
+        rc = lib.ark_ddgi_debug_lbvh_check_plan(tris.ctypes.data, tris.shape[0], 1 if criterion is None else int(criterion), 0 if sah is False else 1,
+                                                1 if plan else 0, out)
+    elif sah is not None:
         rc = lib.ark_ddgi_debug_lbvh_check_sah(tris.ctypes.data, tris.shape[0], 1 if criterion is None else int(criterion), 1 if sah else 0, out)
     elif criterion is None:
         rc = lib.ark_ddgi_debug_lbvh_check(tris.ctypes.data, tris.shape[0], out)
@@ -509,22 +526,34 @@ LBVH_PARITY_MISMATCHES = _LBVH_PARITY_KEYS[5:24]
 # ark_ddgi_debug_lbvh_device_parity_sah's further words
 _LBVH_PARITY_SAH_KEYS = _LBVH_PARITY_KEYS + ("treelets", "treelet_list", "sorted_after_sah", "node_boxes", "prim_boxes")
 LBVH_PARITY_SAH_MISMATCHES = LBVH_PARITY_MISMATCHES + _LBVH_PARITY_SAH_KEYS[30:34]
+# ark_ddgi_debug_lbvh_device_parity_plan's further words
+_LBVH_PARITY_PLAN_KEYS = _LBVH_PARITY_SAH_KEYS + ("upper_nodes", "plan_picks", "plan_costs", "upper_boxes", "upper_list", "upper_rounds")
+LBVH_PARITY_PLAN_MISMATCHES = LBVH_PARITY_SAH_MISMATCHES + _LBVH_PARITY_PLAN_KEYS[35:39]
 LBVH_WHY = ("", "no records", "no triangles", "record of an unknown instance", "too deep", "node scratch", "4 GiB", "other")
 
 
-def lbvh_device_parity(records, class_of, sun_dir=None, w_bits: int | None = None, device: int = 0, sah: bool | None = None) -> tuple:
+def lbvh_device_parity(records, class_of, sun_dir=None, w_bits: int | None = None, device: int = 0, sah: bool | None = None, plan: bool | None = None) -> tuple:
     """ark_ddgi_debug_lbvh_device_parity: the device LBVH build (the world's, or with sun_dir
     the sun's light-space one) run once over triangle records (triangle_records) and compared
     bit for bit, stage by stage, with its host restatement. class_of: instance -> hit-mask
     class. Returns (rc, dict): prims, nodes, records_with_holes, depth, why (LBVH_WHY's text)
     and one mismatch count per stage (LBVH_PARITY_MISMATCHES). sah not None:
     ark_ddgi_debug_lbvh_device_parity_sah, both builds with (True) or without the SAH pass
-    of gpu_rebuild_sah; also treelets and LBVH_PARITY_SAH_MISMATCHES' counts. Needs a GPU."""
+    of gpu_rebuild_sah; also treelets and LBVH_PARITY_SAH_MISMATCHES' counts. plan not None:
+    ark_ddgi_debug_lbvh_device_parity_plan, both builds with (True) or without the collapse plan
+    of gpu_rebuild_plan on top of sah (None: True); also upper_nodes and
+    LBVH_PARITY_PLAN_MISMATCHES' counts. Needs a GPU."""
     lib = abi.load_library()
     rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 12)
     cls = np.ascontiguousarray(class_of, dtype=np.int32).reshape(-1)
     sd = None if sun_dir is None else np.ascontiguousarray(sun_dir, dtype=np.float32).reshape(3)
-    if sah is None:
+    if plan is not None:
+        out = (C.c_uint64 * 48)()
+        rc = lib.ark_ddgi_debug_lbvh_device_parity_plan(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
+                                                        None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits),
+                                                        0 if sah is False else 1, 1 if plan else 0, out)
+        r = dict(zip(_LBVH_PARITY_PLAN_KEYS, (int(v) for v in out)))
+    elif sah is None:
         out = (C.c_uint64 * 32)()
         rc = lib.ark_ddgi_debug_lbvh_device_parity(int(device), rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0],
                                                    None if sd is None else sd.ctypes.data, -1 if w_bits is None else int(w_bits), out)

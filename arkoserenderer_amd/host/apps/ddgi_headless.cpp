@@ -29,7 +29,8 @@
 //                 [--gpu-rebuild MASK]                  device rebuilds after moved instances: 1 the
 //                                                       world BVHs (DDGINode::setGpuRebuild), 2 the
 //                                                       sun's (setGpuRebuildSun), 4 their SAH pass
-//                                                       (setGpuRebuildSah); prints the rebuild counts
+//                                                       (setGpuRebuildSah), 8 their collapse plan
+//                                                       (setGpuRebuildPlan); prints the rebuild counts
 //                 [--exchange-timeout SEC]              deadline of the exchange watchdog
 //                 [--exchange-deadline-test]            1-rank RCCL: stalls the exchange stream for
 //                                                       1.5 s under a 0.2 s deadline; the watchdog
@@ -419,6 +420,7 @@ int main(int argc, char** argv)
         node.setGpuRebuild((gpuRebuild & 1) != 0);
         node.setGpuRebuildSun((gpuRebuild & 2) != 0);
         node.setGpuRebuildSah((gpuRebuild & 4) != 0);
+        node.setGpuRebuildPlan((gpuRebuild & 8) != 0);
         if (slabCount > 1) node.setShard(shardRank, slabCount);
         return pipeline;
     };

@@ -37,6 +37,9 @@ public:
     // ARK_DDGI_FLAG_GPU_REBUILD_SAH (before construct; experimental, off): those device builds
     // rebuild every subtree of at most 256 triangles by a sweep SAH; alone it does nothing
     void setGpuRebuildSah(bool on) { m_gpuRebuildSah = on; }
+    // ARK_DDGI_FLAG_GPU_REBUILD_PLAN (before construct; experimental, off): the device builds
+    // that run the SAH pass collapse by the SAH-optimal plan; without that pass it does nothing
+    void setGpuRebuildPlan(bool on) { m_gpuRebuildPlan = on; }
     // Z-slab ranks: the atlas exchange after each update (RCCL all-gather, or device
     // copies for contexts in one process); frame n+1's shading waits for frame n's.
     void setSlabExchange(SlabExchange* exchange) { m_exchange = exchange; }
@@ -78,6 +81,7 @@ private:
     bool m_gpuRebuild { false };
     bool m_gpuRebuildSun { false };
     bool m_gpuRebuildSah { false };
+    bool m_gpuRebuildPlan { false };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     SlabExchange* m_exchange { nullptr };

@@ -183,7 +183,13 @@ typedef struct ArkDdgiDesc {
  * of at most 256 triangles is rebuilt by a full sweep SAH with its triangles reordered, and
  * the collapse decides by the boxes that pass leaves. When a device build starts, what
  * becomes of it and the host rebuild after the motion stops are unchanged; results are the
- * same. NO_SUN_COVER_MAP: by default a scene with a sun keeps the sun's cover map, a
+ * same. GPU_REBUILD_PLAN (experimental, off by default): modifies the device builds that run
+ * the SAH pass (GPU_REBUILD_SAH with GPU_REBUILD and / or GPU_REBUILD_SUN); without them it is
+ * accepted and does nothing. The pass then splits every subtree down to single triangles, a
+ * bottom-up pass gives every node of the binary tree its SAH-optimal 8-wide collapse plan (the
+ * host build's, Ylitie et al. 2017), and the collapse follows the plan where it otherwise opens
+ * members greedily. When a device build starts, what becomes of it and the host rebuild after
+ * the motion stops are unchanged; results are the same. NO_SUN_COVER_MAP: by default a scene with a sun keeps the sun's cover map, a
  * conservative light-space depth map built on the device at set_scene and by the background
  * rebuilds, with which most of the sun's shadow rays are resolved exactly - occluded or lit -
  * before they are listed for traversal; it is dropped the moment the geometry or the sun it
@@ -201,6 +207,7 @@ typedef struct ArkDdgiDesc {
 #define ARK_DDGI_FLAG_GPU_REBUILD_SAH 0x10u
 #define ARK_DDGI_FLAG_NO_SUN_COVER_MAP 0x20u
 #define ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE 0x40u
+#define ARK_DDGI_FLAG_GPU_REBUILD_PLAN 0x80u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {

@@ -94,6 +94,13 @@ int ark_ddgi_debug_lbvh_check_opts(const float* triangles, uint64_t n, int crite
  * `criterion`; sah = 0: _opts' result word for word). out[9]: _opts' eight, [8] the treelets
  * the pass rebuilt. */
 int ark_ddgi_debug_lbvh_check_sah(const float* triangles, uint64_t n, int criterion, int sah, uint64_t* out);
+/* The same with the collapse plan of ARK_DDGI_FLAG_GPU_REBUILD_PLAN (plan != 0; it does nothing
+ * unless sah != 0): the treelets down to single primitives, the plans, and the cut by their
+ * picks. plan = 0: _sah's result word for word. out[11]: _sah's nine, [9] the plan's cost of
+ * the root as one BVH8 node (the fp32 word; 0 without the plan or for a root of at most three
+ * triangles), [10] the BVH8 nodes other than the root with at most three triangles below them
+ * (0 expected; counted from the finished tree in either mode; with the plan they fail the check). */
+int ark_ddgi_debug_lbvh_check_plan(const float* triangles, uint64_t n, int criterion, int sah, int plan, uint64_t* out);
 
 /* The device LBVH build itself (ARK_DDGI_FLAG_GPU_REBUILD, ARK_DDGI_FLAG_GPU_REBUILD_SUN: the
  * product's driver and kernels, nothing else) run once on `device`, synchronously and without
@@ -131,6 +138,14 @@ int ark_ddgi_debug_lbvh_device_parity(int device, const void* records, uint64_t 
  * per sorted primitive, by bits; they count towards the return value. */
 int ark_ddgi_debug_lbvh_device_parity_sah(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
                                           const float* sun_dir, int w_bits, int sah, uint64_t* out);
+/* The same with the collapse plan (ARK_DDGI_FLAG_GPU_REBUILD_PLAN; plan != 0, with sah != 0)
+ * on both sides; plan = 0: the entry above, word for word. out[48]: [0..33] as above, [34]
+ * the nodes above the treelets, and the mismatch counts [35] the packed picks at every node
+ * index, [36] the eight cost words of every treelet root and upper node, by bits, [37] the
+ * upper nodes' boxes, by bits, [38] the upper list as a set; they count towards the return
+ * value. [39] the rounds the host restatement took above the treelets. */
+int ark_ddgi_debug_lbvh_device_parity_plan(int device, const void* records, uint64_t n_records, const int32_t* class_of, uint32_t n_instances,
+                                           const float* sun_dir, int w_bits, int sah, int plan, uint64_t* out);
 
 /* compare_bvh8_canonical (the tree comparison of ark_ddgi_debug_lbvh_device_parity) tried on
  * the host: the LBVH restatement's tree of n triangles (9 floats each; triangle i of instance
@@ -185,6 +200,11 @@ int ark_ddgi_debug_sun_lbvh_check_opts(const float* triangles, uint64_t n, const
  * sixteen, [16] the treelets the pass rebuilt. */
 int ark_ddgi_debug_sun_lbvh_check_sah(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
                                       int w_bits, int sah, uint64_t* out);
+/* _sah with the collapse plan (plan != 0, with sah != 0; plan = 0: _sah's result word for
+ * word). out[19]: _sah's seventeen, [17] the plan's cost of the root as one BVH8 node (the
+ * fp32 word), [18] the BVH8 nodes other than the root with at most three triangles below them. */
+int ark_ddgi_debug_sun_lbvh_check_plan(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
+                                       int w_bits, int sah, int plan, uint64_t* out);
 
 /* ark_ddgi_debug_world_bvh_check for the installed light-space sun BVH. out[8] = {nodes,
  * leaf children, max depth, violations, records that are not holes, records with holes,

@@ -31,6 +31,9 @@ it, and the time from set_lights to each install.
 SAH pass over subtrees of at most 256 triangles. Run it with and without in turn: the device
 builds' time (rebuild_ms, sun build_ms), the traversal and shadow phases on the tree traced
 right after the motion, the footprint and the rate while moving are the ones to compare.
+
+--gpu-rebuild-plan (with --gpu-rebuild-sah): ARK_DDGI_FLAG_GPU_REBUILD_PLAN, the SAH-optimal
+collapse plan of those builds. Compare it the same way, against a run without it.
 """
 import argparse
 import dataclasses
@@ -63,6 +66,7 @@ def main():
     ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
     ap.add_argument("--gpu-rebuild-sun", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SUN: the light-space sun BVH's background builds on the device")
     ap.add_argument("--gpu-rebuild-sah", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SAH: the device builds' SAH pass over subtrees of at most 256 triangles")
+    ap.add_argument("--gpu-rebuild-plan", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_PLAN: those builds collapse by the SAH-optimal plan")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
     import torch
@@ -74,7 +78,7 @@ def main():
         N = grid.probe_count()
         cfg = D.DDGIConfig(rays_per_probe=R, probe_updates_per_frame=N, max_rays_per_probe=R, max_probe_updates=N, compute_probe_offsets=True,
                            background_rebuild=not args.no_background, gpu_rebuild=args.gpu_rebuild, gpu_rebuild_sun=args.gpu_rebuild_sun,
-                           gpu_rebuild_sah=args.gpu_rebuild_sah)
+                           gpu_rebuild_sah=args.gpu_rebuild_sah, gpu_rebuild_plan=args.gpu_rebuild_plan)
         node = D.DDGINode(cfg)
         node.construct(sc, grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
         app = [D.AppState(0)]
@@ -180,7 +184,7 @@ def main():
                 "ms_per_frame_moving": round(motion_s / args.frames * 1e3, 4),
                 "refit_device_ms": {"median": round(refit_dev[len(refit_dev) // 2], 4), "max": round(refit_dev[-1], 4)},
                 "refit_host_enqueue_ms": round(host_refit / args.frames * 1e3, 4), "background_rebuild": not args.no_background,
-                "gpu_rebuild": bool(args.gpu_rebuild), "gpu_rebuild_sun": bool(args.gpu_rebuild_sun), "gpu_rebuild_sah": bool(args.gpu_rebuild_sah),
+                "gpu_rebuild": bool(args.gpu_rebuild), "gpu_rebuild_sun": bool(args.gpu_rebuild_sun), "gpu_rebuild_sah": bool(args.gpu_rebuild_sah), "gpu_rebuild_plan": bool(args.gpu_rebuild_plan),
                 "trees": trees,
                 "built_refit_version": {"world": int(st2.bvh_built_refit_version), "sun": int(st2.sun_built_refit_version), "refits": int(st2.refit_version)},
                 "installs_while_moving": {"world": int(st1.bvh_rebuilds - st0.bvh_rebuilds), "sun": int(st1.sun_rebuilds - st0.sun_rebuilds)},
