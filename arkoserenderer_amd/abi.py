@@ -58,6 +58,7 @@ ARK_DDGI_FLAG_GPU_REBUILD_SAH = 0x10
 ARK_DDGI_FLAG_GPU_REBUILD_PLAN = 0x80
 ARK_DDGI_FLAG_NO_SUN_COVER_MAP = 0x20
 ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE = 0x40
+ARK_DDGI_FLAG_NO_RAY_SEEDS = 0x100
 
 ARK_TEX_RGBA8_UNORM = 0
 ARK_TEX_RGBA8_SRGB = 1
@@ -537,6 +538,10 @@ EXPORTS = {
     "ark_ddgi_debug_sun_cover_counts_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_shade_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_set_sun_only_small_windows": (C.c_int, [C.c_void_p, C.c_int]),
+    "ark_ddgi_debug_seed_texel": (C.c_uint32, [C.c_float, C.c_float, C.c_float]),
+    "ark_ddgi_debug_seed_candidate_ok": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
+    "ark_ddgi_debug_seed_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_seed_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
 }
 
 _lib = None

@@ -137,6 +137,14 @@ struct ArkDdgiCtx : ErrorSink {
     // working set
     DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork;
     DeviceBuffer raySteps; // counting updates: u16 traversal iterations per probe ray (ARK_DDGI_DEBUG_RAY_STEPS)
+    // The probe rays' hit candidates (seed_cache.h; none with ARK_DDGI_FLAG_NO_RAY_SEEDS):
+    // [N][seed::kProbeWords] triangle records of the world BVHs' opaque class, or seed::kNone.
+    // The words are record indices, so they belong to one record order: the cache is
+    // refilled with kNone on the traversal stream, ahead of the next traversal, whenever the
+    // scene's worldTopologySeq has moved or the context has taken another scene (seedStale).
+    DeviceBuffer seeds;
+    bool seedStale = true;
+    uint32_t seedTopologySeen = 0;
     std::vector<uint32_t> orderHost; // traversal order of the samples for orderR
     uint32_t orderR = 0;
     uint32_t lightCount = 0;
@@ -443,6 +451,7 @@ SceneCall sceneCall(ArkDdgiCtx* ctx)
 int adoptScene(ArkDdgiCtx* ctx, std::shared_ptr<SceneStore> st)
 {
     ctx->geometrySeen = st->geometrySeq;
+    ctx->seedStale = true; // another scene's records
     ctx->hasSun = st->hasSunScene;
     for (int k = 0; k < 3; ++k) {
         ctx->sunColor[k] = st->sunScene.color[k];
@@ -482,7 +491,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     ctx->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     const int shards = desc->shard_count > 0 ? desc->shard_count : 1;
     if (ctx->Rmax > ARK_DDGI_MAX_RAYS_PER_PROBE || ctx->Z % shards != 0 || desc->shard_rank < 0 || desc->shard_rank >= shards ||
-        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_GPU_REBUILD_PLAN | ARK_DDGI_FLAG_NO_SUN_COVER_MAP | ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE)) ||
+        desc->sun_bvh < ARK_DDGI_SUN_BVH_AUTO || desc->sun_bvh > ARK_DDGI_SUN_BVH_LIGHT_SPACE || (desc->flags & ~(ARK_DDGI_FLAG_SERIAL_FRAMES | ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD | ARK_DDGI_FLAG_GPU_REBUILD_SUN | ARK_DDGI_FLAG_GPU_REBUILD_SAH | ARK_DDGI_FLAG_GPU_REBUILD_PLAN | ARK_DDGI_FLAG_NO_SUN_COVER_MAP | ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE | ARK_DDGI_FLAG_NO_RAY_SEEDS)) ||
         desc->build_threads < 0) {
         delete ctx;
         return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -544,6 +553,10 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     if ((e = ctx->surfels.alloc(K * R * 8)) != hipSuccess) return bad(e, "alloc surfels");
     if ((e = ctx->rayCounter.alloc(2 * kRayCounterWords * 4)) != hipSuccess) return bad(e, "alloc counter");
     if ((e = ctx->counters.alloc(10 * sizeof(unsigned long long))) != hipSuccess) return bad(e, "alloc counters");
+    if (!(desc->flags & ARK_DDGI_FLAG_NO_RAY_SEEDS)) {
+        // (filled with seed::kNone by the first update: seedStale)
+        if ((e = ctx->seeds.alloc(static_cast<size_t>(ctx->N) * seed::kProbeWords * 4)) != hipSuccess) return bad(e, "alloc seed cache");
+    }
     if ((e = ctx->seqWords.alloc(128 * 4)) != hipSuccess) return bad(e, "alloc sequence words");
     if ((e = hipMemset(ctx->seqWords.ptr, 0, ctx->seqWords.bytes)) != hipSuccess) return bad(e, "clear sequence words");
     {
@@ -590,7 +603,7 @@ void ark_ddgi_destroy(ArkDdgiCtx* ctx)
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
     for (DeviceBuffer* b : { &ctx->irr, &ctx->vis, &ctx->offsets, &ctx->slots, &ctx->slotOrder, &ctx->fib, &ctx->fibOrder, &ctx->order, &ctx->hits, &ctx->surfels, &ctx->spill, &ctx->rayCounter, &ctx->seqWords, &ctx->shadeWork, &ctx->reflWork,
-                             &ctx->raySteps, &ctx->counters, &ctx->lights, &ctx->bakeTri, &ctx->bakeBary, &ctx->bakeOut, &ctx->bakePixels, &ctx->bakeCounters })
+                             &ctx->raySteps, &ctx->seeds, &ctx->counters, &ctx->lights, &ctx->bakeTri, &ctx->bakeBary, &ctx->bakeOut, &ctx->bakePixels, &ctx->bakeCounters })
         b->release();
     ctx->sceneStore.reset();
     for (auto& ev : ctx->ev)
@@ -844,6 +857,59 @@ int ark_ddgi_debug_shade_schedule(ArkDdgiCtx* ctx, uint64_t* out)
     ARK_HIP(hipMemcpy(&n, ctx->lastDeferredCount, sizeof(n), hipMemcpyDeviceToHost));
     out[0] = 1;
     out[1] = n;
+    return ARK_DDGI_OK;
+}
+
+uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z) { return seed::texelOf(x, y, z); }
+int ark_ddgi_debug_seed_candidate_ok(uint32_t word, uint32_t first, uint32_t end) { return seed::candidateOk(word, first, end) ? 1 : 0; }
+
+int ark_ddgi_debug_seed_info(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    out[0] = ctx->seeds.ptr ? 1u : 0u;
+    out[1] = seed::kTexels;
+    out[2] = ctx->hasScene ? ctx->sceneStore->args.opaque_tri_first : 0u;
+    out[3] = ctx->hasScene ? ctx->sceneStore->args.opaque_tri_end : 0u;
+    out[4] = 0;
+    if (ctx->seeds.ptr && ctx->countersPending) {
+        uint32_t n = 0;
+        ARK_HIP(hipSetDevice(ctx->device));
+        ARK_HIP(hipDeviceSynchronize());
+        ARK_HIP(hipMemcpy(&n, ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 4u, sizeof(n), hipMemcpyDeviceToHost));
+        out[4] = n;
+    }
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_seed_fill(ArkDdgiCtx* ctx, int mode, uint64_t value)
+{
+    if (!ctx || mode < 0 || mode > 2) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "seed fill before ark_ddgi_set_scene");
+    if (!ctx->seeds.ptr) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "the context keeps no seed cache (ARK_DDGI_FLAG_NO_RAY_SEEDS)");
+    const uint32_t first = ctx->sceneStore->args.opaque_tri_first, end = ctx->sceneStore->args.opaque_tri_end;
+    std::vector<uint32_t> words(ctx->seeds.bytes / 4, seed::kNone);
+    if (mode != 0 && end > first) {
+        uint64_t x = value * 0x9e3779b97f4a7c15ull + 0x632be59bd9b4e019ull; // splitmix64
+        for (uint32_t& w : words) {
+            if (mode == 2) {
+                w = static_cast<uint32_t>(value);
+            } else {
+                x += 0x9e3779b97f4a7c15ull;
+                uint64_t z = x;
+                z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+                z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+                z ^= z >> 31;
+                w = first + static_cast<uint32_t>(z % (end - first));
+            }
+            // only words the lookup would accept ever reach the device
+            if (!seed::candidateOk(w, first, end)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "seed fill: record %u outside the opaque class [%u, %u)", w, first, end);
+        }
+    }
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    ARK_HIP(hipMemcpy(ctx->seeds.ptr, words.data(), ctx->seeds.bytes, hipMemcpyHostToDevice));
+    ctx->seedStale = false; // (a whole cache of this record order's words)
+    ctx->seedTopologySeen = ctx->sceneStore->worldTopologySeq;
     return ARK_DDGI_OK;
 }
 
@@ -1119,7 +1185,11 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
     f.ray_counter = ctx->rayCounter.as<uint32_t>() + b * kRayCounterWords;
     f.counters = ctx->counters.as<unsigned long long>();
     f.ray_steps = count ? ctx->raySteps.as<uint16_t>() : nullptr;
-    // (counters.ptr is cleared below when counting: the cover map's counts are its last three words)
+    // (counters.ptr is cleared below when counting: the cover map's counts are its last three
+    // words, the seed candidates' count the word before them)
+    f.seed_cache = ctx->seeds.as<uint32_t>();
+    f.seed_offsets_write = f.seed_cache && f.update_offsets && ctx->scene.root_masked < 0 ? 1u : 0u;
+    f.seed_counts = count && f.seed_cache ? ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 4u : nullptr;
     f.cover_counts = count ? ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 3u : nullptr;
     ctx->coverCountsValid = count;
     // shading work set (ensureShadeWork): per-ray light bits | shadow-ray list
@@ -1157,6 +1227,16 @@ static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStr
     if (ctx->geometrySeen != ctx->sceneStore->geometrySeq) {
         ARK_HIP(hipStreamWaitEvent(ts, ctx->sceneStore->evGeometry, 0));
         ctx->geometrySeen = ctx->sceneStore->geometrySeq;
+    }
+    // a new record order of the world BVHs (set_scene, an installed rebuild - this context's
+    // above, or a sharing context's): the cached record indices are the old order's. The
+    // traversals of a context run one after the other (they share a spill region), so on ts
+    // the fill follows the last traversal that wrote old indices and precedes the first
+    // that reads the new tree.
+    if (f.seed_cache && (ctx->seedStale || ctx->seedTopologySeen != ctx->sceneStore->worldTopologySeq)) {
+        ARK_HIP(launch_fill_u32(ctx->seeds.ptr, ctx->seeds.bytes / 4, seed::kNone, ts));
+        ctx->seedStale = false;
+        ctx->seedTopologySeen = ctx->sceneStore->worldTopologySeq;
     }
     if (count) ARK_HIP(hipMemsetAsync(ctx->counters.ptr, 0, ctx->counters.bytes, s));
     // (k_probe_slots zeroes f.ray_counter)

@@ -1282,6 +1282,7 @@ bool build_world_bvh8(std::vector<BuildTriangle> cls[3], BvhBuildOptions opt, co
         Bvh8BuildResult r = collapse_bvh8(r2, static_cast<uint32_t>(out.nodes.size()), static_cast<uint32_t>(out.tris.size()), copt);
         out.roots[c] = static_cast<int32_t>(out.nodes.size());
         if (c == 0) out.opaqueNodes = static_cast<uint32_t>(r.nodes.size());
+        if (c == 0) out.opaqueRecords = static_cast<uint32_t>(r.tris.size());
         out.depth = std::max(out.depth, r.max_depth);
         out.triangles += r.triangles;
         out.nodes.insert(out.nodes.end(), r.nodes.begin(), r.nodes.end());

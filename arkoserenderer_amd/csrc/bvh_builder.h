@@ -92,6 +92,7 @@ struct WorldBvh8 {
     std::vector<GpuTriangle> tris; // leaf triangle rows, holes included
     int32_t roots[3] = { -1, -1, -1 };
     uint32_t opaqueNodes = 0, depth = 0, maxLeaf = 0;
+    uint32_t opaqueRecords = 0; // the opaque class's records: tris[0 .. opaqueRecords), holes included
     uint64_t triangles = 0;   // records that are not holes
     float sah = 0.0f;         // BVH2 SAH cost of the opaque class
     float inflateAbs = 0.0f;  // one absolute box inflation for all classes (shadow rays test all): bvh8_inflation_box of their bounds

@@ -8,6 +8,7 @@
 #include "../../include/ark_ddgi.h"
 #include "ddgi_types.h"
 #include "lbvh_build.h"
+#include "seed_cache.h"
 #include "sun_cover_map.h"
 
 namespace ark {
@@ -146,6 +147,10 @@ struct SceneArgs {
     int32_t root_masked;
     int32_t root_blend;
     uint32_t opaque_nodes; // node count of the opaque class (breadth-first from root_opaque)
+    // the opaque class's triangle records [first, end) of tris (the classes' records are
+    // contiguous, opaque first; leaf-row holes included): what a seed-cache word may name
+    // (seed::candidateOk)
+    uint32_t opaque_tri_first, opaque_tri_end;
     int32_t texture_count;
     const uint32_t* indices;
     const float* vertices; // RTVertex, 9 floats (36 B) each
@@ -242,6 +247,15 @@ struct FrameArgs {
     unsigned long long* counters; // [0] nodes [1] tris [2] hits [3] shadow rays
     uint32_t* cover_counts;  // counting updates: the sun's rays [0] resolved occluded [1] resolved lit [2] listed (k_shadow_gen); else null
     uint16_t* ray_steps;     // counting updates: traversal iterations of each probe ray (both passes) at its hit-record index
+    // the probe rays' hit candidates (seed_cache.h): [probe index][seed::kProbeWords] triangle
+    // records or seed::kNone; null: no seeding (ARK_DDGI_FLAG_NO_RAY_SEEDS, ray lists)
+    uint32_t* seed_cache;
+    // who leaves the hits in the cache: k_probe_offsets from the hit records (1: it has every
+    // lane enabled and the slot and the rotated direction at hand - 0.06 ms less than k_trace's
+    // write at C4) when it is launched and the scene has no masked class (the records then
+    // hold the opaque pass's hits), else k_trace as its rays retire (the SEEDW instances)
+    uint32_t seed_offsets_write;
+    uint32_t* seed_counts;   // counting updates: [0] probe rays whose candidate was hit; else null
     // ray-list traversals (RT reflections): {origin, tmax}, {direction, pixel} per ray
     const float4* ray_list;
     const uint32_t* list_count;

@@ -969,6 +969,7 @@ __device__ __forceinline__ void grabRaysWave(const FrameArgs& f, uint32_t* heads
 struct PoolRec {
     V3 o, d;
     uint32_t a;
+    uint32_t c; // the ray's hit candidate (seed_cache.h): a triangle record or seed::kNone
 };
 
 // Ray sources of the closest-hit traversal. ProbeRays: the window's probe rays from
@@ -979,14 +980,18 @@ struct PoolRec {
 // grab: the next chunk, called by every lane of the wave; stage(r): the record of ray
 // r (every lane, once per chunk); take(r, a): what a lane starting ray r needs
 // besides o and d (hit record index, tmax), from the record's own word.
+// kSeeds: the source's rays are offered a hit candidate (stage looks it up, checked by
+// seed::candidateOk against the launch's opaque class) and leave their opaque-pass hit in
+// the cache.
 struct ProbeRays {
     static constexpr bool kMaskedPass = true;
+    static constexpr bool kSeeds = true;
     static constexpr float kTmin = 0.0001f;
     __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
     {
         grabRaysWave(f, f.ray_counter, home, lane, tried, b, e, chunk);
     }
-    __device__ static PoolRec stage(const FrameArgs& f, uint32_t r)
+    __device__ static PoolRec stage(const SceneArgs& sc, const FrameArgs& f, uint32_t r)
     {
         const uint32_t qp = r / f.R;
         const uint32_t slot = slotAt(f, qp);
@@ -996,6 +1001,11 @@ struct ProbeRays {
         rec.o = { ps.pos[0], ps.pos[1], ps.pos[2] };
         rec.d = rotate(v3(fv.x, fv.y, fv.z), v3(ps.axis[0], ps.axis[1], ps.axis[2]), ps.angle_sin, ps.angle_cos);
         rec.a = slot * f.R + __float_as_uint(fv.w); // hit record index
+        rec.c = seed::kNone;
+        if (f.seed_cache) {
+            const uint32_t w = f.seed_cache[static_cast<size_t>(ps.probe_index) * seed::kProbeWords + seed::texelOf(rec.d.x, rec.d.y, rec.d.z)];
+            if (seed::candidateOk(w, sc.opaque_tri_first, sc.opaque_tri_end)) rec.c = w;
+        }
         return rec;
     }
     __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t recA, uint32_t& ray, float& tmax)
@@ -1007,18 +1017,20 @@ struct ProbeRays {
 
 struct ListRays {
     static constexpr bool kMaskedPass = false;
+    static constexpr bool kSeeds = false;
     static constexpr float kTmin = 0.01f;
     __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
     {
         grabItemsWave(f.ray_counter, *f.list_count, home, lane, tried, b, e, chunk);
     }
-    __device__ static PoolRec stage(const FrameArgs& f, uint32_t r)
+    __device__ static PoolRec stage(const SceneArgs&, const FrameArgs& f, uint32_t r)
     {
         const float4 a = f.ray_list[2u * r], b = f.ray_list[2u * r + 1u];
         PoolRec rec;
         rec.o = { a.x, a.y, a.z };
         rec.d = { b.x, b.y, b.z };
         rec.a = __float_as_uint(a.w); // tmax
+        rec.c = seed::kNone;
         return rec;
     }
     __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t recA, uint32_t& ray, float& tmax)
@@ -1033,7 +1045,9 @@ struct ListRays {
 // rays at a time, run the 32-slot instance: their three workgroups per CU share the CU
 // with the previous frame's shadow traversal and shading, and 4 KB of LDS per workgroup
 // that no chunk would ever fill are taken from those (launch_trace).
-template<bool COUNT, int WPE, class Src = ProbeRays, int SLOTS = 64>
+// SEEDW: the instance leaves its rays' opaque-pass hits in the seed cache itself
+// (FrameArgs::seed_offsets_write 0 with a cache).
+template<bool COUNT, int WPE, class Src = ProbeRays, int SLOTS = 64, bool SEEDW = false>
 __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace(SceneArgs sc, FrameArgs f)
 {
     if (frameAborted(f.abort_word)) return;
@@ -1052,6 +1066,7 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     const uint32_t chunk = min(f.grab_chunk, static_cast<uint32_t>(SLOTS)); // a chunk fits the pool
     const float tmin = Src::kTmin;
     uint32_t cNodes = 0, cTris = 0, cHits = 0, cIter = 0, rSteps = 0;
+    uint32_t cSeedHits = 0, seedTri = seed::kNone; // (COUNT) rays whose candidate was hit; the candidate of a ray's first step
 
     uint32_t poolNext = 0, poolEnd = 0; // rays of the pool not handed out yet
     uint32_t poolBase = 0;              // the ray whose record is in slot 0
@@ -1075,7 +1090,17 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     // otherwise run almost every step; at a refill it runs once per batch of idle
     // lanes. Lanes that finish after the ray supply is exhausted retire at once.
     bool pending = false;
+    // The opaque pass's hit becomes the candidate of the probe's next ray in this direction
+    // (a plain store: a lost race only changes which valid candidate is seen; a miss writes
+    // nothing). h.tri is a record of the opaque class of the tree this launch traverses.
+    auto seedWrite = [&]() {
+        if (Src::kSeeds && SEEDW && h.tri != kNoHit) {
+            const uint32_t probe = f.slots[ray / f.R].probe_index;
+            f.seed_cache[static_cast<size_t>(probe) * seed::kProbeWords + seed::texelOf(d.x, d.y, d.z)] = h.tri;
+        }
+    };
     auto storeHit = [&]() {
+        if (pass == 0) seedWrite();
         GpuHit out;
         if (h.tri == kNoHit) {
             out.t = __builtin_bit_cast(float, 0x7f800000u);
@@ -1115,12 +1140,13 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
             // on each side of the staging) and that a wave's LDS operations execute
             // in the order issued. A record goes straight into the idle lane's own o
             // and d.
-            uint32_t r = kNoHit, recA = 0;
+            uint32_t r = kNoHit, recA = 0, recC = seed::kNone;
             auto readRec = [&](uint32_t slot) {
                 const uint4 lo = pool[slot], hi = pool[SLOTS + slot];
                 o = { __uint_as_float(lo.x), __uint_as_float(lo.y), __uint_as_float(lo.z) };
                 d = { __uint_as_float(lo.w), __uint_as_float(hi.x), __uint_as_float(hi.y) };
                 recA = hi.z;
+                recC = hi.w;
             };
             if (!active && rank < avail) {
                 r = poolNext + rank;
@@ -1129,9 +1155,9 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
             if (fb < fe) {
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 if (lane < fe - fb) {
-                    const PoolRec s = Src::stage(f, fb + lane);
+                    const PoolRec s = Src::stage(sc, f, fb + lane);
                     pool[lane] = make_uint4(__float_as_uint(s.o.x), __float_as_uint(s.o.y), __float_as_uint(s.o.z), __float_as_uint(s.d.x));
-                    pool[SLOTS + lane] = make_uint4(__float_as_uint(s.d.y), __float_as_uint(s.d.z), s.a, 0u);
+                    pool[SLOTS + lane] = make_uint4(__float_as_uint(s.d.y), __float_as_uint(s.d.z), s.a, s.c);
                 }
                 __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
                 poolBase = __builtin_amdgcn_readfirstlane(fb);
@@ -1150,7 +1176,10 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
                 pass = 0;
                 st.depth = 0;
                 nBits = 0;
-                ts = TravState { static_cast<uint32_t>(sc.root_opaque), sc.root_opaque >= 0 ? rootGroupBits() : 0u, 0u, 0u };
+                // the candidate is the ray's first pending triangle group: the step below tests
+                // it like any leaf triangle, and the root visit of that step sees its h.t
+                ts = TravState { static_cast<uint32_t>(sc.root_opaque), sc.root_opaque >= 0 ? rootGroupBits() : 0u, recC, recC != seed::kNone ? 1u : 0u };
+                if (COUNT) seedTri = recC;
             }
             if (avail < n) {
                 if (fb >= fe) {
@@ -1173,6 +1202,10 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
         // (an active lane is never done here: the check after the step retires or
         // restarts it, and a step of a done lane would change nothing anyway)
         if (active) travStepDual<kTraceBlock, false, true>(sc, nc, ts, nBase, nBits, st, o, d, idir, oct, tmin, h, pass, cNodes, cTris);
+        if (COUNT && active && seedTri != seed::kNone) {
+            cSeedHits += h.tri == seedTri ? 1u : 0u;
+            seedTri = seed::kNone;
+        }
         // ---- pass finished -------------------------------------------------------------
         if (active && done() && (!Src::kMaskedPass || sc.root_masked < 0) && !exhausted) {
             active = false;
@@ -1185,6 +1218,7 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
                 // (backface) is an empty interval.
                 opaqueT = (h.tri != kNoHit) ? (h.backface ? -h.t : h.t) : f.z_far;
                 if (sc.root_masked >= 0 && opaqueT >= tmin) {
+                    seedWrite();
                     pass = 1;
                     finished = false;
                     ts = TravState { static_cast<uint32_t>(sc.root_masked), rootGroupBits(), 0u, 0u };
@@ -1214,6 +1248,7 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
         atomicAdd(&f.counters[1], static_cast<unsigned long long>(cTris));
         atomicAdd(&f.counters[2], static_cast<unsigned long long>(cHits));
         if (lane == 0) atomicAdd(&f.counters[7], static_cast<unsigned long long>(cIter));
+        if (f.seed_counts) atomicAdd(&f.seed_counts[0], cSeedHits);
     }
 }
 
@@ -2585,8 +2620,15 @@ const void* kernel_trace_ptr(bool count)
 hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s)
 {
     void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
+    const bool small = !count && f.grab_chunk <= 32u;
     const void* fn = kernel_trace_ptr(count);
-    if (!count && f.grab_chunk <= 32u) fn = reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::ProbeRays, 32>);
+    if (small) fn = reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::ProbeRays, 32>);
+    if (f.seed_cache && !f.seed_offsets_write) {
+        // the instances that write the seed cache themselves
+        fn = count ? reinterpret_cast<const void*>(&dev::k_trace<true, 1, dev::ProbeRays, 64, true>)
+             : small ? reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::ProbeRays, 32, true>)
+                     : reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::ProbeRays, 64, true>);
+    }
     return hipLaunchKernel(fn, dim3(blocks), dim3(kTraceBlock), args, 0, s);
 }
 

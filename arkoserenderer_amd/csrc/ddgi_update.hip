@@ -432,6 +432,10 @@ __global__ void __launch_bounds__(kOffsetBlock) k_probe_offsets(FrameArgs f)
             const uint32_t cls = (a > 0.0f && a < maxOffset) ? 1u : (a < 0.0f ? 2u : 0u);
             const GpuProbeSlot& ps = f.slots[slot0 + p];
             const V3 d = rotate(v3(fb[k].x, fb[k].y, fb[k].z), v3(ps.axis[0], ps.axis[1], ps.axis[2]), ps.angle_sin, ps.angle_cos);
+            // the hit becomes the candidate of the probe's next ray in this direction
+            // (FrameArgs::seed_offsets_write: this kernel writes the cache, k_trace does not)
+            if (f.seed_offsets_write && h[k].tri != kNoHit)
+                f.seed_cache[static_cast<size_t>(ps.probe_index) * seed::kProbeWords + seed::texelOf(d.x, d.y, d.z)] = h[k].tri;
             float* v = valL + p * stride + 6u * s;
             v[0] = cls == 1u ? d.x : 0.0f;
             v[1] = cls == 1u ? d.y : 0.0f;

@@ -290,6 +290,7 @@ hipError_t buildLbvhGpu(LbvhGpuBuild& g, hipStream_t s, std::string& why)
         }
         nodeTotal = a.levelBase;
         if (c == 0) g.opaqueNodes = nodeTotal;
+        if (c == 0) g.opaqueRecords = counters[kLbvhRecords]; // (the classes' leaf rows follow one another)
     }
     const uint32_t outRecords = counters[kLbvhRecords];
     if (!(DeviceBvh::bytesFor(nodeTotal, outRecords) < (1ull << 32))) {

@@ -41,6 +41,7 @@ struct LbvhGpuBuild {
     // out
     int32_t roots[3] { -1, -1, -1 };
     uint32_t opaqueNodes = 0, prims = 0;
+    uint32_t opaqueRecords = 0;        // the opaque class's records: [0, opaqueRecords) of the result's
     float inflateAbs = 0.0f;           // the boxes' absolute inflation (the sun's refit floor; the world keeps set_scene's)
     std::vector<uint32_t> order;       // the level order on the host
 };

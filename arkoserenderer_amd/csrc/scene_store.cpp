@@ -52,7 +52,7 @@ struct RebuildJob {
     std::vector<int> classOf; // instance -> hit-mask class (0 opaque, 1 masked, 2 blend)
     DeviceBuffer perm;
     int32_t roots[3] { -1, -1, -1 };
-    uint32_t opaqueNodes = 0, maxLeaf = 0;
+    uint32_t opaqueNodes = 0, opaqueRecords = 0, maxLeaf = 0;
     float sah = 0.0f;
     std::string error;
     // sun
@@ -425,6 +425,7 @@ bool hostBuildWorld(RebuildJob* job, const std::vector<GpuTriangle>& rec, int th
     }
     std::copy(w.roots, w.roots + 3, job->roots);
     job->opaqueNodes = w.opaqueNodes;
+    job->opaqueRecords = w.opaqueRecords;
     job->maxLeaf = w.maxLeaf;
     job->sah = w.sah;
     job->bvh.depth = w.depth;
@@ -518,6 +519,7 @@ hipError_t deviceBuild(RebuildJob* job, hipStream_t s, std::string& why)
         // (inflateAbs: worldCollect sets the installed one's)
         std::copy(g.roots, g.roots + 3, job->roots);
         job->opaqueNodes = g.opaqueNodes;
+        job->opaqueRecords = g.opaqueRecords;
         job->maxLeaf = std::min<uint32_t>(g.prims, static_cast<uint32_t>(kBvh8MaxLeafSize));
         job->sah = 0.0f; // not evaluated on the device
     } else {
@@ -561,7 +563,7 @@ void runRebuildJob(RebuildJob* job, int device, int threads, bool tryDevice)
             job->bvh = DeviceBvh {};
             job->perm.release();
             job->roots[0] = job->roots[1] = job->roots[2] = -1;
-            job->opaqueNodes = 0;
+            job->opaqueNodes = job->opaqueRecords = 0;
             job->gpuFallback = true;
         }
     }
@@ -624,12 +626,17 @@ void setWorldArgs(SceneStore& st)
     st.args.instances = st.instances.as<GpuInstance>();
 }
 
-void setWorldRoots(SceneStore& st, const int32_t roots[3], uint32_t opaqueNodes)
+// (set_scene and every install of world BVHs: the record order is a new one, so the
+// contexts' seed caches, which hold record indices, start over - worldTopologySeq)
+void setWorldRoots(SceneStore& st, const int32_t roots[3], uint32_t opaqueNodes, uint32_t opaqueRecords)
 {
     st.args.root_opaque = roots[0];
     st.args.root_masked = roots[1];
     st.args.root_blend = roots[2];
     st.args.opaque_nodes = opaqueNodes;
+    st.args.opaque_tri_first = 0u; // the opaque class is built first
+    st.args.opaque_tri_end = roots[0] >= 0 ? opaqueRecords : 0u;
+    ++st.worldTopologySeq;
 }
 
 void setSunArgs(SceneStore& st)
@@ -880,7 +887,7 @@ int worldCollect(SceneStore& st, const SceneCall& c, hipStream_t s)
         ARK_HIP(retireBuffer(st, job->snap, s));
         ARK_HIP(growBoxes(st, st.world, s));
         setWorldArgs(st);
-        setWorldRoots(st, job->roots, job->opaqueNodes);
+        setWorldRoots(st, job->roots, job->opaqueNodes, job->opaqueRecords);
         st.args.tri_normals = st.triNormals.as<float4>();
         st.bvhMaxDepth = std::max(st.world.depth, st.sunArgs.sun_root >= 0 ? st.sun.depth : 0u);
         st.bvhStats.node_count = st.world.nodeCount;
@@ -1284,7 +1291,7 @@ int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThrea
     }
     SceneArgs& sc = st->args;
     setWorldArgs(*st);
-    setWorldRoots(*st, w.roots, w.opaqueNodes);
+    setWorldRoots(*st, w.roots, w.opaqueNodes, w.opaqueRecords);
     sc.tri_normals = st->triNormals.as<float4>();
     sc.texture_count = static_cast<int32_t>(s->texture_count);
     sc.indices = st->indices.as<uint32_t>();

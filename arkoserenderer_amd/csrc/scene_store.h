@@ -196,6 +196,11 @@ struct SceneStore {
     bool installValid = false;
     hipEvent_t evGeometry = nullptr;
     uint32_t geometrySeq = 0;
+    // counts the record orders of the world BVHs (set_scene, every installed world rebuild;
+    // a refit keeps the order, in all three copies): a context resets its seed cache, whose
+    // words are record indices, on its traversal stream when this has moved (ark_ddgi.cpp
+    // updateImpl, behind its wait for evGeometry and ahead of the traversal)
+    uint32_t worldTopologySeq = 0;
     SceneStore();
     SceneStore(const SceneStore&) = delete;
     SceneStore& operator=(const SceneStore&) = delete;

@@ -92,6 +92,10 @@ class DDGIConfig:
     # the sun-only shading schedule (on by default; False: ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE,
     # the shadow-ray generator runs as for every other scene - same results)
     fused_sun_shade: bool = True
+    # the probe rays' hit candidates (on by default; False: ARK_DDGI_FLAG_NO_RAY_SEEDS, no
+    # per-probe direction -> last-hit cache, every ray enters the BVH with tmax = zFar - same
+    # results)
+    ray_seeds: bool = True
     build_threads: int = 0
 
 
@@ -135,6 +139,7 @@ def desc_for(grid: ProbeGrid, z_far: float, config: DDGIConfig, device: int = 0,
     d.flags |= abi.ARK_DDGI_FLAG_GPU_REBUILD_PLAN if config.gpu_rebuild_plan else 0
     d.flags |= 0 if config.sun_cover_map else abi.ARK_DDGI_FLAG_NO_SUN_COVER_MAP
     d.flags |= 0 if config.fused_sun_shade else abi.ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE
+    d.flags |= 0 if config.ray_seeds else abi.ARK_DDGI_FLAG_NO_RAY_SEEDS
     d.build_threads = int(config.build_threads)
     return d
 
@@ -408,6 +413,20 @@ class DDGIContext:
         out = (C.c_uint64 * 2)()
         self.check(self.lib.ark_ddgi_debug_shade_schedule(self.h, out), "ark_ddgi_debug_shade_schedule")
         return {"sun_only": bool(out[0]), "deferred": int(out[1])}
+
+    def seed_info(self) -> dict:
+        """ark_ddgi_debug_seed_info: the probe rays' hit-candidate cache - whether the context
+        keeps one, its texels per side, the scene's opaque record range, and the probe rays of
+        the last counting update whose candidate was hit."""
+        out = (C.c_uint64 * 5)()
+        self.check(self.lib.ark_ddgi_debug_seed_info(self.h, out), "ark_ddgi_debug_seed_info")
+        return {"enabled": bool(out[0]), "texels": int(out[1]), "first": int(out[2]), "end": int(out[3]), "candidate_hits": int(out[4])}
+
+    def seed_fill(self, mode: int, value: int = 0):
+        """ark_ddgi_debug_seed_fill: overwrites the cache - mode 0 the sentinel, 1 random opaque
+        records from the seed `value`, 2 the record `value` everywhere (refused when it is not
+        a record of the opaque class)."""
+        self.check(self.lib.ark_ddgi_debug_seed_fill(self.h, int(mode), int(value)), "ark_ddgi_debug_seed_fill")
 
     def set_sun_only_small_windows(self, on: bool):
         """ark_ddgi_debug_set_sun_only_small_windows: pipelined half-occupancy windows, which keep

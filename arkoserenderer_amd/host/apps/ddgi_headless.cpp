@@ -31,6 +31,8 @@
 //                                                       sun's (setGpuRebuildSun), 4 their SAH pass
 //                                                       (setGpuRebuildSah), 8 their collapse plan
 //                                                       (setGpuRebuildPlan); prints the rebuild counts
+//                 [--no-ray-seeds]                      no hit candidates for the probe rays
+//                                                       (DDGINode::setRaySeeds(false)); same results
 //                 [--exchange-timeout SEC]              deadline of the exchange watchdog
 //                 [--exchange-deadline-test]            1-rank RCCL: stalls the exchange stream for
 //                                                       1.5 s under a 0.2 s deadline; the watchdog
@@ -338,6 +340,7 @@ int main(int argc, char** argv)
     double exchangeTimeout = 0.0;
     std::string saveStatePath, loadStatePath, frameScriptPath;
     int firstFrame = 0, gpuRebuild = 0;
+    bool raySeeds = true;
     bool deadlineTest = false;
     const std::time_t startedAt = std::time(nullptr);
     float zFar = 10000.0f, exposure = 1.0f, env = 1.0f, ambient = 0.0f;
@@ -375,6 +378,7 @@ int main(int argc, char** argv)
         else if (a == "--first-frame") firstFrame = std::atoi(next());
         else if (a == "--frame-script") frameScriptPath = next();
         else if (a == "--gpu-rebuild") gpuRebuild = std::atoi(next());
+        else if (a == "--no-ray-seeds") raySeeds = false;
         else ARKOSE_LOG(Fatal, "unknown argument %s", a.c_str());
     }
     SceneFile file;
@@ -421,6 +425,7 @@ int main(int argc, char** argv)
         node.setGpuRebuildSun((gpuRebuild & 2) != 0);
         node.setGpuRebuildSah((gpuRebuild & 4) != 0);
         node.setGpuRebuildPlan((gpuRebuild & 8) != 0);
+        node.setRaySeeds(raySeeds);
         if (slabCount > 1) node.setShard(shardRank, slabCount);
         return pipeline;
     };

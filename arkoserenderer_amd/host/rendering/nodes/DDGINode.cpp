@@ -80,7 +80,8 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
     desc.shard_rank = m_shardRank;
     desc.shard_count = m_shardCount;
     desc.flags = (m_gpuRebuild ? ARK_DDGI_FLAG_GPU_REBUILD : 0u) | (m_gpuRebuildSun ? ARK_DDGI_FLAG_GPU_REBUILD_SUN : 0u) |
-                 (m_gpuRebuildSah ? ARK_DDGI_FLAG_GPU_REBUILD_SAH : 0u) | (m_gpuRebuildPlan ? ARK_DDGI_FLAG_GPU_REBUILD_PLAN : 0u);
+                 (m_gpuRebuildSah ? ARK_DDGI_FLAG_GPU_REBUILD_SAH : 0u) | (m_gpuRebuildPlan ? ARK_DDGI_FLAG_GPU_REBUILD_PLAN : 0u) |
+                 (m_raySeeds ? 0u : ARK_DDGI_FLAG_NO_RAY_SEEDS);
     auto created = reg.createOrReuseDdgiContext("ddgi", desc);
     ArkDdgiCtx* ctx = created.first;
     if (!ctx) {

@@ -40,6 +40,9 @@ public:
     // ARK_DDGI_FLAG_GPU_REBUILD_PLAN (before construct; experimental, off): the device builds
     // that run the SAH pass collapse by the SAH-optimal plan; without that pass it does nothing
     void setGpuRebuildPlan(bool on) { m_gpuRebuildPlan = on; }
+    // off: ARK_DDGI_FLAG_NO_RAY_SEEDS (before construct; on by default): no per-probe cache of
+    // the last hit per direction for the probe rays to test first; same results
+    void setRaySeeds(bool on) { m_raySeeds = on; }
     // Z-slab ranks: the atlas exchange after each update (RCCL all-gather, or device
     // copies for contexts in one process); frame n+1's shading waits for frame n's.
     void setSlabExchange(SlabExchange* exchange) { m_exchange = exchange; }
@@ -82,6 +85,7 @@ private:
     bool m_gpuRebuildSun { false };
     bool m_gpuRebuildSah { false };
     bool m_gpuRebuildPlan { false };
+    bool m_raySeeds { true };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     SlabExchange* m_exchange { nullptr };

@@ -199,7 +199,13 @@ typedef struct ArkDdgiDesc {
  * beside the next frame's traversal), runs no shadow-ray generator: the shading kernel looks the map up itself, shades
  * the resolved rays at once, lists the undecided ones, and shades those in a second pass
  * after their traversal. The flag keeps the generator schedule that every other scene runs
- * (A/B runs, tests); results are the same. */
+ * (A/B runs, tests); results are the same. NO_RAY_SEEDS: by default a context keeps, per
+ * probe, a 16 x 16 octahedral map from direction to the triangle record that the last probe
+ * ray in that direction hit (1 KB per probe), and every probe ray tests its texel's record
+ * before it enters the BVH, so that its traversal prunes by a real hit distance from the
+ * root down. The record is only a candidate, tested like any leaf triangle; the closest hit
+ * does not depend on it. The flag disables lookup and write (A/B runs, tests); results are
+ * the same. */
 #define ARK_DDGI_FLAG_SERIAL_FRAMES 0x1u
 #define ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD 0x2u
 #define ARK_DDGI_FLAG_GPU_REBUILD 0x4u
@@ -208,6 +214,7 @@ typedef struct ArkDdgiDesc {
 #define ARK_DDGI_FLAG_NO_SUN_COVER_MAP 0x20u
 #define ARK_DDGI_FLAG_NO_FUSED_SUN_SHADE 0x40u
 #define ARK_DDGI_FLAG_GPU_REBUILD_PLAN 0x80u
+#define ARK_DDGI_FLAG_NO_RAY_SEEDS 0x100u
 
 /* RTVertex, scalar layout, 36 B (RTData.h:9-13 / NonPositionVertex SceneData.h). */
 typedef struct ArkRTVertex {

@@ -264,6 +264,22 @@ int ark_ddgi_debug_shade_schedule(struct ArkDdgiCtx* ctx, uint64_t* out);
  * schedule's chunk and list edge cases at sizes a test can afford). Results are the same. */
 int ark_ddgi_debug_set_sun_only_small_windows(struct ArkDdgiCtx* ctx, int enabled);
 
+/* The probe rays' hit candidates (csrc/seed_cache.h; ARK_DDGI_FLAG_NO_RAY_SEEDS turns them
+ * off). _seed_texel: the cache texel in [0, T * T) of a direction, on the host (the function
+ * the kernels use). _seed_candidate_ok: the lookup's guard, on the host - 1 when `word` may be
+ * tested by a launch whose opaque class owns the records [first, end), else 0 (the sentinel
+ * 0xffffffff, records of other classes, indices past the array). No GPU for either.
+ * _seed_info: out[5] = {1 if the context keeps a cache, T, first, end of the scene's opaque
+ * records, probe rays of the last counting update whose candidate was hit}.
+ * _seed_fill overwrites the whole cache (synchronous; the device is idle): mode 0 the
+ * sentinel, 1 random records of the opaque class from the seed `value`, 2 the record `value`
+ * everywhere. Every word is checked by the guard on the host first: a value outside the
+ * opaque class is refused (ARK_DDGI_E_INVALID_ARGUMENT) and nothing is written. */
+uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z);
+int ark_ddgi_debug_seed_candidate_ok(uint32_t word, uint32_t first, uint32_t end);
+int ark_ddgi_debug_seed_info(struct ArkDdgiCtx* ctx, uint64_t* out);
+int ark_ddgi_debug_seed_fill(struct ArkDdgiCtx* ctx, int mode, uint64_t value);
+
 #ifdef __cplusplus
 }
 #endif

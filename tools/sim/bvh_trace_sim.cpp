@@ -10,6 +10,7 @@
 #include "bvh_trace_sim.h"
 
 #include "../../arkoserenderer_amd/csrc/bvh_builder.h"
+#include "../../arkoserenderer_amd/csrc/seed_cache.h"
 
 #include <algorithm>
 #include <atomic>
@@ -54,8 +55,25 @@ static double rd16(double x, int dir)
 // (host simulation of k_trace's closest-hit order: per node the hit children,
 // those whose box holds the origin first, then octant order; a node's leaf
 // triangles are tested right after it). For comparing BVH builds without a GPU.
-extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t n, const float* rays, uint64_t nRays, int threads, uint64_t* out,
-                                                uint32_t* perRay)
+//
+// seed (ark_ddgi_debug_bvh8_trace_seeded): the dual step with k_trace's hit candidates
+// (csrc/seed_cache.h) - `rays` holds seed->frames blocks of nRays rays (the probes' rays of
+// consecutive updates), traced block by block over one BVH; a ray's candidate record is its
+// first pending triangle group, and between blocks the cache takes the block's hits.
+namespace {
+struct SeedRun {
+    uint32_t frames;           // blocks in `rays`
+    const uint32_t* probeOf;   // [nRays] cache row of each ray of a block
+    uint32_t probes;           // cache rows
+    uint32_t texels;           // T; 0: no cache (only `candidates`, if any)
+    const uint32_t* candidates; // nullable: [nRays] the first block's candidates (record or seed::kNone), ahead of the cache's
+    uint32_t* hitRecords;      // nullable out: [frames][nRays] the closest hit's record, seed::kNone for a miss
+    float* hitT;               // nullable out: [frames][nRays] its distance (tmax for a miss)
+    uint64_t* frameOut;        // [frames][8]: node visits, triangle tests, hits, iterations, rays holding a candidate, candidates hit, 0, 0
+};
+}
+
+static int traceImpl(const float* triangles, uint64_t n, const float* rays, uint64_t nRays, int threads, uint64_t* out, uint32_t* perRay, const SeedRun* seed)
 {
     using namespace ark;
     std::vector<BuildTriangle> tris(n);
@@ -140,11 +158,15 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
     // iterations in perRay / out[5]; =2: the same with two nodes per iteration (the next
     // two children of the group / stack, the second's children pushed below the first's
     // group, up to two waiting leaf groups). Exact box test, k-order (slot ^ octant).
-    const int stepMode = std::getenv("ARK_SIM_STEP") ? std::atoi(std::getenv("ARK_SIM_STEP")) : 0;
+    const int stepMode = seed ? 1 : std::getenv("ARK_SIM_STEP") ? std::atoi(std::getenv("ARK_SIM_STEP")) : 0;
     if (stepMode) {
-        std::atomic<uint64_t> sumIter { 0 };
+        std::atomic<uint64_t> sumIter { 0 }, candHeld { 0 }, candHit { 0 };
+        // the block being traced: its candidates (null: none) and where its hits go
+        const uint32_t* cand = nullptr;
+        uint32_t* hitRec = nullptr;
+        float* hitDist = nullptr;
         auto stepWorker = [&](uint64_t r0, uint64_t r1) {
-            uint64_t cn = 0, ct = 0, ch = 0, ms = 0, it = 0;
+            uint64_t cn = 0, ct = 0, ch = 0, ms = 0, it = 0, held = 0, heldHit = 0;
             struct Group { uint32_t base; uint32_t bits; uint32_t imask; };
             for (uint64_t r = r0; r < r1; ++r) {
                 const float* ry = rays + 7 * r;
@@ -155,6 +177,7 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
                 for (int a = 0; a < 3; ++a) idir[a] = 1.0f / (std::fabs(d[a]) < 1e-20f ? (d[a] < 0.0f ? -1e-20f : 1e-20f) : d[a]);
                 const uint32_t oct = (idir[0] < 0 ? 1u : 0u) | (idir[1] < 0 ? 2u : 0u) | (idir[2] < 0 ? 4u : 0u);
                 bool hit = false;
+                uint32_t hitTri = seed::kNone, hitPrim = 0;
                 auto nextChild = [&](Group& g) {
                     const uint32_t k = static_cast<uint32_t>(__builtin_ctz(g.bits));
                     g.bits &= g.bits - 1u;
@@ -204,9 +227,15 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
                     const float v = (d[0] * q[0] + d[1] * q[1] + d[2] * q[2]) * inv;
                     if (!(v >= 0.0f && u + v <= 1.0f)) return;
                     const float tt = (e2[0] * q[0] + e2[1] * q[1] + e2[2] * q[2]) * inv;
-                    if (tt >= tmin && tt <= tmax) {
+                    // (k_trace's tie rule: equal t keeps the smaller primitive, so the hit does
+                    // not depend on the order in which the triangles are met)
+                    uint32_t prim;
+                    std::memcpy(&prim, &g.t2[2], 4);
+                    if (tt >= tmin && tt <= tmax && !(hit && tt == tmax && prim > hitPrim)) {
                         tmax = tt;
                         hit = true;
+                        hitTri = t;
+                        hitPrim = prim;
                     }
                 };
                 Group G { 0u, 1u, 0u }; // the root alone (k = 0, no internal mask: base + 0)
@@ -214,6 +243,14 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
                 std::vector<uint32_t> triQ, q1, q2, leafA, leafB;
                 size_t triPos = 0;
                 uint64_t iters = 0;
+                // the candidate: the ray's first pending triangle group (its test and the
+                // root's visit share the first iteration, the visit seeing the shortened tmax)
+                const uint32_t cnd = cand ? cand[r] : seed::kNone;
+                const bool seeded = seed::candidateOk(cnd, 0u, static_cast<uint32_t>(r8.tris.size()));
+                if (seeded) {
+                    triQ.push_back(cnd);
+                    held++;
+                }
                 auto addLeaves = [&](std::vector<uint32_t>& L) {
                     if (L.empty()) return;
                     if (triPos >= triQ.size()) { triQ.swap(L); triPos = 0; }
@@ -227,6 +264,7 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
                     if (!doTri && !doNode) break;
                     iters++;
                     if (doTri) testTri(triQ[triPos++]);
+                    if (seeded && iters == 1 && hitTri == cnd) heldHit++;
                     if (doNode) {
                         if (G.bits == 0) { G = S.back(); S.pop_back(); }
                         const uint32_t A = nextChild(G);
@@ -260,18 +298,59 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
                 it += iters;
                 ms = std::max(ms, iters);
                 if (perRay) perRay[r] = static_cast<uint32_t>(iters);
+                if (hitRec) hitRec[r] = hitTri;
+                if (hitDist) hitDist[r] = tmax;
             }
             nodes += cn;
             triTests += ct;
             hits += ch;
             sumIter += it;
+            candHeld += held;
+            candHit += heldHit;
             uint64_t m = maxSteps.load();
             while (ms > m && !maxSteps.compare_exchange_weak(m, ms)) {}
         };
         const int T = std::max(1, threads);
-        std::vector<std::thread> pool;
-        for (int t = 0; t < T; ++t) pool.emplace_back(stepWorker, nRays * t / T, nRays * (t + 1) / T);
-        for (auto& th : pool) th.join();
+        auto runBlock = [&]() {
+            std::vector<std::thread> pool;
+            for (int t = 0; t < T; ++t) pool.emplace_back(stepWorker, nRays * t / T, nRays * (t + 1) / T);
+            for (auto& th : pool) th.join();
+        };
+        if (seed) {
+            const uint32_t TT = seed->texels * seed->texels;
+            std::vector<uint32_t> cache(static_cast<size_t>(seed->probes) * TT, seed::kNone), cands(nRays), blockHits(nRays);
+            const float* allRays = rays;
+            uint32_t* allSteps = perRay;
+            uint64_t total[6] = {};
+            for (uint32_t f = 0; f < seed->frames; ++f) {
+                rays = allRays + 7ull * nRays * f;
+                perRay = allSteps ? allSteps + nRays * f : nullptr;
+                for (uint64_t r = 0; r < nRays; ++r) {
+                    uint32_t c = f == 0 && seed->candidates ? seed->candidates[r] : seed::kNone;
+                    if (TT && c == seed::kNone) c = cache[static_cast<size_t>(seed->probeOf[r]) * TT + seed::texelOfT(rays[7 * r + 3], rays[7 * r + 4], rays[7 * r + 5], seed->texels)];
+                    cands[r] = c;
+                }
+                cand = cands.data();
+                hitRec = blockHits.data();
+                hitDist = seed->hitT ? seed->hitT + nRays * f : nullptr;
+                nodes = triTests = hits = sumIter = candHeld = candHit = 0;
+                runBlock();
+                // the block's hits, in ray order (the last writer of a texel wins)
+                for (uint64_t r = 0; r < nRays && TT; ++r)
+                    if (blockHits[r] != seed::kNone)
+                        cache[static_cast<size_t>(seed->probeOf[r]) * TT + seed::texelOfT(rays[7 * r + 3], rays[7 * r + 4], rays[7 * r + 5], seed->texels)] = blockHits[r];
+                if (seed->hitRecords) std::copy(blockHits.begin(), blockHits.end(), seed->hitRecords + nRays * f);
+                const uint64_t fo[8] = { nodes.load(), triTests.load(), hits.load(), sumIter.load(), candHeld.load(), candHit.load(), 0, 0 };
+                std::copy(fo, fo + 8, seed->frameOut + 8ull * f);
+                for (int k = 0; k < 6; ++k) total[k] += fo[k];
+            }
+            nodes = total[0];
+            triTests = total[1];
+            hits = total[2];
+            sumIter = total[3];
+        } else {
+            runBlock();
+        }
         if (out) {
             out[0] = nodes.load();
             out[1] = triTests.load();
@@ -500,4 +579,21 @@ extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t 
         out[8] = boxViolations.load();
     }
     return 0;
+}
+
+extern "C" int ark_ddgi_debug_bvh8_trace_stats(const float* triangles, uint64_t n, const float* rays, uint64_t nRays, int threads, uint64_t* out,
+                                                uint32_t* perRay)
+{
+    return traceImpl(triangles, n, rays, nRays, threads, out, perRay, nullptr);
+}
+
+extern "C" int ark_ddgi_debug_bvh8_trace_seeded(const float* triangles, uint64_t n, const float* rays, uint64_t nRays, uint32_t frames, const uint32_t* probeOf,
+                                                 uint32_t probes, uint32_t texels, const uint32_t* candidates, int threads, uint64_t* out, uint64_t* frameOut,
+                                                 uint32_t* hitRecords, float* hitT, uint32_t* perRay)
+{
+    if (!frames || !frameOut || (texels && (!probeOf || !probes))) return 1;
+    for (uint64_t r = 0; r < nRays && texels; ++r)
+        if (probeOf[r] >= probes) return 1;
+    const SeedRun s { frames, probeOf, probes, texels, candidates, hitRecords, hitT, frameOut };
+    return traceImpl(triangles, n, rays, nRays, threads, out, perRay, &s);
 }

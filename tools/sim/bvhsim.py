@@ -20,5 +20,8 @@ def load(build: bool = True) -> C.CDLL:
     lib = C.CDLL(LIB)
     lib.ark_ddgi_debug_bvh8_trace_stats.restype = C.c_int
     lib.ark_ddgi_debug_bvh8_trace_stats.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64), C.c_void_p]
+    lib.ark_ddgi_debug_bvh8_trace_seeded.restype = C.c_int
+    lib.ark_ddgi_debug_bvh8_trace_seeded.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p,
+                                                     C.c_int, C.POINTER(C.c_uint64), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     _lib = lib
     return lib
