@@ -28,6 +28,8 @@ ARK_BLEND_MODE_MASKED = 2
 ARK_BLEND_MODE_TRANSLUCENT = 3
 
 ARK_DDGI_OK = 0
+ARK_DDGI_E_INVALID_ARGUMENT = -1
+ARK_DDGI_E_NO_SCENE = -3
 ERRORS = {
     -1: "ARK_DDGI_E_INVALID_ARGUMENT",
     -2: "ARK_DDGI_E_NO_PROBE_GRID",
@@ -144,6 +146,24 @@ class ArkRTInstance(C.Structure):
         ("triangle_count", C.c_uint32),
         ("hit_mask", C.c_uint32),
         ("_pad", C.c_uint32),
+    ]
+
+
+ARK_DDGI_VERTICES_DEVICE = 0x1
+
+
+class ArkDdgiVertexUpdate(C.Structure):
+    """One range of the scene's vertex pools for ark_ddgi_update_geometry (64 B)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("first_vertex", C.c_uint32),
+        ("vertex_count", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("positions", C.c_void_p),
+        ("vertices", C.c_void_p),
+        ("bounds", C.c_float * 6),
+        ("reserved", C.c_int32 * 2),
     ]
 
 
@@ -454,6 +474,7 @@ ABI_STRUCTS = [
     ArkDdgiDesc, ArkRTVertex, ArkRTTriangleMesh, ArkShaderMaterial, ArkTexture, ArkRTInstance,
     ArkDirectionalLight, ArkSpotLight, ArkDdgiScene, ArkDdgiFrameParams, ArkDdgiCounters,
     ArkDdgiDeviceViews, ArkDdgiBvhStats, ArkBakeAoDesc, ArkComposeDesc, ArkProbeDebugDesc, ArkReflectionsDesc,
+    ArkDdgiVertexUpdate,
 ]
 
 # name -> (restype, argtypes)
@@ -467,6 +488,9 @@ EXPORTS = {
     "ark_ddgi_set_lights": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ark_ddgi_set_instances": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32]),
     "ark_ddgi_set_instances_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ark_ddgi_update_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "ark_ddgi_update_geometry_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ark_ddgi_get_geometry_update_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_mark_external_write": (C.c_int, [C.c_void_p]),
     "ark_ddgi_get_next_probe_index": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ark_ddgi_update": (C.c_int, [C.c_void_p, C.POINTER(ArkDdgiFrameParams), C.c_void_p]),
@@ -532,6 +556,7 @@ EXPORTS = {
     "ark_ddgi_debug_sun_lbvh_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_int, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_bvh_installed_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_refit_reach": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_geometry_update_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_cover_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

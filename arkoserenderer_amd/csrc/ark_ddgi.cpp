@@ -729,6 +729,46 @@ int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances
     return ARK_DDGI_OK;
 }
 
+int ark_ddgi_update_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_update_geometry before ark_ddgi_set_scene");
+    SceneStore& st = *ctx->sceneStore;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    if (const int r = checkSequencing(ctx)) return r;
+    ARK_HIP(orderBegin(ctx, s));
+    // set_instances' refit with the vertex ranges written first (scene_store.h)
+    if (const int rc = sceneUpdateGeometry(st, sceneCall(ctx), updates, updateCount, instances, count, s)) return rc;
+    if (ctx->sceneVersion != st.version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    ARK_HIP(orderEnd(ctx, s));
+    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_get_geometry_update_stats(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    std::fill(out, out + 4, uint64_t(0));
+    if (!ctx->hasScene) return ARK_DDGI_OK;
+    ARK_HIP(hipSetDevice(ctx->device));
+    return sceneGeometryStats(*ctx->sceneStore, ctx, out);
+}
+
+int ark_ddgi_debug_geometry_update_info(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "geometry update info before ark_ddgi_set_scene");
+    const SceneStore& st = *ctx->sceneStore;
+    out[0] = st.recordMapAllocs;
+    out[1] = st.recordMapFills;
+    out[2] = st.recordMap.bytes + st.triBase.bytes + st.stageCounters.bytes;
+    out[3] = st.vtx.seq;
+    return ARK_DDGI_OK;
+}
+
 int ark_ddgi_debug_scene_digest(ArkDdgiCtx* ctx, uint64_t* out)
 {
     if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -910,6 +950,17 @@ int ark_ddgi_debug_seed_fill(ArkDdgiCtx* ctx, int mode, uint64_t value)
     ARK_HIP(hipMemcpy(ctx->seeds.ptr, words.data(), ctx->seeds.bytes, hipMemcpyHostToDevice));
     ctx->seedStale = false; // (a whole cache of this record order's words)
     ctx->seedTopologySeen = ctx->sceneStore->worldTopologySeq;
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_update_geometry(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = ark_ddgi_update_geometry_async(ctx, updates, updateCount, instances, count, ctx->stream)) return rc;
+    ARK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ctx->bvhStats = ctx->sceneStore->bvhStats;
     return ARK_DDGI_OK;
 }
 
@@ -1640,6 +1691,7 @@ int ark_ddgi_bake_ao(ArkDdgiCtx* ctx, const ArkBakeAoDesc* d, void* hipStream)
     ARK_HIP(launch_bake(ctx->scene, b, 0, 1, s));
     // the persistent AO kernel uses the traversal spill area sized for shadowBlocks workgroups
     ARK_HIP(launch_bake(ctx->scene, b, ctx->shadowBlocks, 2, s));
+    ARK_HIP(scenePositionsRead(*ctx->sceneStore, s)); // (the next vertex update's positions follow the bake)
     ARK_HIP(orderEnd(ctx, s));
     ctx->bakeW = d->width;
     ctx->bakeH = d->height;

@@ -327,6 +327,28 @@ hipError_t launch_refit_nodes(GpuBvh8Node* nodes, GpuTriangle* tris, float* boxe
                               const uint64_t* masks, const RefitInstance* inst, const uint32_t* indices, const float* positions, hipStream_t s);
 // dst[i] = src[perm[i]] (64-B shading records), perm ~0: zeros (an installed rebuild's record order)
 hipError_t launch_gather_records(float4* dst, const float4* src, const uint32_t* perm, uint64_t count, hipStream_t s);
+// ark_ddgi_update_geometry (k_stage_vertices): what a device-source position is checked
+// against - enabled 0: a plain copy
+struct StageCheck {
+    float lo[3], hi[3]; // ArkDdgiVertexUpdate.bounds
+    uint32_t enabled;
+};
+// `words` floats src -> dst (a pool range); counters[0] rejected, [1] clamped positions (chk.enabled)
+hipError_t launch_stage_vertices(const float* src, float* dst, uint64_t words, const StageCheck& chk, unsigned long long* counters, hipStream_t s);
+// map[triBase[instance] + primitive] = record, over the records of `tris` (triBase: instances + 1 entries)
+hipError_t launch_record_map(const GpuTriangle* tris, uint32_t records, const uint32_t* triBase, uint32_t instances, uint32_t* map, hipStream_t s);
+// an instance whose shading records k_update_surface_records rewrites
+struct SurfaceJob {
+    uint32_t instance, tri_base, count; // its global triangles [tri_base, tri_base + count)
+    uint32_t first_index;
+    int32_t first_vertex;
+};
+constexpr uint32_t kSurfaceJobsPerLaunch = 16;
+struct SurfaceJobs {
+    SurfaceJob job[kSurfaceJobsPerLaunch];
+};
+hipError_t launch_update_surface_records(const SurfaceJobs& jobs, uint32_t jobCount, const uint32_t* map, uint32_t records, const uint32_t* indices, const float* vertices,
+                                         float4* triNormals, hipStream_t s);
 
 // The world BVH8s' topology built on the device (ddgi_bvh_build.hip, lbvh_build.h)
 // what k_lbvh_prims counts and reduces; lo / hi: the scene box in ordered bits

@@ -17,6 +17,10 @@
 //                    coordinates; the sun's light-space BVH its records' light
 //                    coordinates, so it follows the motion instead of being dropped.
 //   k_gather_records the shading records in an installed background rebuild's order.
+//   k_stage_vertices, k_record_map, k_update_surface_records
+//                    deforming meshes (ark_ddgi_update_geometry): new vertices into the
+//                    pools, the triangle -> record map, the touched instances' shading
+//                    records rewritten; the triangle records follow through k_refit_nodes.
 // Every launch is stream-ordered behind the context's earlier work (ark_ddgi_set_instances_async):
 // the boxes' inflation comes from the host with the launch (refitInflations: the
 // instances' object-space boxes through their new transforms), no device round trip.
@@ -24,6 +28,8 @@
 // primitive) tie rule and conservative boxes), only on the triangle records,
 // which equal a fresh set_scene's bit for bit.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
 
 #include "ddgi_kernels.h"
 
@@ -252,7 +258,136 @@ __global__ void __launch_bounds__(256) k_gather_records(float4* __restrict__ dst
     dst[w] = from == 0xffffffffu ? make_float4(0.0f, 0.0f, 0.0f, 0.0f) : src[static_cast<uint64_t>(from) * 4u + (w & 3u)];
 }
 
+// The only writer of the vertex pools after set_scene (ark_ddgi_update_geometry): `words`
+// floats from `src` - a slot of the store's pinned staging ring, or the caller's device
+// buffer - to `dst`, a range of a pool. Twelve words per lane: three 16-B loads and stores
+// where source and destination are both 16-B aligned (the host places a staged source at
+// the destination's alignment), single words otherwise and for the tail.
+// chk.enabled (device-source positions, whose contents the host never saw; twelve words are
+// four positions): a position with a non-finite coordinate keeps the pool's old value, one
+// outside chk's box is clamped into it, and both are counted (counters[0], [1]) - so no
+// refit ever reads a coordinate that is not finite (quantGrid's search for a grid step
+// does not end on an infinite extent), and the instances' object-space boxes, for which
+// the host joined that box with the box of the positions before (a kept position lies in
+// the latter) for the refit's inflation, contain every position.
+__global__ void __launch_bounds__(256) k_stage_vertices(const float* __restrict__ src, float* __restrict__ dst, uint64_t words, StageCheck chk,
+                                                        unsigned long long* __restrict__ counters)
+{
+    const uint64_t w0 = (static_cast<uint64_t>(blockIdx.x) * 256u + threadIdx.x) * 12u;
+    if (w0 >= words) return;
+    const uint32_t n = static_cast<uint32_t>(min(static_cast<uint64_t>(12u), words - w0));
+    const float* s = src + w0;
+    float* d = dst + w0;
+    const bool vec = n == 12u && ((reinterpret_cast<uintptr_t>(s) | reinterpret_cast<uintptr_t>(d)) & 15u) == 0;
+    float v[12];
+    if (vec) {
+        for (int q = 0; q < 3; ++q) {
+            const float4 x = reinterpret_cast<const float4*>(s)[q];
+            v[4 * q] = x.x, v[4 * q + 1] = x.y, v[4 * q + 2] = x.z, v[4 * q + 3] = x.w;
+        }
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 12u; ++k) v[k] = k < n ? s[k] : 0.0f;
+    }
+    if (chk.enabled) {
+        uint32_t rejected = 0, clamped = 0;
+#pragma unroll
+        for (uint32_t t = 0; t < 4u; ++t) {
+            if (3u * t + 2u >= n) break;
+            float* p = v + 3u * t;
+            if (!(isfinite(p[0]) && isfinite(p[1]) && isfinite(p[2]))) {
+                for (int a = 0; a < 3; ++a) p[a] = d[3u * t + a];
+                ++rejected;
+                continue;
+            }
+            bool moved = false;
+            for (int a = 0; a < 3; ++a) {
+                const float x = p[a];
+                p[a] = x < chk.lo[a] ? chk.lo[a] : (x > chk.hi[a] ? chk.hi[a] : x);
+                moved = moved || p[a] != x;
+            }
+            clamped += moved ? 1u : 0u;
+        }
+        if (rejected) atomicAdd(counters, static_cast<unsigned long long>(rejected));
+        if (clamped) atomicAdd(counters + 1, static_cast<unsigned long long>(clamped));
+    }
+    if (vec) {
+        for (int q = 0; q < 3; ++q) reinterpret_cast<float4*>(d)[q] = make_float4(v[4 * q], v[4 * q + 1], v[4 * q + 2], v[4 * q + 3]);
+    } else {
+#pragma unroll
+        for (uint32_t k = 0; k < 12u; ++k)
+            if (k < n) d[k] = v[k];
+    }
+}
+
+// The device map global triangle -> world record index (instance i's primitive p is
+// triangle triBase[i] + p), scattered from the front copy's records, one thread per
+// record; holes and records of unknown instances write nothing (the map is filled with
+// ~0 first).
+__global__ void __launch_bounds__(256) k_record_map(const GpuTriangle* __restrict__ tris, uint32_t records, const uint32_t* __restrict__ triBase, uint32_t instances,
+                                                    uint32_t* __restrict__ map)
+{
+    const uint32_t r = blockIdx.x * 256u + threadIdx.x;
+    if (r >= records) return;
+    const float4 c = reinterpret_cast<const float4*>(tris + r)[2];
+    const uint32_t inst = __float_as_uint(c.y), prim = __float_as_uint(c.z);
+    if (inst >= instances) return; // a hole
+    const uint32_t base = triBase[inst];
+    if (prim >= triBase[inst + 1u] - base) return;
+    map[base + prim] = r;
+}
+
+// The shading records (SceneStore::triNormals, 64 B: three vertex normals, the instance,
+// three UVs) of the triangles of the instances a vertex update touched, rewritten from the
+// vertex pool by set_scene's rule (scene_store.cpp shadingRecords), one thread per
+// (instance, primitive): blockIdx.y picks the instance of this launch's block of jobs.
+__global__ void __launch_bounds__(256) k_update_surface_records(SurfaceJobs jobs, const uint32_t* __restrict__ map, uint32_t records, const uint32_t* __restrict__ indices,
+                                                                const float* __restrict__ vertices, float4* __restrict__ triNormals)
+{
+    const SurfaceJob& j = jobs.job[blockIdx.y];
+    const uint32_t p = blockIdx.x * 256u + threadIdx.x;
+    if (p >= j.count) return;
+    const uint32_t r = map[j.tri_base + p];
+    if (r >= records) return; // not in the BVHs
+    float o[16];
+    for (int q = 0; q < 3; ++q) {
+        const uint32_t idx = indices[static_cast<size_t>(j.first_index) + 3u * p + q];
+        const float* v = vertices + (static_cast<uint64_t>(static_cast<int64_t>(j.first_vertex)) + idx) * 9u;
+        for (int k = 0; k < 3; ++k) o[q * 3 + k] = v[2 + k];
+        o[10 + 2 * q] = v[0];
+        o[11 + 2 * q] = v[1];
+    }
+    o[9] = __uint_as_float(j.instance);
+    float4* dst = triNormals + static_cast<uint64_t>(r) * 4u;
+    for (int q = 0; q < 4; ++q) dst[q] = make_float4(o[4 * q], o[4 * q + 1], o[4 * q + 2], o[4 * q + 3]);
+}
+
 } // namespace dev
+
+hipError_t launch_stage_vertices(const float* src, float* dst, uint64_t words, const StageCheck& chk, unsigned long long* counters, hipStream_t s)
+{
+    if (words == 0) return hipSuccess;
+    const uint64_t lanes = (words + 11u) / 12u;
+    hipLaunchKernelGGL(dev::k_stage_vertices, dim3(static_cast<uint32_t>((lanes + 255u) / 256u)), dim3(256), 0, s, src, dst, words, chk, counters);
+    return hipGetLastError();
+}
+
+hipError_t launch_record_map(const GpuTriangle* tris, uint32_t records, const uint32_t* triBase, uint32_t instances, uint32_t* map, hipStream_t s)
+{
+    if (records == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_record_map, dim3((records + 255u) / 256u), dim3(256), 0, s, tris, records, triBase, instances, map);
+    return hipGetLastError();
+}
+
+hipError_t launch_update_surface_records(const SurfaceJobs& jobs, uint32_t jobCount, const uint32_t* map, uint32_t records, const uint32_t* indices, const float* vertices,
+                                         float4* triNormals, hipStream_t s)
+{
+    uint32_t most = 0;
+    for (uint32_t i = 0; i < jobCount; ++i) most = std::max(most, jobs.job[i].count);
+    if (jobCount == 0 || most == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_update_surface_records, dim3((most + 255u) / 256u, jobCount), dim3(256), 0, s, jobs, map, records, indices, vertices, triNormals);
+    return hipGetLastError();
+}
 
 hipError_t launch_store_lights(const LightBlock& b, GpuSpotLight* dst, hipStream_t s)
 {

@@ -167,24 +167,49 @@ void collectRetired(SceneStore& st)
 
 // `bytes` of host data into `dst` in stream order on `s`, through the store's pinned
 // staging ring (a slot is reused once its previous copy has run).
+// The ring's next slot, free for the host to fill (its last reader, a few calls back, has
+// run) and grown to `bytes`; stageRelease records its reader's end on the reader's stream.
+hipError_t ringAcquire(void** stage, size_t* stageBytes, hipEvent_t* stageDone, int& next, int slots, size_t bytes, int& slot)
+{
+    const int i = slot = next;
+    next = (i + 1) % slots;
+    hipError_t e = hipSuccess;
+    if (!stageDone[i] && (e = hipEventCreateWithFlags(&stageDone[i], hipEventDisableTiming)) != hipSuccess) return e;
+    if (stageBytes[i]) (void)hipEventSynchronize(stageDone[i]); // its last copy (an earlier frame's) has run
+    if (stageBytes[i] < bytes) {
+        if (stage[i]) (void)hipHostFree(stage[i]);
+        stage[i] = nullptr;
+        stageBytes[i] = 0;
+        if ((e = hipHostMalloc(&stage[i], bytes, hipHostMallocDefault)) != hipSuccess) return e;
+        stageBytes[i] = bytes;
+    }
+    return hipSuccess;
+}
+
+hipError_t stageAcquire(SceneStore& st, size_t bytes, int& slot)
+{
+    return ringAcquire(st.stage, st.stageBytes, st.stageDone, st.stageNext, SceneStore::kStageSlots, bytes, slot);
+}
+
+hipError_t stageRelease(SceneStore& st, int slot, hipStream_t s) { return hipEventRecord(st.stageDone[slot], s); }
+
+// the vertex ranges' ring (SceneStore::vstage)
+hipError_t vertexStageAcquire(SceneStore& st, size_t bytes, int& slot)
+{
+    return ringAcquire(st.vstage, st.vstageBytes, st.vstageDone, st.vstageNext, SceneStore::kVertexStageSlots, bytes, slot);
+}
+
+hipError_t vertexStageRelease(SceneStore& st, int slot, hipStream_t s) { return hipEventRecord(st.vstageDone[slot], s); }
+
 hipError_t stagedUpload(SceneStore& st, void* dst, const void* src, size_t bytes, hipStream_t s)
 {
     if (bytes == 0) return hipSuccess;
-    const int i = st.stageNext;
-    st.stageNext = (i + 1) % SceneStore::kStageSlots;
-    hipError_t e = hipSuccess;
-    if (!st.stageDone[i] && (e = hipEventCreateWithFlags(&st.stageDone[i], hipEventDisableTiming)) != hipSuccess) return e;
-    if (st.stageBytes[i]) (void)hipEventSynchronize(st.stageDone[i]); // its last copy (an earlier frame's) has run
-    if (st.stageBytes[i] < bytes) {
-        if (st.stage[i]) (void)hipHostFree(st.stage[i]);
-        st.stage[i] = nullptr;
-        st.stageBytes[i] = 0;
-        if ((e = hipHostMalloc(&st.stage[i], bytes, hipHostMallocDefault)) != hipSuccess) return e;
-        st.stageBytes[i] = bytes;
-    }
+    int i = 0;
+    hipError_t e = stageAcquire(st, bytes, i);
+    if (e != hipSuccess) return e;
     std::memcpy(st.stage[i], src, bytes);
     if ((e = hipMemcpyAsync(dst, st.stage[i], bytes, hipMemcpyHostToDevice, s)) != hipSuccess) return e;
-    return hipEventRecord(st.stageDone[i], s);
+    return stageRelease(st, i, s);
 }
 
 // The boxes' absolute inflations of a refit, as set_scene and build_sun_bvh derive them
@@ -299,8 +324,9 @@ int enqueueRefit(ErrorSink* err, SceneStore& st, hipStream_t s, const DeviceBuff
 // copies share, current: a node is skipped only when nothing below it changed since the
 // scratch last saw it, whichever copy that refit wrote. An instance back at the pose the
 // target copy holds (a nudge and return, a loop of period 3) is re-transformed to the
-// same bits.
-int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* instances, uint32_t count, const std::vector<std::array<float, 12>>* have,
+// same bits. Vertices count as transforms do: an instance whose vertices are newer than the
+// target copy's records (`slot`) or than the refit before's is dirty (st.vtx, vertex_dirty.h).
+int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* instances, uint32_t count, const std::vector<std::array<float, 12>>* have, int slot,
                          hipStream_t s)
 {
     bool allDirty = !have || have->size() != count;
@@ -311,7 +337,8 @@ int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* in
         const float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
         const ArkRTTriangleMesh& mesh = st.meshHost[instances[ii].rt_mesh_index];
         RefitInstance& q = st.refitHost[ii];
-        const bool moved = allDirty || std::memcmp((*have)[ii].data(), M, sizeof(q.m)) != 0 || std::memcmp(st.instHost[ii].object_to_world, M, sizeof(q.m)) != 0;
+        const bool moved = allDirty || std::memcmp((*have)[ii].data(), M, sizeof(q.m)) != 0 || std::memcmp(st.instHost[ii].object_to_world, M, sizeof(q.m)) != 0 ||
+                           st.vtx.dirty(ii, slot);
         std::memcpy(q.m, M, sizeof(q.m));
         q.first_vertex = mesh.first_vertex;
         q.first_index = static_cast<uint32_t>(mesh.first_index);
@@ -744,9 +771,10 @@ int finishInstall(SceneStore& st, const SceneCall& c, RebuildJob& job, InstallBo
         ARK_HIP(clearCoverMap(st, s));
     }
     if (refitsSince) {
-        if (const int rc = uploadRefitInstances(err, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, s)) return rc;
+        if (const int rc = uploadRefitInstances(err, st, st.instHost.data(), static_cast<uint32_t>(st.instHost.size()), nullptr, st.front, s)) return rc;
         if (const int rc = enqueueRefit(err, st, s, st.world.buf, st.sun.buf, st.front)) return rc;
     }
+    st.vtx.installed(st.front, refitsSince != 0);
     ARK_HIP(installedGeometry(st, s));
     ARK_HIP(geometryChanged(st, s));
     ARK_HIP(sharedEnd(c, s));
@@ -1082,18 +1110,24 @@ int decodeTextures(ErrorSink* err,const ArkDdgiScene* s, std::vector<GpuTextureI
     return ARK_DDGI_OK;
 }
 
-// every instance's object-space box (refitInflations)
-void instanceObjectBoxes(const ArkDdgiScene* s, int threads, std::vector<std::array<float, 6>>& boxes)
+// every instance's object-space box (refitInflations) and every RT mesh's vertex span: the
+// largest index any instance of it draws (which instances a vertex update touches)
+void instanceObjectBoxes(const ArkDdgiScene* s, int threads, std::vector<std::array<float, 6>>& boxes, std::vector<MeshSpan>& spans)
 {
     boxes.assign(s->instance_count, { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY });
+    spans.assign(s->mesh_count, MeshSpan {});
     for (uint32_t ii = 0; ii < s->instance_count; ++ii) {
         const ArkRTInstance& in = s->instances[ii];
         const ArkRTTriangleMesh& mesh = s->meshes[in.rt_mesh_index];
         std::array<float, 6>& box = boxes[ii];
+        MeshSpan& span = spans[in.rt_mesh_index];
+        span.first = mesh.first_vertex;
         std::mutex mu;
         parallelFor(static_cast<size_t>(in.triangle_count) * 3u, threads, [&](size_t b, size_t e) {
             float lo[3] = { INFINITY, INFINITY, INFINITY }, hi[3] = { -INFINITY, -INFINITY, -INFINITY };
+            uint32_t most = 0;
             for (size_t k = b; k < e; ++k) {
+                most = std::max(most, s->indices[static_cast<size_t>(mesh.first_index) + k]);
                 const float* P = s->positions + (static_cast<int64_t>(mesh.first_vertex) + s->indices[static_cast<size_t>(mesh.first_index) + k]) * 3;
                 for (int a = 0; a < 3; ++a) {
                     lo[a] = std::min(lo[a], P[a]);
@@ -1104,6 +1138,10 @@ void instanceObjectBoxes(const ArkDdgiScene* s, int threads, std::vector<std::ar
             for (int a = 0; a < 3; ++a) {
                 box[a] = std::min(box[a], lo[a]);
                 box[3 + a] = std::max(box[3 + a], hi[a]);
+            }
+            if (e > b) {
+                span.maxIndex = std::max(span.maxIndex, most);
+                span.used = true;
             }
         });
     }
@@ -1166,13 +1204,17 @@ SceneStore::~SceneStore()
         if (stage[i]) (void)hipHostFree(stage[i]);
         if (stageDone[i]) (void)hipEventDestroy(stageDone[i]);
     }
-    for (hipEvent_t ev : { evFree[0], evFree[1], evFree[2], evInstalled, evGeometry })
+    for (int i = 0; i < kVertexStageSlots; ++i) {
+        if (vstage[i]) (void)hipHostFree(vstage[i]);
+        if (vstageDone[i]) (void)hipEventDestroy(vstageDone[i]);
+    }
+    for (hipEvent_t ev : { evFree[0], evFree[1], evFree[2], evInstalled, evGeometry, evPositionsRead })
         if (ev) (void)hipEventDestroy(ev);
     if (refitStream) (void)hipStreamDestroy(refitStream);
     world.release();
     sun.release();
     coverMap.buf.release();
-    for (DeviceBuffer* b : { &triNormals, &indices, &vertices, &positions, &meshes, &materials, &instances, &texInfos, &texels, &refitInst, &spare[0].world,
+    for (DeviceBuffer* b : { &triNormals, &indices, &vertices, &positions, &meshes, &materials, &instances, &texInfos, &texels, &refitInst, &recordMap, &triBase, &stageCounters, &spare[0].world,
                              &spare[0].sun, &spare[0].instances, &spare[1].world, &spare[1].sun, &spare[1].instances })
         b->release();
 }
@@ -1278,7 +1320,8 @@ int buildScene(ErrorSink* err, const ArkDdgiScene* s, int device, int buildThrea
     st->spare[0].slot = 1;
     st->spare[1].slot = 2;
     st->meshHost.assign(s->meshes, s->meshes + s->mesh_count);
-    instanceObjectBoxes(s, opt.threads, st->instObjBox);
+    instanceObjectBoxes(s, opt.threads, st->instObjBox, st->meshSpans);
+    st->vertexCount = s->vertex_count;
     if ((rc = upload(err, st->meshes, s->meshes, s->mesh_count)) != 0) return rc;
     if ((rc = upload(err, st->materials, s->materials, s->material_count)) != 0) return rc;
     if ((rc = upload(err, st->instances, ginst.data(), ginst.size())) != 0) return rc;
@@ -1410,6 +1453,7 @@ int refitSpare(SceneStore& st, const SceneCall& c, const ArkRTInstance* instance
         st.xf[ts] = st.xf[fs];
         st.inflCopy[ts][0] = st.inflCopy[fs][0];
         st.inflCopy[ts][1] = st.inflCopy[fs][1];
+        st.vtx.copied(ts, fs);
         tgt.valid = true;
     }
     // the instance table of the shading kernels (set_scene's determinant and rows)
@@ -1417,18 +1461,16 @@ int refitSpare(SceneStore& st, const SceneCall& c, const ArkRTInstance* instance
     for (uint32_t ii = 0; ii < count; ++ii) ginst[ii] = gpuInstance(instances[ii], st.meshHost[instances[ii].rt_mesh_index]);
     ARK_HIP(stagedUpload(st, tgt.instances.ptr, ginst.data(), count * sizeof(GpuInstance), rs));
     int rc;
-    if ((rc = uploadRefitInstances(err, st, instances, count, &st.xf[ts], rs)) != 0) return rc;
+    if ((rc = uploadRefitInstances(err, st, instances, count, &st.xf[ts], ts, rs)) != 0) return rc;
     if ((rc = enqueueRefit(err, st, rs, tgt.world, tgt.sun, ts)) != 0) return rc;
     ARK_HIP(geometryChanged(st, rs));
     ARK_HIP(sharedEnd(c, rs));
     return ARK_DDGI_OK;
 }
 
-} // namespace
-
-int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s)
+// set_instances' topology rules: the scene's instance list with new transforms
+int validateInstances(ErrorSink* err, const SceneStore& st, const ArkRTInstance* instances, uint32_t count)
 {
-    ErrorSink* err = c.err;
     if (count != st.instHost.size() || (count && !instances))
         return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "set_instances: %u instances, the scene has %zu", count, st.instHost.size());
     for (uint32_t i = 0; i < count; ++i) {
@@ -1438,6 +1480,273 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
         for (float v : a.object_to_world)
             if (!std::isfinite(v)) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "set_instances: instance %u: non-finite transform", i);
     }
+    return ARK_DDGI_OK;
+}
+
+// The vertex ranges of one ark_ddgi_update_geometry call, checked (validateVertexUpdates):
+// the instances their positions touch (refitted, their object-space boxes renewed) and
+// those their other vertex data touches (shading records rewritten).
+struct VertexWrites {
+    const ArkDdgiVertexUpdate* updates = nullptr;
+    uint32_t count = 0;
+    std::vector<uint8_t> touchedPositions, touchedVertices; // per instance
+    bool anyPositions = false, anyVertices = false, devicePositions = false;
+};
+
+// Every reason to refuse a call's vertex ranges, before anything changes
+int validateVertexUpdates(ErrorSink* err, const SceneStore& st, const ArkDdgiVertexUpdate* updates, uint32_t n, VertexWrites& vw)
+{
+    if (n && !updates) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: null updates");
+    std::vector<uint32_t> instMesh(st.instHost.size());
+    for (size_t i = 0; i < instMesh.size(); ++i) instMesh[i] = st.instHost[i].rt_mesh_index;
+    vw.updates = updates;
+    vw.count = n;
+    vw.touchedPositions.assign(instMesh.size(), 0);
+    vw.touchedVertices.assign(instMesh.size(), 0);
+    for (uint32_t u = 0; u < n; ++u) {
+        const ArkDdgiVertexUpdate& q = updates[u];
+        if (q.struct_size != sizeof(ArkDdgiVertexUpdate)) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: bad ArkDdgiVertexUpdate", u);
+        if (q.flags & ~ARK_DDGI_VERTICES_DEVICE) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: unknown flags 0x%x", u, q.flags);
+        if (!vertexRangeInPool(q.first_vertex, q.vertex_count, st.vertexCount))
+            return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: vertices [%u, +%u) outside the pools' %llu", u, q.first_vertex, q.vertex_count,
+                             static_cast<unsigned long long>(st.vertexCount));
+        if (!q.positions && !q.vertices) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: neither positions nor vertices", u);
+        const bool device = (q.flags & ARK_DDGI_VERTICES_DEVICE) != 0;
+        if (q.positions && device) {
+            bool ok = true, zero = true;
+            for (int a = 0; a < 6; ++a) {
+                ok = ok && std::isfinite(q.bounds[a]);
+                zero = zero && q.bounds[a] == 0.0f;
+            }
+            for (int a = 0; a < 3; ++a) ok = ok && q.bounds[a] <= q.bounds[3 + a];
+            if (!ok || zero) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: device positions need finite bounds (lo <= hi)", u);
+        }
+        if (q.positions && !device)
+            for (size_t k = 0; k < static_cast<size_t>(q.vertex_count) * 3u; ++k)
+                if (!std::isfinite(q.positions[k]))
+                    return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "update_geometry: update %u: position %zu is not finite", u, k / 3u);
+        if (q.positions) {
+            touchedInstances(st.meshSpans, instMesh, q.first_vertex, q.vertex_count, vw.touchedPositions);
+            vw.anyPositions = vw.anyPositions || q.vertex_count != 0;
+            vw.devicePositions = vw.devicePositions || (device && q.vertex_count != 0);
+        }
+        if (q.vertices) {
+            touchedInstances(st.meshSpans, instMesh, q.first_vertex, q.vertex_count, vw.touchedVertices);
+            vw.anyVertices = vw.anyVertices || q.vertex_count != 0;
+        }
+    }
+    return ARK_DDGI_OK;
+}
+
+// The object-space boxes of the instances the new positions touch (refitInflations): of
+// the part of a range inside the mesh's span - the host positions', or a device source's
+// `bounds`, which k_stage_vertices clamps into - replacing the old box when a host range
+// covers the whole span, else joined with it (larger bounds only loosen the boxes).
+void renewObjectBoxes(SceneStore& st, const VertexWrites& vw)
+{
+    for (uint32_t u = 0; u < vw.count; ++u) {
+        const ArkDdgiVertexUpdate& q = vw.updates[u];
+        if (!q.positions || !q.vertex_count) continue;
+        for (size_t m = 0; m < st.meshSpans.size(); ++m) {
+            const MeshSpan& sp = st.meshSpans[m];
+            if (!spanTouched(sp, q.first_vertex, q.vertex_count)) continue;
+            float box[6] = { INFINITY, INFINITY, INFINITY, -INFINITY, -INFINITY, -INFINITY };
+            if (q.flags & ARK_DDGI_VERTICES_DEVICE) {
+                std::copy(q.bounds, q.bounds + 6, box);
+            } else {
+                const int64_t lo = std::max<int64_t>(sp.first, q.first_vertex), hi = std::min<int64_t>(sp.first + sp.maxIndex, static_cast<int64_t>(q.first_vertex) + q.vertex_count - 1);
+                for (int64_t v = lo; v <= hi; ++v) {
+                    const float* P = q.positions + (v - q.first_vertex) * 3;
+                    for (int a = 0; a < 3; ++a) {
+                        box[a] = std::min(box[a], P[a]);
+                        box[3 + a] = std::max(box[3 + a], P[a]);
+                    }
+                }
+            }
+            // (a device source never replaces: a position the kernel drops as non-finite keeps
+            // its old value, which the old box holds and `bounds` need not)
+            const bool whole = !(q.flags & ARK_DDGI_VERTICES_DEVICE) && spanCovered(sp, q.first_vertex, q.vertex_count);
+            for (size_t i = 0; i < st.instHost.size(); ++i) {
+                if (st.instHost[i].rt_mesh_index != m || !st.instHost[i].triangle_count) continue;
+                std::array<float, 6>& b = st.instObjBox[i];
+                for (int a = 0; a < 3; ++a) {
+                    b[a] = whole ? box[a] : std::min(b[a], box[a]);
+                    b[3 + a] = whole ? box[3 + a] : std::max(b[3 + a], box[3 + a]);
+                }
+            }
+        }
+    }
+}
+
+// One pool's part of a call's vertex ranges into the pool on `s` (k_stage_vertices):
+// `floatsPerVertex` 3, the positions pool, or 9, the other vertex data. The host sources
+// share one slot of the vertex ranges' own staging ring, each placed at its destination's 16-B alignment;
+// device sources are read where they are, positions checked against their bounds.
+int stageVertexRanges(ErrorSink* err, SceneStore& st, const VertexWrites& vw, bool positions, hipStream_t s)
+{
+    const uint32_t fpv = positions ? 3u : 9u;
+    float* pool = positions ? st.positions.as<float>() : st.vertices.as<float>();
+    auto source = [&](const ArkDdgiVertexUpdate& q) { return positions ? q.positions : reinterpret_cast<const float*>(q.vertices); };
+    size_t bytes = 0;
+    for (uint32_t u = 0; u < vw.count; ++u)
+        if (source(vw.updates[u]) && !(vw.updates[u].flags & ARK_DDGI_VERTICES_DEVICE)) bytes += static_cast<size_t>(vw.updates[u].vertex_count) * fpv * 4u + 32u;
+    int slot = -1;
+    if (bytes) ARK_HIP(vertexStageAcquire(st, bytes, slot));
+    size_t at = 0;
+    // (a failure below still releases the slot behind the launches made so far: its next
+    // user must not fill it while one of them reads it)
+    hipError_t e = hipSuccess;
+    for (uint32_t u = 0; u < vw.count && e == hipSuccess; ++u) {
+        const ArkDdgiVertexUpdate& q = vw.updates[u];
+        const float* src = source(q);
+        const uint64_t words = static_cast<uint64_t>(q.vertex_count) * fpv;
+        if (!src || !words) continue;
+        float* dst = pool + static_cast<uint64_t>(q.first_vertex) * fpv;
+        StageCheck chk {};
+        if (q.flags & ARK_DDGI_VERTICES_DEVICE) {
+            if (positions) {
+                if (!st.stageCounters.ptr) {
+                    if ((e = st.stageCounters.alloc(16)) == hipSuccess) e = hipMemsetAsync(st.stageCounters.ptr, 0, 16, s);
+                    if (e != hipSuccess) break;
+                }
+                std::copy(q.bounds, q.bounds + 3, chk.lo);
+                std::copy(q.bounds + 3, q.bounds + 6, chk.hi);
+                chk.enabled = 1;
+            }
+        } else {
+            at = ((at + 15u) & ~static_cast<size_t>(15u)) + (reinterpret_cast<uintptr_t>(dst) & 15u);
+            float* staged = reinterpret_cast<float*>(static_cast<char*>(st.vstage[slot]) + at);
+            std::memcpy(staged, src, words * 4u);
+            at += words * 4u;
+            src = staged;
+        }
+        e = launch_stage_vertices(src, dst, words, chk, st.stageCounters.as<unsigned long long>(), s);
+    }
+    if (slot >= 0) {
+        const hipError_t r = vertexStageRelease(st, slot, s);
+        if (e == hipSuccess) e = r;
+    }
+    if (e != hipSuccess) return err->hipFail(e, "staging vertex ranges");
+    return ARK_DDGI_OK;
+}
+
+// The map global triangle -> world record of the front copy's record order on `s`,
+// allocated at its first use and filled again after every installed world rebuild
+int ensureRecordMap(ErrorSink* err, SceneStore& st, hipStream_t s)
+{
+    const uint32_t instances = static_cast<uint32_t>(st.instHost.size());
+    if (st.triBaseHost.empty()) {
+        uint64_t total = 0;
+        std::vector<uint32_t> base(instances + 1u);
+        for (uint32_t i = 0; i < instances; ++i) {
+            base[i] = static_cast<uint32_t>(total);
+            total += st.instHost[i].triangle_count;
+        }
+        if (total >= 0xffffffffull) return err->fail(ARK_DDGI_E_UNSUPPORTED, "update_geometry: %llu triangles", static_cast<unsigned long long>(total));
+        base[instances] = static_cast<uint32_t>(total);
+        if (const int rc = upload(err, st.triBase, base.data(), base.size())) return rc;
+        st.triBaseHost.swap(base);
+    }
+    const uint32_t total = st.triBaseHost[instances];
+    if (!st.recordMap.ptr) {
+        ARK_HIP(st.recordMap.alloc(std::max<size_t>(16, static_cast<size_t>(total) * 4u)));
+        ++st.recordMapAllocs;
+        st.recordMapSeq = st.worldTopologySeq - 1u; // not of this order
+    }
+    if (st.recordMapSeq != st.worldTopologySeq) {
+        ARK_HIP(launch_fill_u32(st.recordMap.ptr, std::max<uint64_t>(4, total), 0xffffffffu, s));
+        ARK_HIP(launch_record_map(st.args.tris, static_cast<uint32_t>(st.world.records), st.triBase.as<uint32_t>(), instances, st.recordMap.as<uint32_t>(), s));
+        st.recordMapSeq = st.worldTopologySeq;
+        ++st.recordMapFills;
+    }
+    return ARK_DDGI_OK;
+}
+
+// The other vertex data of a call's ranges and what follows from it, on the caller's
+// stream `s` (behind the frame in flight, which reads both, and behind this call's refit):
+// the vertex pool, then the shading records of the instances the ranges touch.
+int writeSurfaceData(ErrorSink* err, SceneStore& st, const VertexWrites& vw, hipStream_t s)
+{
+    int rc;
+    if ((rc = stageVertexRanges(err, st, vw, false, s)) != 0) return rc;
+    if ((rc = ensureRecordMap(err, st, s)) != 0) return rc;
+    SurfaceJobs jobs {};
+    uint32_t n = 0;
+    auto flush = [&]() -> hipError_t {
+        const hipError_t e = launch_update_surface_records(jobs, n, st.recordMap.as<uint32_t>(), static_cast<uint32_t>(st.world.records), st.indices.as<uint32_t>(),
+                                                           st.vertices.as<float>(), st.triNormals.as<float4>(), s);
+        n = 0;
+        return e;
+    };
+    for (size_t i = 0; i < st.instHost.size(); ++i) {
+        if (!vw.touchedVertices[i] || !st.instHost[i].triangle_count) continue;
+        const ArkRTTriangleMesh& mesh = st.meshHost[st.instHost[i].rt_mesh_index];
+        jobs.job[n++] = { static_cast<uint32_t>(i), st.triBaseHost[i], st.instHost[i].triangle_count, static_cast<uint32_t>(mesh.first_index), mesh.first_vertex };
+        if (n == kSurfaceJobsPerLaunch) ARK_HIP(flush());
+    }
+    ARK_HIP(flush());
+    return ARK_DDGI_OK;
+}
+
+int refitScene(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s, const VertexWrites* vw);
+
+} // namespace
+
+int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s)
+{
+    if (const int rc = validateInstances(c.err, st, instances, count)) return rc;
+    return refitScene(st, c, instances, count, s, nullptr);
+}
+
+int sceneUpdateGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count,
+                        hipStream_t s)
+{
+    // (a copy: the refit ends by writing the new transforms into instHost)
+    const std::vector<ArkRTInstance> kept = (!instances && !count) ? st.instHost : std::vector<ArkRTInstance>();
+    if (!instances && !count) {
+        instances = kept.data();
+        count = static_cast<uint32_t>(kept.size());
+    }
+    int rc;
+    if ((rc = validateInstances(c.err, st, instances, count)) != 0) return rc;
+    VertexWrites vw;
+    if ((rc = validateVertexUpdates(c.err, st, updates, updateCount, vw)) != 0) return rc;
+    if ((rc = refitScene(st, c, instances, count, s, &vw)) != 0) return rc;
+    // (the calls that went through: a refused or failed one counts nothing)
+    ++st.geometryCalls;
+    for (uint32_t u = 0; u < updateCount; ++u) st.verticesWritten += updates[u].vertex_count;
+    return ARK_DDGI_OK;
+}
+
+int sceneGeometryStats(SceneStore& st, ErrorSink* err, uint64_t* out)
+{
+    out[0] = st.geometryCalls;
+    out[1] = st.verticesWritten;
+    out[2] = out[3] = 0;
+    if (st.stageCounters.ptr) {
+        ARK_HIP(hipStreamSynchronize(st.refitStream));
+        ARK_HIP(hipMemcpy(out + 2, st.stageCounters.ptr, 16, hipMemcpyDeviceToHost));
+    }
+    return ARK_DDGI_OK;
+}
+
+hipError_t scenePositionsRead(SceneStore& st, hipStream_t s)
+{
+    if (!st.positionsStaged) return hipSuccess; // (the first staging waits for the caller's stream)
+    hipError_t e = hipSuccess;
+    if (!st.evPositionsRead) e = hipEventCreateWithFlags(&st.evPositionsRead, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventRecord(st.evPositionsRead, s);
+    st.positionsReadValid = e == hipSuccess;
+    return e;
+}
+
+namespace {
+
+// The refit of ark_ddgi_set_instances and ark_ddgi_update_geometry (vw: its vertex ranges,
+// checked; null: none), the arguments valid
+int refitScene(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s, const VertexWrites* vw)
+{
+    ErrorSink* err = c.err;
     ARK_HIP(sharedBegin(c));
     // the cover map is of the geometry before this refit
     ARK_HIP(clearCoverMap(st, s));
@@ -1474,6 +1783,36 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
         ARK_HIP(hipStreamWaitEvent(st.refitStream, st.evInstalled, 0));
         st.installValid = false;
     }
+    if (vw && vw->anyPositions) {
+        // The new positions, on the refit stream ahead of the refit that reads them. The
+        // pool's other readers are the earlier refits (this stream), an install's forward
+        // refit (evInstalled above) and the AO bake (evPositionsRead) - not the frame in
+        // flight, beside which the refit keeps running. A device source is the caller's
+        // work on `s`: only then does the stream wait for `s` as it stands (evFree[fs]) -
+        // and at the scene's first staging, before which no bake left an event.
+        if (st.positionsReadValid) {
+            ARK_HIP(hipStreamWaitEvent(st.refitStream, st.evPositionsRead, 0));
+            st.positionsReadValid = false;
+        }
+        if (vw->devicePositions || !st.positionsStaged) ARK_HIP(hipStreamWaitEvent(st.refitStream, st.evFree[fs], 0));
+        st.positionsStaged = true;
+        // the touched instances' vertices are newer than every copy's records from here on,
+        // whatever becomes of this refit
+        st.vtx.begin(count);
+        for (uint32_t ii = 0; ii < count; ++ii)
+            if (vw->touchedPositions[ii]) st.vtx.touch(ii);
+        renewObjectBoxes(st, *vw);
+        // A failure here (a HIP launch or allocation error) leaves the pool partly written
+        // and the front copy's records of the old positions: the versions above keep the
+        // touched instances dirty for every copy, so the next refit that succeeds
+        // re-derives them from whatever the pool then holds, reaching every node; until
+        // then only the bake, which reads the pool itself, can see the partial write. The
+        // caller sends the ranges again.
+        if ((rc = stageVertexRanges(err, st, *vw, true, st.refitStream)) != 0) {
+            st.refitFull = true;
+            return rc;
+        }
+    }
     if ((rc = refitSpare(st, c, instances, count, s)) != 0) {
         // the spare may be half written and xf / inflCopy no longer describe it: the next
         // refit copies the front one anew and reaches every node
@@ -1484,6 +1823,7 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
     // the refitted copy becomes the front one
     st.xf[ts].resize(count);
     for (uint32_t ii = 0; ii < count; ++ii) std::memcpy(st.xf[ts][ii].data(), instances[ii].object_to_world, sizeof(float) * 12);
+    st.vtx.refitted(ts);
     rotateGeometry(st);
     // the caller's stream follows the refit (what it runs next sees the new geometry); the
     // contexts' next traversals on their traversal streams wait for it too (geometrySeq)
@@ -1493,10 +1833,29 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
     ++st.refitsSinceBuild;
     ++st.sunRefitsSinceBuild;
     st.bvhStats.refit_version = ++st.refitCount;
+    if (vw && vw->anyVertices) {
+        // The vertex pool (the alpha test of every traversal, the reflections, the bake) and
+        // the shading records (every k_shade) on `s`: behind the frame in flight, which
+        // reads the old ones, and - evGeometry recorded again - ahead of the next
+        // traversal, whichever stream it runs on.
+        // A failure here comes after the refitted copy became the front one: its records
+        // are of the new positions while the vertex pool or the shading records may still
+        // be the old ones. Nothing is out of bounds or stale by pointer (both buffers are
+        // the same ones); the caller sees the error and sends the ranges' `vertices` again,
+        // which rewrites both whatever state they are in. The map is filled anew then.
+        if ((rc = writeSurfaceData(err, st, *vw, s)) != 0) {
+            st.recordMapSeq = st.worldTopologySeq - 1u;
+            return rc;
+        }
+        ARK_HIP(geometryChanged(st, s));
+        ARK_HIP(sharedEnd(c, s));
+    }
     // background rebuilds of the loosened BVHs (world and light-space), from a snapshot
     // taken on s behind this refit
     return sceneMaintenance(st, c, s);
 }
+
+} // namespace
 
 int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out)
 {

@@ -28,6 +28,7 @@
 #include "ddgi_kernels.h"
 #include "device_bvh.h"
 #include "scene_rebuild_policy.h"
+#include "vertex_dirty.h"
 
 namespace ark {
 
@@ -122,6 +123,16 @@ struct SceneStore {
     size_t stageBytes[kStageSlots] {};
     hipEvent_t stageDone[kStageSlots] {};
     int stageNext = 0;
+    // ark_ddgi_update_geometry's host vertex ranges have a ring of their own (allocated at
+    // the first such call), so that a deform call takes the two slots above that a rigid one
+    // takes and the host runs as far ahead; a call's ranges take one slot per pool here, the
+    // vertex data's released only behind the frame in flight, so the large ranges run two
+    // calls ahead and at most kVertexStageSlots buffers of the largest call stay pinned
+    static constexpr int kVertexStageSlots = 4;
+    void* vstage[kVertexStageSlots] {};
+    size_t vstageBytes[kVertexStageSlots] {};
+    hipEvent_t vstageDone[kVertexStageSlots] {};
+    int vstageNext = 0;
     // object-space bounds of every instance's triangles (set_scene): the refit's world and
     // light-space bounds, for its box inflation, from the instances' transforms on the host
     std::vector<std::array<float, 6>> instObjBox;
@@ -201,6 +212,27 @@ struct SceneStore {
     // words are record indices, on its traversal stream when this has moved (ark_ddgi.cpp
     // updateImpl, behind its wait for evGeometry and ahead of the traversal)
     uint32_t worldTopologySeq = 0;
+    // Deforming meshes (ark_ddgi_update_geometry; DESIGN §1 "Deforming meshes"). The pools'
+    // vertex count and every RT mesh's vertex span (set_scene); the instances' vertex
+    // versions against the three copies (vertex_dirty.h). Everything below is allocated at
+    // the first update call: a scene that never makes one holds none of it.
+    uint64_t vertexCount = 0;
+    std::vector<MeshSpan> meshSpans;
+    VertexVersions vtx;
+    // global triangle -> world record index (k_record_map; triBase: the instances' first
+    // global triangles, on the host and the device), filled at the first update that
+    // rewrites shading records and again after each installed world rebuild (recordMapSeq
+    // against worldTopologySeq)
+    DeviceBuffer recordMap, triBase;
+    std::vector<uint32_t> triBaseHost;
+    uint32_t recordMapSeq = 0, recordMapAllocs = 0, recordMapFills = 0;
+    // k_stage_vertices' counts of dropped and clamped device-source positions
+    DeviceBuffer stageCounters;
+    uint64_t geometryCalls = 0, verticesWritten = 0;
+    // ends with the last operation outside the refit stream that reads the positions pool
+    // (the AO bake): the next staging of positions, on the refit stream, waits for it
+    hipEvent_t evPositionsRead = nullptr;
+    bool positionsReadValid = false, positionsStaged = false;
     SceneStore();
     SceneStore(const SceneStore&) = delete;
     SceneStore& operator=(const SceneStore&) = delete;
@@ -237,6 +269,16 @@ bool sunJobPending(const SceneStore& st);
 // ark_ddgi_set_instances_async: the refit of the next spare copy to `instances` on the
 // store's stream, which then becomes the front copy; `s` follows the refit.
 int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* instances, uint32_t count, hipStream_t s);
+// ark_ddgi_update_geometry_async: the same refit with the vertex ranges `updates` written
+// into the pools first - positions on the store's stream ahead of the refit, the other
+// vertex data and the touched instances' shading records on `s`. instances null (count 0):
+// the transforms stay.
+int sceneUpdateGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count,
+                        hipStream_t s);
+// ark_ddgi_get_geometry_update_stats (waits for the refit stream)
+int sceneGeometryStats(SceneStore& st, ErrorSink* err, uint64_t* out);
+// An operation on `s` read the positions pool (the AO bake): the next vertex update follows it
+hipError_t scenePositionsRead(SceneStore& st, hipStream_t s);
 
 // ark_ddgi_debug_scene_digest / _world_bvh_check over the front copy (the device is idle)
 int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out);

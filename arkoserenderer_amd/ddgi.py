@@ -109,6 +109,61 @@ class AppState:
         return self.frame_index == 0
 
 
+class VertexUpdate:
+    """One range of the scene's vertex pools for DDGIContext.update_geometry, starting at
+    the absolute vertex `first_vertex`. positions: n x 3 float32, vertices: n x 9 float32
+    (or the scene's vertex dtype: tex_coord 2, normal 3, tangent 4), either None to keep the
+    pool's. numpy arrays are host sources. torch device tensors are device sources
+    (ARK_DDGI_VERTICES_DEVICE: both must then be device tensors) and positions then need
+    `bounds` = (lo xyz, hi xyz); the object keeps the arrays alive."""
+
+    def __init__(self, first_vertex: int, positions=None, vertices=None, bounds=None):
+        self.first_vertex = int(first_vertex)
+        self.flags = 0
+        self._keep = []
+        self._ptr = [None, None]
+        count = None
+        for k, (a, width) in enumerate(((positions, 3), (vertices, 9))):
+            if a is None:
+                continue
+            if not hasattr(a, "is_cuda"):  # an ndarray, or a list / tuple of rows
+                a = np.asarray(a, dtype=None if isinstance(a, np.ndarray) else np.float32)
+            device = not isinstance(a, np.ndarray) and a.is_cuda
+            if device:  # a torch device tensor
+                a = a.contiguous()
+                if str(a.dtype) != "torch.float32":
+                    raise TypeError("VertexUpdate: float32 tensors")
+                floats, ptr = a.numel(), a.data_ptr()
+            else:
+                a = np.ascontiguousarray(a if isinstance(a, np.ndarray) else a.numpy())
+                if a.dtype != np.float32:
+                    a = a.view(np.float32) if a.dtype.itemsize == 4 * width else a.astype(np.float32)
+                floats, ptr = a.size, a.ctypes.data
+            n = floats // width
+            if floats != n * width:
+                raise ValueError("VertexUpdate: %d floats per vertex" % width)
+            if count is not None and (n != count or device != bool(self.flags)):
+                raise ValueError("VertexUpdate: positions and vertices differ in count or in host / device")
+            count = n
+            self.flags = abi.ARK_DDGI_VERTICES_DEVICE if device else 0
+            self._keep.append(a)
+            self._ptr[k] = ptr
+        self.vertex_count = count or 0
+        self.bounds = None if bounds is None else [float(v) for v in np.asarray(bounds, dtype=np.float32).reshape(6)]
+
+    def to_abi(self) -> abi.ArkDdgiVertexUpdate:
+        u = abi.ArkDdgiVertexUpdate()
+        u.struct_size = C.sizeof(abi.ArkDdgiVertexUpdate)
+        u.first_vertex = self.first_vertex
+        u.vertex_count = self.vertex_count
+        u.flags = self.flags
+        u.positions = self._ptr[0]
+        u.vertices = self._ptr[1]
+        if self.bounds is not None:
+            u.bounds[:] = self.bounds
+        return u
+
+
 def _check(lib, ctx, rc, what):
     if rc != 0:
         msg = lib.ark_ddgi_last_error(ctx)
@@ -203,6 +258,42 @@ class DDGIContext:
         a = np.ascontiguousarray(instances)
         self.check(self.lib.ark_ddgi_set_instances_async(self.h, C.c_void_p(a.ctypes.data), int(a.size), C.c_void_p(stream) if stream else None),
                    "ark_ddgi_set_instances_async")
+
+    def _geometry_args(self, updates, instances):
+        ups = list(updates)
+        arr = (abi.ArkDdgiVertexUpdate * max(1, len(ups)))(*[u.to_abi() for u in ups])
+        inst = None if instances is None else np.ascontiguousarray(instances)
+        return ups, arr, inst
+
+    def update_geometry(self, updates, instances: np.ndarray | None = None):
+        """ark_ddgi_update_geometry: deforming meshes (GpuScene.cpp:629-711, :934-992). `updates`
+        = VertexUpdates, ranges of the scene's vertex pools with new contents; `instances` =
+        the scene's INSTANCE_DTYPE array with new transforms, or None to keep them. One refit."""
+        ups, arr, inst = self._geometry_args(updates, instances)
+        self.check(self.lib.ark_ddgi_update_geometry(self.h, arr, len(ups), C.c_void_p(inst.ctypes.data) if inst is not None else None,
+                                                     int(inst.size) if inst is not None else 0), "ark_ddgi_update_geometry")
+
+    def update_geometry_async(self, updates, instances: np.ndarray | None = None, stream: int | None = None):
+        """ark_ddgi_update_geometry_async: the same enqueued on `stream` (no host wait). Device
+        sources must stay untouched until the stream has passed the call's work."""
+        ups, arr, inst = self._geometry_args(updates, instances)
+        self.check(self.lib.ark_ddgi_update_geometry_async(self.h, arr, len(ups), C.c_void_p(inst.ctypes.data) if inst is not None else None,
+                                                           int(inst.size) if inst is not None else 0, C.c_void_p(stream) if stream else None),
+                   "ark_ddgi_update_geometry_async")
+
+    def geometry_update_stats(self) -> tuple:
+        """ark_ddgi_get_geometry_update_stats: (update_geometry calls, vertices written,
+        device-source positions dropped as non-finite, device-source positions clamped)."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.lib.ark_ddgi_get_geometry_update_stats(self.h, out), "ark_ddgi_get_geometry_update_stats")
+        return tuple(int(v) for v in out)
+
+    def geometry_update_info(self) -> dict:
+        """ark_ddgi_debug_geometry_update_info: what update_geometry allocated for the scene
+        (all 0 for a scene that never called it)."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.lib.ark_ddgi_debug_geometry_update_info(self.h, out), "ark_ddgi_debug_geometry_update_info")
+        return dict(zip(("map_allocations", "map_fills", "device_bytes", "position_updates"), (int(v) for v in out)))
 
     def share_scene(self, src: "DDGIContext"):
         """ark_ddgi_share_scene: use src's device scene and BVH (same GPU), no copy."""

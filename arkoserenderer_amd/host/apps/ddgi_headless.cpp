@@ -43,6 +43,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -341,6 +342,7 @@ int main(int argc, char** argv)
     std::string saveStatePath, loadStatePath, frameScriptPath;
     int firstFrame = 0, gpuRebuild = 0;
     bool raySeeds = true;
+    int wobble = -1; // --wobble I: RT mesh I deforms every frame
     bool deadlineTest = false;
     const std::time_t startedAt = std::time(nullptr);
     float zFar = 10000.0f, exposure = 1.0f, env = 1.0f, ambient = 0.0f;
@@ -379,6 +381,7 @@ int main(int argc, char** argv)
         else if (a == "--frame-script") frameScriptPath = next();
         else if (a == "--gpu-rebuild") gpuRebuild = std::atoi(next());
         else if (a == "--no-ray-seeds") raySeeds = false;
+        else if (a == "--wobble") wobble = std::atoi(next());
         else ARKOSE_LOG(Fatal, "unknown argument %s", a.c_str());
     }
     SceneFile file;
@@ -488,6 +491,7 @@ int main(int argc, char** argv)
         if (!nodeOf(*pipelines[0])->loadState(blob)) ARKOSE_LOG(Fatal, "DDGINode::loadState failed");
         std::printf("ddgi_headless: resumed at probe %d\n", nodeOf(*pipelines[0])->probeUpdateIdx());
     }
+    std::vector<float> wobbleRest;
     std::vector<FrameChange> script;
     if (!frameScriptPath.empty() && !loadFrameScript(frameScriptPath.c_str(), script)) ARKOSE_LOG(Fatal, "cannot read frame script %s", frameScriptPath.c_str());
     for (int f = firstFrame; f < firstFrame + frames; ++f) {
@@ -502,6 +506,30 @@ int main(int argc, char** argv)
                     for (int col = 0; col < 4; ++col) m[col * 4 + r] = r < 3 ? c.transforms[i * 12 + r * 4 + col] : (col == 3 ? 1.0f : 0.0f);
                 scene.setInstanceTransform(i, m);
             }
+        }
+        if (wobble >= 0) {
+            // a deforming mesh (the reference's skinned instances, GpuScene.cpp:629-711): RT
+            // mesh `wobble`'s rest positions displaced by a small periodic bump that moves with
+            // the frame (a parabola per period: exact fp32 steps, the same on every host)
+            const ArkDdgiScene& v = scene.rtScene();
+            if (static_cast<uint32_t>(wobble) >= v.mesh_count) ARKOSE_LOG(Fatal, "--wobble %d: the scene has %u RT meshes", wobble, v.mesh_count);
+            if (wobbleRest.empty()) {
+                uint32_t most = 0, tris = 0;
+                for (uint32_t i = 0; i < v.instance_count; ++i)
+                    if (v.instances[i].rt_mesh_index == static_cast<uint32_t>(wobble)) tris = std::max(tris, v.instances[i].triangle_count);
+                const ArkRTTriangleMesh& m = v.meshes[wobble];
+                for (uint32_t k = 0; k < 3 * tris; ++k) most = std::max(most, v.indices[static_cast<size_t>(m.first_index) + k]);
+                const float* P = v.positions + static_cast<size_t>(m.first_vertex) * 3;
+                wobbleRest.assign(P, P + static_cast<size_t>(most + 1) * 3);
+            }
+            std::vector<float> P(wobbleRest);
+            for (size_t k = 0; k < P.size(); k += 3)
+                for (int a = 0; a < 3; ++a) {
+                    const float x = 0.3f * static_cast<float>(f) + 2.0f * wobbleRest[k + (a + 1) % 3];
+                    const float t = x - std::floor(x);
+                    P[k + a] = wobbleRest[k + a] + 0.05f * (4.0f * t * (1.0f - t));
+                }
+            scene.updateMeshVertices(static_cast<uint32_t>(wobble), P.data(), nullptr);
         }
         scene.update(); // GpuScene::update: the exposure and light data of this frame
         if (f == rebuildAt) {

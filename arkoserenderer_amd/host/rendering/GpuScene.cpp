@@ -1,5 +1,6 @@
 #include "GpuScene.h"
 
+#include <algorithm>
 #include <cstring>
 
 #include "core/Logging.h"
@@ -109,10 +110,43 @@ void GpuScene::setInstanceTransform(size_t index, const float worldMatrix[16])
     ++m_instanceVersion;
 }
 
+void GpuScene::updateMeshVertices(uint32_t rtMeshIndex, const float* positions, const ArkRTVertex* vertices)
+{
+    if (m_rtMeshes.empty()) buildRtInstances();
+    if (rtMeshIndex >= m_rtMeshes.size()) ARKOSE_LOG(Fatal, "GpuScene: no RT mesh %u", rtMeshIndex);
+    if (!positions && !vertices) return;
+    const uint32_t first = static_cast<uint32_t>(m_rtMeshes[rtMeshIndex].first_vertex);
+    uint32_t count = m_rtMeshVertexCounts[rtMeshIndex];
+    if (count == 0 && m_rtMeshIndexCounts[rtMeshIndex] != 0) {
+        const uint32_t* idx = m_indices.data() + m_rtMeshes[rtMeshIndex].first_index;
+        count = 1u + *std::max_element(idx, idx + m_rtMeshIndexCounts[rtMeshIndex]);
+    }
+    if (static_cast<size_t>(first) + count > m_nonPosition.size()) ARKOSE_LOG(Fatal, "GpuScene: RT mesh %u's vertices lie outside the pools", rtMeshIndex);
+    if (positions) std::memcpy(m_positions.data() + static_cast<size_t>(first) * 3, positions, static_cast<size_t>(count) * 3 * sizeof(float));
+    if (vertices) std::memcpy(m_nonPosition.data() + first, vertices, static_cast<size_t>(count) * sizeof(ArkRTVertex));
+    ++m_vertexVersion;
+    m_vertexLog.push_back(VertexRange { m_vertexVersion, first, count, positions != nullptr, vertices != nullptr });
+}
+
+bool GpuScene::vertexRangesSince(uint32_t version, std::vector<VertexRange>& out) const
+{
+    out.clear();
+    if (version < m_vertexLogFloor) return false;
+    for (const VertexRange& r : m_vertexLog)
+        if (r.version > version) out.push_back(r);
+    return true;
+}
+
 void GpuScene::update()
 {
     // m_lightPreExposure = camera().exposure() (:792), then the light buffers (:795-858)
     if (m_lightsManaged) updateLightData();
+    // the vertex ranges of the frame before last go (every node has had a frame to carry them)
+    size_t keep = 0;
+    while (keep < m_vertexLog.size() && m_vertexLog[keep].version <= m_vertexLogMark) ++keep;
+    m_vertexLog.erase(m_vertexLog.begin(), m_vertexLog.begin() + static_cast<std::ptrdiff_t>(keep));
+    m_vertexLogFloor = m_vertexLogMark;
+    m_vertexLogMark = m_vertexVersion;
 }
 
 void GpuScene::buildRtInstances()
@@ -124,6 +158,8 @@ void GpuScene::buildRtInstances()
     // (VertexManager.cpp:1298-1329: the BLAS is the segment's indexed triangles at an
     // identity geometry transform).
     m_rtMeshes.clear();
+    m_rtMeshVertexCounts.clear();
+    m_rtMeshIndexCounts.clear();
     m_rtInstances.clear();
     for (const StaticMeshInstance& inst : m_instances) {
         for (const StaticMeshLOD& lod : m_staticMeshes[inst.mesh].LODs) {
@@ -131,6 +167,9 @@ void GpuScene::buildRtInstances()
                 if (!seg.blasBuilt) continue; // not yet loaded
                 const uint32_t rtMeshIndex = static_cast<uint32_t>(m_rtMeshes.size());
                 m_rtMeshes.push_back(ArkRTTriangleMesh { seg.vertexAllocation.firstVertex, static_cast<int32_t>(seg.vertexAllocation.firstIndex), seg.material });
+                // (0: pools adopted whole - the count is then the segment's largest index + 1, found when asked for)
+                m_rtMeshVertexCounts.push_back(seg.vertexAllocation.vertexCount);
+                m_rtMeshIndexCounts.push_back(seg.vertexAllocation.indexCount);
                 uint32_t hitMask = 0;
                 if (seg.material >= 0 && static_cast<size_t>(seg.material) < m_materials.size()) {
                     switch (m_materials[seg.material].blend_mode) {

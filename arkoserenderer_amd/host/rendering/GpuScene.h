@@ -150,6 +150,27 @@ public:
     // data of the next frame changes (GpuScene.cpp:901-928)
     void setInstanceTransform(size_t index, const float worldMatrix[16]);
     uint32_t instanceVersion() const { return m_instanceVersion; }
+    // A skinned mesh's vertices of this frame (GpuScene.cpp:629-711: each skeletal-mesh
+    // instance is skinned into its own range of the vertex pools): the pools' range of RT
+    // mesh `rtMeshIndex` (rtScene() / rtInstances() number them) replaced - positions
+    // (x 3) and / or the other vertex data, each its segment's vertex count long or null.
+    // The range is logged under the new vertexVersion(). Several nodes draw one GpuScene
+    // (the Z-slab ranks of a process), each with a context and device scene of its own: each
+    // reads the log from the version its context holds (vertexRangesSince), as each pulls
+    // the instance list by instanceVersion(). update() drops the ranges logged before the
+    // update() before it, which every node that executes each frame has carried by then.
+    void updateMeshVertices(uint32_t rtMeshIndex, const float* positions, const ArkRTVertex* vertices);
+    uint32_t vertexVersion() const { return m_vertexVersion; }
+    struct VertexRange {
+        uint32_t version; // vertexVersion() once it was logged
+        uint32_t firstVertex, vertexCount;
+        bool positions, vertices;
+    };
+    // the ranges logged after `version`, oldest first; false when some of them were dropped
+    // already (the caller's pools are older than the log reaches: it builds its scene anew)
+    bool vertexRangesSince(uint32_t version, std::vector<VertexRange>& out) const;
+    const float* positionPool() const { return m_positions.data(); }
+    const ArkRTVertex* vertexPool() const { return m_nonPosition.data(); }
 
     // The per-frame part of GpuScene::update (GpuScene.cpp:790-1009): the exposure is read
     // (:792) and the light data re-computed from the managed lights with it (recorded
@@ -184,6 +205,11 @@ private:
     std::vector<SpotLightData> m_spotLightData;
     bool m_lightsManaged { false }; // update() recomputes the light data from the managed lights
     uint32_t m_instanceVersion { 0 };
+    uint32_t m_vertexVersion { 0 };
+    std::vector<VertexRange> m_vertexLog;
+    uint32_t m_vertexLogFloor { 0 }; // every range up to this version was dropped
+    uint32_t m_vertexLogMark { 0 };  // vertexVersion() at the last update()
+    std::vector<uint32_t> m_rtMeshVertexCounts, m_rtMeshIndexCounts; // beside m_rtMeshes
     // adapter output
     void buildRtInstances(); // m_rtMeshes + m_rtInstances from the instances
     void buildArkLights();   // m_arkSpots from the light data

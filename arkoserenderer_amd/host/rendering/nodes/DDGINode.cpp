@@ -101,6 +101,7 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
         return RenderPipelineNode::NullExecuteCallback;
     }
     m_instanceVersion = scene.instanceVersion(); // set_scene built the BVHs at these transforms
+    m_vertexVersion = scene.vertexVersion();     // ... from these pools
 
     ArkDdgiDeviceViews views {};
     ark_ddgi_get_device_views(ctx, &views);
@@ -145,20 +146,46 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
         // installed when ready - the reference's full build every 60 frames)
         if (int rc = ark_ddgi_set_lights(ctx, &scene.rtLights()); rc != ARK_DDGI_OK)
             ARKOSE_LOG(Error, "DDGINode: ark_ddgi_set_lights failed (%d): %s", rc, ark_ddgi_last_error(ctx));
-        if (scene.instanceVersion() != m_instanceVersion) {
+        if (scene.instanceVersion() != m_instanceVersion || scene.vertexVersion() != m_vertexVersion) {
+            const bool moved = scene.instanceVersion() != m_instanceVersion;
             const std::vector<ArkRTInstance>& instances = scene.rtInstances();
-            // enqueued on this frame's stream ahead of the update (no host wait)
-            int rc = ark_ddgi_set_instances_async(ctx, instances.data(), static_cast<uint32_t>(instances.size()), cmdList.hipStream());
+            // enqueued on this frame's stream ahead of the update (no host wait): the
+            // skinned meshes' vertex ranges since the version this node's context holds
+            // (GpuScene.cpp:629-711, :934-992; the scene's log, which every node of the
+            // scene reads for itself) and the moved transforms in one refit
+            int rc;
+            std::vector<GpuScene::VertexRange> ranges;
+            if (scene.vertexVersion() != m_vertexVersion && !scene.vertexRangesSince(m_vertexVersion, ranges)) {
+                rc = ARK_DDGI_E_INVALID_ARGUMENT; // the log no longer reaches back to this context's pools: set_scene below
+            } else if (scene.vertexVersion() != m_vertexVersion) {
+                std::vector<ArkDdgiVertexUpdate> updates;
+                for (const GpuScene::VertexRange& r : ranges) {
+                    ArkDdgiVertexUpdate u {};
+                    u.struct_size = sizeof(u);
+                    u.first_vertex = r.firstVertex;
+                    u.vertex_count = r.vertexCount;
+                    u.positions = r.positions ? scene.positionPool() + static_cast<size_t>(r.firstVertex) * 3 : nullptr;
+                    u.vertices = r.vertices ? scene.vertexPool() + r.firstVertex : nullptr;
+                    updates.push_back(u);
+                }
+                rc = ark_ddgi_update_geometry_async(ctx, updates.data(), static_cast<uint32_t>(updates.size()), moved ? instances.data() : nullptr,
+                                                    moved ? static_cast<uint32_t>(instances.size()) : 0u, cmdList.hipStream());
+            } else {
+                rc = ark_ddgi_set_instances_async(ctx, instances.data(), static_cast<uint32_t>(instances.size()), cmdList.hipStream());
+            }
             if (rc != ARK_DDGI_OK) {
                 // a refit cannot follow this change (the topology changed: another mesh,
                 // triangle count or hit mask): build the scene anew, as construct() does
                 // (never keep the old transforms for good)
-                ARKOSE_LOG(Warning, "DDGINode: ark_ddgi_set_instances failed (%d): %s; rebuilding the scene", rc, ark_ddgi_last_error(ctx));
+                ARKOSE_LOG(Warning, "DDGINode: the scene's change cannot be refitted (%d): %s; rebuilding the scene", rc, ark_ddgi_last_error(ctx));
                 rc = ark_ddgi_set_scene(ctx, &scene.rtScene());
                 if (rc != ARK_DDGI_OK) ARKOSE_LOG(Error, "DDGINode: ark_ddgi_set_scene failed (%d): %s", rc, ark_ddgi_last_error(ctx));
             }
             // the context follows this version only once it holds it (else: retried next frame)
-            if (rc == ARK_DDGI_OK) m_instanceVersion = scene.instanceVersion();
+            if (rc == ARK_DDGI_OK) {
+                m_instanceVersion = scene.instanceVersion();
+                m_vertexVersion = scene.vertexVersion();
+            }
         }
         if (m_exchange) {
             // Z-slab rank: traversal goes ahead, shading waits for the previous exchange;

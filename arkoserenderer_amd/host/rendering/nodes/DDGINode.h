@@ -88,6 +88,7 @@ private:
     bool m_raySeeds { true };
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
+    uint32_t m_vertexVersion { 0 };   // GpuScene::vertexVersion() its pools follow
     SlabExchange* m_exchange { nullptr };
     void* m_updateDone { nullptr };      // hipEvent_t recorded after each update
     void* m_exchangePending { nullptr }; // hipEvent_t of the last exchange

@@ -24,6 +24,9 @@
  *                           (GpuScene.cpp:790-858, pre-exposure from :792).
  *   ark_ddgi_set_instances(_async) <- the per-frame TLAS instance update + build
  *                           (GpuScene.cpp:872-1009), as a device refit.
+ *   ark_ddgi_update_geometry(_async) <- the skinned instances' per-frame vertex writes
+ *                           and BLAS updates (GpuScene.cpp:629-711, :934-992): ranges of
+ *                           the vertex pools replaced, and transforms, in the same refit.
  *   ark_ddgi_update      <- the DDGINode execute lambda (DDGINode.cpp:132-259):
  *                           traceRays -> irradiance update -> visibility update ->
  *                           border copies -> probe offsets.
@@ -418,6 +421,49 @@ int ark_ddgi_set_lights(ArkDdgiCtx* ctx, const ArkDdgiLights* lights);
  * when the scene is updated; ArkDdgiBvhStats.refit_ms is the call's host time. */
 int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count, void* hip_stream);
 int ark_ddgi_set_instances(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count);
+
+/* Deforming meshes (GpuScene.cpp:629-711, :934-992: skinned instances write their own
+ * range of the vertex pools every frame and their BLASes are updated): new contents for
+ * ranges of the scene's vertex pools and, optionally, new transforms, in one refit.
+ * `instances` NULL with count 0 keeps the transforms; otherwise ark_ddgi_set_instances'
+ * rules hold. Indices, meshes, materials, triangle counts and hit masks do not change.
+ * An instance whose RT mesh can reach a vertex of a range - [first_vertex, first_vertex +
+ * its largest index] of the mesh meets it; instances sharing a mesh and meshes with
+ * overlapping spans are all reached - has its triangle records re-derived by the refit
+ * and, when `vertices` is given, its shading records rewritten. After the call every
+ * later operation sees exactly what ark_ddgi_set_scene with the updated pools and
+ * transforms would build, bit for bit (hits never depend on the BVH's shape); operations
+ * enqueued before keep the old geometry.
+ * Sources are host arrays (copied before the call returns) or, with
+ * ARK_DDGI_VERTICES_DEVICE, HIP device pointers that are complete on `hip_stream` and stay
+ * untouched until the work enqueued by the call is done. Nobody has seen a device
+ * source's contents, so `bounds` (lo xyz, hi xyz, finite) is required with device
+ * positions: a position with a non-finite coordinate is dropped (the vertex keeps its
+ * old position) and one outside `bounds` is clamped into it, both counted
+ * (ark_ddgi_get_geometry_update_stats).
+ * ARK_DDGI_E_INVALID_ARGUMENT, nothing changed: a wrong struct_size, a range outside the
+ * pools, positions and vertices both NULL, a non-finite host position, missing or
+ * non-finite bounds with device positions.
+ * Stream order as ark_ddgi_set_instances_async; new `vertices` are written behind the
+ * frame in flight, so the next update's traversal does not overlap that frame. */
+#define ARK_DDGI_VERTICES_DEVICE 0x1u
+typedef struct ArkDdgiVertexUpdate {
+    uint32_t struct_size;        /* sizeof(ArkDdgiVertexUpdate) */
+    uint32_t first_vertex;       /* absolute index into the scene's vertex pools */
+    uint32_t vertex_count;
+    uint32_t flags;              /* ARK_DDGI_VERTICES_DEVICE: both pointers are HIP device pointers */
+    const float* positions;      /* vertex_count x 3, or NULL: unchanged */
+    const ArkRTVertex* vertices; /* vertex_count, or NULL: unchanged */
+    float bounds[6];             /* lo, hi of the new positions; required (and finite) with _DEVICE + positions */
+    int32_t reserved[2];
+} ArkDdgiVertexUpdate;
+int ark_ddgi_update_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t update_count, const ArkRTInstance* instances, uint32_t instance_count,
+                                   void* hip_stream);
+int ark_ddgi_update_geometry(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t update_count, const ArkRTInstance* instances, uint32_t instance_count);
+/* out[0] ark_ddgi_update_geometry calls of the context's scene so far, [1] vertices written,
+ * [2] device-source positions dropped as non-finite, [3] device-source positions clamped
+ * into bounds (waits for the calls' device work). */
+int ark_ddgi_get_geometry_update_stats(ArkDdgiCtx* ctx, uint64_t out[4]);
 
 /* One DDGI update (DDGINode.cpp:132-259) enqueued on `hip_stream` (NULL = the null
  * stream). Asynchronous: call ark_ddgi_synchronize or synchronize the stream before

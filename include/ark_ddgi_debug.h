@@ -225,6 +225,12 @@ int ark_ddgi_debug_sun_bvh_installed_check(struct ArkDdgiCtx* ctx, uint64_t* out
  * (and a BVH's two after a rebuild was installed, until the next refit). Synchronous. */
 int ark_ddgi_debug_refit_reach(struct ArkDdgiCtx* ctx, uint64_t* out);
 
+/* What ark_ddgi_update_geometry has allocated for the context's scene. out[4] = {allocations
+ * of the triangle -> record map, its fills (the first use, then one per installed world
+ * rebuild in between updates), device bytes held for the feature, update calls that wrote
+ * positions}: all 0 for a scene that never made such a call. No device work. */
+int ark_ddgi_debug_geometry_update_info(struct ArkDdgiCtx* ctx, uint64_t* out);
+
 /* The sun's cover map (csrc/sun_cover_map.h) built on the host (no GPU) from n triangles
  * (9 floats each) for sun_dir, and its verdicts for n_rays origins (3 floats each) against a
  * brute-force any-hit over every triangle with the kernels' fp32 Moller-Trumbore

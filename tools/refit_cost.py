@@ -13,6 +13,14 @@ move one instance (ark_ddgi_set_instances_async on the update's stream, no host 
 frames until the rebuilds of the final state (world BVHs and the light-space sun BVH)
 are installed, and the rate again: it should be back at the static rate.
 
+--deform: --continuous with vertices instead of transforms (ark_ddgi_update_geometry_async):
+the instance of the frame has its positions displaced by a sine of small amplitude (5 cm)
+and the one of the frame before gets its rest positions back - the same instances dirty
+as under --continuous, the same refit. The ranges carry the other vertex data too (as a
+skinned mesh's normals change), unless --positions-only; --device-source hands the ranges
+over as device tensors. The line also tells the vertices per call and the counts of
+ark_ddgi_get_geometry_update_stats. Run --continuous and --deform in turn to compare.
+
 --gpu-rebuild (with --continuous): ARK_DDGI_FLAG_GPU_REBUILD, the world BVHs rebuilt on the
 device while the instances move. The line then also tells the installs' builder, the
 device builds' time and footprint (nodes, records per triangle) as installed at the end
@@ -62,6 +70,9 @@ def main():
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--continuous", action="store_true", help="one instance moved every frame for --frames frames, then back to static")
     ap.add_argument("--frames", type=int, default=300)
+    ap.add_argument("--deform", action="store_true", help="--continuous, the moved instance's positions displaced by a sine instead of translated (update_geometry)")
+    ap.add_argument("--positions-only", action="store_true", help="with --deform: the ranges carry no other vertex data")
+    ap.add_argument("--device-source", action="store_true", help="with --deform: the ranges are device tensors")
     ap.add_argument("--no-background", action="store_true", help="ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: refits only (isolates the rebuild threads' cost)")
     ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
     ap.add_argument("--gpu-rebuild-sun", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SUN: the light-space sun BVH's background builds on the device")
@@ -69,6 +80,7 @@ def main():
     ap.add_argument("--gpu-rebuild-plan", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_PLAN: those builds collapse by the SAH-optimal plan")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
+    args.continuous = args.continuous or args.deform
     import torch
     from arkoserenderer_amd import ddgi as D
 
@@ -132,8 +144,47 @@ def main():
             stream = torch.cuda.current_stream()
             ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(args.frames)]
             host_refit = 0.0
+            final = sc
+            if args.deform:
+                # every instance's range of the pools, at rest and deformed (prepared ahead:
+                # the loop below times the calls, not numpy)
+                inst = inst0
+                poses = []
+                for i in range(n):
+                    mesh = sc.meshes[int(inst0["rt_mesh_index"][i])]
+                    fi = int(mesh["first_index"])
+                    first, cnt = int(mesh["first_vertex"]), int(sc.indices[fi:fi + 3 * int(inst0["triangle_count"][i])].max()) + 1
+                    p0 = np.ascontiguousarray(sc.positions[first:first + cnt], np.float32)
+                    p1 = (p0 + np.float32(0.05) * np.sin(np.float32(2.0) * p0[:, [1, 2, 0]])).astype(np.float32)
+                    vx = None if args.positions_only else np.ascontiguousarray(sc.vertices[first:first + cnt]).view(np.float32).reshape(-1, 9)
+                    lo, hi = np.minimum(p0.min(0), p1.min(0)), np.maximum(p0.max(0), p1.max(0))
+                    if args.device_source:
+                        p0, p1 = torch.from_numpy(p0).cuda(), torch.from_numpy(p1).cuda()
+                        vx = None if vx is None else torch.from_numpy(vx).cuda()
+                    poses.append((first, cnt, p0, p1, vx, np.concatenate([lo, hi])))
+                torch.cuda.synchronize()
+                last = (args.frames - 1) % n
+                P = sc.positions.copy()
+                P[poses[last][0]:poses[last][0] + poses[last][1]] = poses[last][3].cpu().numpy() if args.device_source else poses[last][3]
+                final = dataclasses.replace(sc, positions=P)
+                per_call = 0
             t = time.perf_counter()
             for f in range(args.frames):
+                if args.deform:
+                    first, cnt, p0, p1, vx, box = poses[f % n]
+                    ups = [D.VertexUpdate(first, p1, vx, bounds=box)]
+                    if f > 0 and n > 1:
+                        first, cnt, p0, p1, vx, box = poses[(f - 1) % n]
+                        ups.append(D.VertexUpdate(first, p0, vx, bounds=box))
+                    per_call = max(per_call, sum(u.vertex_count for u in ups))
+                    ev[f][0].record(stream)
+                    th = time.perf_counter()
+                    node.ctx.update_geometry_async(ups, None, sptr)
+                    host_refit += time.perf_counter() - th
+                    ev[f][1].record(stream)
+                    node.execute(app[0], sptr)
+                    app[0] = D.AppState(app[0].frame_index + 1)
+                    continue
                 inst = inst0.copy()
                 m = inst["object_to_world"].reshape(-1, 3, 4)
                 m[f % n, 0, 3] += np.float32(0.3 * np.sin(0.1 * f))  # one instance a frame, back and forth
@@ -173,7 +224,7 @@ def main():
             # a context built from scratch on the final transforms, measured interleaved
             # with the rebuilt one: what "back at the static rate" means for the moved scene
             fresh_node = D.DDGINode(cfg)
-            fresh_node.construct(dataclasses.replace(sc, instances=inst), grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
+            fresh_node.construct(dataclasses.replace(final, instances=inst), grid, zf, light_pre_exposure=1.0, ambient_illuminance=0.02, environment_brightness=1.0)
             fresh = []
             for _ in range(3):
                 fresh.append(round(rate(fresh_node), 1))
@@ -193,6 +244,9 @@ def main():
                 "mrays_per_s_static_before": static, "mrays_per_s_static_after": after,
                 "after_vs_before": round(max(after) / max(static), 4), "mrays_per_s_fresh_build": fresh,
                 "after_vs_fresh": round(sorted(after)[len(after) // 2] / sorted(fresh)[1], 4)}
+            if args.deform:
+                out["continuous"]["deform"] = {"vertices_per_call": int(per_call), "positions_only": bool(args.positions_only), "device_source": bool(args.device_source),
+                                               "stats": list(node.ctx.geometry_update_stats()), "info": node.ctx.geometry_update_info()}
             print(json.dumps(out), flush=True)
             node.ctx.close()
             continue
