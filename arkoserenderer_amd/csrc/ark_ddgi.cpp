@@ -765,7 +765,7 @@ int ark_ddgi_debug_geometry_update_info(ArkDdgiCtx* ctx, uint64_t* out)
     out[0] = st.recordMapAllocs;
     out[1] = st.recordMapFills;
     out[2] = st.recordMap.bytes + st.triBase.bytes + st.stageCounters.bytes;
-    out[3] = st.vtx.seq;
+    out[3] = st.book.vtx.seq;
     return ARK_DDGI_OK;
 }
 

@@ -9,7 +9,7 @@
 //   k_refit_nodes    one BVH8 level (deepest first), the nodes with a moved instance below
 //                    them: the moved instances' records of their leaf slots re-transformed
 //                    from the object-space pools in set_scene's fp32 operation order
-//                    (scene_store.cpp), each node's child boxes - leaf slots
+//                    (scene_build.cpp), each node's child boxes - leaf slots
 //                    from their triangle records, internal children from the level below
 //                    - inflated as the builder inflates them (bvh_builder.cpp inflateChildBox),
 //                    the node's quantization grid and outward-rounded child planes
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(128) k_refit_nodes(GpuBvh8Node* __restrict__ n
     // this one, whichever copy that wrote). Both are of the new transforms and this
     // inflation because the host's dirty set (RefitBoxArgs.dirty) holds every instance whose
     // transform differs from this copy's or from the refit before's, and is all ones when
-    // the inflation differs from this copy's or from the scratch's (scene_store.cpp)
+    // the inflation differs from this copy's or from the scratch's (scene_refit.cpp)
     const bool live = i < count && (masks[n0] & ra.dirty) != 0; // a node's eight lanes alike
     if (!__any(live)) return;
     const uint32_t n = live ? n0 : 0u;
@@ -339,7 +339,7 @@ __global__ void __launch_bounds__(256) k_record_map(const GpuTriangle* __restric
 
 // The shading records (SceneStore::triNormals, 64 B: three vertex normals, the instance,
 // three UVs) of the triangles of the instances a vertex update touched, rewritten from the
-// vertex pool by set_scene's rule (scene_store.cpp shadingRecords), one thread per
+// vertex pool by set_scene's rule (scene_build.cpp shadingRecords), one thread per
 // (instance, primitive): blockIdx.y picks the instance of this launch's block of jobs.
 __global__ void __launch_bounds__(256) k_update_surface_records(SurfaceJobs jobs, const uint32_t* __restrict__ map, uint32_t records, const uint32_t* __restrict__ indices,
                                                                 const float* __restrict__ vertices, float4* __restrict__ triNormals)

@@ -48,7 +48,7 @@ struct DeviceBvh {
     // copies: after every refit boxes[n] is the box of the latest transforms of the
     // instances below n at the inflation boxesInflate, whichever copy that refit wrote (a
     // refit's dirty set holds every instance that changed since the refit before it, and
-    // a refit at another inflation reaches every node: scene_store.cpp)
+    // a refit at another inflation reaches every node: scene_refit.cpp)
     DeviceBuffer order, boxes, masks;
     std::vector<uint32_t> levelOffsets;
     bool masksValid = false;

@@ -1,6 +1,6 @@
 // lbvh_device_build.h — the device build of a BVH8 set from a snapshot of triangle records
 // (ddgi_bvh_build.hip's kernels, rocPRIM's sort and the refit pass, driven from the host):
-// the rebuild jobs' device variant (scene_store.cpp: runRebuildJob) and the traced parity
+// the rebuild jobs' device variant (scene_rebuild.cpp: runRebuildJob) and the traced parity
 // entry (ark_ddgi_debug_lbvh_device_parity, lbvh_device_build.cpp). Knows no SceneStore.
 #pragma once
 

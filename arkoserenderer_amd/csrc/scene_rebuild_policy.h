@@ -76,7 +76,7 @@ inline RebuildStart rebuildToStart(const RebuildState& q)
     return RebuildStart::None;
 }
 
-// How a rebuild job goes on after its device build (scene_store.cpp: runRebuildJob): the
+// How a rebuild job goes on after its device build (scene_rebuild.cpp: runRebuildJob): the
 // result is Installed as built; the job has Failed (the device is not used again by it);
 // or the HostBuild builds this scene from the same snapshot, within the job.
 enum class DeviceBuildOutcome { Installed, HostBuild, Failed };

@@ -25,10 +25,10 @@
 #include <vector>
 
 #include "../../include/ark_ddgi.h"
+#include "copy_book.h"
 #include "ddgi_kernels.h"
 #include "device_bvh.h"
 #include "scene_rebuild_policy.h"
-#include "vertex_dirty.h"
 
 namespace ark {
 
@@ -58,13 +58,56 @@ struct ErrorSink {
         if (_e != hipSuccess) return (sink)->hipFail(_e, #expr);        \
     } while (0)
 
-struct RebuildJob; // a background rebuild (scene_store.cpp)
+struct RebuildJob; // a background rebuild (scene_store_internal.h)
 
 // A buffer replaced while launches enqueued before may still read it: freed once `done`
 // (recorded behind them) has completed.
 struct Retired {
     DeviceBuffer buf;
     hipEvent_t done = nullptr;
+};
+
+// Pinned host staging for stream-ordered uploads, a ring of N buffers made at first use:
+// acquire hands out the next one, free for the host to fill (its last reader, a few calls
+// back, has run) and grown to `need`; release records its reader's end on the reader's stream.
+template<int N>
+struct PinnedRing {
+    void* slot[N] {};
+    size_t bytes[N] {};
+    hipEvent_t done[N] {};
+    int next = 0;
+    hipError_t acquire(size_t need, int& i)
+    {
+        i = next;
+        next = (i + 1) % N;
+        hipError_t e = hipSuccess;
+        if (!done[i] && (e = hipEventCreateWithFlags(&done[i], hipEventDisableTiming)) != hipSuccess) return e;
+        if (bytes[i]) (void)hipEventSynchronize(done[i]); // its last copy (an earlier frame's) has run
+        if (bytes[i] < need) {
+            if (slot[i]) (void)hipHostFree(slot[i]);
+            slot[i] = nullptr;
+            bytes[i] = 0;
+            if ((e = hipHostMalloc(&slot[i], need, hipHostMallocDefault)) != hipSuccess) return e;
+            bytes[i] = need;
+        }
+        return hipSuccess;
+    }
+    hipError_t release(int i, hipStream_t s) { return hipEventRecord(done[i], s); }
+    void destroy()
+    {
+        for (int i = 0; i < N; ++i) {
+            if (slot[i]) (void)hipHostFree(slot[i]);
+            if (done[i]) (void)hipEventDestroy(done[i]);
+        }
+    }
+};
+
+// A spare geometry copy on the device (the front one's buffers are DeviceBvh::buf and
+// SceneStore::instances): both BVHs, the instance table, the event that ends with its last readers.
+struct GeometryCopy {
+    DeviceBuffer world, sun, instances;
+    hipEvent_t free = nullptr;
+    bool freeValid = false;
 };
 
 // The scene of a context on the device (ark_ddgi_set_scene): BVH nodes + triangles,
@@ -111,55 +154,28 @@ struct SceneStore {
     uint32_t version = 0;
     DeviceBuffer refitInst;
     double sunFrameD[9] {};
-    // the refit's transforms: the last ones uploaded (dirty = changed since the target
-    // copy's records were written, or since the refit before); pinned staging of the stream-ordered uploads, two sets in turn
+    // the refit's transforms as uploaded last (refitInflations reads them; which are dirty: book)
     std::vector<RefitInstance> refitHost;
     // pinned staging of the per-frame uploads, a ring: a slot is reused once its copy (a
     // few calls back) has run, so the host runs up to kStageSlots / 2 frames of
     // set_instances_async ahead of the device (two slots: one frame, and every call
     // waited for the previous frame's refit)
     static constexpr int kStageSlots = 8;
-    void* stage[kStageSlots] {};
-    size_t stageBytes[kStageSlots] {};
-    hipEvent_t stageDone[kStageSlots] {};
-    int stageNext = 0;
+    PinnedRing<kStageSlots> stage;
     // ark_ddgi_update_geometry's host vertex ranges have a ring of their own (allocated at
     // the first such call), so that a deform call takes the two slots above that a rigid one
     // takes and the host runs as far ahead; a call's ranges take one slot per pool here, the
     // vertex data's released only behind the frame in flight, so the large ranges run two
     // calls ahead and at most kVertexStageSlots buffers of the largest call stay pinned
     static constexpr int kVertexStageSlots = 4;
-    void* vstage[kVertexStageSlots] {};
-    size_t vstageBytes[kVertexStageSlots] {};
-    hipEvent_t vstageDone[kVertexStageSlots] {};
-    int vstageNext = 0;
+    PinnedRing<kVertexStageSlots> vstage;
     // object-space bounds of every instance's triangles (set_scene): the refit's world and
     // light-space bounds, for its box inflation, from the instances' transforms on the host
     std::vector<std::array<float, 6>> instObjBox;
-    // The geometry a refit writes comes in three copies: the front one (world.buf, sun.buf,
-    // instances above: what the kernels read) and two spares. A refit brings the next
-    // spare from the transforms it holds (xf[slot]) to the new ones on the store's
-    // refit stream and makes it the front one: it waits only for the operations that read
-    // that copy while it was the front one, two refits before (the frame before last),
-    // so that it runs beside the frame in flight's traversal and the next traversal does
-    // not wait for it (with two copies it waited for the previous frame's shading, and
-    // the frames ran one after the other: C4 4.3 ms per moving frame, static 3.3). An
-    // install (a new topology) drops the spares; the next refit copies the front one.
-    struct Spare {
-        DeviceBuffer world, sun, instances;
-        bool valid = false;
-        int slot = 0;
-    };
-    Spare spare[2]; // spare[0]: the next refit's target
-    // the inflations each copy's boxes hold ([slot][0 world, 1 sun]; 0: set_scene's own,
-    // so the first refit of that copy reaches every node); refitFull: the next refit reaches
-    // every node (a new topology, or boxes scratch not of this one). The boxes scratch
-    // (DeviceBvh::boxes) is one for the three copies: after every refit it holds, for every
-    // node, the box of the latest transforms at DeviceBvh::boxesInflate
-    bool refitFull = true;
-    float inflCopy[3][2] {};
-    int front = 0; // slot of the front copy (xf index)
-    std::vector<std::array<float, 12>> xf[3];
+    // The three geometry copies: the front one (world.buf, sun.buf, instances, frontFree) and
+    // the spares, spare[0] the next refit's target. What each holds: the book (copy_book.h).
+    GeometryCopy spare[2];
+    CopyBook book;
     // the light-space BVH follows the sun: set_scene chose it (sunWanted), and after a
     // sun-direction change it is rebuilt in the background (sceneSunStep)
     bool sunWanted = false;
@@ -194,15 +210,16 @@ struct SceneStore {
     // The order of the writes to the three geometry copies, owned with them (the contexts
     // sharing the store see one record of who read which copy): refits run on refitStream,
     // at the device's highest priority (its per-level launches are dispatched ahead of the
-    // frame in flight's work when both wait for a CU). evFree[slot] ends with the operations
-    // that read that slot's copy while it was the front one (recorded when a refit swapped
-    // it out, on the refitting call's stream, which follows the others); evInstalled with
-    // the last install (a rebuild installed on a caller's stream writes the front copy).
+    // frame in flight's work when both wait for a CU). A copy's `free` event (frontFree: the
+    // front one's; they rotate with the buffers) ends with the operations that read it
+    // while it was the front one (recorded when a refit swapped it out, on the refitting
+    // call's stream, which follows the others); evInstalled with the last install (a
+    // rebuild installed on a caller's stream writes the front copy).
     // evGeometry ends with the last refit or install, geometrySeq counts its recordings: a
     // context's next traversal waits for it when the count has moved since its last wait.
     hipStream_t refitStream = nullptr;
-    hipEvent_t evFree[3] = {};
-    bool freeValid[3] = { false, false, false };
+    hipEvent_t frontFree = nullptr;
+    bool frontFreeValid = false;
     hipEvent_t evInstalled = nullptr;
     bool installValid = false;
     hipEvent_t evGeometry = nullptr;
@@ -213,12 +230,10 @@ struct SceneStore {
     // updateImpl, behind its wait for evGeometry and ahead of the traversal)
     uint32_t worldTopologySeq = 0;
     // Deforming meshes (ark_ddgi_update_geometry; DESIGN §1 "Deforming meshes"). The pools'
-    // vertex count and every RT mesh's vertex span (set_scene); the instances' vertex
-    // versions against the three copies (vertex_dirty.h). Everything below is allocated at
-    // the first update call: a scene that never makes one holds none of it.
+    // vertex count and every RT mesh's vertex span (set_scene). Everything below is
+    // allocated at the first update call: a scene that never makes one holds none of it.
     uint64_t vertexCount = 0;
     std::vector<MeshSpan> meshSpans;
-    VertexVersions vtx;
     // global triangle -> world record index (k_record_map; triBase: the instances' first
     // global triangles, on the host and the device), filled at the first update that
     // rewrites shading records and again after each installed world rebuild (recordMapSeq

@@ -24,7 +24,7 @@ void sun_ray_dir(const float sun_dir[3], float L[3]);
 void sun_frame(const float sun_dir[3], double frame[3][3]);
 void sun_add_triangles(SunBvhInput& in, const std::vector<BuildTriangle>& world_tris, int threads = 0);
 // The same from world-space triangle records as the world BVHs hold them (holes skipped):
-// the background rebuild after a sun-direction change or a refit (scene_store.cpp hostBuildSun)
+// the background rebuild after a sun-direction change or a refit (scene_rebuild.cpp hostBuildSun)
 void sun_add_records(SunBvhInput& in, const std::vector<GpuTriangle>& records, int threads = 0);
 // Builds the BVH2 (opt; its inflation replaced by the light-space bound), the BVH8
 // (copt, slots sorted by w) and swaps in the world records; consumes in.tris and

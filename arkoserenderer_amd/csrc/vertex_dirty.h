@@ -1,5 +1,5 @@
 // vertex_dirty.h — which instances a vertex range update touches and which of them a refit
-// must re-derive (ark_ddgi_update_geometry, scene_store.cpp). Pure host code without a HIP
+// must re-derive (ark_ddgi_update_geometry, scene_refit.cpp). Pure host code without a HIP
 // dependency, so that it is tested on its own (tests/cpp/vertex_dirty_test.cpp).
 #pragma once
 
@@ -53,8 +53,8 @@ inline void touchedInstances(const std::vector<MeshSpan>& spans, const std::vect
     }
 }
 
-// The vertex versions of a scene's instances against its three geometry copies (DESIGN §1
-// "Deforming meshes"). seq counts the update calls that touched an instance; inst[i] is the
+// The vertex versions of a scene's instances against its three geometry copies (a member
+// of their book, copy_book.h; DESIGN §1 "Deforming meshes"). seq counts the update calls that touched an instance; inst[i] is the
 // call that touched instance i last; copy[slot] the call up to which the slot's records
 // were re-derived; scratch the call up to which the shared boxes scratch was (the refit
 // before, whichever copy it wrote).
