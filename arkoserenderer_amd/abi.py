@@ -167,6 +167,58 @@ class ArkDdgiVertexUpdate(C.Structure):
     ]
 
 
+class ArkSkinningVertex(C.Structure):
+    """SkinningVertex (SceneData.h:33-36), 32 B."""
+
+    _fields_ = [("joint_indices", C.c_uint32 * 4), ("joint_weights", C.c_float * 4)]
+
+
+class ArkMorphTargetVertex(C.Structure):
+    """MorphTargetVertex (SceneData.h:38-42), scalar layout, 36 B."""
+
+    _fields_ = [("position", C.c_float * 3), ("normal", C.c_float * 3), ("tangent", C.c_float * 3)]
+
+
+class ArkDdgiSkinDesc(C.Structure):
+    """A skin for ark_ddgi_register_skin (72 B)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("first_vertex", C.c_uint32),
+        ("vertex_count", C.c_uint32),
+        ("joint_count", C.c_uint32),
+        ("morph_target_count", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("positions", C.c_void_p),
+        ("vertices", C.c_void_p),
+        ("skinning", C.c_void_p),
+        ("morph_targets", C.c_void_p),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+class ArkDdgiSkinPose(C.Structure):
+    """One skin's pose for ark_ddgi_skin_geometry (32 B)."""
+
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("skin", C.c_uint32),
+        ("joint_matrices", C.c_void_p),
+        ("morph_weights", C.c_void_p),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+class ArkDdgiSkinViews(C.Structure):
+    _fields_ = [
+        ("positions", C.c_void_p),
+        ("vertices", C.c_void_p),
+        ("velocities", C.c_void_p),
+        ("vertex_count", C.c_uint32),
+        ("runs", C.c_uint32),
+    ]
+
+
 class ArkDirectionalLight(C.Structure):
     _fields_ = [("color", C.c_float * 3), ("world_space_direction", C.c_float * 3)]
 
@@ -474,7 +526,7 @@ ABI_STRUCTS = [
     ArkDdgiDesc, ArkRTVertex, ArkRTTriangleMesh, ArkShaderMaterial, ArkTexture, ArkRTInstance,
     ArkDirectionalLight, ArkSpotLight, ArkDdgiScene, ArkDdgiFrameParams, ArkDdgiCounters,
     ArkDdgiDeviceViews, ArkDdgiBvhStats, ArkBakeAoDesc, ArkComposeDesc, ArkProbeDebugDesc, ArkReflectionsDesc,
-    ArkDdgiVertexUpdate,
+    ArkDdgiVertexUpdate, ArkSkinningVertex, ArkMorphTargetVertex, ArkDdgiSkinDesc, ArkDdgiSkinPose, ArkDdgiSkinViews,
 ]
 
 # name -> (restype, argtypes)
@@ -491,6 +543,12 @@ EXPORTS = {
     "ark_ddgi_update_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
     "ark_ddgi_update_geometry_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
     "ark_ddgi_get_geometry_update_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_register_skin": (C.c_int, [C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ark_ddgi_unregister_skin": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ark_ddgi_skin_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32]),
+    "ark_ddgi_skin_geometry_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_uint32, C.c_void_p]),
+    "ark_ddgi_get_skin_views": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ArkDdgiSkinViews)]),
+    "ark_ddgi_get_skin_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_mark_external_write": (C.c_int, [C.c_void_p]),
     "ark_ddgi_get_next_probe_index": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
     "ark_ddgi_update": (C.c_int, [C.c_void_p, C.POINTER(ArkDdgiFrameParams), C.c_void_p]),
@@ -557,6 +615,9 @@ EXPORTS = {
     "ark_ddgi_debug_sun_bvh_installed_check": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_refit_reach": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_geometry_update_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_refit_inflation": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
+    "ark_ddgi_debug_skin_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ark_ddgi_debug_skin_device_parity": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_check": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_uint64, C.c_float, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_cover_map_device": (C.c_int, [C.c_int, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_sun_cover_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),

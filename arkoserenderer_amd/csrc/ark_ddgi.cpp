@@ -748,6 +748,67 @@ int ark_ddgi_update_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* u
     return ARK_DDGI_OK;
 }
 
+int ark_ddgi_register_skin(ArkDdgiCtx* ctx, const ArkDdgiSkinDesc* desc, uint32_t* outSkin)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_register_skin before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    return sceneRegisterSkin(*ctx->sceneStore, ctx, desc, outSkin);
+}
+
+int ark_ddgi_unregister_skin(ArkDdgiCtx* ctx, uint32_t skin)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_unregister_skin before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    return sceneUnregisterSkin(*ctx->sceneStore, ctx, skin);
+}
+
+int ark_ddgi_skin_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t poseCount, const ArkRTInstance* instances, uint32_t count, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_skin_geometry before ark_ddgi_set_scene");
+    SceneStore& st = *ctx->sceneStore;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    if (const int r = checkSequencing(ctx)) return r;
+    ARK_HIP(orderBegin(ctx, s));
+    // the skins' runs on `s`, then update_geometry's refit with their outputs as device sources
+    if (const int rc = sceneSkinGeometry(st, sceneCall(ctx), poses, poseCount, instances, count, s)) return rc;
+    if (ctx->sceneVersion != st.version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    ARK_HIP(orderEnd(ctx, s));
+    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_skin_geometry(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t poseCount, const ArkRTInstance* instances, uint32_t count)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = ark_ddgi_skin_geometry_async(ctx, poses, poseCount, instances, count, ctx->stream)) return rc;
+    ARK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ctx->bvhStats = ctx->sceneStore->bvhStats;
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_get_skin_views(ArkDdgiCtx* ctx, uint32_t skin, ArkDdgiSkinViews* out)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_get_skin_views before ark_ddgi_set_scene");
+    return sceneSkinViews(*ctx->sceneStore, ctx, skin, out);
+}
+
+int ark_ddgi_get_skin_stats(ArkDdgiCtx* ctx, uint64_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    std::fill(out, out + 4, uint64_t(0));
+    if (ctx->hasScene) sceneSkinStats(*ctx->sceneStore, out);
+    return ARK_DDGI_OK;
+}
+
 int ark_ddgi_get_geometry_update_stats(ArkDdgiCtx* ctx, uint64_t* out)
 {
     if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
@@ -803,6 +864,15 @@ int ark_ddgi_debug_refit_reach(ArkDdgiCtx* ctx, uint64_t* out)
     ARK_HIP(hipSetDevice(ctx->device));
     ARK_HIP(hipDeviceSynchronize());
     return sceneRefitReach(*ctx->sceneStore, ctx, out);
+}
+
+int ark_ddgi_debug_refit_inflation(ArkDdgiCtx* ctx, float* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "refit inflation before ark_ddgi_set_scene");
+    out[0] = ctx->sceneStore->world.boxesInflate;
+    out[1] = ctx->sceneStore->sun.boxesInflate;
+    return ARK_DDGI_OK;
 }
 
 static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement);

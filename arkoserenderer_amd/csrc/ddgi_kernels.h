@@ -349,6 +349,25 @@ struct SurfaceJobs {
 };
 hipError_t launch_update_surface_records(const SurfaceJobs& jobs, uint32_t jobCount, const uint32_t* map, uint32_t records, const uint32_t* indices, const float* vertices,
                                          float4* triNormals, hipStream_t s);
+// ark_ddgi_skin_geometry (k_skin_vertices, ddgi_skinning.hip): one run of a skin, every
+// pointer a device pointer. skinning: two 16-B words per vertex (four joint indices, four
+// weights; 16-B aligned), or null: morph-only. joints: 12 floats each (skinning.h; 16-B
+// aligned); every index < jointCount (checked at registration). prev: the previous run's
+// positions, or null: the first run. The outputs may start at any word.
+struct SkinArgs {
+    const float* bindPositions;  // 3 n
+    const float* bindVertices;   // 9 n
+    const float* morph;          // 9 K n
+    const uint4* skinning;       // 2 n
+    const float* joints;         // 12 jointCount
+    const float* morphWeights;   // K
+    const float* prev;           // 3 n
+    float* outPositions;         // 3 n
+    float* outVertices;          // 9 n
+    float* outVelocities;        // 3 n
+    uint32_t vertexCount, morphCount, jointCount;
+};
+hipError_t launch_skin_vertices(const SkinArgs& a, hipStream_t s);
 
 // The world BVH8s' topology built on the device (ddgi_bvh_build.hip, lbvh_build.h)
 // what k_lbvh_prims counts and reduces; lo / hi: the scene box in ordered bits

@@ -176,6 +176,9 @@ struct VertexWrites {
     uint32_t count = 0;
     std::vector<uint8_t> touchedPositions, touchedVertices; // per instance
     bool anyPositions = false, anyVertices = false, devicePositions = false;
+    // per update, or null: a device source whose bounds are known to hold every position it
+    // will write, all of them finite (a skin's: sceneSkinGeometry) - nothing is dropped
+    const uint8_t* trusted = nullptr;
 };
 
 // Every reason to refuse a call's vertex ranges, before anything changes
@@ -250,7 +253,9 @@ void renewObjectBoxes(SceneStore& st, const VertexWrites& vw)
             }
             // (a device source never replaces: a position the kernel drops as non-finite keeps
             // its old value, which the old box holds and `bounds` need not)
-            const bool whole = !(q.flags & ARK_DDGI_VERTICES_DEVICE) && spanCovered(sp, q.first_vertex, q.vertex_count);
+            // (a trusted one does: without it a walking character's box, and the refit's
+            // inflation step with it, would grow for ever)
+            const bool whole = (!(q.flags & ARK_DDGI_VERTICES_DEVICE) || (vw.trusted && vw.trusted[u])) && spanCovered(sp, q.first_vertex, q.vertex_count);
             for (size_t i = 0; i < st.instHost.size(); ++i) {
                 if (st.instHost[i].rt_mesh_index != m || !st.instHost[i].triangle_count) continue;
                 std::array<float, 6>& b = st.instObjBox[i];
@@ -536,6 +541,12 @@ int sceneSetInstances(SceneStore& st, const SceneCall& c, const ArkRTInstance* i
 int sceneUpdateGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count,
                         hipStream_t s)
 {
+    return sceneProducedGeometry(st, c, updates, updateCount, instances, count, s, nullptr, nullptr);
+}
+
+int sceneProducedGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count,
+                          hipStream_t s, const uint8_t* trusted, const std::function<int()>* produce)
+{
     // (a copy: the refit ends by writing the new transforms into instHost)
     const std::vector<ArkRTInstance> kept = (!instances && !count) ? st.instHost : std::vector<ArkRTInstance>();
     if (!instances && !count) {
@@ -546,6 +557,9 @@ int sceneUpdateGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexU
     if ((rc = validateInstances(c.err, st, instances, count)) != 0) return rc;
     VertexWrites vw;
     if ((rc = validateVertexUpdates(c.err, st, updates, updateCount, vw)) != 0) return rc;
+    vw.trusted = trusted;
+    // (nothing was enqueued for a refused call)
+    if (produce && (rc = (*produce)()) != 0) return rc;
     if ((rc = refitScene(st, c, instances, count, s, &vw)) != 0) return rc;
     // (the calls that went through: a refused or failed one counts nothing)
     ++st.geometryCalls;

@@ -152,6 +152,7 @@ SceneStore::~SceneStore()
     }
     stage.destroy();
     vstage.destroy();
+    destroySkinSet(skins);
     for (hipEvent_t ev : { frontFree, spare[0].free, spare[1].free, evInstalled, evGeometry, evPositionsRead })
         if (ev) (void)hipEventDestroy(ev);
     if (refitStream) (void)hipStreamDestroy(refitStream);

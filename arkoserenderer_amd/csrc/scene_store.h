@@ -248,6 +248,9 @@ struct SceneStore {
     // (the AO bake): the next staging of positions, on the refit stream, waits for it
     hipEvent_t evPositionsRead = nullptr;
     bool positionsReadValid = false, positionsStaged = false;
+    // Skins (ark_ddgi_register_skin; DESIGN §1 "Skinning"; scene_skin.cpp): made by the first
+    // registration, so a scene without a skin allocates and launches nothing for them
+    struct SkinSet* skins = nullptr;
     SceneStore();
     SceneStore(const SceneStore&) = delete;
     SceneStore& operator=(const SceneStore&) = delete;
@@ -294,6 +297,17 @@ int sceneUpdateGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexU
 int sceneGeometryStats(SceneStore& st, ErrorSink* err, uint64_t* out);
 // An operation on `s` read the positions pool (the AO bake): the next vertex update follows it
 hipError_t scenePositionsRead(SceneStore& st, hipStream_t s);
+
+// ark_ddgi_register_skin / _unregister_skin (synchronous; unregistering waits for the device)
+int sceneRegisterSkin(SceneStore& st, ErrorSink* err, const ArkDdgiSkinDesc* desc, uint32_t* outSkin);
+int sceneUnregisterSkin(SceneStore& st, ErrorSink* err, uint32_t skin);
+// ark_ddgi_skin_geometry_async: every pose's skin computed on `s` into the skin's own
+// buffers (k_skin_vertices), which sceneUpdateGeometry's path then takes as device sources
+// with the poses' host bounds - one refit for all of them and the transforms.
+int sceneSkinGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiSkinPose* poses, uint32_t poseCount, const ArkRTInstance* instances, uint32_t count, hipStream_t s);
+int sceneSkinViews(const SceneStore& st, ErrorSink* err, uint32_t skin, ArkDdgiSkinViews* out);
+void sceneSkinStats(const SceneStore& st, uint64_t* out);
+void destroySkinSet(struct SkinSet* set); // ~SceneStore (the device is idle)
 
 // ark_ddgi_debug_scene_digest / _world_bvh_check over the front copy (the device is idle)
 int sceneDigest(const SceneStore& st, ErrorSink* err, uint64_t* out);

@@ -4,6 +4,7 @@
 
 #include <algorithm>
 #include <atomic>
+#include <functional>
 #include <thread>
 
 #include "bvh_builder.h"
@@ -100,5 +101,10 @@ int startRebuild(SceneStore& st, const SceneCall& c, hipStream_t s, bool sunOnly
 // scene_refit.cpp
 int uploadRefitInstances(ErrorSink* err, SceneStore& st, const ArkRTInstance* instances, uint32_t count, CopyBook::Refit which, hipStream_t s);
 int enqueueRefit(ErrorSink* err, SceneStore& st, hipStream_t s, const DeviceBuffer& world, const DeviceBuffer& sun, int slot);
+// sceneUpdateGeometry for device sources that the call itself produces (scene_skin.cpp):
+// `produce` enqueues their producers on `s` once every argument has been accepted, ahead of
+// the refit; trusted[u]: update u's bounds hold every position its source will contain.
+int sceneProducedGeometry(SceneStore& st, const SceneCall& c, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count,
+                          hipStream_t s, const uint8_t* trusted, const std::function<int()>* produce);
 
 } // namespace ark

@@ -164,6 +164,103 @@ class VertexUpdate:
         return u
 
 
+class Skin:
+    """A skin for DDGIContext.register_skin: a range of the scene's vertex pools starting at
+    `first_vertex` with its bind pose. positions n x 3 and vertices n x 9 float32 (or the
+    scene's vertex dtype); joint_indices n x 4 uint32 with joint_weights n x 4 float32, or
+    both None: morph-only; morph_targets K x n x 9 float32 (position, normal, tangent
+    deltas), or None. The object keeps the arrays alive."""
+
+    def __init__(self, first_vertex: int, positions, vertices, joint_indices=None, joint_weights=None, joint_count: int = 0, morph_targets=None):
+        f32 = lambda a, w: np.ascontiguousarray(np.asarray(a).view(np.float32) if np.asarray(a).dtype.itemsize == 4 * w and np.asarray(a).dtype != np.float32  # noqa: E731
+                                                 else np.asarray(a, dtype=np.float32)).reshape(-1, w)
+        self.first_vertex = int(first_vertex)
+        self.positions = f32(positions, 3)
+        self.vertices = f32(vertices, 9)
+        n = self.positions.shape[0]
+        if self.vertices.shape[0] != n:
+            raise ValueError("Skin: positions and vertices differ in count")
+        self.vertex_count = n
+        self.skinning = None
+        self.joint_count = 0
+        if (joint_indices is None) != (joint_weights is None):
+            raise ValueError("Skin: joint_indices and joint_weights go together")
+        if joint_indices is not None:
+            sk = np.zeros(n, dtype=np.dtype([("joint_indices", np.uint32, 4), ("joint_weights", np.float32, 4)]))
+            sk["joint_indices"] = np.asarray(joint_indices, dtype=np.uint32).reshape(n, 4)
+            sk["joint_weights"] = np.asarray(joint_weights, dtype=np.float32).reshape(n, 4)
+            self.skinning = sk
+            self.joint_count = int(joint_count)
+        self.morph_targets = None
+        self.morph_target_count = 0
+        if morph_targets is not None and np.asarray(morph_targets).size:
+            m = np.ascontiguousarray(np.asarray(morph_targets, dtype=np.float32)).reshape(-1, n, 9)
+            self.morph_targets = m
+            self.morph_target_count = m.shape[0]
+
+    def to_abi(self) -> abi.ArkDdgiSkinDesc:
+        d = abi.ArkDdgiSkinDesc()
+        d.struct_size = C.sizeof(abi.ArkDdgiSkinDesc)
+        d.first_vertex = self.first_vertex
+        d.vertex_count = self.vertex_count
+        d.joint_count = self.joint_count
+        d.morph_target_count = self.morph_target_count
+        d.positions = self.positions.ctypes.data
+        d.vertices = self.vertices.ctypes.data
+        d.skinning = self.skinning.ctypes.data if self.skinning is not None else None
+        d.morph_targets = self.morph_targets.ctypes.data if self.morph_targets is not None else None
+        return d
+
+
+class SkinPose:
+    """One skin's pose for DDGIContext.skin_geometry: `skin` the handle register_skin
+    returned, joint_matrices joint_count x 4 x 4 float32 with each matrix column-major (the
+    reference's appliedJointMatrices: element [j, c, r] is row r of column c; from row-major
+    numpy matrices M pass M.transpose(0, 2, 1)), or None for a morph-only skin;
+    morph_weights K float32, or None."""
+
+    def __init__(self, skin: int, joint_matrices=None, morph_weights=None):
+        self.skin = int(skin)
+        self.joint_matrices = None if joint_matrices is None else np.ascontiguousarray(np.asarray(joint_matrices, dtype=np.float32)).reshape(-1, 16)
+        self.morph_weights = None if morph_weights is None else np.ascontiguousarray(np.asarray(morph_weights, dtype=np.float32)).reshape(-1)
+
+    def to_abi(self) -> abi.ArkDdgiSkinPose:
+        p = abi.ArkDdgiSkinPose()
+        p.struct_size = C.sizeof(abi.ArkDdgiSkinPose)
+        p.skin = self.skin
+        p.joint_matrices = self.joint_matrices.ctypes.data if self.joint_matrices is not None else None
+        p.morph_weights = self.morph_weights.ctypes.data if self.morph_weights is not None and self.morph_weights.size else None
+        return p
+
+
+def skin_host(skin: Skin, pose: SkinPose, prev_positions=None, lib=None):
+    """ark_ddgi_debug_skin_host: the skinning pass restated on the host (no GPU). Returns
+    (positions n x 3, vertices n x 9, velocities n x 3, bounds 6); raises ArkDdgiError for a
+    skin or a pose that registration or skin_geometry would refuse."""
+    lib = lib or abi.load_library()
+    n = skin.vertex_count
+    d, p = skin.to_abi(), pose.to_abi()
+    prev = None if prev_positions is None else np.ascontiguousarray(np.asarray(prev_positions, dtype=np.float32)).reshape(n, 3)
+    pos, vert, vel, bounds = np.zeros((n, 3), np.float32), np.zeros((n, 9), np.float32), np.zeros((n, 3), np.float32), np.zeros(6, np.float32)
+    rc = lib.ark_ddgi_debug_skin_host(C.byref(d), C.byref(p), prev.ctypes.data if prev is not None else None, pos.ctypes.data, vert.ctypes.data, vel.ctypes.data,
+                                      bounds.ctypes.data)
+    if rc != 0:
+        raise abi.ArkDdgiError(rc, "ark_ddgi_debug_skin_host")
+    return pos, vert, vel, bounds
+
+
+def skin_device_parity(skin: Skin, pose: SkinPose, prev_positions=None, dst_first_vertex: int = 0, device: int = 0, lib=None) -> dict:
+    """ark_ddgi_debug_skin_device_parity: k_skin_vertices against the host restatement by bits."""
+    lib = lib or abi.load_library()
+    d, p = skin.to_abi(), pose.to_abi()
+    prev = None if prev_positions is None else np.ascontiguousarray(np.asarray(prev_positions, dtype=np.float32)).reshape(skin.vertex_count, 3)
+    out = (C.c_uint64 * 5)()
+    rc = lib.ark_ddgi_debug_skin_device_parity(int(device), C.byref(d), C.byref(p), prev.ctypes.data if prev is not None else None, int(dst_first_vertex), out)
+    if rc != 0:
+        raise abi.ArkDdgiError(rc, "ark_ddgi_debug_skin_device_parity")
+    return dict(zip(("positions", "vertices", "velocities", "outside", "kernel_ns"), (int(v) for v in out)))
+
+
 def _check(lib, ctx, rc, what):
     if rc != 0:
         msg = lib.ark_ddgi_last_error(ctx)
@@ -287,6 +384,49 @@ class DDGIContext:
         out = (C.c_uint64 * 4)()
         self.check(self.lib.ark_ddgi_get_geometry_update_stats(self.h, out), "ark_ddgi_get_geometry_update_stats")
         return tuple(int(v) for v in out)
+
+    def register_skin(self, skin: "Skin") -> int:
+        """ark_ddgi_register_skin: the skin's arrays copied to the device; returns its handle.
+        Valid after set_scene; a new set_scene drops every skin."""
+        d = skin.to_abi()
+        h = C.c_uint32()
+        self.check(self.lib.ark_ddgi_register_skin(self.h, C.byref(d), C.byref(h)), "ark_ddgi_register_skin")
+        return int(h.value)
+
+    def unregister_skin(self, skin: int):
+        self.check(self.lib.ark_ddgi_unregister_skin(self.h, int(skin)), "ark_ddgi_unregister_skin")
+
+    def _skin_args(self, poses, instances):
+        ps = list(poses)
+        arr = (abi.ArkDdgiSkinPose * max(1, len(ps)))(*[p.to_abi() for p in ps])
+        inst = None if instances is None else np.ascontiguousarray(instances)
+        return ps, arr, inst
+
+    def skin_geometry(self, poses, instances: np.ndarray | None = None):
+        """ark_ddgi_skin_geometry: every pose's skin computed on the device (skinning.comp) and
+        written over its range of the pools, with optional new transforms: one refit."""
+        ps, arr, inst = self._skin_args(poses, instances)
+        self.check(self.lib.ark_ddgi_skin_geometry(self.h, arr, len(ps), C.c_void_p(inst.ctypes.data) if inst is not None else None,
+                                                   int(inst.size) if inst is not None else 0), "ark_ddgi_skin_geometry")
+
+    def skin_geometry_async(self, poses, instances: np.ndarray | None = None, stream: int | None = None):
+        """ark_ddgi_skin_geometry_async: the same enqueued on `stream` (no host wait)."""
+        ps, arr, inst = self._skin_args(poses, instances)
+        self.check(self.lib.ark_ddgi_skin_geometry_async(self.h, arr, len(ps), C.c_void_p(inst.ctypes.data) if inst is not None else None,
+                                                         int(inst.size) if inst is not None else 0, C.c_void_p(stream) if stream else None),
+                   "ark_ddgi_skin_geometry_async")
+
+    def skin_views(self, skin: int) -> abi.ArkDdgiSkinViews:
+        """ark_ddgi_get_skin_views: device pointers to the skin's latest positions, vertices and velocities."""
+        v = abi.ArkDdgiSkinViews()
+        self.check(self.lib.ark_ddgi_get_skin_views(self.h, int(skin), C.byref(v)), "ark_ddgi_get_skin_views")
+        return v
+
+    def skin_stats(self) -> dict:
+        """ark_ddgi_get_skin_stats."""
+        out = (C.c_uint64 * 4)()
+        self.check(self.lib.ark_ddgi_get_skin_stats(self.h, out), "ark_ddgi_get_skin_stats")
+        return dict(zip(("calls", "vertices", "rejected", "skins"), (int(v) for v in out)))
 
     def geometry_update_info(self) -> dict:
         """ark_ddgi_debug_geometry_update_info: what update_geometry allocated for the scene
@@ -542,6 +682,13 @@ class DDGIContext:
         out = (C.c_uint64 * 4)()
         self.check(self.lib.ark_ddgi_debug_refit_reach(self.h, out), "ark_ddgi_debug_refit_reach")
         return dict(zip(("world_nodes", "world_reached", "sun_nodes", "sun_reached"), (int(v) for v in out)))
+
+
+    def refit_inflation(self) -> tuple:
+        """ark_ddgi_debug_refit_inflation: the last refit's box inflation steps (world, light space)."""
+        out = (C.c_float * 2)()
+        self.check(self.lib.ark_ddgi_debug_refit_inflation(self.h, out), "ark_ddgi_debug_refit_inflation")
+        return float(out[0]), float(out[1])
 
 
 _BVH_CHECK_KEYS = ("nodes", "leaf_children", "max_depth", "violations", "records", "records_with_holes", "record_digest", "installed_builder")

@@ -190,6 +190,47 @@ void populate(GpuScene& gs, const ArkDdgiScene& s)
     gs.setEnvironmentMap(s.environment_texture);
 }
 
+// --skin FILE: one skeletal mesh instance and its pose per frame, as scene.save_skin_binary
+// writes them: "ARKSKIN1", u32 vertices n, indices, joints J (0: morph-only), morph targets K,
+// frames F; then the bind positions (3 n floats), vertices (9 n), indices, skinning vertices
+// (8 n words; none with J = 0), morph targets (9 K n), the world matrix (16, column-major),
+// the material (ArkShaderMaterial) and F poses of 16 J + K floats.
+struct SkinFile {
+    uint32_t n = 0, indexCount = 0, joints = 0, K = 0, frames = 0;
+    std::vector<float> positions, poses;
+    std::vector<ArkRTVertex> vertices;
+    std::vector<uint32_t> indices;
+    std::vector<ArkSkinningVertex> skinning;
+    std::vector<ArkMorphTargetVertex> morph;
+    float world[16] {};
+    ArkShaderMaterial material {};
+};
+
+bool loadSkin(const char* path, SkinFile& s)
+{
+    FILE* fh = std::fopen(path, "rb");
+    if (!fh) return false;
+    char magic[8];
+    uint32_t head[5];
+    bool ok = std::fread(magic, 1, 8, fh) == 8 && std::memcmp(magic, "ARKSKIN1", 8) == 0 && std::fread(head, 4, 5, fh) == 5;
+    auto read = [&](auto& v, size_t count) {
+        v.resize(count);
+        ok = ok && std::fread(v.data(), sizeof(v[0]), count, fh) == count;
+    };
+    if (ok) {
+        s.n = head[0], s.indexCount = head[1], s.joints = head[2], s.K = head[3], s.frames = head[4];
+        read(s.positions, 3 * static_cast<size_t>(s.n));
+        read(s.vertices, s.n);
+        read(s.indices, s.indexCount);
+        read(s.skinning, s.joints ? s.n : 0u);
+        read(s.morph, static_cast<size_t>(s.K) * s.n);
+        ok = ok && std::fread(s.world, 4, 16, fh) == 16 && std::fread(&s.material, sizeof(s.material), 1, fh) == 1;
+        read(s.poses, static_cast<size_t>(s.frames) * (16u * s.joints + s.K));
+    }
+    std::fclose(fh);
+    return ok;
+}
+
 std::vector<uint8_t> readResource(ArkDdgiCtx* ctx, int which)
 {
     uint64_t bytes = 0;
@@ -339,7 +380,7 @@ int main(int argc, char** argv)
     int shards = 1, world = 1, rank = 0;
     std::string ncclIdPath, ncclNonce;
     double exchangeTimeout = 0.0;
-    std::string saveStatePath, loadStatePath, frameScriptPath;
+    std::string saveStatePath, loadStatePath, frameScriptPath, skinPath;
     int firstFrame = 0, gpuRebuild = 0;
     bool raySeeds = true;
     int wobble = -1; // --wobble I: RT mesh I deforms every frame
@@ -382,6 +423,7 @@ int main(int argc, char** argv)
         else if (a == "--gpu-rebuild") gpuRebuild = std::atoi(next());
         else if (a == "--no-ray-seeds") raySeeds = false;
         else if (a == "--wobble") wobble = std::atoi(next());
+        else if (a == "--skin") skinPath = next();
         else ARKOSE_LOG(Fatal, "unknown argument %s", a.c_str());
     }
     SceneFile file;
@@ -402,6 +444,17 @@ int main(int argc, char** argv)
     GpuScene scene(backend);
     populate(scene, *rt);
     if (scene.rtScene().instance_count != rt->instance_count) ARKOSE_LOG(Fatal, "GpuScene adapter dropped instances");
+    // --skin: the file's mesh enters the pools as an asset (its bind pose) and is drawn by one
+    // skeletal mesh instance, which the file's poses bend frame by frame
+    SkinFile skin;
+    size_t skeletal = 0;
+    if (!skinPath.empty()) {
+        if (!loadSkin(skinPath.c_str(), skin)) ARKOSE_LOG(Fatal, "cannot read skin %s", skinPath.c_str());
+        StaticMeshSegment seg;
+        seg.vertexAllocation = scene.allocateVertices(skin.positions.data(), skin.vertices.data(), skin.n, skin.indices.data(), skin.indexCount);
+        seg.material = scene.registerMaterial(skin.material);
+        skeletal = scene.addSkeletalMeshInstance(seg, skin.joints ? skin.skinning.data() : nullptr, skin.joints, skin.K ? skin.morph.data() : nullptr, skin.K, skin.world);
+    }
     scene.scene().setProbeGrid(grid);
     scene.scene().setAmbientIlluminance(ambient);
     scene.scene().setEnvironmentBrightness(env);
@@ -530,6 +583,11 @@ int main(int argc, char** argv)
                     P[k + a] = wobbleRest[k + a] + 0.05f * (4.0f * t * (1.0f - t));
                 }
             scene.updateMeshVertices(static_cast<uint32_t>(wobble), P.data(), nullptr);
+        }
+        if (!skinPath.empty() && static_cast<uint32_t>(f - firstFrame) < skin.frames) {
+            const float* pose = skin.poses.data() + static_cast<size_t>(f - firstFrame) * (16u * skin.joints + skin.K);
+            if (skin.joints) scene.setJointMatrices(skeletal, pose);
+            if (skin.K) scene.setMorphTargetWeights(skeletal, pose + 16u * skin.joints);
         }
         scene.update(); // GpuScene::update: the exposure and light data of this frame
         if (f == rebuildAt) {

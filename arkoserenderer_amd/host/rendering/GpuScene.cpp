@@ -110,6 +110,60 @@ void GpuScene::setInstanceTransform(size_t index, const float worldMatrix[16])
     ++m_instanceVersion;
 }
 
+size_t GpuScene::addSkeletalMeshInstance(const StaticMeshSegment& segment, const ArkSkinningVertex* skinning, uint32_t jointCount, const ArkMorphTargetVertex* morphTargets,
+                                         uint32_t morphTargetCount, const float worldMatrix[16])
+{
+    const VertexAllocation& src = segment.vertexAllocation;
+    if (src.vertexCount == 0 || static_cast<size_t>(src.firstVertex) + src.vertexCount > m_nonPosition.size() ||
+        static_cast<size_t>(src.firstIndex) + src.indexCount > m_indices.size())
+        ARKOSE_LOG(Fatal, "GpuScene: a skeletal mesh instance needs a segment with its vertex allocation in the pools");
+    if ((skinning != nullptr) != (jointCount != 0) || (morphTargets != nullptr) != (morphTargetCount != 0) || (!skinning && !morphTargets))
+        ARKOSE_LOG(Fatal, "GpuScene: a skeletal mesh instance needs skinning data with joints, morph targets, or both");
+    SkeletalMeshInstance sk;
+    sk.source = src;
+    // (copies first: allocateVertices grows the pools it would read from)
+    const std::vector<float> positions(m_positions.begin() + static_cast<std::ptrdiff_t>(src.firstVertex) * 3,
+                                       m_positions.begin() + (static_cast<std::ptrdiff_t>(src.firstVertex) + src.vertexCount) * 3);
+    const std::vector<ArkRTVertex> vertices(m_nonPosition.begin() + src.firstVertex, m_nonPosition.begin() + src.firstVertex + src.vertexCount);
+    const std::vector<uint32_t> indices(m_indices.begin() + src.firstIndex, m_indices.begin() + src.firstIndex + src.indexCount);
+    sk.target = allocateVertices(positions.data(), vertices.data(), src.vertexCount, indices.data(), src.indexCount);
+    sk.jointCount = jointCount;
+    sk.morphTargetCount = morphTargetCount;
+    if (skinning) sk.skinning.assign(skinning, skinning + src.vertexCount);
+    if (morphTargets) sk.morphTargets.assign(morphTargets, morphTargets + static_cast<size_t>(morphTargetCount) * src.vertexCount);
+    sk.jointMatrices.assign(static_cast<size_t>(jointCount) * 16, 0.0f);
+    for (uint32_t j = 0; j < jointCount; ++j)
+        for (int d = 0; d < 4; ++d) sk.jointMatrices[j * 16 + d * 5] = 1.0f;
+    sk.morphTargetWeights.assign(morphTargetCount, 0.0f);
+    StaticMeshSegment seg = segment;
+    seg.vertexAllocation = sk.target;
+    StaticMesh mesh;
+    mesh.LODs.push_back(StaticMeshLOD { { seg } });
+    StaticMeshInstance inst;
+    inst.mesh = addStaticMesh(std::move(mesh));
+    std::memcpy(inst.worldMatrix, worldMatrix, sizeof(inst.worldMatrix));
+    addStaticMeshInstance(inst);
+    sk.instance = m_instances.size() - 1;
+    m_skeletal.push_back(std::move(sk));
+    return m_skeletal.size() - 1;
+}
+
+void GpuScene::setJointMatrices(size_t index, const float* matrices)
+{
+    if (index >= m_skeletal.size()) ARKOSE_LOG(Fatal, "GpuScene: no skeletal mesh instance %zu", index);
+    SkeletalMeshInstance& sk = m_skeletal[index];
+    std::memcpy(sk.jointMatrices.data(), matrices, sk.jointMatrices.size() * sizeof(float));
+    sk.poseVersion = ++m_poseVersion;
+}
+
+void GpuScene::setMorphTargetWeights(size_t index, const float* weights)
+{
+    if (index >= m_skeletal.size()) ARKOSE_LOG(Fatal, "GpuScene: no skeletal mesh instance %zu", index);
+    SkeletalMeshInstance& sk = m_skeletal[index];
+    std::memcpy(sk.morphTargetWeights.data(), weights, sk.morphTargetWeights.size() * sizeof(float));
+    sk.poseVersion = ++m_poseVersion;
+}
+
 void GpuScene::updateMeshVertices(uint32_t rtMeshIndex, const float* positions, const ArkRTVertex* vertices)
 {
     if (m_rtMeshes.empty()) buildRtInstances();

@@ -169,6 +169,30 @@ public:
     // the ranges logged after `version`, oldest first; false when some of them were dropped
     // already (the caller's pools are older than the log reaches: it builds its scene anew)
     bool vertexRangesSince(uint32_t version, std::vector<VertexRange>& out) const;
+    // A skeletal mesh instance (GpuScene.cpp:629-711; VertexManager::allocateSkeletalMeshInstance):
+    // one static mesh segment - its vertices in the pools are the bind pose, its indices are
+    // shared in content - with skinning data (null: morph-only) and K morph targets (target
+    // k's vertices at k * vertexCount). The instance gets a target range of its own in the
+    // pools, which starts as a copy of the bind pose and which the skinning pass rewrites
+    // every frame on the device: the host pools keep the bind pose there. Returns its index.
+    struct SkeletalMeshInstance {
+        VertexAllocation source, target;
+        size_t instance { 0 }; // its static mesh instance (the transform: setInstanceTransform)
+        uint32_t jointCount { 0 }, morphTargetCount { 0 };
+        std::vector<ArkSkinningVertex> skinning;
+        std::vector<ArkMorphTargetVertex> morphTargets;
+        std::vector<float> jointMatrices;      // jointCount x 16, column-major (appliedJointMatrices); identity at first
+        std::vector<float> morphTargetWeights; // K; 0 at first
+        uint32_t poseVersion { 0 };            // poseVersion() once its pose was set last; 0: never (the bind pose)
+    };
+    size_t addSkeletalMeshInstance(const StaticMeshSegment& segment, const ArkSkinningVertex* skinning, uint32_t jointCount, const ArkMorphTargetVertex* morphTargets,
+                                   uint32_t morphTargetCount, const float worldMatrix[16]);
+    // this frame's pose of skeletal instance i (Skeleton::appliedJointMatrices, the morph target weights)
+    void setJointMatrices(size_t index, const float* matrices);
+    void setMorphTargetWeights(size_t index, const float* weights);
+    // counts the pose changes; a node sends the poses newer than the version its context holds
+    uint32_t poseVersion() const { return m_poseVersion; }
+    const std::vector<SkeletalMeshInstance>& skeletalMeshInstances() const { return m_skeletal; }
     const float* positionPool() const { return m_positions.data(); }
     const ArkRTVertex* vertexPool() const { return m_nonPosition.data(); }
 
@@ -206,6 +230,8 @@ private:
     bool m_lightsManaged { false }; // update() recomputes the light data from the managed lights
     uint32_t m_instanceVersion { 0 };
     uint32_t m_vertexVersion { 0 };
+    std::vector<SkeletalMeshInstance> m_skeletal;
+    uint32_t m_poseVersion { 0 };
     std::vector<VertexRange> m_vertexLog;
     uint32_t m_vertexLogFloor { 0 }; // every range up to this version was dropped
     uint32_t m_vertexLogMark { 0 };  // vertexVersion() at the last update()

@@ -45,6 +45,47 @@ bool DDGINode::loadState(const std::vector<uint8_t>& blob)
     return true;
 }
 
+bool DDGINode::registerSkins(GpuScene& scene)
+{
+    m_skins.clear();
+    m_poseVersion = 0; // the pools set_scene was given hold the bind pose in every skin's range
+    for (const GpuScene::SkeletalMeshInstance& sk : scene.skeletalMeshInstances()) {
+        ArkDdgiSkinDesc d {};
+        d.struct_size = sizeof(d);
+        d.first_vertex = static_cast<uint32_t>(sk.target.firstVertex);
+        d.vertex_count = sk.target.vertexCount;
+        d.joint_count = sk.jointCount;
+        d.morph_target_count = sk.morphTargetCount;
+        d.positions = scene.positionPool() + static_cast<size_t>(sk.source.firstVertex) * 3;
+        d.vertices = scene.vertexPool() + sk.source.firstVertex;
+        d.skinning = sk.skinning.empty() ? nullptr : sk.skinning.data();
+        d.morph_targets = sk.morphTargets.empty() ? nullptr : sk.morphTargets.data();
+        uint32_t handle = 0;
+        if (int rc = ark_ddgi_register_skin(m_ctx, &d, &handle); rc != ARK_DDGI_OK) {
+            ARKOSE_LOG(Error, "DDGINode: ark_ddgi_register_skin failed (%d): %s", rc, ark_ddgi_last_error(m_ctx));
+            return false;
+        }
+        m_skins.push_back(handle);
+    }
+    return true;
+}
+
+int DDGINode::sendPoses(GpuScene& scene, const ArkRTInstance* instances, uint32_t instanceCount, void* stream)
+{
+    std::vector<ArkDdgiSkinPose> poses;
+    const std::vector<GpuScene::SkeletalMeshInstance>& all = scene.skeletalMeshInstances();
+    for (size_t i = 0; i < all.size() && i < m_skins.size(); ++i) {
+        if (all[i].poseVersion <= m_poseVersion) continue;
+        ArkDdgiSkinPose p {};
+        p.struct_size = sizeof(p);
+        p.skin = m_skins[i];
+        p.joint_matrices = all[i].jointMatrices.empty() ? nullptr : all[i].jointMatrices.data();
+        p.morph_weights = all[i].morphTargetWeights.empty() ? nullptr : all[i].morphTargetWeights.data();
+        poses.push_back(p);
+    }
+    return ark_ddgi_skin_geometry_async(m_ctx, poses.data(), static_cast<uint32_t>(poses.size()), instances, instanceCount, stream);
+}
+
 RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registry& reg)
 {
     // DDGINode.cpp:39-42
@@ -102,6 +143,7 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
     }
     m_instanceVersion = scene.instanceVersion(); // set_scene built the BVHs at these transforms
     m_vertexVersion = scene.vertexVersion();     // ... from these pools
+    if (!registerSkins(scene)) return RenderPipelineNode::NullExecuteCallback; // ... with every skin at its bind pose
 
     ArkDdgiDeviceViews views {};
     ark_ddgi_get_device_views(ctx, &views);
@@ -146,18 +188,23 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
         // installed when ready - the reference's full build every 60 frames)
         if (int rc = ark_ddgi_set_lights(ctx, &scene.rtLights()); rc != ARK_DDGI_OK)
             ARKOSE_LOG(Error, "DDGINode: ark_ddgi_set_lights failed (%d): %s", rc, ark_ddgi_last_error(ctx));
-        if (scene.instanceVersion() != m_instanceVersion || scene.vertexVersion() != m_vertexVersion) {
+        if (scene.instanceVersion() != m_instanceVersion || scene.vertexVersion() != m_vertexVersion || scene.poseVersion() != m_poseVersion) {
             const bool moved = scene.instanceVersion() != m_instanceVersion;
+            const bool ranged = scene.vertexVersion() != m_vertexVersion, posed = scene.poseVersion() != m_poseVersion;
             const std::vector<ArkRTInstance>& instances = scene.rtInstances();
+            const uint32_t instanceCount = static_cast<uint32_t>(instances.size());
             // enqueued on this frame's stream ahead of the update (no host wait): the
             // skinned meshes' vertex ranges since the version this node's context holds
             // (GpuScene.cpp:629-711, :934-992; the scene's log, which every node of the
-            // scene reads for itself) and the moved transforms in one refit
-            int rc;
+            // scene reads for itself) and the moved transforms in one refit; the skeletal
+            // mesh instances' poses newer than the context's (skinning.comp on the device)
+            // with the moved transforms in one refit - after the ranges' refit, which then
+            // carries the transforms, when a frame has both
+            int rc = ARK_DDGI_OK;
             std::vector<GpuScene::VertexRange> ranges;
-            if (scene.vertexVersion() != m_vertexVersion && !scene.vertexRangesSince(m_vertexVersion, ranges)) {
+            if (ranged && !scene.vertexRangesSince(m_vertexVersion, ranges)) {
                 rc = ARK_DDGI_E_INVALID_ARGUMENT; // the log no longer reaches back to this context's pools: set_scene below
-            } else if (scene.vertexVersion() != m_vertexVersion) {
+            } else if (ranged) {
                 std::vector<ArkDdgiVertexUpdate> updates;
                 for (const GpuScene::VertexRange& r : ranges) {
                     ArkDdgiVertexUpdate u {};
@@ -168,23 +215,34 @@ RenderPipelineNode::ExecuteCallback DDGINode::construct(GpuScene& scene, Registr
                     u.vertices = r.vertices ? scene.vertexPool() + r.firstVertex : nullptr;
                     updates.push_back(u);
                 }
-                rc = ark_ddgi_update_geometry_async(ctx, updates.data(), static_cast<uint32_t>(updates.size()), moved ? instances.data() : nullptr,
-                                                    moved ? static_cast<uint32_t>(instances.size()) : 0u, cmdList.hipStream());
-            } else {
-                rc = ark_ddgi_set_instances_async(ctx, instances.data(), static_cast<uint32_t>(instances.size()), cmdList.hipStream());
+                rc = ark_ddgi_update_geometry_async(ctx, updates.data(), static_cast<uint32_t>(updates.size()), moved ? instances.data() : nullptr, moved ? instanceCount : 0u,
+                                                    cmdList.hipStream());
+            } else if (!posed) {
+                rc = ark_ddgi_set_instances_async(ctx, instances.data(), instanceCount, cmdList.hipStream());
+            }
+            if (rc == ARK_DDGI_OK && posed) {
+                const bool carry = moved && !ranged;
+                rc = sendPoses(scene, carry ? instances.data() : nullptr, carry ? instanceCount : 0u, cmdList.hipStream());
             }
             if (rc != ARK_DDGI_OK) {
                 // a refit cannot follow this change (the topology changed: another mesh,
                 // triangle count or hit mask): build the scene anew, as construct() does
-                // (never keep the old transforms for good)
+                // (never keep the old transforms for good), register the skins
+                // again - a set_scene drops them - and pose them all
                 ARKOSE_LOG(Warning, "DDGINode: the scene's change cannot be refitted (%d): %s; rebuilding the scene", rc, ark_ddgi_last_error(ctx));
                 rc = ark_ddgi_set_scene(ctx, &scene.rtScene());
                 if (rc != ARK_DDGI_OK) ARKOSE_LOG(Error, "DDGINode: ark_ddgi_set_scene failed (%d): %s", rc, ark_ddgi_last_error(ctx));
+                if (rc == ARK_DDGI_OK && !registerSkins(scene)) rc = ARK_DDGI_E_INVALID_ARGUMENT;
+                if (rc == ARK_DDGI_OK && scene.poseVersion() != 0) {
+                    rc = sendPoses(scene, nullptr, 0, cmdList.hipStream());
+                    if (rc != ARK_DDGI_OK) ARKOSE_LOG(Error, "DDGINode: ark_ddgi_skin_geometry_async failed (%d): %s", rc, ark_ddgi_last_error(ctx));
+                }
             }
             // the context follows this version only once it holds it (else: retried next frame)
             if (rc == ARK_DDGI_OK) {
                 m_instanceVersion = scene.instanceVersion();
                 m_vertexVersion = scene.vertexVersion();
+                m_poseVersion = scene.poseVersion();
             }
         }
         if (m_exchange) {

@@ -89,6 +89,12 @@ private:
     ArkDdgiCtx* m_ctx { nullptr };
     uint32_t m_instanceVersion { 0 }; // GpuScene::instanceVersion() the context's BVHs follow
     uint32_t m_vertexVersion { 0 };   // GpuScene::vertexVersion() its pools follow
+    uint32_t m_poseVersion { 0 };     // GpuScene::poseVersion() its skins' ranges follow (0: the bind pose)
+    std::vector<uint32_t> m_skins;    // the context's skin of each skeletal mesh instance
+    // the scene's skeletal mesh instances registered with the context (after every set_scene, which drops them)
+    bool registerSkins(GpuScene& scene);
+    // the poses newer than m_poseVersion, with `instances` (null: the transforms stay), in one refit on `stream`
+    int sendPoses(GpuScene& scene, const ArkRTInstance* instances, uint32_t instanceCount, void* stream);
     SlabExchange* m_exchange { nullptr };
     void* m_updateDone { nullptr };      // hipEvent_t recorded after each update
     void* m_exchangePending { nullptr }; // hipEvent_t of the last exchange

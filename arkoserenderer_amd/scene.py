@@ -678,3 +678,106 @@ def city_block(box_count: int = 250_000, extent: float = 240.0, seed: int = 0xB1
     return SceneData(positions=np.concatenate(positions), vertices=verts, indices=indices, meshes=meshes, materials=mats,
                      instances=inst, textures=textures, sun=((3.0, 2.9, 2.7), tuple(sun_dir)), spots=spots,
                      environment_texture=len(ies_sources))
+
+
+def skinned_tube(rings: int = 12, segments: int = 8, joints: int = 4, morph_targets: int = 0, radius: float = 0.15, length: float = 1.6,
+                 base=(0.0, 0.2, 0.0), tint=(0.3, 0.7, 0.4)) -> tuple[SceneData, dict]:
+    """A test asset for skinning (ark_ddgi_register_skin): a tube of `rings` rings of
+    `segments` vertices along +y from `base`, bound to a chain of `joints` joints spread
+    evenly along it with smooth (linear) weights over the two nearest joints, plus optional
+    morph targets (target k: a bulge of the rings around height (k + 1) / (K + 1), with the
+    normal tilted along the tube). Returns the one-mesh scene and the skin arrays:
+    joint_indices n x 4 uint32, joint_weights n x 4 float32, joint_count, joint_origins
+    joints x 3 (each joint's pivot, for building poses), morph_targets K x n x 9 float32."""
+    base = np.asarray(base, np.float32)
+    t = np.linspace(0.0, 1.0, rings, dtype=np.float64)
+    a = np.linspace(0.0, 2.0 * np.pi, segments, endpoint=False)
+    ring = np.stack([np.cos(a), np.zeros_like(a), np.sin(a)], -1)
+    P = (base + np.concatenate([radius * ring + np.array([0.0, length * h, 0.0]) for h in t])).astype(np.float32)
+    n = rings * segments
+    V = np.zeros(n, dtype=VERTEX_DTYPE)
+    V["normal"] = np.tile(ring, (rings, 1)).astype(np.float32)
+    V["tangent"][:, :3] = np.tile(np.stack([-np.sin(a), np.zeros_like(a), np.cos(a)], -1), (rings, 1)).astype(np.float32)
+    V["tangent"][:, 3] = 1.0
+    V["tex_coord"][:, 0] = np.tile(a / (2.0 * np.pi), rings)
+    V["tex_coord"][:, 1] = np.repeat(t, segments)
+    tris = []
+    for r in range(rings - 1):
+        for s in range(segments):
+            i0, i1 = r * segments + s, r * segments + (s + 1) % segments
+            j0, j1 = i0 + segments, i1 + segments
+            tris += [(i0, j0, i1), (i1, j0, j1)]  # CCW seen from outside
+    idx = np.array(tris, np.uint32).reshape(-1)
+    # smooth weights over the chain: joint j sits at height j / joints of the tube
+    x = np.repeat(t, segments) * joints - 0.5
+    j0 = np.clip(np.floor(x), 0, joints - 1).astype(np.int64)
+    j1 = np.clip(j0 + 1, 0, joints - 1)
+    w1 = np.clip(x - j0, 0.0, 1.0).astype(np.float32)
+    w1[j1 == j0] = 0.0
+    ji = np.zeros((n, 4), np.uint32)
+    jw = np.zeros((n, 4), np.float32)
+    ji[:, 0], ji[:, 1] = j0, j1
+    jw[:, 0], jw[:, 1] = np.float32(1.0) - w1, w1
+    origins = (base + np.stack([np.zeros(joints), length * np.arange(joints) / joints, np.zeros(joints)], -1)).astype(np.float32)
+    morph = np.zeros((morph_targets, n, 9), np.float32)
+    h = np.repeat(t, segments)
+    for k in range(morph_targets):
+        c = (k + 1.0) / (morph_targets + 1.0)
+        g = np.exp(-((h - c) / 0.18) ** 2)
+        morph[k, :, 0:3] = (0.6 * radius * g)[:, None] * V["normal"]
+        morph[k, :, 4] = -1.5 * g * (h - c)  # the normal tilts away from the bulge's crest
+        morph[k, :, 6:9] = 0.0
+    mat = default_material()
+    mat["metallic_factor"], mat["roughness_factor"] = 0.0, 0.6
+    mat["color_tint"] = (*tint, 1.0)
+    inst = np.zeros(1, dtype=INSTANCE_DTYPE)
+    inst["object_to_world"][0] = np.eye(3, 4, dtype=np.float32).reshape(12)
+    inst["triangle_count"] = len(tris)
+    inst["hit_mask"] = abi.ARK_RT_HIT_MASK_OPAQUE
+    sc = SceneData(positions=P, vertices=V, indices=idx, meshes=np.zeros(1, dtype=MESH_DTYPE), materials=np.array([mat], dtype=MATERIAL_DTYPE), instances=inst)
+    return sc, dict(joint_indices=ji, joint_weights=jw, joint_count=joints, joint_origins=origins, morph_targets=morph)
+
+
+def save_skin_binary(path: str, tube: SceneData, skin: dict, poses: list, world: np.ndarray | None = None):
+    """Writes the ARKSKIN1 container ddgi_headless --skin reads: a one-mesh scene (its bind
+    pose, indices and material), its skin arrays as skinned_tube returns them, the instance's
+    world matrix (4 x 4 row-major; None: identity) and one pose per frame, each a pair (joint
+    matrices joints x 4 x 4 column-major, morph weights K)."""
+    import struct
+
+    n, K = len(tube.positions), len(skin["morph_targets"])
+    J = int(skin["joint_count"]) if skin.get("joint_indices") is not None else 0
+    with open(path, "wb") as fh:
+        fh.write(b"ARKSKIN1")
+        fh.write(struct.pack("<5I", n, tube.indices.size, J, K, len(poses)))
+        fh.write(np.ascontiguousarray(tube.positions, np.float32).tobytes())
+        fh.write(np.ascontiguousarray(tube.vertices).tobytes())
+        fh.write(np.ascontiguousarray(tube.indices, np.uint32).tobytes())
+        if J:
+            fh.write(np.concatenate([np.asarray(skin["joint_indices"], np.uint32), np.asarray(skin["joint_weights"], np.float32).view(np.uint32)], axis=1).tobytes())
+        fh.write(np.ascontiguousarray(skin["morph_targets"], np.float32).tobytes())
+        fh.write(np.ascontiguousarray((np.eye(4) if world is None else np.asarray(world)).T, np.float32).tobytes())
+        fh.write(np.ascontiguousarray(tube.materials[:1]).tobytes())
+        for joints, weights in poses:
+            if J:
+                fh.write(np.ascontiguousarray(joints, np.float32).tobytes())
+            fh.write(np.ascontiguousarray(weights if K else [], np.float32).tobytes())
+
+
+def bend_pose(origins: np.ndarray, angle: float, translate=(0.0, 0.0, 0.0), scale: float = 1.0) -> np.ndarray:
+    """Applied joint matrices of a chain bent about z: joint j rotates by `angle` about its
+    pivot on top of its parent's transform, the root also scaled and translated. Returns
+    joints x 4 x 4 float32 with each matrix column-major (SkinPose's layout)."""
+    out = []
+    M = np.eye(4)
+    M[:3, :3] *= scale
+    M[:3, 3] = translate
+    c, s = math.cos(angle), math.sin(angle)
+    for o in np.asarray(origins, np.float64):
+        R = np.eye(4)
+        R[:3, :3] = [[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]
+        T, Ti = np.eye(4), np.eye(4)
+        T[:3, 3], Ti[:3, 3] = o, -o
+        M = M @ T @ R @ Ti
+        out.append(M.T.copy())  # column-major
+    return np.asarray(out, np.float32)

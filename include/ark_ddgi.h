@@ -465,6 +465,83 @@ int ark_ddgi_update_geometry(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates
  * into bounds (waits for the calls' device work). */
 int ark_ddgi_get_geometry_update_stats(ArkDdgiCtx* ctx, uint64_t out[4]);
 
+/* Skinned and morphed meshes on the device (arkose/shaders/skinning/skinning.comp, run per
+ * segment of every skeletal-mesh instance ahead of its BLAS update, GpuScene.cpp:629-711):
+ * the producer of the vertices ark_ddgi_update_geometry takes. A skin is a range of the
+ * scene's vertex pools with its bind pose - positions, ArkRTVertex, optionally four joint
+ * indices and weights per vertex (NULL: morph-only) and K morph targets (target k's
+ * vertices at k * vertex_count) - registered once after ark_ddgi_set_scene (host arrays,
+ * copied). It belongs to the scene: contexts sharing it (ark_ddgi_share_scene) see it, a new
+ * ark_ddgi_set_scene drops every skin, ark_ddgi_unregister_skin one.
+ * ARK_DDGI_E_INVALID_ARGUMENT, nothing registered: a wrong struct_size, a range outside
+ * the pools, missing arrays, neither skeleton nor morph targets, a joint weight that is
+ * negative or not finite, a joint index >= joint_count, non-finite bind or morph data.
+ *
+ * ark_ddgi_skin_geometry(_async): per pose - a skin, its joint_count column-major mat4s (the
+ * reference's appliedJointMatrices; row 3 is not read) and its K morph weights - the skin's
+ * vertices are computed on the device (k_skin_vertices: morph blending, renormalisation,
+ * four-joint blending, the inverse transpose for normal and tangent, a per-vertex
+ * velocity) into buffers the skin owns, and those replace the skin's range of the pools
+ * through ark_ddgi_update_geometry's path as a device source, together with the optional
+ * new transforms: one refit per call, no vertex crossing the host link. A skin may appear
+ * once per call. The positions' bound comes from the pose on the host, conservative for
+ * the kernel's fp32 arithmetic, so nothing is dropped or clamped; when the skin's range
+ * covers a mesh's span the bound replaces the instances' object-space boxes. After the call
+ * every later operation sees, bit for bit, what ark_ddgi_set_scene would build from pools
+ * whose ranges hold ark_ddgi_debug_skin_host's output, with those transforms.
+ * ARK_DDGI_E_INVALID_ARGUMENT, nothing enqueued (counted in the stats): an unknown skin, a
+ * skin twice, a non-finite joint matrix or morph weight, a bound that is not finite.
+ * Stream order as ark_ddgi_update_geometry_async. */
+typedef struct ArkSkinningVertex {
+    uint32_t joint_indices[4];
+    float joint_weights[4];
+} ArkSkinningVertex;
+typedef struct ArkMorphTargetVertex {
+    float position[3];
+    float normal[3];
+    float tangent[3];
+} ArkMorphTargetVertex;
+typedef struct ArkDdgiSkinDesc {
+    uint32_t struct_size;        /* sizeof(ArkDdgiSkinDesc) */
+    uint32_t first_vertex;       /* the skin's destination range of the scene's vertex pools */
+    uint32_t vertex_count;
+    uint32_t joint_count;        /* matrices per pose (0 with skinning NULL) */
+    uint32_t morph_target_count; /* K */
+    uint32_t reserved0;
+    const float* positions;                    /* bind pose, vertex_count x 3 */
+    const ArkRTVertex* vertices;               /* bind pose, vertex_count */
+    const ArkSkinningVertex* skinning;         /* vertex_count, or NULL: morph-only */
+    const ArkMorphTargetVertex* morph_targets; /* K x vertex_count, or NULL with K = 0 */
+    int32_t reserved[4];
+} ArkDdgiSkinDesc;
+typedef struct ArkDdgiSkinPose {
+    uint32_t struct_size;        /* sizeof(ArkDdgiSkinPose) */
+    uint32_t skin;
+    const float* joint_matrices; /* joint_count x 16, column-major (NULL for a morph-only skin) */
+    const float* morph_weights;  /* K (NULL with K = 0) */
+    int32_t reserved[2];
+} ArkDdgiSkinPose;
+/* The skin's latest output on the device, valid on the stream of the call that produced it
+ * until the skin's next call (a consumer on another stream orders itself, as with any
+ * kernel's output): the engine's motion-vector consumers read the velocities, the DDGI path
+ * does not. runs 0: never skinned, the pointers are NULL. */
+typedef struct ArkDdgiSkinViews {
+    const float* positions;      /* vertex_count x 3 */
+    const ArkRTVertex* vertices; /* vertex_count */
+    const float* velocities;     /* vertex_count x 3: position - previous position, 0 after the first run */
+    uint32_t vertex_count;
+    uint32_t runs;
+} ArkDdgiSkinViews;
+int ark_ddgi_register_skin(ArkDdgiCtx* ctx, const ArkDdgiSkinDesc* desc, uint32_t* out_skin);
+int ark_ddgi_unregister_skin(ArkDdgiCtx* ctx, uint32_t skin);
+int ark_ddgi_skin_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t pose_count, const ArkRTInstance* instances, uint32_t instance_count,
+                                 void* hip_stream);
+int ark_ddgi_skin_geometry(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t pose_count, const ArkRTInstance* instances, uint32_t instance_count);
+int ark_ddgi_get_skin_views(ArkDdgiCtx* ctx, uint32_t skin, ArkDdgiSkinViews* out_views);
+/* out[0] skin_geometry calls of the context's scene that went through, [1] vertices skinned,
+ * [2] calls refused for their poses, [3] skins registered now. No device work. */
+int ark_ddgi_get_skin_stats(ArkDdgiCtx* ctx, uint64_t out[4]);
+
 /* One DDGI update (DDGINode.cpp:132-259) enqueued on `hip_stream` (NULL = the null
  * stream). Asynchronous: call ark_ddgi_synchronize or synchronize the stream before
  * reading.

@@ -8,6 +8,8 @@
 
 #include <stdint.h>
 
+#include "ark_ddgi.h" /* the skin entries' structs */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -285,6 +287,30 @@ uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z);
 int ark_ddgi_debug_seed_candidate_ok(uint32_t word, uint32_t first, uint32_t end);
 int ark_ddgi_debug_seed_info(struct ArkDdgiCtx* ctx, uint64_t* out);
 int ark_ddgi_debug_seed_fill(struct ArkDdgiCtx* ctx, int mode, uint64_t value);
+
+/* The absolute inflation steps of the last refit's boxes (a power of two each, from the
+ * instances' object-space boxes through their transforms): out[2] = {world BVHs, light-space
+ * sun BVH}; 0 before the first refit. A scene whose object-space boxes only ever grow would
+ * see them grow with it. No device work. */
+int ark_ddgi_debug_refit_inflation(struct ArkDdgiCtx* ctx, float* out);
+
+/* The skinning pass (csrc/skinning.h) restated serially on the host, no GPU: the skin `desc`
+ * describes (ark_ddgi_register_skin's checks; first_vertex is not used) run for `pose`
+ * (pose->skin is not used). prev_positions: the previous run's positions, or NULL: the
+ * skin's first run (velocity 0). out_positions and out_velocities vertex_count x 3,
+ * out_vertices vertex_count, out_bounds[6] the host bound of the pose's positions (lo, hi)
+ * that ark_ddgi_skin_geometry hands the refit. ARK_DDGI_E_INVALID_ARGUMENT for a desc or a
+ * pose that registration or ark_ddgi_skin_geometry would refuse. */
+int ark_ddgi_debug_skin_host(const ArkDdgiSkinDesc* desc, const ArkDdgiSkinPose* pose, const float* prev_positions, float* out_positions, ArkRTVertex* out_vertices,
+                             float* out_velocities, float* out_bounds);
+/* k_skin_vertices against that restatement for the same input, on a stream of its own
+ * without a context; the kernel's outputs start at vertex dst_first_vertex of larger arrays
+ * (a destination range may begin at any vertex). out[5] = {position words that differ by
+ * bits, vertex words, velocity words (a NaN equals any NaN), words outside the outputs'
+ * ranges that were written, nanoseconds of a second, timed run of the kernel (HIP events)}.
+ * Synchronous. */
+int ark_ddgi_debug_skin_device_parity(int device, const ArkDdgiSkinDesc* desc, const ArkDdgiSkinPose* pose, const float* prev_positions, uint32_t dst_first_vertex,
+                                      uint64_t* out);
 
 #ifdef __cplusplus
 }

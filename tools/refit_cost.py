@@ -21,6 +21,17 @@ skinned mesh's normals change), unless --positions-only; --device-source hands t
 over as device tensors. The line also tells the vertices per call and the counts of
 ark_ddgi_get_geometry_update_stats. Run --continuous and --deform in turn to compare.
 
+--skin: --deform with the vertices produced on the device (ark_ddgi_skin_geometry_async): every
+instance's range is a registered skin - four joints per vertex on a chain of 16 joints, all of
+them the identity, and one morph target, the sine displacement - and the frame's call poses two
+skins, the instance of the frame with morph weight 1 and the one of the frame before with
+weight 0: the same ranges dirty as under --deform, the same refit, no vertex crossing the host
+link. The line also tells k_skin_vertices' own time for the largest skin (HIP events around a
+run on a stream of its own, ark_ddgi_debug_skin_device_parity) and the byte model's traffic.
+--skin-host: the same poses skinned on the host (the serial restatement) and sent as host
+ranges, which is what a caller without the device path does. Run --deform --device-source,
+--skin and --skin-host in turn to compare.
+
 --gpu-rebuild (with --continuous): ARK_DDGI_FLAG_GPU_REBUILD, the world BVHs rebuilt on the
 device while the instances move. The line then also tells the installs' builder, the
 device builds' time and footprint (nodes, records per triangle) as installed at the end
@@ -73,6 +84,8 @@ def main():
     ap.add_argument("--deform", action="store_true", help="--continuous, the moved instance's positions displaced by a sine instead of translated (update_geometry)")
     ap.add_argument("--positions-only", action="store_true", help="with --deform: the ranges carry no other vertex data")
     ap.add_argument("--device-source", action="store_true", help="with --deform: the ranges are device tensors")
+    ap.add_argument("--skin", action="store_true", help="--deform, the vertices skinned on the device from poses (skin_geometry)")
+    ap.add_argument("--skin-host", action="store_true", help="--deform, the same poses skinned on the host and sent as host ranges")
     ap.add_argument("--no-background", action="store_true", help="ARK_DDGI_FLAG_NO_BACKGROUND_REBUILD: refits only (isolates the rebuild threads' cost)")
     ap.add_argument("--gpu-rebuild", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD: the world BVHs' background rebuilds on the device")
     ap.add_argument("--gpu-rebuild-sun", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_SUN: the light-space sun BVH's background builds on the device")
@@ -80,6 +93,7 @@ def main():
     ap.add_argument("--gpu-rebuild-plan", action="store_true", help="ARK_DDGI_FLAG_GPU_REBUILD_PLAN: those builds collapse by the SAH-optimal plan")
     ap.add_argument("--sun-turn", action="store_true", help="instead of refits: turn the sun by 10 deg, wait for the background rebuild, turn it back, wait again")
     args = ap.parse_args()
+    args.deform = args.deform or args.skin or args.skin_host
     args.continuous = args.continuous or args.deform
     import torch
     from arkoserenderer_amd import ddgi as D
@@ -158,6 +172,19 @@ def main():
                     p1 = (p0 + np.float32(0.05) * np.sin(np.float32(2.0) * p0[:, [1, 2, 0]])).astype(np.float32)
                     vx = None if args.positions_only else np.ascontiguousarray(sc.vertices[first:first + cnt]).view(np.float32).reshape(-1, 9)
                     lo, hi = np.minimum(p0.min(0), p1.min(0)), np.maximum(p0.max(0), p1.max(0))
+                    if args.skin or args.skin_host:
+                        rng = np.random.default_rng(i)
+                        ji = rng.integers(0, 16, (cnt, 4)).astype(np.uint32)
+                        jw = rng.uniform(0.1, 1.0, (cnt, 4))
+                        jw = (jw / jw.sum(1, keepdims=True)).astype(np.float32)
+                        morph = np.zeros((1, cnt, 9), np.float32)
+                        morph[0, :, 0:3] = p1 - p0
+                        skin = D.Skin(first, p0, np.ascontiguousarray(sc.vertices[first:first + cnt]), ji, jw, 16, morph)
+                        handle = node.ctx.register_skin(skin) if args.skin else i
+                        joints = np.tile(np.eye(4, dtype=np.float32), (16, 1, 1))
+                        pair = [D.SkinPose(handle, joints, [w]) for w in (0.0, 1.0)]
+                        poses.append((first, cnt, skin, pair))
+                        continue
                     if args.device_source:
                         p0, p1 = torch.from_numpy(p0).cuda(), torch.from_numpy(p1).cuda()
                         vx = None if vx is None else torch.from_numpy(vx).cuda()
@@ -165,11 +192,33 @@ def main():
                 torch.cuda.synchronize()
                 last = (args.frames - 1) % n
                 P = sc.positions.copy()
-                P[poses[last][0]:poses[last][0] + poses[last][1]] = poses[last][3].cpu().numpy() if args.device_source else poses[last][3]
+                if args.skin or args.skin_host:
+                    P[poses[last][0]:poses[last][0] + poses[last][1]] = D.skin_host(poses[last][2], poses[last][3][1])[0]
+                else:
+                    P[poses[last][0]:poses[last][0] + poses[last][1]] = poses[last][3].cpu().numpy() if args.device_source else poses[last][3]
                 final = dataclasses.replace(sc, positions=P)
                 per_call = 0
             t = time.perf_counter()
             for f in range(args.frames):
+                if args.skin or args.skin_host:
+                    call = [poses[f % n][3][1]] + ([poses[(f - 1) % n][3][0]] if f > 0 and n > 1 else [])
+                    per_call = max(per_call, poses[f % n][1] + (poses[(f - 1) % n][1] if len(call) > 1 else 0))
+                    ev[f][0].record(stream)
+                    th = time.perf_counter()
+                    if args.skin:
+                        node.ctx.skin_geometry_async(call, None, sptr)
+                    else:
+                        ups = []
+                        for q in call:
+                            first, cnt, skin, _ = poses[q.skin]
+                            p, v, _, _ = D.skin_host(skin, q)
+                            ups.append(D.VertexUpdate(first, p, None if args.positions_only else v))
+                        node.ctx.update_geometry_async(ups, None, sptr)
+                    host_refit += time.perf_counter() - th
+                    ev[f][1].record(stream)
+                    node.execute(app[0], sptr)
+                    app[0] = D.AppState(app[0].frame_index + 1)
+                    continue
                 if args.deform:
                     first, cnt, p0, p1, vx, box = poses[f % n]
                     ups = [D.VertexUpdate(first, p1, vx, bounds=box)]
@@ -247,6 +296,16 @@ def main():
             if args.deform:
                 out["continuous"]["deform"] = {"vertices_per_call": int(per_call), "positions_only": bool(args.positions_only), "device_source": bool(args.device_source),
                                                "stats": list(node.ctx.geometry_update_stats()), "info": node.ctx.geometry_update_info()}
+            if args.skin or args.skin_host:
+                out["continuous"]["deform"]["source"] = "skin" if args.skin else "skin-host"
+            if args.skin:
+                # the kernel alone, for the largest skin: bytes by ddgi_skinning.hip's model (K = 1, a previous position)
+                first, cnt, skin, pair = max(poses, key=lambda q: q[1])
+                prev = D.skin_host(skin, pair[0])[0]
+                runs = sorted(D.skin_device_parity(skin, pair[1], prev)["kernel_ns"] for _ in range(5))
+                model = cnt * (140 + 36 + 12)
+                out["continuous"]["skin"] = {"stats": node.ctx.skin_stats(), "kernel_vertices": int(cnt), "kernel_us": [round(r / 1e3, 2) for r in runs],
+                                             "model_bytes": int(model), "model_tb_per_s_at_median": round(model / runs[2] / 1e3, 3)}
             print(json.dumps(out), flush=True)
             node.ctx.close()
             continue
