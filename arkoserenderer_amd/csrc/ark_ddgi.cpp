@@ -1,71 +1,15 @@
-// ark_ddgi.cpp — the C-ABI context of the MI355X DDGI path (include/ark_ddgi.h).
-//
-// Owns the device memory of one DDGI node instance on one GPU: the persistent
-// atlases/offsets (the DDGISamplingSet, DDGINode.cpp:62-66), the per-update
-// working set (slot table, hit records, surfels) and its lights, and holds the scene
-// (scene_store.h: BVH + RT mesh data + materials, possibly shared with other
-// contexts). Every update is enqueued on one HIP stream.
-#include <hip/hip_runtime.h>
-#include <rocprofiler-sdk-roctx/roctx.h>
-
-#include <algorithm>
+// ark_ddgi.cpp — the C-ABI context of the MI355X DDGI path (include/ark_ddgi.h,
+// ddgi_context.h): its lifetime, scene, lights and resources. The update itself is in
+// ddgi_frame.cpp, the other passes in ddgi_passes.cpp.
 #include <chrono>
-#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <string>
-#include <vector>
 
-#include "../../include/ark_ddgi.h"
-#include "../../include/ark_ddgi_debug.h"
-#include "ark_fmath.h"
-#include "ddgi_kernels.h"
-#include "scene_store.h"
-#include "shade_schedule.h"
-#include "sun_bvh.h"
-#include "sun_cover_build.h"
-
-using namespace ark;
+#include "ddgi_context.h"
+#include "sun_cover_map.h"
 
 namespace {
-
-// pipelined windows below this many probe rays trace at half occupancy (ctx->pipeTraceBlocks)
-constexpr uint32_t kPipeHalfRays = 5u << 20;
-constexpr int kPipeTracePerCu = 3; // traversal workgroups per CU of such a window (ctx->pipeTraceBlocks; 2, 4, 5 measured slower)
-// Idle traversal lanes are refilled in batches of >= kRefillMin (the refill then stalls
-// a wave once per 16 finished rays, and the rays it starts descend from the root
-// together: C4 2.98 vs 3.30 ms at 1 in round 1; with the fetches outside branches 16
-// is the best: step 3.53 -> 3.46 ms against 4, 24 and 32, profiles/r03_as, r03_at; with
-// k_trace's refills reading staged records from LDS, measured again: C4 2,566 / 2,580 /
-// 2,589 / 2,565 Mrays/s at 8 / 12 / 16 / 24, means of three interleaved runs,
-// EXPERIMENTS.md "LDS ray pool"). The
-// sun's any-hit rays in the light-space BVH are short: 32 (profiles/r05_q: C4 shadow
-// phase 0.648 -> 0.630 ms, K = 2048 0.327 -> 0.320 ms; the world BVHs' shadow rays keep
-// 16: 32 there made C5's shadow phase 1.92 -> 2.07 ms). kGrabChunk: rays per
-// partition-head grab, 64 = a probe quarter of direction-clustered rays per wave pool
-// (16 and 8 measured slower on 1/8 slabs).
-constexpr uint32_t kRefillMin = 16, kSunRefillMin = 32, kGrabChunk = 64;
-static_assert(kGrabChunk <= 64, "a wave stages one ray of a chunk per lane (k_trace's pool, the shadow traversal's refill)");
-
-// roctx range over a scope (host-side enqueue markers, named after the reference's
-// ScopedDebugZone labels, DDGINode.cpp:152-247); end() closes it early.
-class RoctxRange {
-public:
-    explicit RoctxRange(const char* name) { roctxRangePushA(name); }
-    ~RoctxRange() { end(); }
-    void end()
-    {
-        if (m_open) roctxRangePop();
-        m_open = false;
-    }
-    RoctxRange(const RoctxRange&) = delete;
-    RoctxRange& operator=(const RoctxRange&) = delete;
-
-private:
-    bool m_open { true };
-};
 
 uint16_t f32_to_f16_host(float f)
 {
@@ -75,177 +19,6 @@ uint16_t f32_to_f16_host(float f)
     std::memcpy(&u, &h, 2);
     return u;
 }
-
-// Traversal order of a probe's R samples: groups of 64 (one wave's refill pool)
-// with nearby directions, so the lanes of a wave descend similar BVH paths.
-// Balanced greedy clustering around ceil(R/64) spherical-Fibonacci centres.
-// Only the lane -> sample assignment changes; every sample is traced exactly
-// once and its hit record is stored at its own index, so results do not depend
-// on the order.
-void sampleTraversalOrder(uint32_t R, std::vector<uint32_t>& order)
-{
-    order.resize(R);
-    for (uint32_t i = 0; i < R; ++i) order[i] = i;
-    const uint32_t G = (R + 63) / 64;
-    if (G <= 1) return;
-    auto fib = [](uint32_t i, uint32_t n, double* d) { // same point set as sphericalFibonacci (math accuracy irrelevant here)
-        const double phi = 2.0 * M_PI * std::fmod(i * 0.6180339887498949, 1.0);
-        const double z = 1.0 - (2.0 * i + 1.0) / n, r = std::sqrt(std::max(0.0, 1.0 - z * z));
-        d[0] = std::cos(phi) * r; d[1] = std::sin(phi) * r; d[2] = z;
-    };
-    std::vector<double> pts(3 * R), ctr(3 * G);
-    for (uint32_t i = 0; i < R; ++i) fib(i, R, &pts[3 * i]);
-    for (uint32_t g = 0; g < G; ++g) fib(g, G, &ctr[3 * g]);
-    struct Pair { double d; uint32_t i, g; };
-    std::vector<Pair> pairs;
-    pairs.reserve(static_cast<size_t>(R) * G);
-    for (uint32_t i = 0; i < R; ++i)
-        for (uint32_t g = 0; g < G; ++g)
-            pairs.push_back({ pts[3 * i] * ctr[3 * g] + pts[3 * i + 1] * ctr[3 * g + 1] + pts[3 * i + 2] * ctr[3 * g + 2], i, g });
-    std::stable_sort(pairs.begin(), pairs.end(), [](const Pair& a, const Pair& b) { return a.d > b.d; });
-    std::vector<int> groupOf(R, -1);
-    std::vector<uint32_t> room(G, 64u);
-    room[G - 1] = R - 64u * (G - 1);
-    for (const Pair& q : pairs)
-        if (groupOf[q.i] < 0 && room[q.g] > 0) { groupOf[q.i] = static_cast<int>(q.g); room[q.g]--; }
-    uint32_t k = 0;
-    for (uint32_t g = 0; g < G; ++g)
-        for (uint32_t i = 0; i < R; ++i)
-            if (groupOf[i] == static_cast<int>(g)) order[k++] = i;
-}
-
-} // namespace
-
-struct ArkDdgiCtx : ErrorSink {
-    ArkDdgiDesc desc {};
-    hipStream_t stream = nullptr; // internal (clears); synchronous use only
-    // Call order across streams: every operation records evOrder on its stream when
-    // enqueued, and the next one waits for it when given another stream (orderBegin).
-    hipEvent_t evOrder = nullptr;
-    hipStream_t orderStream = nullptr;
-    bool orderValid = false;
-    // traversal refill batch (probe and shadow rays, the sun's), rays per partition-head grab
-    uint32_t refillMin = kRefillMin, sunRefillMin = kSunRefillMin, grabChunk = kGrabChunk;
-    int device = 0;
-    int cuCount = 0;
-    int X = 0, Y = 0, Z = 0, N = 0;
-    int Wi = 0, Hi = 0, Wv = 0, Hv = 0;
-    int Kmax = 0, Rmax = 0;
-    int slabZ0 = 0, slabZ1 = 0;
-    // persistent resources
-    DeviceBuffer irr, vis, offsets;
-    // working set
-    DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork;
-    DeviceBuffer raySteps; // counting updates: u16 traversal iterations per probe ray (ARK_DDGI_DEBUG_RAY_STEPS)
-    // The probe rays' hit candidates (seed_cache.h; none with ARK_DDGI_FLAG_NO_RAY_SEEDS):
-    // [N][seed::kProbeWords] triangle records of the world BVHs' opaque class, or seed::kNone.
-    // The words are record indices, so they belong to one record order: the cache is
-    // refilled with kNone on the traversal stream, ahead of the next traversal, whenever the
-    // scene's worldTopologySeq has moved or the context has taken another scene (seedStale).
-    DeviceBuffer seeds;
-    bool seedStale = true;
-    uint32_t seedTopologySeen = 0;
-    std::vector<uint32_t> orderHost; // traversal order of the samples for orderR
-    uint32_t orderR = 0;
-    uint32_t lightCount = 0;
-    uint32_t spillEntries = 0;
-    uint32_t traceBlocks = 0, shadeBlocks = 0, shadowBlocks = 0, shadowBlocksPerCu = 1;
-    // Frames in flight (updateImpl): the per-frame buffers the traversal writes come in
-    // two sets (slot table, slot order, sample directions, hit records, work counters);
-    // frame n uses set n & 1. Frame n's slot table, primary traversal and probe offsets
-    // run on traceStream as soon as frame n - 2 (the previous user of the set) is done,
-    // after frame n - 1's offsets (same stream), overlapping frame n - 1's shadow
-    // rays, shading and probe update on the caller's stream.
-    bool pipelining = true;        // ARK_DDGI_FLAG_SERIAL_FRAMES: every update runs serially
-    int sunBvh = -1;               // ArkDdgiDesc.sun_bvh: 0 the sun's shadow rays traverse the world BVHs, 1 the light-space BVH, -1: by cost (sun_bvh_pays)
-    uint32_t pipeTraceBlocks = 0; // primary-traversal grid of a pipelined window below kPipeHalfRays rays
-    bool pipeReady = false;        // the previous context operation was an update
-    uint32_t parity = 0;           // buffer set of the next update
-    uint32_t prevR = 0;
-    bool prevPipelined = false;    // the previous update's offsets ran on traceStream
-    hipStream_t traceStream = nullptr;
-    hipEvent_t evTraced = nullptr, evFrameDone[2] = {};
-    bool frameDoneValid[2] = { false, false };
-    // Device-side frame sequencing of pipelined frames (k_seq_signal / k_seq_wait
-    // instead of cross-queue event waits): seqWords [0] = the last frame whose
-    // traversal-stream part (slot table, traversal, offsets) is done, [32] = the last
-    // frame whose caller-stream part is done, [64] = a wait timed out (a signal folded
-    // into the last kernel - its last workgroup storing the word after a device-scope
-    // fence per workgroup - measured slower: the fences write back L2, K = 2048 frames
-    // 0.371 -> 0.387 ms, profiles/r03_y). setSeq[b] = the
-    // frame that last used buffer set b, when that frame was sequenced this way
-    // (else its evFrameDone[b] is recorded). ark_ddgi_set_sequencing(ctx, 0, ...): events throughout.
-    bool seqSync = true;
-    DeviceBuffer seqWords;
-    uint32_t frameSeq = 0;
-    uint32_t setSeq[2] = { 0, 0 };
-    bool setSeqValid[2] = { false, false };
-    uint64_t seqTimeoutTicks = 0;
-    uint32_t seqTimeoutMs = 10000;
-    uint64_t wallClockKhz = 100000;
-    // fail-closed sequencing: a k_seq_wait that gives up sets seqWords[64] (every path
-    // kernel then skips: frameAborted) and this host-mapped word, which the next
-    // update / exchange_begin / synchronize polls (checkSequencing)
-    uint32_t* hostAbort = nullptr;    // host pointer (hipHostMalloc, coherent)
-    uint32_t* hostAbortDev = nullptr; // its device address
-    uint32_t seqTimeouts = 0;         // timeouts reported so far
-    // Z-slab exchange sequencing (ark_ddgi_exchange_begin/_end, ark_ddgi_update_exchanged):
-    // seqWords [96] = the last exchange completed on the caller's exchange stream
-    uint32_t lastMainSeq = 0;        // the last update's caller-stream sequence number (0: not sequenced)
-    hipStream_t lastStream = nullptr; // the last update's stream
-    hipEvent_t evExchangeSrc = nullptr; // exchange_begin after an unsequenced update
-    hipEvent_t evExchangeDone = nullptr; // exchange_end without sequence words (seqSync off)
-    uint32_t exchSeq = 0;            // exchanges ended so far
-    uint32_t pendingExchange = 0;    // the exchange the next update_exchanged waits for before shading
-    uint32_t lastParity = 0;       // buffer set of the last update (debug hit records)
-    uint32_t fibR[2] = { 0, 0 };
-    uint64_t spillRegionWords = 0; // spill region 1 = the primary traversal's
-    // scene
-    bool hasScene = false;
-    std::shared_ptr<SceneStore> sceneStore; // device scene (possibly shared with other contexts)
-    uint32_t sceneVersion = 0;              // sceneStore->version that `scene` was derived at
-    // Per-frame lights (ark_ddgi_set_lights; set_scene / share_scene start them with the
-    // scene's): the sun travels in `scene` (kernel arguments), the spots in `lights` on
-    // the device, stored there in stream order ahead of the next operation that reads
-    // them (flushLights) when lightsDirty
-    DeviceBuffer lights; // GpuSpotLight[kMaxLights - 1]
-    std::vector<GpuSpotLight> spotHost;
-    int32_t hasSun = 0;
-    float sunColor[3] { 0, 0, 0 }, sunDir[3] { 0, 0, 0 };
-    bool lightsDirty = false;
-    // AO bake results (ark_ddgi_bake_ao)
-    DeviceBuffer bakeTri, bakeBary, bakeOut, bakePixels, bakeCounters;
-    uint32_t bakeW = 0, bakeH = 0;
-    int bakeBent = 0;
-    SceneArgs scene {};          // = sceneStore->args
-    ArkDdgiBvhStats bvhStats {}; // = sceneStore->bvhStats
-    uint32_t bvhMaxDepth = 0;
-    // instrumentation
-    bool counting = false;
-    bool lastSunOnly = false;          // the last update ran the sun-only shading schedule (shade_schedule.h) ...
-    const uint32_t* lastDeferredCount = nullptr; // ... and this device word holds the rays it deferred
-    bool sunOnlySmallWindows = false;  // ark_ddgi_debug_set_sun_only_small_windows
-    bool coverCountsValid = false; // the last update was a counting one (ark_ddgi_debug_sun_cover_counts) ...
-    FrameArgs coverFrame {};       // ... and its shading arguments
-    bool timing = false;
-    hipEvent_t ev[6] = {};
-    float lastMs[5] = {};
-    bool timingValid = false;
-    ArkDdgiCounters lastCounters {};
-    bool countersPending = false;
-    uint64_t lastRays = 0, lastProbes = 0;
-    uint32_t nextProbeIndex = 0; // (first + K) % N of the last update, or of a loaded state
-    uint32_t lastFirst = 0, lastK = 0; // the last update's window (ark_ddgi_window_exchange_info)
-    // the refits and installed rebuilds of the scene (by any context sharing it) that this
-    // context's traversal stream has waited for: SceneStore::geometrySeq at its last wait
-    // for the store's evGeometry (updateImpl). The ordering of the scene's geometry
-    // copies itself belongs to the store.
-    uint32_t geometrySeen = 0;
-};
-
-#define ARK_HIP(expr) ARK_HIP_TO(ctx, expr)
-
-namespace {
 
 int clearHistory(ArkDdgiCtx* ctx)
 {
@@ -264,102 +37,6 @@ int clearHistory(ArkDdgiCtx* ctx)
     ARK_HIP(hipStreamSynchronize(ctx->stream));
     return ARK_DDGI_OK;
 }
-
-hipError_t drainContext(ArkDdgiCtx* ctx);
-
-int ensureSpill(ArkDdgiCtx* ctx)
-{
-    // a node group is pushed at most once per BVH8 level: depth + 2 entries of 2 words
-    uint32_t need = std::max<uint32_t>(1u, ctx->bvhMaxDepth + 2u > static_cast<uint32_t>(kStackLds) ? ctx->bvhMaxDepth + 2u - kStackLds : 1u);
-    uint32_t threads = std::max(ctx->traceBlocks, ctx->shadowBlocks) * kTraceBlock; // the traversal kernels
-    const uint64_t words = static_cast<uint64_t>(need) * 2 * threads;
-    const size_t bytes = 2 * words * sizeof(uint32_t); // region 0: all but the primary traversal
-    if (ctx->spill.bytes >= bytes) {
-        ctx->spillRegionWords = words;
-        return ARK_DDGI_OK;
-    }
-    if (ctx->spill.ptr) ARK_HIP(drainContext(ctx)); // a deeper BVH (a rebuilt sun BVH): frames in flight use it
-    ctx->spillRegionWords = words;
-    ARK_HIP(ctx->spill.alloc(bytes));
-    ctx->spillEntries = need;
-    return ARK_DDGI_OK;
-}
-
-// The stream of an asynchronous entry point: NULL is the legacy default (null)
-// stream, which orders against every blocking stream of the process (torch's
-// default stream among them), like any other HIP API taking a stream.
-hipStream_t streamOf(void* h) { return static_cast<hipStream_t>(h); }
-
-// Operations of one context execute in call order, whatever streams they are given
-// (they share the traversal spill area, the hit records and the atlases): an
-// operation on another stream than the previous one first waits for it.
-hipError_t orderBegin(ArkDdgiCtx* ctx, hipStream_t s)
-{
-    if (ctx->orderValid && ctx->orderStream != s) return hipStreamWaitEvent(s, ctx->evOrder, 0);
-    return hipSuccess;
-}
-
-hipError_t orderEnd(ArkDdgiCtx* ctx, hipStream_t s)
-{
-    const hipError_t e = hipEventRecord(ctx->evOrder, s);
-    ctx->orderStream = s;
-    ctx->orderValid = e == hipSuccess;
-    return e;
-}
-
-// Shading work set for the largest window: per-ray light bits, then k_shadow_gen's
-// shadow-ray list (at most one ray per probe ray and light).
-struct ShadeWorkLayout {
-    uint64_t bits, list, total;
-};
-
-ShadeWorkLayout shadeWorkLayout(const ArkDdgiCtx* ctx)
-{
-    auto al = [](uint64_t b) { return (b + 255) & ~static_cast<uint64_t>(255); };
-    const uint64_t rays = static_cast<uint64_t>(ctx->Kmax) * ctx->Rmax;
-    const uint64_t entries = rays * ctx->lightCount;
-    ShadeWorkLayout w {};
-    w.bits = 0;
-    w.list = al(rays * 4);
-    w.total = w.list + al(entries * sizeof(ShadowRay));
-    return w;
-}
-
-int ensureShadeWork(ArkDdgiCtx* ctx)
-{
-    const uint64_t rays = static_cast<uint64_t>(ctx->Kmax) * ctx->Rmax;
-    if (rays >= (1ull << 28) && ctx->lightCount > 0)
-        return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "%llu rays per update: shadow-ray owners pack (ray << 4) | light in 32 bits", static_cast<unsigned long long>(rays));
-    const ShadeWorkLayout w = shadeWorkLayout(ctx);
-    if (ctx->shadeWork.bytes < w.total) ARK_HIP(ctx->shadeWork.alloc(w.total));
-    return ARK_DDGI_OK;
-}
-
-// RT reflections' ray-list work set for `pixels` rays (ark_ddgi_rt_reflections)
-// Workgroups of the persistent shadow traversal for `rays` closest-hit rays (~0.25
-// shadow rays each on C4): the launch is a tail of the longest shadow rays when
-// there are few, and fewer co-resident waves shorten each one's iterations
-// (measured on C4: K = 2048 windows 0.228 -> 0.180 ms at 3 workgroups per CU,
-// K = 4096 0.246 -> 0.225, the full grid (8.4 M rays) unchanged from 5 to 6).
-constexpr uint64_t kShadowMinPerCu = 3; // 1 and 2 measured slower or within noise (profiles/r04_p)
-uint32_t shadowBlocksFor(const ArkDdgiCtx* ctx, uint64_t rays)
-{
-    const uint64_t perCu = std::min<uint64_t>(ctx->shadowBlocksPerCu, std::max<uint64_t>(kShadowMinPerCu, rays >> 20));
-    return static_cast<uint32_t>(perCu * ctx->cuCount);
-}
-
-int ensureReflWork(ArkDdgiCtx* ctx, uint64_t pixels)
-{
-    if (pixels >= (1ull << 28) && ctx->lightCount > 0)
-        return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "%llu reflection rays: shadow-ray owners pack (ray << 4) | light in 32 bits", static_cast<unsigned long long>(pixels));
-    auto al = [](uint64_t b) { return (b + 255) & ~static_cast<uint64_t>(255); };
-    const uint64_t bytes = al(pixels * 32) + al(pixels * sizeof(GpuHit)) + al(pixels * 4) + al((kRayCounterWords + kRayCounterStride) * 4) +
-                           al(pixels * ctx->lightCount * sizeof(ShadowRay));
-    if (ctx->reflWork.bytes < bytes) ARK_HIP(ctx->reflWork.alloc(bytes));
-    return ARK_DDGI_OK;
-}
-
-static_assert(ARK_DDGI_MAX_SPOT_LIGHTS == kMaxLights - 1, "spot light capacity");
 
 // The context's kernel view of its scene: the store's world BVHs, pools and tables with
 // the context's own lights (sun by value, spots in its light buffer); the light-space
@@ -402,11 +79,32 @@ void deriveSceneArgs(ArkDdgiCtx* ctx)
     ctx->sceneVersion = st.version;
 }
 
+} // namespace
+
+int ark::ensureSpill(ArkDdgiCtx* ctx)
+{
+    // a node group is pushed at most once per BVH8 level: depth + 2 entries of 2 words
+    uint32_t need = std::max<uint32_t>(1u, ctx->bvhMaxDepth + 2u > static_cast<uint32_t>(kStackLds) ? ctx->bvhMaxDepth + 2u - kStackLds : 1u);
+    uint32_t threads = std::max(ctx->traceBlocks, ctx->shadowBlocks) * kTraceBlock; // the traversal kernels
+    const uint64_t words = static_cast<uint64_t>(need) * 2 * threads;
+    const size_t bytes = 2 * words * sizeof(uint32_t); // region 0: all but the primary traversal
+    if (ctx->spill.bytes >= bytes) {
+        ctx->spillRegionWords = words;
+        return ARK_DDGI_OK;
+    }
+    if (ctx->spill.ptr) ARK_HIP(drainContext(ctx)); // a deeper BVH (a rebuilt sun BVH): frames in flight use it
+    ctx->spillRegionWords = words;
+    ARK_HIP(ctx->spill.alloc(bytes));
+    return ARK_DDGI_OK;
+}
+
+static_assert(ARK_DDGI_MAX_SPOT_LIGHTS == kMaxLights - 1, "spot light capacity");
+
 // deriveSceneArgs plus a traversal spill area deep enough for every BVH the derived
 // args reach. Every caller goes through here: a sharing context may
 // have installed a deeper sun BVH, and marking the store's version as seen without
 // growing the spill area would let the next traversal overrun it.
-int refreshScene(ArkDdgiCtx* ctx)
+int ark::refreshScene(ArkDdgiCtx* ctx)
 {
     deriveSceneArgs(ctx);
     return ensureSpill(ctx);
@@ -414,7 +112,7 @@ int refreshScene(ArkDdgiCtx* ctx)
 
 // The context's spot lights reach the device in stream order on `s`, ahead of the
 // operation that reads them (a by-value kernel argument: no host buffer to keep alive).
-hipError_t flushLights(ArkDdgiCtx* ctx, hipStream_t s)
+hipError_t ark::flushLights(ArkDdgiCtx* ctx, hipStream_t s)
 {
     if (!ctx->lightsDirty) return hipSuccess;
     LightBlock b {};
@@ -426,7 +124,7 @@ hipError_t flushLights(ArkDdgiCtx* ctx, hipStream_t s)
 }
 
 // Waits for every operation of the context enqueued so far (both of its streams).
-hipError_t drainContext(ArkDdgiCtx* ctx)
+hipError_t ark::drainContext(ArkDdgiCtx* ctx)
 {
     hipError_t e = hipStreamSynchronize(ctx->traceStream);
     if (e == hipSuccess && ctx->orderValid) e = hipEventSynchronize(ctx->evOrder);
@@ -434,7 +132,7 @@ hipError_t drainContext(ArkDdgiCtx* ctx)
 }
 
 // What the scene's calls (scene_store.h) take from the calling context
-SceneCall sceneCall(ArkDdgiCtx* ctx)
+SceneCall ark::sceneCall(ArkDdgiCtx* ctx)
 {
     SceneCall c {};
     c.err = ctx;
@@ -443,6 +141,19 @@ SceneCall sceneCall(ArkDdgiCtx* ctx)
     std::copy(ctx->sunDir, ctx->sunDir + 3, c.sunDir);
     c.shared = ctx->sceneStore.use_count() > 1;
     return c;
+}
+
+namespace {
+
+// The shading work set (shadeWorkLayout) holds the largest window with `lightCount` lights
+int ensureShadeWork(ArkDdgiCtx* ctx, uint32_t lightCount)
+{
+    const uint64_t rays = static_cast<uint64_t>(ctx->Kmax) * ctx->Rmax;
+    if (rays >= (1ull << 28) && lightCount > 0)
+        return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "%llu rays per update: shadow-ray owners pack (ray << 4) | light in 32 bits", static_cast<unsigned long long>(rays));
+    const ShadeWorkLayout w = shadeWorkLayout(ctx, lightCount);
+    if (ctx->shadeWork.bytes < w.total) ARK_HIP(ctx->shadeWork.alloc(w.total));
+    return ARK_DDGI_OK;
 }
 
 // Makes `st` the context's scene with the scene's lights: the per-context work sets
@@ -464,9 +175,44 @@ int adoptScene(ArkDdgiCtx* ctx, std::shared_ptr<SceneStore> st)
     ctx->lightsDirty = false;
     deriveSceneArgs(ctx);
     int rc;
-    if ((rc = ensureShadeWork(ctx)) != 0) return rc;
+    if ((rc = ensureShadeWork(ctx, ctx->lightCount)) != 0) return rc;
     if ((rc = ensureSpill(ctx)) != 0) return rc;
     ctx->hasScene = true;
+    return ARK_DDGI_OK;
+}
+
+// A refit entry (set_instances, update_geometry, skin_geometry): `refit` is the store's call
+// on `s` - the refit of the next geometry copy on the store's stream, which `s` then
+// follows; finished background rebuilds installed and new ones started on `s`
+template<class Refit>
+int refitEntry(ArkDdgiCtx* ctx, const char* before, void* hipStream, Refit refit)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "%s before ark_ddgi_set_scene", before);
+    SceneStore& st = *ctx->sceneStore;
+    const auto t0 = std::chrono::steady_clock::now();
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    if (const int r = checkSequencing(ctx)) return r;
+    ARK_HIP(orderBegin(ctx, s));
+    if (const int rc = refit(st, sceneCall(ctx), s)) return rc;
+    if (ctx->sceneVersion != st.version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    ARK_HIP(orderEnd(ctx, s));
+    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ARK_DDGI_OK;
+}
+
+// The blocking form of a refit entry: on the context's internal stream, then waited for
+template<class Async>
+int refitBlocking(ArkDdgiCtx* ctx, Async async)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (const int rc = async(ctx->stream)) return rc;
+    ARK_HIP(hipStreamSynchronize(ctx->stream));
+    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    ctx->bvhStats = ctx->sceneStore->bvhStats;
     return ARK_DDGI_OK;
 }
 
@@ -521,7 +267,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     if ((e = hipEventCreateWithFlags(&ctx->evOrder, hipEventDisableTiming)) != hipSuccess) return bad(e, "hipEventCreate");
     // the desc's options (ArkDdgiDesc.sun_bvh / flags); the traversal's refill and grab
     // sizes are the constants kRefillMin / kSunRefillMin / kGrabChunk
-    ctx->pipelining = (desc->flags & ARK_DDGI_FLAG_SERIAL_FRAMES) == 0;
+    ctx->frames.pipelining = (desc->flags & ARK_DDGI_FLAG_SERIAL_FRAMES) == 0;
     ctx->sunBvh = desc->sun_bvh == ARK_DDGI_SUN_BVH_WORLD ? 0 : desc->sun_bvh == ARK_DDGI_SUN_BVH_LIGHT_SPACE ? 1 : -1;
     // a counter-collecting profiler (rocprofv3 --pmc) runs one kernel at a time across
     // queues: a polling wait could then hold the GPU while the kernel it waits for queues
@@ -529,7 +275,7 @@ int ark_ddgi_create(const ArkDdgiDesc* desc, ArkDdgiCtx** outCtx)
     // dropping frames; such a context starts with events instead (the profiler's own
     // environment, not a tuning knob; ark_ddgi_set_sequencing overrides it)
     if (const char* pc = std::getenv("ROCPROF_COUNTER_COLLECTION"))
-        if (*pc && std::strcmp(pc, "0") != 0 && std::strcmp(pc, "false") != 0) ctx->seqSync = false;
+        if (*pc && std::strcmp(pc, "0") != 0 && std::strcmp(pc, "false") != 0) ctx->frames.setSequencing(false);
     if ((e = hipStreamCreateWithFlags(&ctx->traceStream, hipStreamNonBlocking)) != hipSuccess) return bad(e, "hipStreamCreate");
     // stream-order events of the frames in flight
     const unsigned syncFlags = hipEventDisableTiming;
@@ -625,7 +371,7 @@ const char* ark_ddgi_last_error(const ArkDdgiCtx* ctx) { return ctx ? ctx->lastE
 int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
 {
     if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
+    ctx->frames.externalWrite();
     if (!s || s->struct_size != sizeof(ArkDdgiScene)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiScene");
     ARK_HIP(hipSetDevice(ctx->device));
     ARK_HIP(hipDeviceSynchronize());
@@ -641,7 +387,7 @@ int ark_ddgi_set_scene(ArkDdgiCtx* ctx, const ArkDdgiScene* s)
 int ark_ddgi_share_scene(ArkDdgiCtx* ctx, const ArkDdgiCtx* src)
 {
     if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
+    ctx->frames.externalWrite();
     if (!src || src == ctx || !src->hasScene || !src->sceneStore) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "share_scene: the source context has no scene");
     if (src->device != ctx->device) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "share_scene: contexts on devices %d and %d", src->device, ctx->device);
     ARK_HIP(hipSetDevice(ctx->device));
@@ -666,20 +412,9 @@ int ark_ddgi_set_lights(ArkDdgiCtx* ctx, const ArkDdgiLights* L)
     if (count > ctx->lightCount) {
         // the shadow-ray list holds one ray per probe ray and light: grow it once the
         // frames in flight (which use it) are done
-        const ShadeWorkLayout need = [&] {
-            const uint32_t keep = ctx->lightCount;
-            ctx->lightCount = count;
-            const ShadeWorkLayout w = shadeWorkLayout(ctx);
-            ctx->lightCount = keep;
-            return w;
-        }();
-        if (ctx->shadeWork.bytes < need.total) {
+        if (ctx->shadeWork.bytes < shadeWorkLayout(ctx, count).total) {
             ARK_HIP(drainContext(ctx));
-            const uint32_t keep = ctx->lightCount;
-            ctx->lightCount = count;
-            const int rc = ensureShadeWork(ctx);
-            ctx->lightCount = keep;
-            if (rc) return rc;
+            if (const int rc = ensureShadeWork(ctx, count)) return rc;
         }
     }
     ctx->hasSun = L->has_directional_light ? 1 : 0;
@@ -707,45 +442,28 @@ int ark_ddgi_set_lights(ArkDdgiCtx* ctx, const ArkDdgiLights* L)
     return ARK_DDGI_OK;
 }
 
-static int checkSequencing(ArkDdgiCtx* ctx);
-
 int ark_ddgi_set_instances_async(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count, void* hipStream)
 {
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_set_instances before ark_ddgi_set_scene");
-    SceneStore& st = *ctx->sceneStore;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    if (const int r = checkSequencing(ctx)) return r;
-    ARK_HIP(orderBegin(ctx, s));
-    // the refit of the next geometry copy on the store's stream, which `s` then follows;
-    // finished background rebuilds installed and new ones started on `s`
-    if (const int rc = sceneSetInstances(st, sceneCall(ctx), instances, count, s)) return rc;
-    if (ctx->sceneVersion != st.version)
-        if (const int rc = refreshScene(ctx)) return rc;
-    ARK_HIP(orderEnd(ctx, s));
-    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ARK_DDGI_OK;
+    return refitEntry(ctx, "ark_ddgi_set_instances", hipStream,
+                      [&](SceneStore& st, const SceneCall& c, hipStream_t s) { return sceneSetInstances(st, c, instances, count, s); });
 }
 
+int ark_ddgi_set_instances(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count)
+{
+    return refitBlocking(ctx, [&](void* s) { return ark_ddgi_set_instances_async(ctx, instances, count, s); });
+}
+
+// set_instances' refit with the vertex ranges written first (scene_store.h)
 int ark_ddgi_update_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count, void* hipStream)
 {
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_update_geometry before ark_ddgi_set_scene");
-    SceneStore& st = *ctx->sceneStore;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    if (const int r = checkSequencing(ctx)) return r;
-    ARK_HIP(orderBegin(ctx, s));
-    // set_instances' refit with the vertex ranges written first (scene_store.h)
-    if (const int rc = sceneUpdateGeometry(st, sceneCall(ctx), updates, updateCount, instances, count, s)) return rc;
-    if (ctx->sceneVersion != st.version)
-        if (const int rc = refreshScene(ctx)) return rc;
-    ARK_HIP(orderEnd(ctx, s));
-    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ARK_DDGI_OK;
+    return refitEntry(ctx, "ark_ddgi_update_geometry", hipStream, [&](SceneStore& st, const SceneCall& c, hipStream_t s) {
+        return sceneUpdateGeometry(st, c, updates, updateCount, instances, count, s);
+    });
+}
+
+int ark_ddgi_update_geometry(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count)
+{
+    return refitBlocking(ctx, [&](void* s) { return ark_ddgi_update_geometry_async(ctx, updates, updateCount, instances, count, s); });
 }
 
 int ark_ddgi_register_skin(ArkDdgiCtx* ctx, const ArkDdgiSkinDesc* desc, uint32_t* outSkin)
@@ -764,34 +482,17 @@ int ark_ddgi_unregister_skin(ArkDdgiCtx* ctx, uint32_t skin)
     return sceneUnregisterSkin(*ctx->sceneStore, ctx, skin);
 }
 
+// the skins' runs on `s`, then update_geometry's refit with their outputs as device sources
 int ark_ddgi_skin_geometry_async(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t poseCount, const ArkRTInstance* instances, uint32_t count, void* hipStream)
 {
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_skin_geometry before ark_ddgi_set_scene");
-    SceneStore& st = *ctx->sceneStore;
-    const auto t0 = std::chrono::steady_clock::now();
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    if (const int r = checkSequencing(ctx)) return r;
-    ARK_HIP(orderBegin(ctx, s));
-    // the skins' runs on `s`, then update_geometry's refit with their outputs as device sources
-    if (const int rc = sceneSkinGeometry(st, sceneCall(ctx), poses, poseCount, instances, count, s)) return rc;
-    if (ctx->sceneVersion != st.version)
-        if (const int rc = refreshScene(ctx)) return rc;
-    ARK_HIP(orderEnd(ctx, s));
-    st.bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ARK_DDGI_OK;
+    return refitEntry(ctx, "ark_ddgi_skin_geometry", hipStream, [&](SceneStore& st, const SceneCall& c, hipStream_t s) {
+        return sceneSkinGeometry(st, c, poses, poseCount, instances, count, s);
+    });
 }
 
 int ark_ddgi_skin_geometry(ArkDdgiCtx* ctx, const ArkDdgiSkinPose* poses, uint32_t poseCount, const ArkRTInstance* instances, uint32_t count)
 {
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (const int rc = ark_ddgi_skin_geometry_async(ctx, poses, poseCount, instances, count, ctx->stream)) return rc;
-    ARK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->bvhStats = ctx->sceneStore->bvhStats;
-    return ARK_DDGI_OK;
+    return refitBlocking(ctx, [&](void* s) { return ark_ddgi_skin_geometry_async(ctx, poses, poseCount, instances, count, s); });
 }
 
 int ark_ddgi_get_skin_views(ArkDdgiCtx* ctx, uint32_t skin, ArkDdgiSkinViews* out)
@@ -818,657 +519,6 @@ int ark_ddgi_get_geometry_update_stats(ArkDdgiCtx* ctx, uint64_t* out)
     return sceneGeometryStats(*ctx->sceneStore, ctx, out);
 }
 
-int ark_ddgi_debug_geometry_update_info(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "geometry update info before ark_ddgi_set_scene");
-    const SceneStore& st = *ctx->sceneStore;
-    out[0] = st.recordMapAllocs;
-    out[1] = st.recordMapFills;
-    out[2] = st.recordMap.bytes + st.triBase.bytes + st.stageCounters.bytes;
-    out[3] = st.book.vtx.seq;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_debug_scene_digest(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "scene digest before ark_ddgi_set_scene");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    return sceneDigest(*ctx->sceneStore, ctx, out);
-}
-
-int ark_ddgi_debug_world_bvh_check(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "world BVH check before ark_ddgi_set_scene");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    return sceneWorldBvhCheck(*ctx->sceneStore, ctx, out);
-}
-
-int ark_ddgi_debug_sun_bvh_installed_check(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "sun BVH check before ark_ddgi_set_scene");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    return sceneSunBvhCheck(*ctx->sceneStore, ctx, out);
-}
-
-int ark_ddgi_debug_refit_reach(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "refit reach before ark_ddgi_set_scene");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    return sceneRefitReach(*ctx->sceneStore, ctx, out);
-}
-
-int ark_ddgi_debug_refit_inflation(ArkDdgiCtx* ctx, float* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "refit inflation before ark_ddgi_set_scene");
-    out[0] = ctx->sceneStore->world.boxesInflate;
-    out[1] = ctx->sceneStore->sun.boxesInflate;
-    return ARK_DDGI_OK;
-}
-
-static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement);
-int ark_ddgi_debug_sun_cover_counts(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, true); }
-int ark_ddgi_debug_sun_cover_counts_device(ArkDdgiCtx* ctx, uint64_t* out) { return sunCoverCounts(ctx, out, false); }
-
-static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "cover counts before ark_ddgi_set_scene");
-    if (!ctx->coverCountsValid) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "cover counts: the last update was not a counting one (ark_ddgi_set_counting)");
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    std::fill(out, out + 12, 0ull);
-    const SceneStore& st = *ctx->sceneStore;
-    const FrameArgs& f = ctx->coverFrame;
-    uint32_t dc[3] = { 0, 0, 0 };
-    ARK_HIP(hipMemcpy(dc, f.cover_counts, sizeof(dc), hipMemcpyDeviceToHost));
-    const bool inUse = ctx->scene.sun_map != nullptr;
-    for (int k = 0; k < 3; ++k) out[k] = dc[k];
-    out[3] = inUse ? 1 : 0;
-    if (inUse) {
-        out[4] = st.coverMap.grid.nx;
-        out[5] = st.coverMap.grid.ny;
-        out[6] = st.coverMap.buf.bytes;
-        out[7] = static_cast<uint64_t>(st.coverMap.buildMs * 1000.0f);
-    }
-    if (!hostRestatement || !ctx->hasSun || f.window_rays == 0) return ARK_DDGI_OK;
-    // the host restatement: the update's sun-ray origins, the map of the installed records
-    DeviceBuffer pts;
-    ARK_HIP(pts.alloc(static_cast<size_t>(f.window_rays) * sizeof(float4)));
-    hipError_t e = launch_sun_points(f, pts.as<float4>(), nullptr);
-    std::vector<float> P(static_cast<size_t>(f.window_rays) * 4u);
-    if (e == hipSuccess) e = hipMemcpy(P.data(), pts.ptr, P.size() * 4u, hipMemcpyDeviceToHost);
-    pts.release();
-    ARK_HIP(e);
-    cover::Grid grid {};
-    std::vector<float> map;
-    bool ok = false;
-    float F[9] {};
-    if (inUse) {
-        std::vector<GpuTriangle> rec(st.world.records);
-        ARK_HIP(hipMemcpy(rec.data(), st.world.tris(st.world.buf), rec.size() * sizeof(GpuTriangle), hipMemcpyDeviceToHost));
-        double frame[3][3];
-        sun_frame(ctx->sunDir, frame);
-        float L[3];
-        sunRayDirection(ctx->sunDir, L);
-        ok = hostBuildCoverMap(rec.data(), rec.size(), &frame[0][0], L, cover::kDefaultBudget, grid, map) && 2.0f * ctx->desc.z_far >= grid.wExtent;
-        for (int k = 0; k < 9; ++k) F[k] = static_cast<float>((&frame[0][0])[k]);
-        if (ok) {
-            if (std::memcmp(&grid, &st.coverMap.grid, sizeof(grid)) != 0) {
-                out[11] = ~0ull;
-            } else {
-                std::vector<float> dmap(map.size());
-                ARK_HIP(hipMemcpy(dmap.data(), st.coverMap.buf.ptr, dmap.size() * 4u, hipMemcpyDeviceToHost));
-                for (size_t i = 0; i < map.size(); ++i) out[11] += cover::floatBits(map[i]) != cover::floatBits(dmap[i]);
-            }
-        }
-    }
-    const float lift = cover::kTmin + grid.margin, reach = cover::kTmin - grid.margin;
-    for (uint32_t i = 0; i < f.window_rays; ++i) {
-        const float* o = &P[4u * i];
-        if (o[3] == 0.0f) continue;
-        int vd = cover::kUndecided;
-        if (ok) {
-            // sunCoords
-            const float pl[3] = { std::fma(o[0], F[0], std::fma(o[1], F[1], o[2] * F[2])), std::fma(o[0], F[3], std::fma(o[1], F[4], o[2] * F[5])),
-                                  std::fma(o[0], F[6], std::fma(o[1], F[7], o[2] * F[8])) };
-            const int64_t c = cover::cellIndex(grid, pl[0], pl[1]);
-            if (c >= 0) vd = cover::verdict(pl[2], lift, reach, map[2 * c], map[2 * c + 1]);
-        }
-        out[vd == cover::kOccluded ? 8 : vd == cover::kLit ? 9 : 10]++;
-    }
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_debug_set_sun_only_small_windows(ArkDdgiCtx* ctx, int enabled)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->sunOnlySmallWindows = enabled != 0;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_debug_shade_schedule(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    out[0] = out[1] = 0;
-    if (!ctx->lastSunOnly) return ARK_DDGI_OK;
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    uint32_t n = 0;
-    ARK_HIP(hipMemcpy(&n, ctx->lastDeferredCount, sizeof(n), hipMemcpyDeviceToHost));
-    out[0] = 1;
-    out[1] = n;
-    return ARK_DDGI_OK;
-}
-
-uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z) { return seed::texelOf(x, y, z); }
-int ark_ddgi_debug_seed_candidate_ok(uint32_t word, uint32_t first, uint32_t end) { return seed::candidateOk(word, first, end) ? 1 : 0; }
-
-int ark_ddgi_debug_seed_info(ArkDdgiCtx* ctx, uint64_t* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    out[0] = ctx->seeds.ptr ? 1u : 0u;
-    out[1] = seed::kTexels;
-    out[2] = ctx->hasScene ? ctx->sceneStore->args.opaque_tri_first : 0u;
-    out[3] = ctx->hasScene ? ctx->sceneStore->args.opaque_tri_end : 0u;
-    out[4] = 0;
-    if (ctx->seeds.ptr && ctx->countersPending) {
-        uint32_t n = 0;
-        ARK_HIP(hipSetDevice(ctx->device));
-        ARK_HIP(hipDeviceSynchronize());
-        ARK_HIP(hipMemcpy(&n, ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 4u, sizeof(n), hipMemcpyDeviceToHost));
-        out[4] = n;
-    }
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_debug_seed_fill(ArkDdgiCtx* ctx, int mode, uint64_t value)
-{
-    if (!ctx || mode < 0 || mode > 2) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "seed fill before ark_ddgi_set_scene");
-    if (!ctx->seeds.ptr) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "the context keeps no seed cache (ARK_DDGI_FLAG_NO_RAY_SEEDS)");
-    const uint32_t first = ctx->sceneStore->args.opaque_tri_first, end = ctx->sceneStore->args.opaque_tri_end;
-    std::vector<uint32_t> words(ctx->seeds.bytes / 4, seed::kNone);
-    if (mode != 0 && end > first) {
-        uint64_t x = value * 0x9e3779b97f4a7c15ull + 0x632be59bd9b4e019ull; // splitmix64
-        for (uint32_t& w : words) {
-            if (mode == 2) {
-                w = static_cast<uint32_t>(value);
-            } else {
-                x += 0x9e3779b97f4a7c15ull;
-                uint64_t z = x;
-                z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-                z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-                z ^= z >> 31;
-                w = first + static_cast<uint32_t>(z % (end - first));
-            }
-            // only words the lookup would accept ever reach the device
-            if (!seed::candidateOk(w, first, end)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "seed fill: record %u outside the opaque class [%u, %u)", w, first, end);
-        }
-    }
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    ARK_HIP(hipMemcpy(ctx->seeds.ptr, words.data(), ctx->seeds.bytes, hipMemcpyHostToDevice));
-    ctx->seedStale = false; // (a whole cache of this record order's words)
-    ctx->seedTopologySeen = ctx->sceneStore->worldTopologySeq;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_update_geometry(ArkDdgiCtx* ctx, const ArkDdgiVertexUpdate* updates, uint32_t updateCount, const ArkRTInstance* instances, uint32_t count)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (const int rc = ark_ddgi_update_geometry_async(ctx, updates, updateCount, instances, count, ctx->stream)) return rc;
-    ARK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->bvhStats = ctx->sceneStore->bvhStats;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_set_instances(ArkDdgiCtx* ctx, const ArkRTInstance* instances, uint32_t count)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const auto t0 = std::chrono::steady_clock::now();
-    if (const int rc = ark_ddgi_set_instances_async(ctx, instances, count, ctx->stream)) return rc;
-    ARK_HIP(hipStreamSynchronize(ctx->stream));
-    ctx->sceneStore->bvhStats.refit_ms = std::chrono::duration<float, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    ctx->bvhStats = ctx->sceneStore->bvhStats;
-    return ARK_DDGI_OK;
-}
-
-static uint32_t countSlabProbes(const ArkDdgiCtx* ctx, uint32_t first, uint32_t K)
-{
-    if (ctx->desc.shard_count <= 1) return K;
-    return slabRankOf(static_cast<uint32_t>(ctx->X), static_cast<uint32_t>(ctx->Y), static_cast<uint32_t>(ctx->Z), static_cast<uint32_t>(ctx->slabZ0),
-                      static_cast<uint32_t>(ctx->slabZ1), first, K);
-}
-
-static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream, void* shadeWaitEvent, void* doneEvent, uint32_t shadeWaitSeq = 0);
-
-// Fail-closed frame sequencing (VERDICT r03 "do this" #3): a k_seq_wait that gave up
-// has set the context's timed-out word, so every path kernel that starts after it
-// skips (frameAborted) and leaves atlases, surfels and offsets as they were (a launch
-// already running when the wait gave up completes). The first context
-// call that sees the host-mapped flag drains the device (the late producer ends by
-// itself), clears both words, switches the context to event sequencing (which no
-// queue order can stall) and reports ARK_DDGI_E_DEVICE; the calls after it run.
-static int checkSequencing(ArkDdgiCtx* ctx)
-{
-    if (!ctx->hostAbort || __atomic_load_n(ctx->hostAbort, __ATOMIC_ACQUIRE) == 0u) return ARK_DDGI_OK;
-    ARK_HIP(hipSetDevice(ctx->device));
-    // the whole device (ADVICE r04 low asked for the context's own streams only): the
-    // late producer may sit on a caller's stream (an exchange stream) whose end the
-    // context recorded as a sequence word; once the context switches to events, nothing
-    // else would order the next frame's shading after it
-    ARK_HIP(hipDeviceSynchronize());
-    ARK_HIP(hipMemset(ctx->seqWords.as<uint32_t>() + 64, 0, 4));
-    __atomic_store_n(ctx->hostAbort, 0u, __ATOMIC_RELEASE);
-    ctx->seqSync = false;
-    ctx->pipeReady = false;
-    ++ctx->seqTimeouts;
-    return ctx->fail(ARK_DDGI_E_DEVICE,
-                     "a frame-sequencing wait between the context's streams gave up after %u ms: every update kernel that started after it skipped "
-                     "(its atlases, surfels and offsets left as they were); the context now orders its streams with events",
-                     ctx->seqTimeoutMs);
-}
-
-int ark_ddgi_set_sequencing(ArkDdgiCtx* ctx, int device_sequence_words, uint32_t timeout_ms)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (timeout_ms > 3600u * 1000u) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "sequencing timeout %u ms above one hour", timeout_ms);
-    ctx->seqSync = device_sequence_words != 0;
-    if (timeout_ms) {
-        ctx->seqTimeoutMs = timeout_ms;
-        ctx->seqTimeoutTicks = ctx->wallClockKhz * timeout_ms;
-    }
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_get_sequencing(const ArkDdgiCtx* ctx, int* out_device_sequence_words, uint32_t* out_timeout_ms, uint32_t* out_timeouts)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (out_device_sequence_words) *out_device_sequence_words = ctx->seqSync ? 1 : 0;
-    if (out_timeout_ms) *out_timeout_ms = ctx->seqTimeoutMs;
-    if (out_timeouts) *out_timeouts = ctx->seqTimeouts;
-    return ARK_DDGI_OK;
-}
-
-
-int ark_ddgi_update(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream)
-{
-    return updateImpl(ctx, p, hipStream, nullptr, nullptr);
-}
-
-int ark_ddgi_update_overlapped(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream, void* shadeWaitEvent, void* doneEvent)
-{
-    return updateImpl(ctx, p, hipStream, shadeWaitEvent, doneEvent);
-}
-
-int ark_ddgi_update_exchanged(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const uint32_t wait = ctx->pendingExchange;
-    // without sequence words the exchange's end is an event (ark_ddgi_exchange_end)
-    const int r = ctx->seqSync ? updateImpl(ctx, p, hipStream, nullptr, nullptr, wait)
-                               : updateImpl(ctx, p, hipStream, wait ? ctx->evExchangeDone : nullptr, nullptr);
-    if (r == ARK_DDGI_OK) ctx->pendingExchange = 0;
-    return r;
-}
-
-int ark_ddgi_exchange_begin(ArkDdgiCtx* ctx, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const hipStream_t x = streamOf(hipStream);
-    if (const int r = checkSequencing(ctx)) return r;
-    ARK_HIP(hipSetDevice(ctx->device));
-    if (ctx->lastMainSeq) {
-        uint32_t* w = ctx->seqWords.as<uint32_t>();
-        ARK_HIP(launch_seq_wait(w + 32, ctx->lastMainSeq, w + 64, ctx->hostAbortDev, ctx->seqTimeoutTicks, x));
-    } else {
-        // the last update was not sequenced: everything enqueued on its stream so far
-        ARK_HIP(hipEventRecord(ctx->evExchangeSrc, ctx->lastStream));
-        ARK_HIP(hipStreamWaitEvent(x, ctx->evExchangeSrc, 0));
-    }
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_exchange_end(ArkDdgiCtx* ctx, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ARK_HIP(hipSetDevice(ctx->device));
-    const uint32_t n = ++ctx->exchSeq;
-    if (ctx->seqSync) ARK_HIP(launch_seq_signal(ctx->seqWords.as<uint32_t>() + 96, n, streamOf(hipStream)));
-    else ARK_HIP(hipEventRecord(ctx->evExchangeDone, streamOf(hipStream)));
-    ctx->pendingExchange = n;
-    return ARK_DDGI_OK;
-}
-
-static ArkDdgiWindowExchange windowExchangeInfo(const ArkDdgiCtx* ctx)
-{
-    ArkDdgiWindowExchange w {};
-    w.struct_size = sizeof(w);
-    w.first_probe = ctx->lastFirst;
-    w.probe_updates = ctx->lastK;
-    const uint32_t P = static_cast<uint32_t>(ctx->desc.shard_count), Zs = static_cast<uint32_t>(ctx->Z) / P;
-    w.full_bands = ctx->lastK == static_cast<uint32_t>(ctx->N) ? 1u : 0u;
-    for (uint32_t q = 0; q < P; ++q) {
-        const uint32_t n = slabRankOf(static_cast<uint32_t>(ctx->X), static_cast<uint32_t>(ctx->Y), static_cast<uint32_t>(ctx->Z), q * Zs, (q + 1) * Zs, ctx->lastFirst,
-                                      ctx->lastK);
-        w.probes_per_rank = std::max(w.probes_per_rank, n);
-        if (q == static_cast<uint32_t>(ctx->desc.shard_rank)) w.my_probes = n;
-    }
-    w.bytes_per_rank = w.full_bands ? 0u : static_cast<uint64_t>(w.probes_per_rank) * kWindowPacketBytes;
-    return w;
-}
-
-int ark_ddgi_window_exchange_info(const ArkDdgiCtx* ctx, ArkDdgiWindowExchange* out)
-{
-    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
-    *out = windowExchangeInfo(ctx);
-    return ARK_DDGI_OK;
-}
-
-static int windowPack(ArkDdgiCtx* ctx, void* buf, uint64_t bytes, void* hipStream, bool unpack)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const ArkDdgiWindowExchange w = windowExchangeInfo(ctx);
-    if (w.full_bands) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "window exchange: the last window covered the grid (exchange the bands)");
-    const uint64_t need = unpack ? w.bytes_per_rank * static_cast<uint64_t>(ctx->desc.shard_count) : w.bytes_per_rank;
-    if (bytes != need) return ctx->fail(ARK_DDGI_E_SIZE_MISMATCH, "window exchange: %llu bytes, the window needs %llu", (unsigned long long)bytes, (unsigned long long)need);
-    if (need && !buf) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "window exchange: null buffer");
-    ARK_HIP(hipSetDevice(ctx->device));
-    WindowExchangeArgs a {};
-    a.X = ctx->X; a.Y = ctx->Y; a.Z = ctx->Z; a.N = ctx->N;
-    a.first = ctx->lastFirst;
-    a.K = ctx->lastK;
-    a.Wi = ctx->Wi; a.Wv = ctx->Wv;
-    a.slabDepth = static_cast<uint32_t>(ctx->Z / ctx->desc.shard_count);
-    a.rank = static_cast<uint32_t>(ctx->desc.shard_rank);
-    a.world = static_cast<uint32_t>(ctx->desc.shard_count);
-    a.bytesPerRank = w.bytes_per_rank;
-    a.irr = ctx->irr.as<uint16_t>();
-    a.vis = ctx->vis.as<uint16_t>();
-    a.buf = static_cast<uint8_t*>(buf);
-    if (need) ARK_HIP(launch_window_pack(a, unpack, streamOf(hipStream)));
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_pack_window(ArkDdgiCtx* ctx, void* dst, uint64_t bytes, void* hipStream) { return windowPack(ctx, dst, bytes, hipStream, false); }
-
-int ark_ddgi_unpack_window(ArkDdgiCtx* ctx, const void* src, uint64_t bytes, void* hipStream)
-{
-    return windowPack(ctx, const_cast<void*>(src), bytes, hipStream, true);
-}
-
-// The caller's stream s waits for the traversal stream's part of a pipelined frame
-// (slot table, traversal, offsets): device-side sequencing, or an event.
-static hipError_t tracedSync(ArkDdgiCtx* ctx, bool seq, uint32_t seqN, hipStream_t ts, hipStream_t s)
-{
-    if (seq) {
-        uint32_t* w = ctx->seqWords.as<uint32_t>();
-        hipError_t e = launch_seq_signal(w, seqN, ts);
-        return e != hipSuccess ? e : launch_seq_wait(w, seqN, w + 64, ctx->hostAbortDev, ctx->seqTimeoutTicks, s);
-    }
-    hipError_t e = hipEventRecord(ctx->evTraced, ts);
-    return e != hipSuccess ? e : hipStreamWaitEvent(s, ctx->evTraced, 0);
-}
-
-static int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream, void* shadeWaitEvent, void* doneEvent, uint32_t shadeWaitSeq)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!p || p->struct_size != sizeof(ArkDdgiFrameParams)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiFrameParams");
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_update before ark_ddgi_set_scene");
-    const uint32_t N = static_cast<uint32_t>(ctx->N);
-    const uint32_t K = std::min(p->probe_updates, N);
-    const uint32_t R = p->rays_per_probe;
-    if (K == 0 || R == 0 || K > static_cast<uint32_t>(ctx->Kmax) || R > static_cast<uint32_t>(ctx->Rmax))
-        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "probe_updates %u / rays_per_probe %u outside [1,%d] / [1,%d]", K, R, ctx->Kmax, ctx->Rmax);
-    const hipStream_t s = streamOf(hipStream);
-    if (const int r = checkSequencing(ctx)) return r;
-    ARK_HIP(hipSetDevice(ctx->device));
-    FrameArgs f {};
-    f.abort_word = ctx->seqWords.as<uint32_t>() + 64;
-    f.X = ctx->X; f.Y = ctx->Y; f.Z = ctx->Z;
-    f.Wi = ctx->Wi; f.Hi = ctx->Hi; f.Wv = ctx->Wv; f.Hv = ctx->Hv;
-    for (int k = 0; k < 3; ++k) {
-        f.spacing[k] = ctx->desc.probe_spacing[k];
-        f.origin[k] = ctx->desc.offset_to_first[k];
-    }
-    f.z_far = ctx->desc.z_far;
-    f.frame = p->frame_index;
-    f.first = p->first_probe_index % N;
-    f.window = K;
-    f.sharded = ctx->desc.shard_count > 1 ? 1 : 0;
-    f.slab_z0 = ctx->slabZ0;
-    f.slab_z1 = ctx->slabZ1;
-    f.window_probes = countSlabProbes(ctx, f.first, K);
-    f.R = R;
-    f.Rmax = static_cast<uint32_t>(ctx->Rmax);
-    f.window_rays = f.window_probes * R;
-    f.hysteresis_irradiance = p->hysteresis_irradiance;
-    f.hysteresis_visibility = p->hysteresis_visibility;
-    f.visibility_sharpness = p->visibility_sharpness;
-    f.ambient_amount = p->ambient_amount;
-    f.environment_multiplier = p->environment_multiplier;
-    f.delta_time = p->delta_time;
-    f.update_offsets = p->update_offsets;
-    f.irr = ctx->irr.as<uint16_t>();
-    f.vis = ctx->vis.as<uint16_t>();
-    f.offsets = ctx->offsets.as<float4>();
-    const bool timing = ctx->timing;
-    const bool count = ctx->counting;
-    // Frames in flight: this frame's slot table, traversal and probe offsets read the
-    // scene, the sample order and the probe offsets only, which nothing of the
-    // previous frame's shadow rays, shading or atlas update writes (its offsets ran
-    // before them). They may start before the previous frame is done when the sample
-    // order is the same and no other writing context operation came in between.
-    // Instrumented updates (per-kernel events, counters) run serially.
-    const bool pipe = ctx->pipelining && ctx->pipeReady && !timing && !count && R == ctx->prevR;
-    const uint32_t b = ctx->parity;
-    const uint64_t Kmax = static_cast<uint64_t>(ctx->Kmax), Rmax = static_cast<uint64_t>(ctx->Rmax);
-    f.slots = ctx->slots.as<GpuProbeSlot>() + b * Kmax;
-    f.fib = ctx->fib.as<float4>() + b * Rmax;
-    RoctxRange ddgiZone("DDGI");
-    ARK_HIP(orderBegin(ctx, s));
-    // finished background rebuilds installed (and refitted forward) on s, new ones started
-    if (const int rc = sceneMaintenance(*ctx->sceneStore, sceneCall(ctx), s)) return rc;
-    if (ctx->sceneVersion != ctx->sceneStore->version) // a rebuild installed above, or a sharing context refitted the scene or installed one
-        if (const int rc = refreshScene(ctx)) return rc;
-    // lights changed since the last update: stored ahead of this frame's shadow rays and
-    // shading on s (the traversal on the traversal stream reads no light)
-    ARK_HIP(flushLights(ctx, s));
-    if (ctx->orderR != R) {
-        sampleTraversalOrder(R, ctx->orderHost);
-        ARK_HIP(hipMemcpyAsync(ctx->order.ptr, ctx->orderHost.data(), R * 4, hipMemcpyHostToDevice, s));
-        ctx->orderR = R;
-    }
-    f.order = ctx->order.as<uint32_t>();
-    f.fib_order = ctx->fibOrder.as<float4>() + b * Rmax;
-    f.hits = ctx->hits.as<GpuHit>() + b * Kmax * Rmax;
-    f.surfels = ctx->surfels.as<uint16_t>();
-    f.spill = ctx->spill.as<uint32_t>() + ctx->spillRegionWords; // region 1 (primary traversal)
-    f.light_count = ctx->lightCount;
-    f.refill_min = ctx->refillMin;
-    f.sun_refill_min = ctx->sunRefillMin;
-    // a half-occupancy window (below kPipeHalfRays) hands out 32 rays per partition-head
-    // grab to the probe-ray and shadow-ray queues (K = 2048 windows 0.429 -> 0.420 ms;
-    // the whole grid keeps 64: 4.13 vs 4.18 ms at 32, profiles/r02_m19)
-    f.grab_chunk = (pipe && f.window_rays < kPipeHalfRays) ? std::min<uint32_t>(ctx->grabChunk, 32u) : ctx->grabChunk;
-    f.ray_counter = ctx->rayCounter.as<uint32_t>() + b * kRayCounterWords;
-    f.counters = ctx->counters.as<unsigned long long>();
-    f.ray_steps = count ? ctx->raySteps.as<uint16_t>() : nullptr;
-    // (counters.ptr is cleared below when counting: the cover map's counts are its last three
-    // words, the seed candidates' count the word before them)
-    f.seed_cache = ctx->seeds.as<uint32_t>();
-    f.seed_offsets_write = f.seed_cache && f.update_offsets && ctx->scene.root_masked < 0 ? 1u : 0u;
-    f.seed_counts = count && f.seed_cache ? ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 4u : nullptr;
-    f.cover_counts = count ? ctx->counters.as<uint32_t>() + ctx->counters.bytes / 4u - 3u : nullptr;
-    ctx->coverCountsValid = count;
-    // shading work set (ensureShadeWork): per-ray light bits | shadow-ray list
-    {
-        const ShadeWorkLayout l = shadeWorkLayout(ctx);
-        char* w = static_cast<char*>(ctx->shadeWork.ptr);
-        f.shadow_bits = reinterpret_cast<uint32_t*>(w + l.bits);
-        f.shadow_rays = reinterpret_cast<ShadowRay*>(w + l.list);
-    }
-    f.shadow_count = f.ray_counter + kShadowCountWord;
-    f.shadow_heads = f.ray_counter + kShadowHeadWord;
-    // the sun's shadow rays in their own list (the first Kmax x Rmax entries of the
-    // list area, the other lights' after them) for the light-space BVH
-    if (ctx->scene.sun_root >= 0) {
-        f.sun_rays = f.shadow_rays;
-        f.shadow_rays += Kmax * Rmax;
-        f.sun_count = f.ray_counter + kSunCountWord;
-        f.sun_heads = f.ray_counter + kSunHeadWord;
-    }
-    // the slot table and the primary traversal: on traceStream after frame n - 2 (the
-    // last user of buffer set b) when pipelined, else in line on the caller's stream
-    const hipStream_t ts = pipe ? ctx->traceStream : s;
-    uint32_t* seqTrace = ctx->seqWords.as<uint32_t>();
-    uint32_t* seqMain = seqTrace + 32;
-    uint32_t* seqTimedOut = seqTrace + 64;
-    const bool seq = pipe && ctx->seqSync;
-    const uint32_t seqN = seq ? ++ctx->frameSeq : 0u;
-    if (pipe && ctx->setSeqValid[b]) ARK_HIP(launch_seq_wait(seqMain, ctx->setSeq[b], seqTimedOut, ctx->hostAbortDev, ctx->seqTimeoutTicks, ts));
-    else if (pipe && ctx->frameDoneValid[b]) ARK_HIP(hipStreamWaitEvent(ts, ctx->evFrameDone[b], 0));
-    // a serial previous frame wrote its offsets on the caller's stream
-    if (pipe && !ctx->prevPipelined && ctx->frameDoneValid[b ^ 1u]) ARK_HIP(hipStreamWaitEvent(ts, ctx->evFrameDone[b ^ 1u], 0));
-    // a refit or an installed rebuild of the scene enqueued since this context's last
-    // update (on any stream, by any context sharing the scene): the traversal reads the
-    // BVH it writes
-    if (ctx->geometrySeen != ctx->sceneStore->geometrySeq) {
-        ARK_HIP(hipStreamWaitEvent(ts, ctx->sceneStore->evGeometry, 0));
-        ctx->geometrySeen = ctx->sceneStore->geometrySeq;
-    }
-    // a new record order of the world BVHs (set_scene, an installed rebuild - this context's
-    // above, or a sharing context's): the cached record indices are the old order's. The
-    // traversals of a context run one after the other (they share a spill region), so on ts
-    // the fill follows the last traversal that wrote old indices and precedes the first
-    // that reads the new tree.
-    if (f.seed_cache && (ctx->seedStale || ctx->seedTopologySeen != ctx->sceneStore->worldTopologySeq)) {
-        ARK_HIP(launch_fill_u32(ctx->seeds.ptr, ctx->seeds.bytes / 4, seed::kNone, ts));
-        ctx->seedStale = false;
-        ctx->seedTopologySeen = ctx->sceneStore->worldTopologySeq;
-    }
-    if (count) ARK_HIP(hipMemsetAsync(ctx->counters.ptr, 0, ctx->counters.bytes, s));
-    // (k_probe_slots zeroes f.ray_counter)
-    if (timing) ARK_HIP(hipEventRecord(ctx->ev[0], s));
-    f.slot_order = ctx->slotOrder.as<uint32_t>() + b * Kmax; // written by k_probe_slots
-    ARK_HIP(launch_probe_slots(f, ts));
-    if (f.window_probes > 0) {
-        RoctxRange traceZone("Trace rays");
-        const bool half = pipe && f.window_rays < kPipeHalfRays;
-        ARK_HIP(launch_trace(ctx->scene, f, half ? ctx->pipeTraceBlocks : ctx->traceBlocks, count, ts));
-        if (pipe) {
-            // probeUpdateOffset (k_probe_offsets: from the hit records), so that the
-            // next frame's slot table may follow on this stream. The rest of the frame
-            // needs only the hit records, but waiting for the offsets too costs less
-            // (7 us) than a second cross-stream wait for them at the end of the frame
-            // (each wait ~11 us of queue latency, satisfied or not: profiles/r03_v)
-            ARK_HIP(launch_probe_offsets(f, ts));
-            ARK_HIP(tracedSync(ctx, seq, seqN, ts, s));
-        }
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[1], s));
-        FrameArgs fs = f;
-        fs.spill = ctx->spill.as<uint32_t>(); // region 0
-        if (count) ctx->coverFrame = fs;
-        // the sun alone, with its cover map: shading resolves the sun's rays itself, and
-        // only what the map leaves undecided is listed, traced and shaded in a second pass
-        // (not beside a half-occupancy traversal: shade_schedule.h)
-        const bool sunOnly = shadeScheduleOf({ f.light_count, ctx->scene.has_sun != 0, ctx->scene.sun_map != nullptr, ctx->desc.flags, half,
-                                               ctx->sunOnlySmallWindows }) == ShadeSchedule::SunOnly;
-        ctx->lastSunOnly = sunOnly;
-        ctx->lastDeferredCount = fs.sun_rays ? fs.sun_count : fs.shadow_count;
-        if (f.light_count > 0 && !sunOnly) {
-            ARK_HIP(launch_shadow_gen(ctx->scene, fs, s));
-            // (the grid stays sized by the window although the cover map leaves a few percent of
-            // the sun's rays on the list: an eighth of it measured the same, EXPERIMENTS.md)
-            ARK_HIP(launch_trace_shadow(ctx->scene, fs, count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays), count, s));
-        }
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[5], s));
-        // shading reads the previous frame's atlases at arbitrary probes: on a Z-slab
-        // rank it waits here for the previous exchange (the traversal above did not)
-        if (shadeWaitEvent) ARK_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(shadeWaitEvent), 0));
-        if (shadeWaitSeq) ARK_HIP(launch_seq_wait(seqTrace + 96, shadeWaitSeq, seqTimedOut, ctx->hostAbortDev, ctx->seqTimeoutTicks, s));
-        ARK_HIP(launch_shade(ctx->scene, fs, ctx->shadeBlocks, count, s, sunOnly));
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[2], s));
-        if (sunOnly) {
-            // (timings: "shade" is pass 1, "shadow" the traversal and the deferred pass)
-            ARK_HIP(launch_trace_shadow(ctx->scene, fs, count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays), count, s));
-            ARK_HIP(launch_shade_deferred(ctx->scene, fs, s));
-        }
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[4], s));
-        traceZone.end();
-        // probeUpdateOffset (serial frames), probeUpdateIrradiance/Visibility + border
-        // corners/edges, fused
-        RoctxRange updateZone("Update probes");
-        if (!pipe) ARK_HIP(launch_probe_offsets(fs, s));
-        ARK_HIP(launch_probe_update(fs, s));
-    } else {
-        ctx->lastSunOnly = false;
-        if (pipe) ARK_HIP(tracedSync(ctx, seq, seqN, ts, s));
-        if (shadeWaitEvent) ARK_HIP(hipStreamWaitEvent(s, static_cast<hipEvent_t>(shadeWaitEvent), 0));
-        if (shadeWaitSeq) ARK_HIP(launch_seq_wait(seqTrace + 96, shadeWaitSeq, seqTimedOut, ctx->hostAbortDev, ctx->seqTimeoutTicks, s));
-        if (timing) {
-            ARK_HIP(hipEventRecord(ctx->ev[1], s));
-            ARK_HIP(hipEventRecord(ctx->ev[5], s));
-            ARK_HIP(hipEventRecord(ctx->ev[2], s));
-            ARK_HIP(hipEventRecord(ctx->ev[4], s));
-        }
-    }
-    if (timing) ARK_HIP(hipEventRecord(ctx->ev[3], s));
-    if (seq) {
-        ARK_HIP(launch_seq_signal(seqMain, seqN, s));
-        ctx->setSeq[b] = seqN;
-        ctx->setSeqValid[b] = true;
-    } else {
-        ARK_HIP(hipEventRecord(ctx->evFrameDone[b], s));
-        ctx->setSeqValid[b] = false;
-    }
-    ctx->frameDoneValid[b] = true;
-    ctx->lastMainSeq = seq ? seqN : 0u;
-    ctx->lastStream = s;
-    if (doneEvent) ARK_HIP(hipEventRecord(static_cast<hipEvent_t>(doneEvent), s));
-    ARK_HIP(orderEnd(ctx, s));
-    ctx->parity = b ^ 1u;
-    ctx->pipeReady = true;
-    ctx->prevR = R;
-    ctx->prevPipelined = pipe;
-    ctx->lastParity = b;
-    ctx->timingValid = timing;
-    ctx->countersPending = count;
-    ctx->lastRays = f.window_rays;
-    ctx->lastProbes = f.window_probes;
-    ctx->nextProbeIndex = (f.first + K) % N;
-    ctx->lastFirst = f.first;
-    ctx->lastK = K;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_mark_external_write(ArkDdgiCtx* ctx)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_synchronize(ArkDdgiCtx* ctx)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    return checkSequencing(ctx);
-}
-
 static int resourceInfo(const ArkDdgiCtx* ctx, int which, void** ptr, uint64_t* bytes)
 {
     switch (which) {
@@ -1476,7 +526,7 @@ static int resourceInfo(const ArkDdgiCtx* ctx, int which, void** ptr, uint64_t* 
     case ARK_DDGI_ATLAS_VISIBILITY: *ptr = ctx->vis.ptr; *bytes = ctx->vis.bytes; return 0;
     case ARK_DDGI_SURFELS: *ptr = ctx->surfels.ptr; *bytes = ctx->surfels.bytes; return 0;
     case ARK_DDGI_PROBE_OFFSETS: *ptr = ctx->offsets.ptr; *bytes = ctx->offsets.bytes; return 0;
-    case ARK_DDGI_DEBUG_HITS: *ptr = ctx->hits.as<GpuHit>() + static_cast<uint64_t>(ctx->lastParity) * ctx->Kmax * ctx->Rmax; *bytes = ctx->hits.bytes / 2; return 0;
+    case ARK_DDGI_DEBUG_HITS: *ptr = ctx->hits.as<GpuHit>() + static_cast<uint64_t>(ctx->frames.lastSet()) * ctx->Kmax * ctx->Rmax; *bytes = ctx->hits.bytes / 2; return 0;
     case ARK_DDGI_DEBUG_RAY_STEPS: *ptr = ctx->raySteps.ptr; *bytes = ctx->raySteps.bytes; return ctx->raySteps.ptr ? 0 : ARK_DDGI_E_INVALID_ARGUMENT;
     default: return ARK_DDGI_E_INVALID_ARGUMENT;
     }
@@ -1505,7 +555,7 @@ int ark_ddgi_read(ArkDdgiCtx* ctx, int which, void* dst, uint64_t bytes)
 int ark_ddgi_write(ArkDdgiCtx* ctx, int which, const void* src, uint64_t bytes)
 {
     if (!ctx || !src) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
+    ctx->frames.externalWrite();
     void* p;
     uint64_t n;
     if (resourceInfo(ctx, which, &p, &n) != 0) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "unknown resource %d", which);
@@ -1582,7 +632,7 @@ int ark_ddgi_save_state(ArkDdgiCtx* ctx, void* dst, uint64_t bytes)
 int ark_ddgi_load_state(ArkDdgiCtx* ctx, const void* src, uint64_t bytes)
 {
     if (!ctx || !src) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
+    ctx->frames.externalWrite();
     uint64_t need = 0;
     ark_ddgi_state_size(ctx, &need);
     if (bytes != need) return ctx->fail(ARK_DDGI_E_SIZE_MISMATCH, "state is %llu bytes, got %llu", (unsigned long long)need, (unsigned long long)bytes);
@@ -1638,7 +688,7 @@ int ark_ddgi_get_device_views(ArkDdgiCtx* ctx, ArkDdgiDeviceViews* v)
 int ark_ddgi_reset_history(ArkDdgiCtx* ctx)
 {
     if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    ctx->pipeReady = false; // the next update's traversal waits for this
+    ctx->frames.externalWrite();
     ARK_HIP(hipSetDevice(ctx->device));
     ARK_HIP(hipDeviceSynchronize());
     return clearHistory(ctx);
@@ -1711,192 +761,6 @@ int ark_ddgi_get_bvh_stats(ArkDdgiCtx* ctx, ArkDdgiBvhStats* out)
 {
     if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
     *out = ctx->hasScene ? ctx->sceneStore->bvhStats : ctx->bvhStats; // the store's: installs and refits of any sharing context
-    return ARK_DDGI_OK;
-}
-
-// AO / bent-normal bake (include/ark_ddgi.h; BakeAmbientOcclusionNode.cpp:15-131):
-// raster -> barycentrics (+ covered-texel list) -> persistent AO rays, one stream.
-int ark_ddgi_bake_ao(ArkDdgiCtx* ctx, const ArkBakeAoDesc* d, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!d || d->struct_size != sizeof(ArkBakeAoDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkBakeAoDesc");
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: no scene");
-    if (d->instance_index >= ctx->sceneStore->instHost.size()) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: instance %u out of range", d->instance_index);
-    if (d->width == 0 || d->height == 0 || d->width > 16384 || d->height > 16384 || d->sample_count == 0)
-        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: extent %ux%u / %u samples", d->width, d->height, d->sample_count);
-    const ArkRTInstance& inst = ctx->sceneStore->instHost[d->instance_index];
-    const ArkRTTriangleMesh& mesh = ctx->sceneStore->meshHost[inst.rt_mesh_index];
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    if (ctx->sceneVersion != ctx->sceneStore->version) // a sharing context refitted the scene or installed a deeper sun BVH
-        if (const int rc = refreshScene(ctx)) return rc;
-    ARK_HIP(orderBegin(ctx, s));
-    const size_t texels = static_cast<size_t>(d->width) * d->height;
-    const size_t outBytes = texels * (d->bent_normals ? 4 : 1);
-    if (ctx->bakeTri.bytes < texels * 4) ARK_HIP(ctx->bakeTri.alloc(texels * 4));
-    if (ctx->bakeBary.bytes < texels * 8) ARK_HIP(ctx->bakeBary.alloc(texels * 8));
-    if (ctx->bakeOut.bytes < outBytes) ARK_HIP(ctx->bakeOut.alloc(outBytes));
-    if (ctx->bakePixels.bytes < texels * 4) ARK_HIP(ctx->bakePixels.alloc(texels * 4));
-    if (ctx->bakeCounters.bytes < 256) ARK_HIP(ctx->bakeCounters.alloc(256));
-    ARK_HIP(hipMemsetAsync(ctx->bakeTri.ptr, 0, texels * 4, s)); // ClearValue::blackAtMaxDepth
-    ARK_HIP(hipMemsetAsync(ctx->bakeCounters.ptr, 0, 256, s));
-    BakeArgs b {};
-    b.W = d->width;
-    b.H = d->height;
-    b.samples = d->sample_count;
-    b.tri_count = inst.triangle_count;
-    b.bent = d->bent_normals ? 1 : 0;
-    b.first_index = static_cast<uint32_t>(mesh.first_index);
-    b.first_vertex = static_cast<uint32_t>(mesh.first_vertex);
-    b.indices = ctx->sceneStore->indices.as<uint32_t>();
-    b.positions = ctx->sceneStore->positions.as<float>();
-    b.vertices = ctx->sceneStore->vertices.as<float>();
-    b.tri_idx = ctx->bakeTri.as<uint32_t>();
-    b.bary = ctx->bakeBary.as<uint16_t>();
-    b.out = ctx->bakeOut.as<uint8_t>();
-    b.pixels = ctx->bakePixels.as<uint32_t>();
-    b.counters = ctx->bakeCounters.as<uint32_t>();
-    b.spill = ctx->spill.as<uint32_t>();
-    if (b.tri_count > 0) ARK_HIP(launch_bake(ctx->scene, b, 0, 0, s));
-    ARK_HIP(launch_bake(ctx->scene, b, 0, 1, s));
-    // the persistent AO kernel uses the traversal spill area sized for shadowBlocks workgroups
-    ARK_HIP(launch_bake(ctx->scene, b, ctx->shadowBlocks, 2, s));
-    ARK_HIP(scenePositionsRead(*ctx->sceneStore, s)); // (the next vertex update's positions follow the bake)
-    ARK_HIP(orderEnd(ctx, s));
-    ctx->bakeW = d->width;
-    ctx->bakeH = d->height;
-    ctx->bakeBent = b.bent;
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_bake_read(ArkDdgiCtx* ctx, int which, void* dst, uint64_t bytes)
-{
-    if (!ctx || !dst) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const size_t texels = static_cast<size_t>(ctx->bakeW) * ctx->bakeH;
-    const void* src = nullptr;
-    size_t n = 0;
-    switch (which) {
-    case ARK_BAKE_TRIANGLE_INDEX: src = ctx->bakeTri.ptr; n = texels * 4; break;
-    case ARK_BAKE_BARYCENTRICS: src = ctx->bakeBary.ptr; n = texels * 8; break;
-    case ARK_BAKE_OUTPUT: src = ctx->bakeOut.ptr; n = texels * (ctx->bakeBent ? 4 : 1); break;
-    default: return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: unknown resource %d", which);
-    }
-    if (texels == 0) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: no bake yet");
-    if (bytes != n) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: %llu bytes, resource has %zu", static_cast<unsigned long long>(bytes), n);
-    ARK_HIP(hipSetDevice(ctx->device));
-    ARK_HIP(hipDeviceSynchronize());
-    ARK_HIP(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_lighting_compose(ArkDdgiCtx* ctx, const ArkComposeDesc* desc, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!desc || desc->struct_size != sizeof(ArkComposeDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkComposeDesc");
-    if (!desc->out) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "lighting_compose: no output plane");
-    if (static_cast<uint64_t>(desc->width) * desc->height >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "lighting_compose: target too large");
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    // the DDGISamplingSet (DDGINode.cpp:45-66): grid constants + both atlases
-    FrameArgs f {};
-    f.X = ctx->X; f.Y = ctx->Y; f.Z = ctx->Z;
-    f.Wi = ctx->Wi; f.Hi = ctx->Hi; f.Wv = ctx->Wv; f.Hv = ctx->Hv;
-    for (int k = 0; k < 3; ++k) {
-        f.spacing[k] = ctx->desc.probe_spacing[k];
-        f.origin[k] = ctx->desc.offset_to_first[k];
-    }
-    f.irr = ctx->irr.as<uint16_t>();
-    f.vis = ctx->vis.as<uint16_t>();
-    ArkComposeDesc c = *desc;
-    ARK_HIP(orderBegin(ctx, s));
-    ARK_HIP(launch_lighting_compose(f, c, s));
-    ARK_HIP(orderEnd(ctx, s));
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_rt_reflections(ArkDdgiCtx* ctx, const ArkReflectionsDesc* desc, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!desc || desc->struct_size != sizeof(ArkReflectionsDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkReflectionsDesc");
-    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "rt_reflections before ark_ddgi_set_scene");
-    if (!desc->out_radiance || !desc->out_direction) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: no output image");
-    if (desc->blue_noise && (desc->noise_width == 0 || desc->noise_height == 0)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: empty blue noise");
-    if (static_cast<uint64_t>(desc->width) * desc->height >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: target too large");
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    int rc;
-    // the scene first: a sharing context's deeper sun BVH may grow,
-    // i.e. reallocate, the spill area that f.spill points into below
-    if (ctx->sceneVersion != ctx->sceneStore->version) {
-        if ((rc = refreshScene(ctx)) != 0) return rc;
-    } else if ((rc = ensureSpill(ctx)) != 0) {
-        return rc;
-    }
-    FrameArgs f {};
-    f.X = ctx->X; f.Y = ctx->Y; f.Z = ctx->Z;
-    f.Wi = ctx->Wi; f.Hi = ctx->Hi; f.Wv = ctx->Wv; f.Hv = ctx->Hv;
-    for (int k = 0; k < 3; ++k) {
-        f.spacing[k] = ctx->desc.probe_spacing[k];
-        f.origin[k] = ctx->desc.offset_to_first[k];
-    }
-    f.irr = ctx->irr.as<uint16_t>();
-    f.vis = ctx->vis.as<uint16_t>();
-    f.z_far = ctx->desc.z_far;
-    f.ambient_amount = desc->ambient_amount;
-    f.environment_multiplier = desc->environment_multiplier;
-    f.spill = ctx->spill.as<uint32_t>();
-    // ray-list work set (ensureReflWork): rays, hit records, light bits, shadow rays, counters
-    const uint64_t pixels = static_cast<uint64_t>(desc->width) * desc->height;
-    if (pixels == 0) return ARK_DDGI_OK;
-    if ((rc = ensureReflWork(ctx, pixels)) != 0) return rc;
-    {
-        char* w = static_cast<char*>(ctx->reflWork.ptr);
-        auto take = [&](uint64_t bytes) {
-            char* q = w;
-            w += (bytes + 255) & ~static_cast<uint64_t>(255);
-            return q;
-        };
-        f.ray_list = reinterpret_cast<const float4*>(take(pixels * 32));
-        f.hits = reinterpret_cast<GpuHit*>(take(pixels * sizeof(GpuHit)));
-        f.shadow_bits = reinterpret_cast<uint32_t*>(take(pixels * 4));
-        f.ray_counter = reinterpret_cast<uint32_t*>(take((kRayCounterWords + kRayCounterStride) * 4));
-        f.shadow_rays = reinterpret_cast<ShadowRay*>(take(pixels * ctx->lightCount * sizeof(ShadowRay)));
-    }
-    f.shadow_count = f.ray_counter + kShadowCountWord;
-    f.shadow_heads = f.ray_counter + kShadowHeadWord;
-    f.list_count = f.ray_counter + kRayCounterWords;
-    f.light_count = ctx->lightCount;
-    f.refill_min = ctx->refillMin;
-    f.sun_refill_min = ctx->sunRefillMin;
-    f.grab_chunk = ctx->grabChunk;
-    f.counters = ctx->counters.as<unsigned long long>();
-    ARK_HIP(orderBegin(ctx, s));
-    ARK_HIP(flushLights(ctx, s));
-    ARK_HIP(hipMemsetAsync(f.ray_counter, 0, (kRayCounterWords + kRayCounterStride) * 4, s));
-    ARK_HIP(launch_rt_reflections(ctx->scene, f, *desc, ctx->traceBlocks, shadowBlocksFor(ctx, pixels), s));
-    ARK_HIP(orderEnd(ctx, s));
-    return ARK_DDGI_OK;
-}
-
-int ark_ddgi_probe_debug(ArkDdgiCtx* ctx, const ArkProbeDebugDesc* desc, void* hipStream)
-{
-    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
-    if (!desc || desc->struct_size != sizeof(ArkProbeDebugDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkProbeDebugDesc");
-    if (desc->count && (!desc->probe_indices || !desc->directions || !desc->out)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "probe_debug: null plane");
-    const hipStream_t s = streamOf(hipStream);
-    ARK_HIP(hipSetDevice(ctx->device));
-    FrameArgs f {};
-    f.X = ctx->X; f.Y = ctx->Y; f.Z = ctx->Z;
-    f.Wi = ctx->Wi; f.Hi = ctx->Hi; f.Wv = ctx->Wv; f.Hv = ctx->Hv;
-    for (int k = 0; k < 3; ++k) {
-        f.spacing[k] = ctx->desc.probe_spacing[k];
-        f.origin[k] = ctx->desc.offset_to_first[k];
-    }
-    f.irr = ctx->irr.as<uint16_t>();
-    f.vis = ctx->vis.as<uint16_t>();
-    ARK_HIP(orderBegin(ctx, s));
-    ARK_HIP(launch_probe_debug(f, *desc, s));
-    ARK_HIP(orderEnd(ctx, s));
     return ARK_DDGI_OK;
 }
 

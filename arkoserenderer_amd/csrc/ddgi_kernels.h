@@ -265,7 +265,7 @@ struct FrameArgs {
     const uint32_t* abort_word;
 };
 
-// Fail-closed frame sequencing (ark_ddgi.cpp updateImpl): true when a frame-sequencing
+// Fail-closed frame sequencing (ddgi_frame.cpp checkSequencing): true when a frame-sequencing
 // wait of this context has timed out, so this launch must not compute (its inputs may
 // not be ready). Read once per workgroup by thread 0 and broadcast through LDS, so the
 // workgroup takes one decision (its waves share barriers further on).

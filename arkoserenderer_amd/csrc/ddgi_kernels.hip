@@ -2278,7 +2278,7 @@ __global__ void __launch_bounds__(256) k_sun_points(FrameArgs f, float4* __restr
     out[pos] = o;
 }
 
-// Frame sequencing between a context's two streams (ark_ddgi.cpp updateImpl): the
+// Frame sequencing between a context's two streams (ddgi_frame.cpp, frame_book.h): the
 // producer stream ends its part of frame n with k_seq_signal (word = n, a release
 // store after the kernels before it on that stream), the consumer stream starts with
 // k_seq_wait (one wave polls the word with acquire loads until it reaches n). A
@@ -2291,7 +2291,7 @@ __global__ void __launch_bounds__(256) k_sun_points(FrameArgs f, float4* __restr
 // when an earlier wait of the context already gave up) it sets *timed_out, which
 // every kernel of the path checks at entry (frameAborted: the frame's remaining
 // launches leave their outputs untouched), and the host-mapped *host_flag, which the
-// context's next call polls (ark_ddgi.cpp checkSequencing: ARK_DDGI_E_DEVICE, then
+// context's next call polls (ddgi_frame.cpp checkSequencing: ARK_DDGI_E_DEVICE, then
 // event sequencing). Signals are never skipped, so the sequence words stay in step.
 __global__ void __launch_bounds__(64) k_seq_signal(uint32_t* word, uint32_t value)
 {

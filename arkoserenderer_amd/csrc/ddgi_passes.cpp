@@ -1,0 +1,185 @@
+// ddgi_passes.cpp — the context's passes beside the update: the AO / bent-normal bake and
+// its read-back, the DDGI consumers (lighting compose, RT reflections) and the probe debug
+// view. Each is enqueued whole on the caller's stream, in call order (orderBegin / orderEnd).
+#include "ddgi_context.h"
+
+namespace {
+
+// RT reflections' ray-list work set for `pixels` rays (ark_ddgi_rt_reflections)
+int ensureReflWork(ArkDdgiCtx* ctx, uint64_t pixels)
+{
+    if (pixels >= (1ull << 28) && ctx->lightCount > 0)
+        return ctx->fail(ARK_DDGI_E_UNSUPPORTED, "%llu reflection rays: shadow-ray owners pack (ray << 4) | light in 32 bits", static_cast<unsigned long long>(pixels));
+    auto al = [](uint64_t b) { return (b + 255) & ~static_cast<uint64_t>(255); };
+    const uint64_t bytes = al(pixels * 32) + al(pixels * sizeof(GpuHit)) + al(pixels * 4) + al((kRayCounterWords + kRayCounterStride) * 4) +
+                           al(pixels * ctx->lightCount * sizeof(ShadowRay));
+    if (ctx->reflWork.bytes < bytes) ARK_HIP(ctx->reflWork.alloc(bytes));
+    return ARK_DDGI_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+// AO / bent-normal bake (include/ark_ddgi.h; BakeAmbientOcclusionNode.cpp:15-131):
+// raster -> barycentrics (+ covered-texel list) -> persistent AO rays, one stream.
+int ark_ddgi_bake_ao(ArkDdgiCtx* ctx, const ArkBakeAoDesc* d, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!d || d->struct_size != sizeof(ArkBakeAoDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkBakeAoDesc");
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: no scene");
+    if (d->instance_index >= ctx->sceneStore->instHost.size()) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: instance %u out of range", d->instance_index);
+    if (d->width == 0 || d->height == 0 || d->width > 16384 || d->height > 16384 || d->sample_count == 0)
+        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake: extent %ux%u / %u samples", d->width, d->height, d->sample_count);
+    const ArkRTInstance& inst = ctx->sceneStore->instHost[d->instance_index];
+    const ArkRTTriangleMesh& mesh = ctx->sceneStore->meshHost[inst.rt_mesh_index];
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    if (ctx->sceneVersion != ctx->sceneStore->version) // a sharing context refitted the scene or installed a deeper sun BVH
+        if (const int rc = refreshScene(ctx)) return rc;
+    ARK_HIP(orderBegin(ctx, s));
+    const size_t texels = static_cast<size_t>(d->width) * d->height;
+    const size_t outBytes = texels * (d->bent_normals ? 4 : 1);
+    if (ctx->bakeTri.bytes < texels * 4) ARK_HIP(ctx->bakeTri.alloc(texels * 4));
+    if (ctx->bakeBary.bytes < texels * 8) ARK_HIP(ctx->bakeBary.alloc(texels * 8));
+    if (ctx->bakeOut.bytes < outBytes) ARK_HIP(ctx->bakeOut.alloc(outBytes));
+    if (ctx->bakePixels.bytes < texels * 4) ARK_HIP(ctx->bakePixels.alloc(texels * 4));
+    if (ctx->bakeCounters.bytes < 256) ARK_HIP(ctx->bakeCounters.alloc(256));
+    ARK_HIP(hipMemsetAsync(ctx->bakeTri.ptr, 0, texels * 4, s)); // ClearValue::blackAtMaxDepth
+    ARK_HIP(hipMemsetAsync(ctx->bakeCounters.ptr, 0, 256, s));
+    BakeArgs b {};
+    b.W = d->width;
+    b.H = d->height;
+    b.samples = d->sample_count;
+    b.tri_count = inst.triangle_count;
+    b.bent = d->bent_normals ? 1 : 0;
+    b.first_index = static_cast<uint32_t>(mesh.first_index);
+    b.first_vertex = static_cast<uint32_t>(mesh.first_vertex);
+    b.indices = ctx->sceneStore->indices.as<uint32_t>();
+    b.positions = ctx->sceneStore->positions.as<float>();
+    b.vertices = ctx->sceneStore->vertices.as<float>();
+    b.tri_idx = ctx->bakeTri.as<uint32_t>();
+    b.bary = ctx->bakeBary.as<uint16_t>();
+    b.out = ctx->bakeOut.as<uint8_t>();
+    b.pixels = ctx->bakePixels.as<uint32_t>();
+    b.counters = ctx->bakeCounters.as<uint32_t>();
+    b.spill = ctx->spill.as<uint32_t>();
+    if (b.tri_count > 0) ARK_HIP(launch_bake(ctx->scene, b, 0, 0, s));
+    ARK_HIP(launch_bake(ctx->scene, b, 0, 1, s));
+    // the persistent AO kernel uses the traversal spill area sized for shadowBlocks workgroups
+    ARK_HIP(launch_bake(ctx->scene, b, ctx->shadowBlocks, 2, s));
+    ARK_HIP(scenePositionsRead(*ctx->sceneStore, s)); // (the next vertex update's positions follow the bake)
+    ARK_HIP(orderEnd(ctx, s));
+    ctx->bakeW = d->width;
+    ctx->bakeH = d->height;
+    ctx->bakeBent = b.bent;
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_bake_read(ArkDdgiCtx* ctx, int which, void* dst, uint64_t bytes)
+{
+    if (!ctx || !dst) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const size_t texels = static_cast<size_t>(ctx->bakeW) * ctx->bakeH;
+    const void* src = nullptr;
+    size_t n = 0;
+    switch (which) {
+    case ARK_BAKE_TRIANGLE_INDEX: src = ctx->bakeTri.ptr; n = texels * 4; break;
+    case ARK_BAKE_BARYCENTRICS: src = ctx->bakeBary.ptr; n = texels * 8; break;
+    case ARK_BAKE_OUTPUT: src = ctx->bakeOut.ptr; n = texels * (ctx->bakeBent ? 4 : 1); break;
+    default: return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: unknown resource %d", which);
+    }
+    if (texels == 0) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: no bake yet");
+    if (bytes != n) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bake_read: %llu bytes, resource has %zu", static_cast<unsigned long long>(bytes), n);
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    ARK_HIP(hipMemcpy(dst, src, n, hipMemcpyDeviceToHost));
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_lighting_compose(ArkDdgiCtx* ctx, const ArkComposeDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkComposeDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkComposeDesc");
+    if (!desc->out) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "lighting_compose: no output plane");
+    if (static_cast<uint64_t>(desc->width) * desc->height >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "lighting_compose: target too large");
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    const FrameArgs f = samplingSetArgs(ctx);
+    ArkComposeDesc c = *desc;
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(launch_lighting_compose(f, c, s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_rt_reflections(ArkDdgiCtx* ctx, const ArkReflectionsDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkReflectionsDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkReflectionsDesc");
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "rt_reflections before ark_ddgi_set_scene");
+    if (!desc->out_radiance || !desc->out_direction) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: no output image");
+    if (desc->blue_noise && (desc->noise_width == 0 || desc->noise_height == 0)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: empty blue noise");
+    if (static_cast<uint64_t>(desc->width) * desc->height >= (1ull << 32)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections: target too large");
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    int rc;
+    // the scene first: a sharing context's deeper sun BVH may grow,
+    // i.e. reallocate, the spill area that f.spill points into below
+    if (ctx->sceneVersion != ctx->sceneStore->version) {
+        if ((rc = refreshScene(ctx)) != 0) return rc;
+    } else if ((rc = ensureSpill(ctx)) != 0) {
+        return rc;
+    }
+    FrameArgs f = samplingSetArgs(ctx);
+    f.z_far = ctx->desc.z_far;
+    f.ambient_amount = desc->ambient_amount;
+    f.environment_multiplier = desc->environment_multiplier;
+    f.spill = ctx->spill.as<uint32_t>();
+    // ray-list work set (ensureReflWork): rays, hit records, light bits, shadow rays, counters
+    const uint64_t pixels = static_cast<uint64_t>(desc->width) * desc->height;
+    if (pixels == 0) return ARK_DDGI_OK;
+    if ((rc = ensureReflWork(ctx, pixels)) != 0) return rc;
+    {
+        char* w = static_cast<char*>(ctx->reflWork.ptr);
+        auto take = [&](uint64_t bytes) {
+            char* q = w;
+            w += (bytes + 255) & ~static_cast<uint64_t>(255);
+            return q;
+        };
+        f.ray_list = reinterpret_cast<const float4*>(take(pixels * 32));
+        f.hits = reinterpret_cast<GpuHit*>(take(pixels * sizeof(GpuHit)));
+        f.shadow_bits = reinterpret_cast<uint32_t*>(take(pixels * 4));
+        f.ray_counter = reinterpret_cast<uint32_t*>(take((kRayCounterWords + kRayCounterStride) * 4));
+        f.shadow_rays = reinterpret_cast<ShadowRay*>(take(pixels * ctx->lightCount * sizeof(ShadowRay)));
+    }
+    f.shadow_count = f.ray_counter + kShadowCountWord;
+    f.shadow_heads = f.ray_counter + kShadowHeadWord;
+    f.list_count = f.ray_counter + kRayCounterWords;
+    f.light_count = ctx->lightCount;
+    f.refill_min = ctx->refillMin;
+    f.sun_refill_min = ctx->sunRefillMin;
+    f.grab_chunk = ctx->grabChunk;
+    f.counters = ctx->counters.as<unsigned long long>();
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(flushLights(ctx, s));
+    ARK_HIP(hipMemsetAsync(f.ray_counter, 0, (kRayCounterWords + kRayCounterStride) * 4, s));
+    ARK_HIP(launch_rt_reflections(ctx->scene, f, *desc, ctx->traceBlocks, shadowBlocksFor(ctx, pixels), s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_probe_debug(ArkDdgiCtx* ctx, const ArkProbeDebugDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkProbeDebugDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkProbeDebugDesc");
+    if (desc->count && (!desc->probe_indices || !desc->directions || !desc->out)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "probe_debug: null plane");
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    const FrameArgs f = samplingSetArgs(ctx);
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(launch_probe_debug(f, *desc, s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+} // extern "C"

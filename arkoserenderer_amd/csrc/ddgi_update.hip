@@ -364,7 +364,7 @@ __global__ void __launch_bounds__(kUpdateBlock) k_probe_update(FrameArgs f)
 // record's t (front face), t * 0.2 (back face, t stored negative) or zFar (miss),
 // rounded to fp16 as the surfel stores it (raygen.rgen:108-139). So this kernel runs
 // right after the traversal, and with frames in flight the next frame's slot table
-// and traversal follow it on the traversal stream (ark_ddgi.cpp updateImpl).
+// and traversal follow it on the traversal stream (ddgi_frame.cpp traversalPart).
 // P probes per workgroup (P * R = 1,024 summands per kind). Phase 1, all 256 threads
 // (their hit loads in flight together): each ray's class and rotated direction give
 // the six summands of its probe's sums - direction component c % 3 of a class-1 ray

@@ -1,12 +1,12 @@
 // scene_store.h — the scene of the DDGI contexts on the device (include/ark_ddgi.h:
 // ark_ddgi_set_scene, _share_scene, _set_instances) and what maintains it: the
 // stream-ordered refits of its three geometry copies and the background rebuilds of its
-// BVHs. ark_ddgi.cpp holds the contexts; a store knows none of them, and contexts that
+// BVHs. ddgi_context.h holds the contexts; a store knows none of them, and contexts that
 // share a store call into it one at a time (the C ABI's rule for one GPU's contexts).
 //
 // Stream order is a precondition, not a call. Every entry point that takes a stream `s`
 // requires that the caller has ordered `s` behind everything its context enqueued before
-// (ark_ddgi.cpp: orderBegin); whatever it enqueues - an install on `s`, a snapshot on `s`,
+// (ddgi_context.h: orderBegin); whatever it enqueues - an install on `s`, a snapshot on `s`,
 // a refit on the store's own stream that `s` then waits for - is ordered behind that point,
 // and the caller ends the operation on `s` (orderEnd). After any scene call the caller
 // compares SceneStore::version with the one its kernel view was derived at and derives it
@@ -226,8 +226,8 @@ struct SceneStore {
     uint32_t geometrySeq = 0;
     // counts the record orders of the world BVHs (set_scene, every installed world rebuild;
     // a refit keeps the order, in all three copies): a context resets its seed cache, whose
-    // words are record indices, on its traversal stream when this has moved (ark_ddgi.cpp
-    // updateImpl, behind its wait for evGeometry and ahead of the traversal)
+    // words are record indices, on its traversal stream when this has moved (ddgi_frame.cpp
+    // traversalPart, behind its wait for evGeometry and ahead of the traversal)
     uint32_t worldTopologySeq = 0;
     // Deforming meshes (ark_ddgi_update_geometry; DESIGN §1 "Deforming meshes"). The pools'
     // vertex count and every RT mesh's vertex span (set_scene). Everything below is

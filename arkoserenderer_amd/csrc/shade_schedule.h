@@ -1,4 +1,4 @@
-// shade_schedule.h — which shading schedule an update runs (ark_ddgi.cpp: updateImpl). Pure
+// shade_schedule.h — which shading schedule an update runs (ddgi_frame.cpp: callerPart). Pure
 // host logic over plain values: no device call, so that the decision is tested on the CPU
 // (tests/cpp/shade_schedule_test.cpp).
 #pragma once
@@ -22,7 +22,7 @@ struct ShadeScheduleState {
     bool hasSun = false;
     bool coverMapInUse = false; // SceneArgs::sun_map != nullptr: valid for this geometry, sun direction and z_far
     uint32_t flags = 0;         // ArkDdgiDesc.flags
-    // the update is a pipelined window whose traversal runs the half-occupancy grid (ark_ddgi.cpp:
+    // the update is a pipelined window whose traversal runs the half-occupancy grid (ddgi_context.h:
     // kPipeHalfRays): the previous frame's shading chain runs beside the next traversal
     bool halfOccupancyWindow = false;
     bool sunOnlyInSmallWindows = false; // ark_ddgi_debug_set_sun_only_small_windows (tests)

@@ -66,7 +66,7 @@ int ark_ddgi_debug_bvh8_check_opts(const float* triangles, uint64_t n, int sah_o
 int ark_ddgi_debug_sun_bvh_check(const float* triangles, uint64_t n, const float* sun_dir, const float* origins, uint64_t n_rays, float tmax,
                                  uint64_t* out);
 
-/* set_scene's choice of structure for the sun's shadow rays (ark_ddgi.cpp,
+/* set_scene's choice of structure for the sun's shadow rays (scene_build.cpp,
  * ArkDdgiDesc.sun_bvh = ARK_DDGI_SUN_BVH_AUTO): the world BVH8 and the light-space BVH8 of the triangles are built, sample
  * sun shadow rays from sun-facing points traced any-hit through both on the host;
  * out[4] = {world steps per ray, light-space steps per ray, 1 if the light-space BVH
