@@ -495,6 +495,34 @@ class ArkReflectionsDesc(C.Structure):
     ]
 
 
+ARK_RT_SHADOWS_MAX_LIGHTS = 16
+
+
+class ArkRtShadowLight(C.Structure):
+    _fields_ = [
+        ("position", C.c_float * 3),
+        ("direction", C.c_float * 3),
+        ("outer_cone_angle_cos", C.c_float),
+        ("source_radius", C.c_float),
+        ("out_mask", C.c_void_p),
+    ]
+
+
+class ArkRtShadowsDesc(C.Structure):
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("frame_index", C.c_uint32),
+        ("world_from_view", C.c_float * 16),
+        ("view_from_projection", C.c_float * 16),
+        ("depth", C.c_void_p),
+        ("lights", C.POINTER(ArkRtShadowLight)),
+        ("light_count", C.c_uint32),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
 # G-buffer plane name -> (dtype, channels) in ArkComposeDesc order
 COMPOSE_PLANES = [
     ("depth", "float32", 1), ("base_color", "uint8", 4), ("material", "uint8", 4),
@@ -527,6 +555,7 @@ ABI_STRUCTS = [
     ArkDirectionalLight, ArkSpotLight, ArkDdgiScene, ArkDdgiFrameParams, ArkDdgiCounters,
     ArkDdgiDeviceViews, ArkDdgiBvhStats, ArkBakeAoDesc, ArkComposeDesc, ArkProbeDebugDesc, ArkReflectionsDesc,
     ArkDdgiVertexUpdate, ArkSkinningVertex, ArkMorphTargetVertex, ArkDdgiSkinDesc, ArkDdgiSkinPose, ArkDdgiSkinViews,
+    ArkRtShadowLight, ArkRtShadowsDesc,
 ]
 
 # name -> (restype, argtypes)
@@ -593,6 +622,12 @@ EXPORTS = {
     # ark_ddgi_debug.h
     "ark_ddgi_debug_fmath": (C.c_int, [C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
     "ark_ddgi_debug_fmath_host": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]),
+    "ark_ddgi_rt_local_shadows": (C.c_int, [C.c_void_p, C.POINTER(ArkRtShadowsDesc), C.c_void_p]),
+    "ark_ddgi_debug_rt_shadows_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_uint32, C.POINTER(ArkRtShadowsDesc), C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_rt_shadows_host_ctx": (C.c_int, [C.c_void_p, C.c_uint32, C.POINTER(ArkRtShadowsDesc), C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_rt_shadows_check_desc": (C.c_int, [C.POINTER(ArkRtShadowsDesc)]),
+    "ark_ddgi_debug_rt_shadows_sample": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
+    "ark_ddgi_debug_rt_shadows_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
     "ark_ddgi_debug_struct_sizes": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
     "ark_ddgi_debug_bvh8_check": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_bvh8_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),

@@ -63,7 +63,7 @@ struct ArkDdgiCtx : ErrorSink {
     // persistent resources
     DeviceBuffer irr, vis, offsets;
     // working set
-    DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork;
+    DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork, rtShadowWork;
     DeviceBuffer raySteps; // counting updates: u16 traversal iterations per probe ray (ARK_DDGI_DEBUG_RAY_STEPS)
     // The probe rays' hit candidates (seed_cache.h; none with ARK_DDGI_FLAG_NO_RAY_SEEDS):
     // [N][seed::kProbeWords] triangle records of the world BVHs' opaque class, or seed::kNone.

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ddgi_context.h"
+#include "rt_shadows_host.h"
 #include "sun_bvh.h"
 #include "sun_cover_build.h"
 
@@ -138,6 +139,25 @@ static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement)
         out[vd == cover::kOccluded ? 8 : vd == cover::kLit ? 9 : 10]++;
     }
     return ARK_DDGI_OK;
+}
+
+// The local-light shadow masks' host restatement over the front copy's records (whatever
+// the refits and vertex updates so far made of them) and the instances' classes.
+int ark_ddgi_debug_rt_shadows_host_ctx(ArkDdgiCtx* ctx, uint32_t class_mask, const ArkRtShadowsDesc* desc, uint64_t* counts)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkRtShadowsDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkRtShadowsDesc");
+    if (const char* why = rtshadow::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_shadows_host_ctx: %s", why);
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "rt_shadows_host_ctx before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    if (ctx->sceneVersion != ctx->sceneStore->version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    std::vector<uint32_t> rec;
+    std::vector<int32_t> cls;
+    if (const int rc = sceneRecordsAndClasses(*ctx->sceneStore, ctx, rec, cls)) return rc;
+    const int rc = rtshadow::hostShadows(rec.data(), rec.size() / 12u, cls.data(), cls.size(), class_mask, *desc, counts);
+    return rc == 0 ? ARK_DDGI_OK : ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_shadows_host_ctx: bad arguments");
 }
 
 int ark_ddgi_debug_set_sun_only_small_windows(ArkDdgiCtx* ctx, int enabled)

@@ -503,6 +503,19 @@ hipError_t launch_lighting_compose(const FrameArgs& f, const ArkComposeDesc& c, 
 // 1 closest-hit traversal, 2 shadow-ray list, 3 shadow traversal, 4 shading
 hipError_t launch_rt_reflections(const SceneArgs& sc, const FrameArgs& f, const ArkReflectionsDesc& r, uint32_t traceBlocks, uint32_t shadowBlocks,
                                  hipStream_t s);
+// RT local shadows (ddgi_rt_shadows.inc): the call's lights travel as kernel arguments
+constexpr uint64_t kRtShadowRayBudget = 512ull << 20; // bytes of one traversal launch's worst-case ray list
+struct RtShadowArgs {
+    uint32_t width, height, frame_index, light_count;
+    float world_from_view[16], view_from_projection[16];
+    const float* depth;
+    uint32_t* result;      // one word per pixel: bit l = light l's ray is listed, bit 16 + l = occluded
+    float lights[16][8];   // ArkRtShadowLight's floats: position, direction, cone cosine, radius
+    uint8_t* masks[16];
+};
+// the ray list of lights [l0, l1) into f.shadow_rays / f.shadow_count, and its opaque-only traversal
+hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s);
+hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s);
 hipError_t launch_probe_debug(const FrameArgs& f, const ArkProbeDebugDesc& d, hipStream_t s);
 hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
 // sunFused: the sun-only schedule (shade_schedule.h) - no launch_shadow_gen before it;

@@ -39,6 +39,7 @@
 #include "../../include/ark_ddgi.h"
 #include "ddgi_device.h"
 #include "ddgi_kernels.h"
+#include "rt_shadows.h"
 
 namespace ark {
 
@@ -1927,9 +1928,12 @@ __device__ __forceinline__ V3 shfl3(V3 v, uint32_t src)
 // kShadowSunWorld - both in one launch: each wave drains the sun's list, then takes
 // rays from the other list, so the first list's tail overlaps the second list's work
 // instead of ending a launch (C5: 1.98 ms one list, 3.27 ms two launches).
-constexpr int kShadowWorld = 0, kShadowSun = 1, kShadowSunWorld = 2;
+// kShadowOpaque - the list through the opaque class's world BVH only (cullMask
+// RT_HIT_MASK_OPAQUE: rt-shadow/raygen.rgen:64-65, ddgi_rt_shadows.inc); an instantiation
+// of its own, the other modes' code is what it was.
+constexpr int kShadowWorld = 0, kShadowSun = 1, kShadowSunWorld = 2, kShadowOpaque = 3;
 
-template<bool COUNT, bool SUN>
+template<bool COUNT, bool SUN, bool OPAQUE_ONLY = false>
 __device__ __forceinline__ void shadowPhase(const SceneArgs& sc, const FrameArgs& f, const NodeCache& nc, Stack<kTraceBlock>& st, const TailLds& tl,
                                             uint32_t& cNodes, uint32_t& cTris, uint32_t& cShadow)
 {
@@ -1939,7 +1943,7 @@ __device__ __forceinline__ void shadowPhase(const SceneArgs& sc, const FrameArgs
     const uint32_t total = SUN ? *f.sun_count : *f.shadow_count;
     uint32_t* const heads = SUN ? f.sun_heads : f.shadow_heads;
     const ShadowRay* const list = SUN ? f.sun_rays : f.shadow_rays;
-    const int32_t roots[3] = { SUN ? sc.sun_root : sc.root_opaque, SUN ? -1 : sc.root_masked, SUN ? -1 : sc.root_blend };
+    const int32_t roots[3] = { SUN ? sc.sun_root : sc.root_opaque, SUN || OPAQUE_ONLY ? -1 : sc.root_masked, SUN || OPAQUE_ONLY ? -1 : sc.root_blend };
 
     uint32_t poolNext = 0, poolEnd = 0;
     const uint32_t home = xccId();
@@ -2099,8 +2103,12 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     const uint32_t gtid = blockIdx.x * kTraceBlock + threadIdx.x;
     Stack<kTraceBlock> st { ldsStack + threadIdx.x, f.spill + gtid, gridDim.x * kTraceBlock, 0 };
     uint32_t cNodes = 0, cTris = 0, cShadow = 0;
-    if constexpr (MODE != kShadowWorld) shadowPhase<COUNT, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
-    if constexpr (MODE != kShadowSun) shadowPhase<COUNT, false>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
+    if constexpr (MODE == kShadowOpaque) {
+        shadowPhase<COUNT, false, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
+    } else {
+        if constexpr (MODE != kShadowWorld) shadowPhase<COUNT, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
+        if constexpr (MODE != kShadowSun) shadowPhase<COUNT, false>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
+    }
     if (COUNT) {
         atomicAdd(&f.counters[4], static_cast<unsigned long long>(cNodes));
         atomicAdd(&f.counters[5], static_cast<unsigned long long>(cTris));
@@ -2590,6 +2598,7 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
 
 #include "ddgi_compose.inc"
 #include "ddgi_reflections.inc"
+#include "ddgi_rt_shadows.inc"
 
 } // namespace dev
 
@@ -2769,6 +2778,26 @@ hipError_t launch_rt_reflections(const SceneArgs& sc, const FrameArgs& f, const 
         if (e != hipSuccess) return e;
     }
     hipLaunchKernelGGL(dev::k_refl_shade, dim3(static_cast<uint32_t>((pixels + 255) / 256)), dim3(256), 0, s, sc, f, r);
+    return hipGetLastError();
+}
+
+// One batch of lights [l0, l1) of ark_ddgi_rt_local_shadows: the ray list, then its
+// traversal through the opaque class (never the counting instantiation: the shadow
+// counters stay the DDGI path's).
+hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s)
+{
+    const uint64_t slots = static_cast<uint64_t>((a.width + 7u) / 8u) * ((a.height + 7u) / 8u) * 64u;
+    if (slots == 0 || l0 >= l1 || l1 > rtshadow::kMaxLights) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_rtshadow_gen, dim3(static_cast<uint32_t>((slots + 255u) / 256u)), dim3(256), 0, s, a, l0, l1, f.shadow_rays, f.shadow_count);
+    void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
+    return hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace_shadow<false, kShadowWpe, dev::kShadowOpaque>), dim3(shadowBlocks), dim3(kTraceBlock), args, 0, s);
+}
+
+hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s)
+{
+    const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
+    if (pixels == 0 || a.light_count == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_rtshadow_resolve, dim3(static_cast<uint32_t>((pixels + 255u) / 256u)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -1,7 +1,11 @@
 // ddgi_passes.cpp — the context's passes beside the update: the AO / bent-normal bake and
-// its read-back, the DDGI consumers (lighting compose, RT reflections) and the probe debug
-// view. Each is enqueued whole on the caller's stream, in call order (orderBegin / orderEnd).
+// its read-back, the DDGI consumers (lighting compose, RT reflections), the ray-traced
+// local-light shadow masks and the probe debug view. Each is enqueued whole on the caller's stream, in call order (orderBegin / orderEnd).
+#include <algorithm>
+#include <cstring>
+
 #include "ddgi_context.h"
+#include "rt_shadows_host.h"
 
 namespace {
 
@@ -164,6 +168,70 @@ int ark_ddgi_rt_reflections(ArkDdgiCtx* ctx, const ArkReflectionsDesc* desc, voi
     ARK_HIP(flushLights(ctx, s));
     ARK_HIP(hipMemsetAsync(f.ray_counter, 0, (kRayCounterWords + kRayCounterStride) * 4, s));
     ARK_HIP(launch_rt_reflections(ctx->scene, f, *desc, ctx->traceBlocks, shadowBlocksFor(ctx, pixels), s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+// Ray-traced local-light shadow masks (include/ark_ddgi.h; RTLocalShadowNode.cpp:47-90):
+// per batch of lights the ray list and its opaque-only traversal, then one resolve.
+int ark_ddgi_rt_local_shadows(ArkDdgiCtx* ctx, const ArkRtShadowsDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkRtShadowsDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkRtShadowsDesc");
+    if (const char* why = rtshadow::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_local_shadows: %s", why);
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "rt_local_shadows before ark_ddgi_set_scene");
+    const uint64_t pixels = static_cast<uint64_t>(desc->width) * desc->height;
+    if (pixels == 0 || desc->light_count == 0) return ARK_DDGI_OK;
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    int rc;
+    // the scene first, as ark_ddgi_rt_reflections: a deeper sun BVH may reallocate the spill area
+    if (ctx->sceneVersion != ctx->sceneStore->version) {
+        if ((rc = refreshScene(ctx)) != 0) return rc;
+    } else if ((rc = ensureSpill(ctx)) != 0) {
+        return rc;
+    }
+    RtShadowArgs a {};
+    a.width = desc->width;
+    a.height = desc->height;
+    a.frame_index = desc->frame_index;
+    a.light_count = desc->light_count;
+    std::memcpy(a.world_from_view, desc->world_from_view, sizeof(a.world_from_view));
+    std::memcpy(a.view_from_projection, desc->view_from_projection, sizeof(a.view_from_projection));
+    a.depth = desc->depth;
+    for (uint32_t l = 0; l < desc->light_count; ++l) {
+        rtshadow::lightFloats(desc->lights[l], a.lights[l]);
+        a.masks[l] = desc->lights[l].out_mask;
+    }
+    // work set: result words, counters, the largest batch's ray list (ddgi_rt_shadows.inc: kRtShadowRayBudget)
+    const uint32_t perBatch = static_cast<uint32_t>(std::min<uint64_t>(desc->light_count, std::max<uint64_t>(1, kRtShadowRayBudget / (pixels * sizeof(ShadowRay)))));
+    auto al = [](uint64_t b) { return (b + 255) & ~static_cast<uint64_t>(255); };
+    const uint64_t counterBytes = (kRayCounterWords + kRayCounterStride) * 4;
+    const uint64_t bytes = al(pixels * 4) + al(counterBytes) + al(pixels * perBatch * sizeof(ShadowRay));
+    if (ctx->rtShadowWork.bytes < bytes) ARK_HIP(ctx->rtShadowWork.alloc(bytes));
+    FrameArgs f = samplingSetArgs(ctx);
+    f.spill = ctx->spill.as<uint32_t>();
+    {
+        char* w = static_cast<char*>(ctx->rtShadowWork.ptr);
+        a.result = reinterpret_cast<uint32_t*>(w);
+        w += al(pixels * 4);
+        f.ray_counter = reinterpret_cast<uint32_t*>(w);
+        w += al(counterBytes);
+        f.shadow_rays = reinterpret_cast<ShadowRay*>(w);
+    }
+    f.shadow_bits = a.result;
+    f.shadow_count = f.ray_counter + kShadowCountWord;
+    f.shadow_heads = f.ray_counter + kShadowHeadWord;
+    f.refill_min = ctx->refillMin;
+    f.sun_refill_min = ctx->sunRefillMin;
+    f.grab_chunk = ctx->grabChunk;
+    ARK_HIP(orderBegin(ctx, s));
+    for (uint32_t l0 = 0; l0 < desc->light_count; l0 += perBatch) {
+        const uint32_t l1 = std::min(desc->light_count, l0 + perBatch);
+        ARK_HIP(hipMemsetAsync(f.ray_counter, 0, counterBytes, s));
+        ARK_HIP(launch_rt_shadow_batch(ctx->scene, f, a, l0, l1, shadowBlocksFor(ctx, pixels * (l1 - l0)), s));
+    }
+    ARK_HIP(launch_rt_shadow_resolve(a, s));
     ARK_HIP(orderEnd(ctx, s));
     return ARK_DDGI_OK;
 }

@@ -76,7 +76,7 @@ extern "C" int ark_ddgi_debug_struct_sizes(uint32_t* out, int n)
                                sizeof(ArkRTInstance), sizeof(ArkDirectionalLight), sizeof(ArkSpotLight), sizeof(ArkDdgiScene), sizeof(ArkDdgiFrameParams),
                                sizeof(ArkDdgiCounters), sizeof(ArkDdgiDeviceViews), sizeof(ArkDdgiBvhStats), sizeof(ArkBakeAoDesc), sizeof(ArkComposeDesc), sizeof(ArkProbeDebugDesc), sizeof(ArkReflectionsDesc),
                                sizeof(ArkDdgiVertexUpdate), sizeof(ArkSkinningVertex), sizeof(ArkMorphTargetVertex), sizeof(ArkDdgiSkinDesc), sizeof(ArkDdgiSkinPose),
-                               sizeof(ArkDdgiSkinViews) };
+                               sizeof(ArkDdgiSkinViews), sizeof(ArkRtShadowLight), sizeof(ArkRtShadowsDesc) };
     int m = static_cast<int>(sizeof(sizes) / sizeof(sizes[0]));
     for (int i = 0; i < n && i < m; ++i) out[i] = sizes[i];
     return m < n ? m : n;

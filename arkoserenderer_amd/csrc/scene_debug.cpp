@@ -98,6 +98,16 @@ int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out)
     return installedBvhCheck(err, "sun", st.sun, st.sunArgs.sun_nodes, st.sunArgs.sun_tris, &st.sun.levelOffsets, &root, 1, nullptr, st.sunFrameD, st.sunGpuBuilt, 0, out);
 }
 
+int sceneRecordsAndClasses(const SceneStore& st, ErrorSink* err, std::vector<uint32_t>& records, std::vector<int32_t>& classOf)
+{
+    static_assert(sizeof(GpuTriangle) == 48, "12 words per record");
+    records.assign(static_cast<size_t>(st.world.records) * 12u, 0u);
+    if (!records.empty()) ARK_HIP(hipMemcpy(records.data(), st.args.tris, records.size() * 4u, hipMemcpyDeviceToHost));
+    const std::vector<int> cls = instanceClasses(st);
+    classOf.assign(cls.begin(), cls.end());
+    return ARK_DDGI_OK;
+}
+
 int sceneRefitReach(const SceneStore& st, ErrorSink* err, uint64_t* out)
 {
     std::fill(out, out + 4, uint64_t(0));

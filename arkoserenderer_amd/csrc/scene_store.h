@@ -317,6 +317,9 @@ int sceneSunBvhCheck(const SceneStore& st, ErrorSink* err, uint64_t* out);
 // ark_ddgi_debug_refit_reach: the nodes of the world and the light-space BVHs and those the
 // last refit reached (the node masks downloaded; the device is idle)
 int sceneRefitReach(const SceneStore& st, ErrorSink* err, uint64_t* out);
+// ark_ddgi_debug_rt_shadows_host_ctx: the front copy's triangle records (n x 12 words) and the
+// instances' hit-mask classes, downloaded (the device is idle)
+int sceneRecordsAndClasses(const SceneStore& st, ErrorSink* err, std::vector<uint32_t>& records, std::vector<int32_t>& classOf);
 
 // SpotLightData as the closest hit reads it
 GpuSpotLight gpuSpotLight(const ArkSpotLight& sl);

@@ -593,6 +593,11 @@ class DDGIContext:
         self.check(self.lib.ark_ddgi_lighting_compose(self.h, C.byref(d), C.c_void_p(stream) if stream else None),
                    "ark_ddgi_lighting_compose")
 
+    def rt_local_shadows(self, desc: abi.ArkRtShadowsDesc, stream: int | None = None):
+        """ark_ddgi_rt_local_shadows: `desc` holds device pointers (include/ark_ddgi.h; rt_shadows_desc)."""
+        desc.struct_size = C.sizeof(abi.ArkRtShadowsDesc)
+        self.check(self.lib.ark_ddgi_rt_local_shadows(self.h, C.byref(desc), C.c_void_p(stream) if stream else None), "ark_ddgi_rt_local_shadows")
+
     def rt_reflections(self, desc: abi.ArkReflectionsDesc, stream: int | None = None):
         """ark_ddgi_rt_reflections: `desc` holds device pointers (include/ark_ddgi.h)."""
         desc.struct_size = C.sizeof(abi.ArkReflectionsDesc)
@@ -1122,3 +1127,128 @@ class RTReflectionsNode:
         d = reflections_desc(w, h, camera, planes, self.no_tracing_roughness_threshold, environment_multiplier, ambient_amount)
         s = _tensor_stream(out_radiance, stream)
         ctx.rt_reflections(d, s)
+
+
+
+class RTShadowLight:
+    """A ray-traced spot light as RTLocalShadowNode passes it (RTLocalShadowNode.cpp:60-75):
+    the transform's position and forward(), the outer cone angle (the full angle SpotLight
+    stores; the raygen gets cos(angle / 2), RTLocalShadowNode.cpp:77) and lightSourceRadius (SpotLight.h:45)."""
+
+    def __init__(self, position, direction, outer_cone_angle: float, source_radius: float = 0.025):
+        self.position = tuple(float(v) for v in position)
+        self.direction = tuple(float(v) for v in direction)
+        self.outer_cone_angle = float(outer_cone_angle)
+        self.source_radius = float(source_radius)
+
+    @property
+    def outer_cone_angle_cos(self) -> float:
+        return float(np.cos(np.float32(self.outer_cone_angle / 2.0), dtype=np.float32))
+
+
+def rt_shadows_desc(width: int, height: int, camera: dict, depth, lights, masks, frame_index: int = 0) -> abi.ArkRtShadowsDesc:
+    """ArkRtShadowsDesc from a camera dict (world_from_view, view_from_projection:
+    column-major 16 floats), the depth plane's address, RTShadowLight objects and one mask
+    address per light (device addresses for DDGIContext.rt_local_shadows, host addresses for
+    rt_shadows_host). frame_index is what the raygen's frameIndex() returns. The lights array
+    lives as long as the descriptor."""
+    d = abi.ArkRtShadowsDesc()
+    d.struct_size = C.sizeof(abi.ArkRtShadowsDesc)
+    d.width, d.height, d.frame_index = int(width), int(height), int(frame_index) & 0xFFFFFFFF
+    for k in ("world_from_view", "view_from_projection"):
+        getattr(d, k)[:] = [float(v) for v in np.asarray(camera[k], np.float32).reshape(16)]
+    d.depth = int(depth) if depth else None
+    lights = list(lights)
+    masks = list(masks)
+    if len(masks) != len(lights):
+        raise ValueError(f"rt_shadows_desc: {len(lights)} lights, {len(masks)} masks")
+    arr = (abi.ArkRtShadowLight * max(1, len(lights)))()
+    for a, l, m in zip(arr, lights, masks):
+        a.position[:] = l.position
+        a.direction[:] = l.direction
+        a.outer_cone_angle_cos = l.outer_cone_angle_cos
+        a.source_radius = l.source_radius
+        a.out_mask = int(m) if m else None
+    d._lights_keepalive = arr
+    d.lights = C.cast(arr, C.POINTER(abi.ArkRtShadowLight)) if lights else None
+    d.light_count = len(lights)
+    return d
+
+
+RT_SHADOW_COUNTS = ("sky", "culled", "lit", "occluded")
+
+
+def _rt_shadows_host_desc(width, height, camera, depth, lights, frame_index):
+    depth = np.ascontiguousarray(depth, dtype=np.float32)
+    if depth.shape != (height, width):
+        raise ValueError(f"rt_shadows_host: depth must be [{height}, {width}], got {list(depth.shape)}")
+    lights = list(lights)
+    masks = [np.full((height, width), 0xAA, np.uint8) for _ in lights]
+    d = rt_shadows_desc(width, height, camera, depth.ctypes.data if depth.size else 1, lights, [m.ctypes.data if m.size else 1 + k for k, m in enumerate(masks)],
+                        frame_index)
+    return d, depth, masks
+
+
+def _rt_shadow_counts(out, n):
+    return [dict(zip(RT_SHADOW_COUNTS, (int(out[4 * l + k]) for k in range(4)))) for l in range(n)]
+
+
+def rt_shadows_host(records, class_of, class_mask: int, width: int, height: int, camera: dict, depth, lights, frame_index: int = 0):
+    """ark_ddgi_debug_rt_shadows_host: the shadow masks of ark_ddgi_rt_local_shadows restated on
+    the host over triangle records (triangle_records) by brute force, no GPU. class_of:
+    instance -> hit-mask class; bit c of class_mask: class c occludes (1: opaque only, the
+    feature; 7: every class). depth: float32 [h, w] host array. Returns (masks, counts): one
+    uint8 [h, w] array and one {sky, culled, lit, occluded} dict per light."""
+    lib = abi.load_library()
+    rec = np.ascontiguousarray(records, dtype=np.uint32).reshape(-1, 12)
+    cls = np.ascontiguousarray(class_of, dtype=np.int32).reshape(-1)
+    d, depth, masks = _rt_shadows_host_desc(width, height, camera, depth, lights, frame_index)
+    out = (C.c_uint64 * (4 * max(1, len(masks))))()
+    rc = lib.ark_ddgi_debug_rt_shadows_host(rec.ctypes.data, rec.shape[0], cls.ctypes.data, cls.shape[0], int(class_mask), C.byref(d), out)
+    if rc != 0:
+        raise abi.ArkDdgiError(rc, "ark_ddgi_debug_rt_shadows_host: a descriptor ark_ddgi_rt_local_shadows refuses")
+    return masks, _rt_shadow_counts(out, len(masks))
+
+
+def rt_shadows_host_ctx(ctx: DDGIContext, class_mask: int, width: int, height: int, camera: dict, depth, lights, frame_index: int = 0):
+    """ark_ddgi_debug_rt_shadows_host_ctx: rt_shadows_host over the records of the context's
+    front copy (it follows refits and vertex updates). Synchronous; needs the context's GPU."""
+    d, depth, masks = _rt_shadows_host_desc(width, height, camera, depth, lights, frame_index)
+    out = (C.c_uint64 * (4 * max(1, len(masks))))()
+    ctx.check(ctx.lib.ark_ddgi_debug_rt_shadows_host_ctx(ctx.h, int(class_mask), C.byref(d), out), "ark_ddgi_debug_rt_shadows_host_ctx")
+    return masks, _rt_shadow_counts(out, len(masks))
+
+
+class RTLocalShadowNode:
+    """Mirror of RTLocalShadowNode (name "RT local shadows", RTLocalShadowNode.cpp:47-90):
+    every ray-traced spot light's screen-size R8 shadow mask, all lights in one call. The
+    raygen's frame parameter is frameIndex % 8 (RTLocalShadowNode.cpp:69)."""
+
+    FRAME_PERIOD = 8
+
+    def name(self) -> str:
+        return "RT local shadows"
+
+    def frame_parameter(self, frame_index: int) -> int:
+        return int(frame_index) % self.FRAME_PERIOD
+
+    def execute(self, ctx: DDGIContext, camera: dict, depth, lights, masks, frame_index: int, stream: int | None = None):
+        """depth: float32 [h, w] device tensor; lights: RTShadowLight objects; masks: one uint8
+        [h, w] device tensor per light, each written whole."""
+        import torch
+
+        node = "RTLocalShadowNode"
+        h, w = int(depth.shape[0]), int(depth.shape[1])
+        _check_plane(node, "depth", depth, h, w, None, (torch.float32,))
+        lights, masks = list(lights), list(masks)
+        if len(lights) != len(masks):
+            raise ValueError(f"{node}: {len(lights)} lights, {len(masks)} masks")
+        for k, m in enumerate(masks):
+            _check_plane(node, f"mask {k}", m, h, w, None, (torch.uint8,))
+        d = rt_shadows_desc(w, h, camera, depth.data_ptr(), lights, [m.data_ptr() for m in masks], self.frame_parameter(frame_index))
+        ctx.rt_local_shadows(d, _tensor_stream(depth, stream))
+
+    def execute_host(self, records, class_of, class_mask: int, camera: dict, depth, lights, frame_index: int):
+        """The same frame through rt_shadows_host (no GPU): (masks, counts)."""
+        depth = np.asarray(depth)
+        return rt_shadows_host(records, class_of, class_mask, int(depth.shape[1]), int(depth.shape[0]), camera, depth, lights, self.frame_parameter(frame_index))

@@ -37,6 +37,10 @@
  *                           offsets + grid header): a checkpoint of what the reference
  *                           keeps only in its Registry textures (no reference
  *                           counterpart; SURVEY §8(b) suggested ABI).
+ *   ark_ddgi_rt_local_shadows <- RTLocalShadowNode's execute lambda
+ *                           (RTLocalShadowNode.cpp:47-90): the clear, one traceRays of
+ *                           rt-shadow/raygen.rgen per ray-traced spot light and the copy
+ *                           into the light's shadow mask, all lights in one call.
  *
  * Profiling: ark_ddgi_update brackets its launches in roctx ranges named after the
  * reference's debug zones (DDGINode.cpp:152-247): "DDGI" > "Trace rays" (slot
@@ -845,6 +849,46 @@ typedef struct ArkReflectionsDesc {
  * operation of this context called before it (it shares the update's traversal
  * stack space). */
 int ark_ddgi_rt_reflections(ArkDdgiCtx* ctx, const ArkReflectionsDesc* desc, void* hip_stream);
+
+/* ---- Ray-traced local-light shadow masks -----------------------------------------
+ * Replaces the traceRays of RTLocalShadowNode (RTLocalShadowNode.cpp:47-90) and its
+ * raygen rt-shadow/raygen.rgen:33-80 for all ray-traced spot lights of a frame in one
+ * call: per pixel and light one any-hit ray from the depth buffer's surface point to a
+ * jittered point on the light's disc, tmin 0.025, tmax the distance, against the opaque
+ * hit-mask class only (cullMask RT_HIT_MASK_OPAQUE: masked and translucent geometry does
+ * not shadow). Every byte of every mask is written: 255 lit, 0 occluded, 0 for
+ * depth >= 1 - 1e-6 (the reference leaves the cleared texel) and for a pixel outside the
+ * light's cone. A ray with !(tmax >= 0.025), a NaN length included, is not traced and is
+ * lit. The lights are this call's own (the node passes the lights' transforms), independent
+ * of ark_ddgi_set_lights. */
+#define ARK_RT_SHADOWS_MAX_LIGHTS 16
+typedef struct ArkRtShadowLight {
+    float position[3];           /* parameter1..3 */
+    float direction[3];          /* parameter4..6: transform().forward() */
+    float outer_cone_angle_cos;  /* parameter7: cos(outerConeAngle / 2) */
+    float source_radius;         /* parameter8: lightSourceRadius (SpotLight.h:45, default 0.025) */
+    uint8_t* out_mask;           /* device, R8, width x height: the light's shadowMaskTexture */
+} ArkRtShadowLight;
+typedef struct ArkRtShadowsDesc {
+    uint32_t struct_size;
+    uint32_t width, height;      /* rt_LaunchSize */
+    uint32_t frame_index;        /* what the raygen's frameIndex() returns; the node passes frameIndex % 8 */
+    float world_from_view[16];   /* CameraState, column-major as GLSL mat4 */
+    float view_from_projection[16];
+    const float* depth;          /* SceneDepth (non-linear), device, required */
+    const ArkRtShadowLight* lights; /* host array [light_count], not retained */
+    uint32_t light_count;        /* <= ARK_RT_SHADOWS_MAX_LIGHTS */
+    int32_t reserved[4];
+} ArkRtShadowsDesc;
+
+/* Enqueues the shadow rays of every light on `hip_stream` (NULL = the null stream), after
+ * every operation of this context called before it (refits, vertex updates and installs
+ * among them; it shares the update's traversal stack space). ARK_DDGI_E_INVALID_ARGUMENT,
+ * with nothing enqueued, for a wrong struct_size, no depth, a null or repeated out_mask,
+ * light_count > 16, a non-finite light field or matrix, width * height >= 2^28;
+ * ARK_DDGI_E_NO_SCENE before a scene is set. light_count == 0 or an empty image: OK,
+ * nothing is enqueued. */
+int ark_ddgi_rt_local_shadows(ArkDdgiCtx* ctx, const ArkRtShadowsDesc* desc, void* hip_stream);
 
 /* ---- DDGI probe debug visualisation --------------------------
  * The fragment stage of DDGIProbeDebug (DDGIProbeDebug.cpp:34-71,

@@ -312,6 +312,32 @@ int ark_ddgi_debug_skin_host(const ArkDdgiSkinDesc* desc, const ArkDdgiSkinPose*
 int ark_ddgi_debug_skin_device_parity(int device, const ArkDdgiSkinDesc* desc, const ArkDdgiSkinPose* pose, const float* prev_positions, uint32_t dst_first_vertex,
                                       uint64_t* out);
 
+/* The ray-traced local-light shadow masks (ark_ddgi_rt_local_shadows) restated serially on
+ * the host from the functions the generator kernel calls (csrc/rt_shadows.h), each ray
+ * tested against every triangle record by brute force with the kernels' Möller–Trumbore.
+ * `desc` is the entry's, except that depth and every out_mask are HOST pointers.
+ * _host: no GPU. records: n_records x 12 words as the world BVHs hold them (instance
+ * 0xffffffff: a hole); class_of[instance]: hit-mask class 0 opaque, 1 masked, 2 translucent;
+ * bit c of class_mask: class c occludes (1 is what ark_ddgi_rt_local_shadows traces, 7 what
+ * the DDGI path's shadow rays do). _host_ctx: the same over the records of the context's
+ * front copy and its instances' classes, downloaded; it follows refits and vertex updates by
+ * construction. Synchronous. counts (may be NULL): 4 per light = {sky, outside the cone,
+ * lit, occluded} pixels. ARK_DDGI_E_INVALID_ARGUMENT for a descriptor the entry refuses.
+ * _check_desc: the entry's argument checks alone (struct_size included), no context and no
+ * device: ARK_DDGI_OK or ARK_DDGI_E_INVALID_ARGUMENT; pointers are compared, never followed.
+ * _sample: the generator of pixel (px, py) at frame_index: out_state[3] = {the seed after
+ * wang_hash, the state after the first and after the second xorshift}, out_disk[2] =
+ * randomPointInDisk() (radius 1). _layout: out[0 .. n) of {offsetof(ArkRtShadowLight,
+ * direction), outer_cone_angle_cos, source_radius, out_mask, offsetof(ArkRtShadowsDesc,
+ * frame_index), world_from_view, view_from_projection, depth, lights, light_count,
+ * reserved}; returns how many it wrote. */
+int ark_ddgi_debug_rt_shadows_host(const uint32_t* records, uint64_t n_records, const int32_t* class_of, uint64_t n_instances, uint32_t class_mask,
+                                   const ArkRtShadowsDesc* desc, uint64_t* counts);
+int ark_ddgi_debug_rt_shadows_host_ctx(struct ArkDdgiCtx* ctx, uint32_t class_mask, const ArkRtShadowsDesc* desc, uint64_t* counts);
+int ark_ddgi_debug_rt_shadows_check_desc(const ArkRtShadowsDesc* desc);
+int ark_ddgi_debug_rt_shadows_sample(uint32_t frame_index, uint32_t px, uint32_t py, uint32_t* out_state, float* out_disk);
+int ark_ddgi_debug_rt_shadows_layout(uint32_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif
