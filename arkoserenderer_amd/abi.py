@@ -523,6 +523,40 @@ class ArkRtShadowsDesc(C.Structure):
     ]
 
 
+ARK_REFL_DENOISE_FIRST_FRAME = 1 << 0
+ARK_REFL_DENOISE_DISABLED = 1 << 1
+ARK_REFL_KAT_ROUND_UP8, ARK_REFL_KAT_CLIP_AABB, ARK_REFL_KAT_KERNEL_WEIGHT, ARK_REFL_KAT_TILE_REDUCTION = 0, 1, 2, 3
+ARK_REFL_KAT_EXP, ARK_REFL_KAT_POW512, ARK_REFL_KAT_HALF = 4, 5, 6
+
+# ArkReflDenoiseDesc's planes in declaration order: name -> (dtype, channels, per tile instead of per pixel)
+REFL_DENOISE_PLANES = [
+    ("radiance", "float16", 4, False), ("depth", "float32", 1, False), ("material", "uint8", 4, False), ("normal_velocity", "float16", 4, False),
+    ("radiance_history", "float16", 4, False), ("normal_history", "float16", 4, False), ("depth_history", "float16", 4, False),
+    ("reprojected", "float16", 4, False), ("average_radiance", "float16", 4, True), ("variance", "float32", 1, False),
+    ("num_samples", "float32", 1, False), ("resolved", "float16", 4, False), ("temporal_accumulation", "float16", 4, False),
+]
+REFL_DENOISE_INPUTS = ("radiance", "depth", "material", "normal_velocity")
+
+
+class ArkReflDenoiseDesc(C.Structure):
+    """Not in ABI_STRUCTS (ark_ddgi_debug_struct_sizes' list is closed): its size is the last
+    word of ark_ddgi_debug_refl_denoise_layout."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("no_tracing_roughness", C.c_float),
+        ("temporal_stability", C.c_float),
+        ("world_from_view", C.c_float * 16),
+        ("view_from_projection", C.c_float * 16),
+        ("previous_frame_view_from_world", C.c_float * 16),
+        ("previous_frame_projection_from_view", C.c_float * 16),
+        ("z_near", C.c_float),
+        ("z_far", C.c_float),
+    ] + [(name, C.c_void_p) for name, _, _, _ in REFL_DENOISE_PLANES]
+
+
 # G-buffer plane name -> (dtype, channels) in ArkComposeDesc order
 COMPOSE_PLANES = [
     ("depth", "float32", 1), ("base_color", "uint8", 4), ("material", "uint8", 4),
@@ -628,6 +662,12 @@ EXPORTS = {
     "ark_ddgi_debug_rt_shadows_check_desc": (C.c_int, [C.POINTER(ArkRtShadowsDesc)]),
     "ark_ddgi_debug_rt_shadows_sample": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "ark_ddgi_debug_rt_shadows_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_rt_reflections_denoise": (C.c_int, [C.c_void_p, C.POINTER(ArkReflDenoiseDesc), C.c_void_p]),
+    "ark_ddgi_debug_refl_denoise_host": (C.c_int, [C.POINTER(ArkReflDenoiseDesc)]),
+    "ark_ddgi_debug_refl_denoise_check_desc": (C.c_int, [C.POINTER(ArkReflDenoiseDesc)]),
+    "ark_ddgi_debug_refl_denoise_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_debug_refl_denoise_kat": (C.c_int, [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]),
+    "ark_ddgi_debug_refl_denoise_pass": (C.c_int, [C.c_void_p, C.POINTER(ArkReflDenoiseDesc), C.c_int, C.c_void_p]),
     "ark_ddgi_debug_struct_sizes": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
     "ark_ddgi_debug_bvh8_check": (C.c_int, [C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_bvh8_check_opts": (C.c_int, [C.c_void_p, C.c_uint64, C.c_int, C.c_float, C.POINTER(C.c_uint64)]),

@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ddgi_context.h"
+#include "refl_denoise_host.h"
 #include "rt_shadows_host.h"
 #include "sun_bvh.h"
 #include "sun_cover_build.h"
@@ -138,6 +139,21 @@ static int sunCoverCounts(ArkDdgiCtx* ctx, uint64_t* out, bool hostRestatement)
         }
         out[vd == cover::kOccluded ? 8 : vd == cover::kLit ? 9 : 10]++;
     }
+    return ARK_DDGI_OK;
+}
+
+// One pass of ark_ddgi_rt_reflections_denoise on its own (tools/refl_denoise_cost.py times each).
+int ark_ddgi_debug_refl_denoise_pass(ArkDdgiCtx* ctx, const ArkReflDenoiseDesc* desc, int pass, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkReflDenoiseDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkReflDenoiseDesc");
+    if (const char* why = refl::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "refl_denoise_pass: %s", why);
+    if (pass < 0 || pass > 4) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "refl_denoise_pass: pass %d", pass);
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(launch_refl_denoise_pass(refl::argsOf(*desc), pass, s));
+    ARK_HIP(orderEnd(ctx, s));
     return ARK_DDGI_OK;
 }
 

@@ -516,6 +516,12 @@ struct RtShadowArgs {
 // the ray list of lights [l0, l1) into f.shadow_rays / f.shadow_count, and its opaque-only traversal
 hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s);
 hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s);
+// the reflection denoiser (ddgi_refl_denoise.hip; refl::Args in refl_denoise.h): pass 0 historyCopy
+// with firstCopy, 1 reproject, 2 prefilter, 3 resolveTemporal, 4 historyCopy
+namespace refl {
+struct Args;
+}
+hipError_t launch_refl_denoise_pass(const refl::Args& a, int pass, hipStream_t s);
 hipError_t launch_probe_debug(const FrameArgs& f, const ArkProbeDebugDesc& d, hipStream_t s);
 hipError_t launch_trace(const SceneArgs& sc, const FrameArgs& f, uint32_t blocks, bool count, hipStream_t s);
 // sunFused: the sun-only schedule (shade_schedule.h) - no launch_shadow_gen before it;

@@ -1,10 +1,11 @@
 // ddgi_passes.cpp — the context's passes beside the update: the AO / bent-normal bake and
 // its read-back, the DDGI consumers (lighting compose, RT reflections), the ray-traced
-// local-light shadow masks and the probe debug view. Each is enqueued whole on the caller's stream, in call order (orderBegin / orderEnd).
+// local-light shadow masks, the reflection denoiser passes and the probe debug view. Each is enqueued whole on the caller's stream, in call order (orderBegin / orderEnd).
 #include <algorithm>
 #include <cstring>
 
 #include "ddgi_context.h"
+#include "refl_denoise_host.h"
 #include "rt_shadows_host.h"
 
 namespace {
@@ -232,6 +233,28 @@ int ark_ddgi_rt_local_shadows(ArkDdgiCtx* ctx, const ArkRtShadowsDesc* desc, voi
         ARK_HIP(launch_rt_shadow_batch(ctx->scene, f, a, l0, l1, shadowBlocksFor(ctx, pixels * (l1 - l0)), s));
     }
     ARK_HIP(launch_rt_shadow_resolve(a, s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+// The reflection denoiser passes (include/ark_ddgi.h; RTReflectionsNode.cpp:86-139), in the
+// node's order on one stream. No scene, no state: every plane is the caller's.
+int ark_ddgi_rt_reflections_denoise(ArkDdgiCtx* ctx, const ArkReflDenoiseDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkReflDenoiseDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkReflDenoiseDesc");
+    if (const char* why = refl::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_reflections_denoise: %s", why);
+    const uint64_t pixels = static_cast<uint64_t>(desc->width) * desc->height;
+    if (pixels == 0) return ARK_DDGI_OK;
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    const refl::Args a = refl::argsOf(*desc);
+    ARK_HIP(orderBegin(ctx, s));
+    if (desc->flags & ARK_REFL_DENOISE_DISABLED) {
+        ARK_HIP(hipMemcpyAsync(desc->resolved, desc->radiance, pixels * 8, hipMemcpyDeviceToDevice, s));
+    } else {
+        for (int pass = (desc->flags & ARK_REFL_DENOISE_FIRST_FRAME) ? 0 : 1; pass <= 4; ++pass) ARK_HIP(launch_refl_denoise_pass(a, pass, s));
+    }
     ARK_HIP(orderEnd(ctx, s));
     return ARK_DDGI_OK;
 }

@@ -598,6 +598,11 @@ class DDGIContext:
         desc.struct_size = C.sizeof(abi.ArkRtShadowsDesc)
         self.check(self.lib.ark_ddgi_rt_local_shadows(self.h, C.byref(desc), C.c_void_p(stream) if stream else None), "ark_ddgi_rt_local_shadows")
 
+    def rt_reflections_denoise(self, desc: abi.ArkReflDenoiseDesc, stream: int | None = None):
+        """ark_ddgi_rt_reflections_denoise: `desc` holds device pointers (include/ark_ddgi.h; refl_denoise_desc)."""
+        desc.struct_size = C.sizeof(abi.ArkReflDenoiseDesc)
+        self.check(self.lib.ark_ddgi_rt_reflections_denoise(self.h, C.byref(desc), C.c_void_p(stream) if stream else None), "ark_ddgi_rt_reflections_denoise")
+
     def rt_reflections(self, desc: abi.ArkReflectionsDesc, stream: int | None = None):
         """ark_ddgi_rt_reflections: `desc` holds device pointers (include/ark_ddgi.h)."""
         desc.struct_size = C.sizeof(abi.ArkReflectionsDesc)
@@ -1086,23 +1091,105 @@ def reflections_desc(width: int, height: int, camera: dict, planes: dict, no_tra
     return d
 
 
+REFL_DENOISE_CAMERA_KEYS = ("world_from_view", "view_from_projection", "previous_frame_view_from_world", "previous_frame_projection_from_view")
+
+
+def refl_denoise_desc(width: int, height: int, camera: dict, planes: dict, flags: int = 0, no_tracing_roughness: float = 0.6,
+                      temporal_stability: float = 0.7) -> abi.ArkReflDenoiseDesc:
+    """ArkReflDenoiseDesc from a camera dict (REFL_DENOISE_CAMERA_KEYS: column-major 16 floats;
+    z_near, z_far) and a dict of plane addresses (abi.REFL_DENOISE_PLANES; missing = NULL):
+    device addresses for DDGIContext.rt_reflections_denoise, host addresses for
+    refl_denoise_host. The defaults are RTReflectionsNode's members (RTReflectionsNode.h:20, :25)."""
+    d = abi.ArkReflDenoiseDesc()
+    d.struct_size = C.sizeof(abi.ArkReflDenoiseDesc)
+    d.width, d.height, d.flags = int(width), int(height), int(flags)
+    d.no_tracing_roughness, d.temporal_stability = float(no_tracing_roughness), float(temporal_stability)
+    for k in REFL_DENOISE_CAMERA_KEYS:
+        getattr(d, k)[:] = [float(v) for v in np.asarray(camera[k], np.float32).reshape(16)]
+    d.z_near, d.z_far = float(camera["z_near"]), float(camera["z_far"])
+    for k, _, _, _ in abi.REFL_DENOISE_PLANES:
+        v = planes.get(k)
+        setattr(d, k, int(v) if v else None)
+    return d
+
+
+def refl_denoise_plane_shape(name: str, width: int, height: int):
+    """(shape, numpy dtype) of one of abi.REFL_DENOISE_PLANES; 16-bit planes as uint16 words."""
+    _, dtype, ch, per_tile = next(p for p in abi.REFL_DENOISE_PLANES if p[0] == name)
+    h, w = ((height + 7) // 8, (width + 7) // 8) if per_tile else (height, width)
+    return ((h, w) if ch == 1 else (h, w, ch)), {"float16": np.uint16, "float32": np.float32, "uint8": np.uint8}[dtype]
+
+
+def refl_denoise_host(width: int, height: int, camera: dict, planes: dict, flags: int = 0, no_tracing_roughness: float = 0.6,
+                      temporal_stability: float = 0.7):
+    """ark_ddgi_debug_refl_denoise_host: the denoiser passes restated on the host, no GPU.
+    planes: every one of abi.REFL_DENOISE_PLANES as a C-contiguous numpy array of
+    refl_denoise_plane_shape (16-bit planes as uint16 or float16); the written ones are
+    written in place, as the device entry writes the caller's planes."""
+    lib = abi.load_library()
+    addr = {}
+    for k, _, _, _ in abi.REFL_DENOISE_PLANES:
+        a = planes[k]
+        shape, dtype = refl_denoise_plane_shape(k, width, height)
+        if not isinstance(a, np.ndarray) or not a.flags["C_CONTIGUOUS"] or a.shape != shape or a.dtype.itemsize != np.dtype(dtype).itemsize:
+            raise ValueError(f"refl_denoise_host: plane {k} must be a contiguous {list(shape)} array of {np.dtype(dtype)}")
+        addr[k] = a.ctypes.data
+    d = refl_denoise_desc(width, height, camera, addr, flags, no_tracing_roughness, temporal_stability)
+    rc = lib.ark_ddgi_debug_refl_denoise_host(C.byref(d))
+    if rc != 0:
+        raise abi.ArkDdgiError(rc, "ark_ddgi_debug_refl_denoise_host: a descriptor ark_ddgi_rt_reflections_denoise refuses")
+    return planes
+
+
 class RTReflectionsNode:
-    """Mirror of RTReflectionsNode's ray-tracing pass (RTReflectionsNode.cpp:60-82):
-    the raygen with WITH_DDGI on torch G-buffer planes; the temporal denoiser passes
-    are not on the path. Defaults are the node's members (RTReflectionsNode.h:19-20)."""
+    """Mirror of RTReflectionsNode (RTReflectionsNode.cpp:60-139): the raygen with WITH_DDGI on
+    torch G-buffer planes, then the denoiser passes (historyCopy, reproject, prefilter,
+    resolveTemporal, historyCopy) over planes the node owns, as the reference node owns its
+    textures. Defaults are the node's members (RTReflectionsNode.h:19-25)."""
 
     def __init__(self):
         self.no_tracing_roughness_threshold = 0.6  # m_noTracingRoughnessThreshold (parameter2)
         self.mirror_roughness_threshold = 0.001    # m_mirrorRoughnessThreshold (parameter1): read by no code path of the raygen
+        self.denoise_enabled = True                # m_denoiseEnabled
+        self.temporal_stability = 0.7              # m_temporalStability
+        self.denoise_planes = None                 # allocate_denoise_planes
+        self.relative_first_frame = True           # appState.isRelativeFirstFrame(): set again by a resize
 
     def name(self) -> str:
         return "RT reflections"
+
+    def allocate_denoise_planes(self, width: int, height: int, device) -> dict:
+        """The denoiser's nine written planes for a resolution, zeroed (reproject leaves the
+        non-glossy pixels of reprojected / variance / num_samples untouched and the later
+        passes read them), and the relative-first-frame flag set: the next execute runs the
+        initial historyCopy. 16-bit planes are float16 tensors."""
+        import torch
+
+        planes = {}
+        for k, dtype, _, _ in abi.REFL_DENOISE_PLANES:
+            if k in abi.REFL_DENOISE_INPUTS or k == "radiance":
+                continue
+            shape, _ = refl_denoise_plane_shape(k, width, height)
+            planes[k] = torch.zeros(shape, dtype=getattr(torch, dtype), device=device)
+        self.denoise_planes = planes
+        self._denoise_extent = (int(width), int(height), torch.device(device))
+        self.relative_first_frame = True
+        return planes
 
     def execute(self, ctx: DDGIContext, camera: dict, gbuffer: dict, blue_noise, out_radiance, out_direction,
                 environment_multiplier: float = 1.0, ambient_amount: float = 0.0, stream: int | None = None):
         """gbuffer: depth float32 [h, w], material uint8 [h, w, 4], normal_velocity
         16-bit [h, w, 4] (missing = NULL, read as 0); blue_noise float32 [hn, wn, 2]
-        (one RG layer); out_radiance / out_direction 16-bit [h, w, 4]."""
+        (one RG layer); out_radiance / out_direction 16-bit [h, w, 4].
+
+        A camera that also carries the denoiser's CameraState fields
+        (previous_frame_view_from_world, previous_frame_projection_from_view, z_near, z_far)
+        runs the denoiser after the raygen and returns the DenoisedReflections plane
+        (denoise_planes["resolved"]); its planes are allocated for out_radiance's resolution
+        on first use and again after a resize, which is a relative first frame. With
+        denoise_enabled off the raygen's radiance is copied to that plane
+        (RTReflectionsNode.cpp:134-138). Without those fields only the raygen runs, as before
+        the denoiser existed, and None is returned."""
         import torch
 
         h, w = int(out_radiance.shape[0]), int(out_radiance.shape[1])
@@ -1127,6 +1214,21 @@ class RTReflectionsNode:
         d = reflections_desc(w, h, camera, planes, self.no_tracing_roughness_threshold, environment_multiplier, ambient_amount)
         s = _tensor_stream(out_radiance, stream)
         ctx.rt_reflections(d, s)
+        if "previous_frame_view_from_world" not in camera:
+            return None
+        for k in ("depth", "material", "normal_velocity"):
+            if gbuffer.get(k) is None:
+                raise ValueError(f"{node}: the denoiser needs plane {k}")
+        if self.denoise_planes is None or self._denoise_extent != (w, h, out_radiance.device):
+            self.allocate_denoise_planes(w, h, out_radiance.device)
+        addr = {k: t.data_ptr() for k, t in self.denoise_planes.items()}
+        addr.update(radiance=out_radiance.data_ptr(), depth=gbuffer["depth"].data_ptr(), material=gbuffer["material"].data_ptr(),
+                    normal_velocity=gbuffer["normal_velocity"].data_ptr())
+        flags = (0 if self.denoise_enabled else abi.ARK_REFL_DENOISE_DISABLED) | (abi.ARK_REFL_DENOISE_FIRST_FRAME if self.relative_first_frame else 0)
+        ctx.rt_reflections_denoise(refl_denoise_desc(w, h, camera, addr, flags, self.no_tracing_roughness_threshold, self.temporal_stability), s)
+        if self.denoise_enabled:
+            self.relative_first_frame = False  # (a disabled frame copies no history: the next enabled one is still a first frame)
+        return self.denoise_planes["resolved"]
 
 
 

@@ -825,7 +825,7 @@ int ark_ddgi_lighting_compose(ArkDdgiCtx* ctx, const ArkComposeDesc* desc, void*
  * the environment on a miss. Writes the reflection radiance + signed ray length and
  * the world reflection direction as RGBA16F. Depth >= 1 - 1e-6: result 0, direction
  * left as is; roughness >= no_tracing_roughness: both 0 (raygen.rgen:60-76). The
- * temporal denoiser passes after it (reproject/resolve/prefilter) are not on the path. */
+ * denoiser passes after it are ark_ddgi_rt_reflections_denoise (below). */
 typedef struct ArkReflectionsDesc {
     uint32_t struct_size;
     uint32_t width, height;              /* rt_LaunchSize */
@@ -849,6 +849,60 @@ typedef struct ArkReflectionsDesc {
  * operation of this context called before it (it shares the update's traversal
  * stack space). */
 int ark_ddgi_rt_reflections(ArkDdgiCtx* ctx, const ArkReflectionsDesc* desc, void* hip_stream);
+
+/* ---- RT reflections: the denoiser passes --------------------------------------------
+ * Replaces the four compute passes RTReflectionsNode runs after its raygen
+ * (RTReflectionsNode.cpp:86-139): historyCopy.comp (firstCopy, on a relative first frame
+ * only), reproject.comp, prefilter.comp, resolveTemporal.comp and historyCopy.comp again,
+ * the middle three over the FidelityFX reflection denoiser headers
+ * (shaders/rt-reflections/ffx-denoiser). The wiring is the node's: prefilter reads the
+ * noisy radiance and writes `resolved` (DenoisedReflections: rgb radiance, a variance), the
+ * plane ark_ddgi_lighting_compose reads as `reflections`; resolve reads the noisy radiance
+ * too and writes `temporal_accumulation`, which nothing downstream reads; historyCopy
+ * copies the noisy radiance.
+ *
+ * The library keeps no state: every plane is a caller-owned device pointer, width x height
+ * texels row-major (average_radiance: ceil(width / 8) x ceil(height / 8)), RGBA16F planes
+ * 8-byte aligned. reproject stores reprojected, variance and num_samples only for pixels
+ * with roughness < no_tracing_roughness and leaves the others untouched, while prefilter,
+ * resolve and historyCopy read variance and num_samples of every pixel: the caller zeroes
+ * these planes once when it allocates them. The three history planes carry one frame to
+ * the next; a first frame (after allocation, a resize) sets ARK_REFL_DENOISE_FIRST_FRAME. */
+#define ARK_REFL_DENOISE_FIRST_FRAME (1u << 0) /* run historyCopy with firstCopy = true before reproject (:90-100) */
+#define ARK_REFL_DENOISE_DISABLED    (1u << 1) /* m_denoiseEnabled false: copy radiance to resolved, nothing else (:134-138) */
+typedef struct ArkReflDenoiseDesc {
+    uint32_t struct_size;
+    uint32_t width, height;
+    uint32_t flags;                              /* ARK_REFL_DENOISE_* */
+    float no_tracing_roughness;                  /* m_noTracingRoughnessThreshold (RTReflectionsNode.h:20, 0.6) */
+    float temporal_stability;                    /* m_temporalStability (RTReflectionsNode.h:25, 0.7) */
+    float world_from_view[16];                   /* CameraState, column-major as GLSL mat4 */
+    float view_from_projection[16];
+    float previous_frame_view_from_world[16];
+    float previous_frame_projection_from_view[16];
+    float z_near, z_far;
+    const uint16_t* radiance;                    /* NoisyReflections RGBA16F: rgb radiance, a signed ray length */
+    const float* depth;                          /* SceneDepth (non-linear) */
+    const uint8_t* material;                     /* SceneMaterial RGBA8: byte 0 roughness */
+    const uint16_t* normal_velocity;             /* SceneNormalVelocity RGBA16F: rg octahedral view-space normal, ba motion vector (uv, previous to current) */
+    uint16_t* radiance_history;                  /* RGBA16F: rgb, 0 */
+    uint16_t* normal_history;                    /* RGBA16F: world-space normal, 0 */
+    uint16_t* depth_history;                     /* RGBA16F: depth, roughness, variance, numSamples */
+    uint16_t* reprojected;                       /* RGBA16F, glossy pixels only */
+    uint16_t* average_radiance;                  /* RGBA16F, one texel per 8 x 8 tile */
+    float* variance;                             /* R32F, glossy pixels only */
+    float* num_samples;                          /* R32F, glossy pixels only */
+    uint16_t* resolved;                          /* DenoisedReflections RGBA16F: rgb radiance, a variance */
+    uint16_t* temporal_accumulation;             /* RGBA16F: rgb radiance, a variance */
+} ArkReflDenoiseDesc;
+
+/* Enqueues the passes on `hip_stream` (NULL = the null stream), after every operation of
+ * this context called before it. Needs no scene. ARK_DDGI_E_INVALID_ARGUMENT, with nothing
+ * enqueued, for a wrong struct_size, an unknown flag, a non-finite matrix or scalar,
+ * z_near == z_far, width * height >= 2^28 and, unless the image is empty, a null or
+ * misaligned plane or two planes whose byte ranges overlap. An empty image: OK, nothing is
+ * enqueued. */
+int ark_ddgi_rt_reflections_denoise(ArkDdgiCtx* ctx, const ArkReflDenoiseDesc* desc, void* hip_stream);
 
 /* ---- Ray-traced local-light shadow masks -----------------------------------------
  * Replaces the traceRays of RTLocalShadowNode (RTLocalShadowNode.cpp:47-90) and its

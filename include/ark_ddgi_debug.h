@@ -338,6 +338,35 @@ int ark_ddgi_debug_rt_shadows_check_desc(const ArkRtShadowsDesc* desc);
 int ark_ddgi_debug_rt_shadows_sample(uint32_t frame_index, uint32_t px, uint32_t py, uint32_t* out_state, float* out_disk);
 int ark_ddgi_debug_rt_shadows_layout(uint32_t* out, int n);
 
+/* The reflection denoiser passes (ark_ddgi_rt_reflections_denoise) restated serially on the
+ * host, tile by tile and lane by lane through the functions the kernels call
+ * (csrc/refl_denoise.h). All host-only, no context and no device.
+ * _host: `desc` is the entry's, except that every plane is a HOST pointer; the same planes
+ * are written. ARK_DDGI_E_INVALID_ARGUMENT for a descriptor the entry refuses.
+ * _check_desc: the entry's argument checks alone (struct_size included); pointers are
+ * compared, never followed.
+ * _layout: out[0 .. n) of the offsets of ArkReflDenoiseDesc's fields from width on, in
+ * declaration order (24 words), then sizeof(ArkReflDenoiseDesc); returns how many it wrote.
+ * _kat: known answers of the shared functions, in[n_in] -> out[n_out]:
+ *   ROUND_UP8 1 -> 1; CLIP_AABB {min, max, sample} 9 -> 3; KERNEL_WEIGHT 1 -> 1;
+ *   TILE_REDUCTION 64 lanes x 4 (lane = gy * 8 + gx) -> the 4 sums after the three fp16
+ *   levels; EXP, POW512 (x^512), HALF (through fp16 and back) n -> n. */
+#define ARK_REFL_KAT_ROUND_UP8      0
+#define ARK_REFL_KAT_CLIP_AABB      1
+#define ARK_REFL_KAT_KERNEL_WEIGHT  2
+#define ARK_REFL_KAT_TILE_REDUCTION 3
+#define ARK_REFL_KAT_EXP            4
+#define ARK_REFL_KAT_POW512         5
+#define ARK_REFL_KAT_HALF           6
+int ark_ddgi_debug_refl_denoise_host(const ArkReflDenoiseDesc* desc);
+int ark_ddgi_debug_refl_denoise_check_desc(const ArkReflDenoiseDesc* desc);
+int ark_ddgi_debug_refl_denoise_layout(uint32_t* out, int n);
+int ark_ddgi_debug_refl_denoise_kat(int which, const float* in, int n_in, float* out, int n_out);
+/* One pass of ark_ddgi_rt_reflections_denoise alone, on the device with the entry's checks
+ * and ordering: 0 historyCopy with firstCopy, 1 reproject, 2 prefilter, 3 resolveTemporal,
+ * 4 historyCopy. For timing the passes (tools/refl_denoise_cost.py). */
+int ark_ddgi_debug_refl_denoise_pass(struct ArkDdgiCtx* ctx, const ArkReflDenoiseDesc* desc, int pass, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
