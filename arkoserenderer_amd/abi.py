@@ -557,6 +557,44 @@ class ArkReflDenoiseDesc(C.Structure):
     ] + [(name, C.c_void_p) for name, _, _, _ in REFL_DENOISE_PLANES]
 
 
+ARK_PATH_TRACER_RESET = 1 << 0
+ARK_PATH_TRACER_ACCUMULATE = 1 << 1
+PATH_TRACER_MAX_SEGMENTS = 16
+
+
+class ArkPathTracerDesc(C.Structure):
+    """Not in ABI_STRUCTS (ark_ddgi_debug_struct_sizes' list is closed): its size is word 14 of
+    ark_ddgi_debug_path_tracer_layout."""
+    _fields_ = [
+        ("struct_size", C.c_uint32),
+        ("width", C.c_uint32),
+        ("height", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("frame_index", C.c_uint32),
+        ("accumulated_frames", C.c_uint32),
+        ("max_paths_per_batch", C.c_uint32),
+        ("environment_multiplier", C.c_float),
+        ("z_near", C.c_float),
+        ("z_far", C.c_float),
+        ("world_from_view", C.c_float * 16),
+        ("view_from_projection", C.c_float * 16),
+        ("image", C.c_void_p),
+        ("accumulation", C.c_void_p),
+        ("reserved", C.c_int32 * 4),
+    ]
+
+
+# one segment of one path as ark_ddgi_debug_path_tracer_host[_ctx] records it (33 words)
+PATH_TRACER_VERTEX = [
+    ("status", "<u4"), ("rng_before", "<u4"), ("origin", "<f4", 3), ("direction", "<f4", 3), ("tmin", "<f4"), ("tri", "<u4"), ("t", "<f4"),
+    ("u", "<f4"), ("v", "<f4"), ("backface", "<u4"), ("shadow_bits", "<u4"), ("attenuation_before", "<f4", 3), ("radiance_before", "<f4", 3),
+    ("attenuation_after", "<f4", 3), ("radiance_after", "<f4", 3), ("scattered", "<f4", 3), ("rng_after", "<u4"), ("alpha_rejected", "<u4"),
+    ("glass", "<u4"),
+]
+PATH_VERTEX_NONE, PATH_VERTEX_SCATTERED, PATH_VERTEX_MISS, PATH_VERTEX_KILLED, PATH_VERTEX_LAST = 0, 1, 2, 3, 4
+PATH_TRACER_COUNTS = ("glass", "alpha_rejected", "killed", "segment8", "occluded", "lit", "missed", "vertices")
+
+
 # G-buffer plane name -> (dtype, channels) in ArkComposeDesc order
 COMPOSE_PLANES = [
     ("depth", "float32", 1), ("base_color", "uint8", 4), ("material", "uint8", 4),
@@ -662,6 +700,17 @@ EXPORTS = {
     "ark_ddgi_debug_rt_shadows_check_desc": (C.c_int, [C.POINTER(ArkRtShadowsDesc)]),
     "ark_ddgi_debug_rt_shadows_sample": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32), C.POINTER(C.c_float)]),
     "ark_ddgi_debug_rt_shadows_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_path_trace": (C.c_int, [C.c_void_p, C.POINTER(ArkPathTracerDesc), C.c_void_p]),
+    "ark_ddgi_debug_path_tracer_host": (C.c_int, [C.POINTER(ArkDdgiScene), C.POINTER(ArkPathTracerDesc), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_path_tracer_host_ctx": (C.c_int, [C.c_void_p, C.POINTER(ArkPathTracerDesc), C.c_void_p, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_path_tracer_check_desc": (C.c_int, [C.POINTER(ArkPathTracerDesc)]),
+    "ark_ddgi_debug_path_tracer_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_debug_path_tracer_accumulate_host": (C.c_int, [C.POINTER(ArkPathTracerDesc)]),
+    "ark_ddgi_debug_path_tracer_last_counts": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "ark_ddgi_debug_path_tracer_set_segments": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "ark_ddgi_debug_path_tracer_random": (C.c_int, [C.c_uint32, C.POINTER(C.c_float), C.POINTER(C.c_uint32)]),
+    "ark_ddgi_debug_path_tracer_sample": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint32),
+                                                   C.POINTER(C.c_float)]),
     "ark_ddgi_rt_reflections_denoise": (C.c_int, [C.c_void_p, C.POINTER(ArkReflDenoiseDesc), C.c_void_p]),
     "ark_ddgi_debug_refl_denoise_host": (C.c_int, [C.POINTER(ArkReflDenoiseDesc)]),
     "ark_ddgi_debug_refl_denoise_check_desc": (C.c_int, [C.POINTER(ArkReflDenoiseDesc)]),

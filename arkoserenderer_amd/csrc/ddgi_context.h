@@ -63,7 +63,7 @@ struct ArkDdgiCtx : ErrorSink {
     // persistent resources
     DeviceBuffer irr, vis, offsets;
     // working set
-    DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork, rtShadowWork;
+    DeviceBuffer slots, slotOrder, fib, fibOrder, order, hits, surfels, spill, rayCounter, counters, shadeWork, reflWork, rtShadowWork, ptWork;
     DeviceBuffer raySteps; // counting updates: u16 traversal iterations per probe ray (ARK_DDGI_DEBUG_RAY_STEPS)
     // The probe rays' hit candidates (seed_cache.h; none with ARK_DDGI_FLAG_NO_RAY_SEEDS):
     // [N][seed::kProbeWords] triangle records of the world BVHs' opaque class, or seed::kNone.
@@ -140,6 +140,7 @@ struct ArkDdgiCtx : ErrorSink {
     bool timingValid = false;
     bool countersPending = false;
     uint64_t lastRays = 0, lastProbes = 0;
+    uint32_t ptSegments = 16; // ark_ddgi_debug_path_tracer_set_segments (timing only)
     uint32_t nextProbeIndex = 0; // (first + K) % N of the last update, or of a loaded state
     uint32_t lastFirst = 0, lastK = 0; // the last update's window (ark_ddgi_window_exchange_info)
     // the refits and installed rebuilds of the scene (by any context sharing it) that this

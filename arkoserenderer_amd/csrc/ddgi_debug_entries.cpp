@@ -4,6 +4,7 @@
 #include <cstring>
 
 #include "ddgi_context.h"
+#include "path_tracer_host.h"
 #include "refl_denoise_host.h"
 #include "rt_shadows_host.h"
 #include "sun_bvh.h"
@@ -174,6 +175,52 @@ int ark_ddgi_debug_rt_shadows_host_ctx(ArkDdgiCtx* ctx, uint32_t class_mask, con
     if (const int rc = sceneRecordsAndClasses(*ctx->sceneStore, ctx, rec, cls)) return rc;
     const int rc = rtshadow::hostShadows(rec.data(), rec.size() / 12u, cls.data(), cls.size(), class_mask, *desc, counts);
     return rc == 0 ? ARK_DDGI_OK : ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "rt_shadows_host_ctx: bad arguments");
+}
+
+int ark_ddgi_debug_path_tracer_host_ctx(ArkDdgiCtx* ctx, const ArkPathTracerDesc* desc, void* vertices, uint64_t* counts)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkPathTracerDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkPathTracerDesc");
+    if (const char* why = pt::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "path_tracer_host_ctx: %s", why);
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "path_tracer_host_ctx before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    if (ctx->sceneVersion != ctx->sceneStore->version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    pt::HostScene hs;
+    if (const int rc = sceneHostCopy(*ctx->sceneStore, ctx, hs)) return rc;
+    // the context's lights (ark_ddgi_set_lights), as the entry's kernels get them
+    hs.hasSun = ctx->scene.has_sun;
+    for (int k = 0; k < 3; ++k) {
+        hs.sunColor[k] = ctx->scene.sun_color[k];
+        hs.sunDir[k] = ctx->scene.sun_dir[k];
+    }
+    hs.spots = ctx->spotHost;
+    const int rc = pt::hostPathTrace(hs.view(), hs.tris.size(), *desc, static_cast<pt::Vertex*>(vertices), counts);
+    return rc == 0 ? ARK_DDGI_OK : ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "path_tracer_host_ctx: bad arguments");
+}
+
+int ark_ddgi_debug_path_tracer_set_segments(ArkDdgiCtx* ctx, uint32_t segments)
+{
+    if (!ctx || segments == 0 || segments > pt::kMaxSegments) return ARK_DDGI_E_INVALID_ARGUMENT;
+    ctx->ptSegments = segments;
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_path_tracer_last_counts(ArkDdgiCtx* ctx, uint32_t* out)
+{
+    if (!ctx || !out) return ARK_DDGI_E_INVALID_ARGUMENT;
+    std::memset(out, 0, sizeof(uint32_t) * 2 * pt::kMaxSegments);
+    if (ctx->ptWork.bytes < kPtCounterWords * 4u) return ARK_DDGI_OK; // no path_trace call yet
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    std::vector<uint32_t> words(kPtCounterWords);
+    ARK_HIP(hipMemcpy(words.data(), ctx->ptWork.ptr, words.size() * 4u, hipMemcpyDeviceToHost));
+    for (uint32_t s = 0; s < pt::kMaxSegments; ++s) {
+        out[s] = words[s * kPtSegmentWords + kPtListCountWord];
+        out[pt::kMaxSegments + s] = words[s * kPtSegmentWords + kPtShadowCountWord];
+    }
+    return ARK_DDGI_OK;
 }
 
 int ark_ddgi_debug_set_sun_only_small_windows(ArkDdgiCtx* ctx, int enabled)

@@ -516,6 +516,31 @@ struct RtShadowArgs {
 // the ray list of lights [l0, l1) into f.shadow_rays / f.shadow_count, and its opaque-only traversal
 hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s);
 hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s);
+// The path tracer (ddgi_path_tracer.inc). Its counters, per segment on lines of their own: the
+// trace's partition heads, the shadow list's count and heads, the path list's count; one
+// block more for the count the last segment's shading is handed.
+constexpr uint32_t kPtShadowCountWord = kRayParts * kRayCounterStride;
+constexpr uint32_t kPtShadowHeadWord = kPtShadowCountWord + kRayCounterStride;
+constexpr uint32_t kPtListCountWord = kPtShadowHeadWord + kRayParts * kRayCounterStride;
+constexpr uint32_t kPtSegmentWords = kPtListCountWord + kRayCounterStride;
+constexpr uint32_t kPtCounterWords = 17u * kPtSegmentWords;
+constexpr uint64_t kPathTracerBudget = 512ull << 20; // bytes of one batch's lists and path state (kRtShadowRayBudget's rule)
+struct PtArgs {
+    uint32_t width, height, frame_index, flags, accumulated_frames;
+    float environment_multiplier, z_near, z_far;
+    float world_from_view[16], view_from_projection[16];
+    uint16_t* image;
+    float* accumulation;
+    uint32_t slot0, slot1; // the batch: global slots of the 8 x 8 tile order (whole tiles)
+    float4* state;         // [2 x batch slots] {attenuation, rng}, {radiance, -}
+    float4* lists[2];      // [2 x batch slots] {origin, tmin}, {direction, slot}, ping-pong
+    float4* surf;          // [4 x batch slots] the hit stage's surface, at the list index
+};
+// bytes of a batch's work set per slot: state, two lists, surface, hit record, light word, shadow rays
+inline uint64_t ptBytesPerSlot(uint32_t lightCount) { return 32u + 64u + 64u + sizeof(GpuHit) + 4u + static_cast<uint64_t>(lightCount) * sizeof(ShadowRay); }
+hipError_t launch_path_trace_batch(const SceneArgs& sc, const FrameArgs& f, const PtArgs& a, uint32_t* counters, uint32_t traceBlocks, uint32_t shadowBlocks,
+                                   hipStream_t s, uint32_t segments = 16u);
+hipError_t launch_path_trace_accumulate(const PtArgs& a, hipStream_t s);
 // the reflection denoiser (ddgi_refl_denoise.hip; refl::Args in refl_denoise.h): pass 0 historyCopy
 // with firstCopy, 1 reproject, 2 prefilter, 3 resolveTemporal, 4 historyCopy
 namespace refl {

@@ -39,15 +39,14 @@
 #include "../../include/ark_ddgi.h"
 #include "ddgi_device.h"
 #include "ddgi_kernels.h"
+#include "path_tracer.h"
 #include "rt_shadows.h"
 
 namespace ark {
 
 __device__ __forceinline__ float4 SceneArgs::sample(int idx, float u, float v) const
 {
-    const int r = resolveTexture(idx);
-    if (r == white_texture && fabsf(u) < INFINITY && fabsf(v) < INFINITY) return make_float4(1.0f, 1.0f, 1.0f, 1.0f);
-    return dev::sampleTexture(tex_infos, texels, r, u, v);
+    return dev::sampleOrWhite(tex_infos, texels, texture_count, white_texture, idx, u, v);
 }
 
 namespace dev {
@@ -216,42 +215,7 @@ __device__ __forceinline__ V3 safeInv(V3 d)
     return { f(d.x), f(d.y), f(d.z) };
 }
 
-// Möller–Trumbore, identical op order to the oracle's intersectTri. The cross and dot
-// products are fused explicitly (crossFma / dotFma: 6 and 3 VALU instead of 9 and 5;
-// the ray-triangle test is the traversal step's second largest block), in the same
-// places as the oracle, so results stay bit-exact under -ffp-contract=off.
-__device__ __forceinline__ V3 crossFma(V3 a, V3 b)
-{
-    return { fmaf(a.y, b.z, -(a.z * b.y)), fmaf(a.z, b.x, -(a.x * b.z)), fmaf(a.x, b.y, -(a.y * b.x)) };
-}
-__device__ __forceinline__ float dotFma3(V3 a, V3 b) { return fmaf(a.x, b.x, fmaf(a.y, b.y, a.z * b.z)); }
-
-// Branch free: in a wave some lane passes each early-out test on almost every
-// step, so the early returns saved no VALU and cost an exec-mask branch each
-// (~14 SALU per traversal step). The accepted set is the oracle's: u <= 1 follows
-// from v >= 0 and RN(u + v) <= 1 (rounding is monotonic), and det == 0 gives
-// inv = +-inf, so u or v is NaN or infinite and one of u >= 0, v >= 0, u + v <= 1
-// fails, as the oracle's early return rejects it; the values of an accepted hit
-// are computed exactly as the oracle computes them.
-__device__ __forceinline__ bool intersectTri(V3 o, V3 d, float tmin, float tmax, const GpuTriangle& tr, float* outT, float* outU, float* outV, bool* backfaceDet)
-{
-    V3 v0 = { tr.t0[0], tr.t0[1], tr.t0[2] };
-    V3 e1 = { tr.t0[3], tr.t1[0], tr.t1[1] };
-    V3 e2 = { tr.t1[2], tr.t1[3], tr.t2[0] };
-    V3 p = crossFma(d, e2);
-    float det = dotFma3(e1, p);
-    float inv = 1.0f / det;
-    V3 s = o - v0;
-    float u = dotFma3(s, p) * inv;
-    V3 q = crossFma(s, e1);
-    float v = dotFma3(d, q) * inv;
-    float tt = dotFma3(e2, q) * inv;
-    *outT = tt;
-    *outU = u;
-    *outV = v;
-    *backfaceDet = det < 0.0f;
-    return (u >= 0.0f) & (v >= 0.0f) & (u + v <= 1.0f) & (tt >= tmin) & (tt <= tmax);
-}
+// crossFma, dotFma3 and intersectTri (Möller–Trumbore) are shading_math.h's: the host restatements call the same function.
 
 __device__ __forceinline__ GpuTriangle loadTri(const GpuTriangle* __restrict__ tris, uint32_t i)
 {
@@ -283,6 +247,9 @@ __device__ bool alphaAccept(const SceneArgs& sc, uint32_t inst, uint32_t prim, f
     float4 c = sc.sample(mat.base_color, uvx, uvy);
     return !(c.w < mat.mask_cutoff);
 }
+
+// anyhit.rahit of the path tracer (ddgi_path_tracer.inc): only BLEND_MODE_MASKED materials are tested
+__device__ bool alphaAcceptPath(const SceneArgs& sc, uint32_t inst, uint32_t prim, float u, float v);
 
 // Ray octant (bit a: idir[a] < 0); slots are visited in increasing (slot ^ oct).
 __device__ __forceinline__ uint32_t rayOctant(V3 idir)
@@ -539,7 +506,7 @@ __device__ __forceinline__ bool travDoneDual(const TravState& ts, uint32_t nBits
     return ts.tBits == 0 && nBits == 0 && (ts.gBits & 0xffu) == 0 && st.depth == 0;
 }
 
-template<int BLOCK, bool ANY, bool GF = false>
+template<int BLOCK, bool ANY, bool GF = false, bool PATH = false>
 __device__ __forceinline__ bool travStepDual(const SceneArgs& sc, const NodeCache& nc, TravState& ts, uint32_t& nBase, uint32_t& nBits, Stack<BLOCK>& st,
                                              V3 o, V3 d, V3 idir, uint32_t oct, float tmin, RayHit& h, int pass, uint32_t& cNodes, uint32_t& cTris)
 {
@@ -614,7 +581,7 @@ __device__ __forceinline__ bool travStepDual(const SceneArgs& sc, const NodeCach
             const uint32_t inst = c.y, prim = c.z;
             if (ANY) anyHit = true;
             else if (!(h.tri != kNoHit && tt == h.t && (inst > h.inst || (inst == h.inst && prim > h.prim))) &&
-                !(pass == 1 && !alphaAccept(sc, inst, prim, uu, vv))) {
+                !(pass == 1 && !(PATH ? alphaAcceptPath(sc, inst, prim, uu, vv) : alphaAccept(sc, inst, prim, uu, vv)))) {
                 h.t = tt;
                 h.u = uu;
                 h.v = vv;
@@ -985,6 +952,7 @@ struct PoolRec {
 // seed::candidateOk against the launch's opaque class) and leave their opaque-pass hit in
 // the cache.
 struct ProbeRays {
+    static constexpr bool kAllClasses = false;
     static constexpr bool kMaskedPass = true;
     static constexpr bool kSeeds = true;
     static constexpr float kTmin = 0.0001f;
@@ -1017,6 +985,7 @@ struct ProbeRays {
 };
 
 struct ListRays {
+    static constexpr bool kAllClasses = false;
     static constexpr bool kMaskedPass = false;
     static constexpr bool kSeeds = false;
     static constexpr float kTmin = 0.01f;
@@ -1041,6 +1010,37 @@ struct ListRays {
     }
 };
 
+// PathRays: the path tracer's list (pathtracer.rgen:42-50: RayFlags_None, cullMask opaque |
+// masked | blend): {origin, tmin}, {direction, slot}, tmax zFar on every segment. One closest
+// hit over the three classes: the lane walks the roots in turn and keeps its hit, so tmax
+// shrinks from class to class and the tie rule holds across them; `pass` is the class, and
+// class 1's candidates take the path tracer's alpha test. An empty list returns at once.
+struct PathRays {
+    static constexpr bool kAllClasses = true;
+    static constexpr bool kMaskedPass = false;
+    static constexpr bool kSeeds = false;
+    static constexpr float kTmin = 0.0001f; // (each ray carries its own)
+    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
+    {
+        grabItemsWave(f.ray_counter, *f.list_count, home, lane, tried, b, e, chunk);
+    }
+    __device__ static PoolRec stage(const SceneArgs&, const FrameArgs& f, uint32_t r)
+    {
+        const float4 a = f.ray_list[2u * r], b = f.ray_list[2u * r + 1u];
+        PoolRec rec;
+        rec.o = { a.x, a.y, a.z };
+        rec.d = { b.x, b.y, b.z };
+        rec.a = __float_as_uint(a.w); // tmin
+        rec.c = seed::kNone;
+        return rec;
+    }
+    __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t, uint32_t& ray, float& tmax)
+    {
+        ray = r;
+        tmax = f.z_far;
+    }
+};
+
 // SLOTS: records per wave pool. A chunk never exceeds it (the grab size is clamped to
 // it below). 64 for the whole-grid launches; the half-occupancy windows, which grab 32
 // rays at a time, run the 32-slot instance: their three workgroups per CU share the CU
@@ -1052,6 +1052,8 @@ template<bool COUNT, int WPE, class Src = ProbeRays, int SLOTS = 64, bool SEEDW 
 __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace(SceneArgs sc, FrameArgs f)
 {
     if (frameAborted(f.abort_word)) return;
+    if constexpr (Src::kAllClasses)
+        if (*f.list_count == 0u) return;
     __shared__ uint32_t ldsStack[kStackLds * 2 * kTraceBlock];
     // nodes from global memory only (GF dual steps): no LDS node cache, the octant table
     __shared__ uint4 ldsNodes[5];
@@ -1065,7 +1067,8 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     const uint32_t lane = threadIdx.x & 63u;
     uint4* const pool = ldsPool + 2u * SLOTS * (threadIdx.x >> 6);
     const uint32_t chunk = min(f.grab_chunk, static_cast<uint32_t>(SLOTS)); // a chunk fits the pool
-    const float tmin = Src::kTmin;
+    float tmin = Src::kTmin;
+    auto classRoot = [&](int c) { return c == 0 ? sc.root_opaque : (c == 1 ? sc.root_masked : sc.root_blend); }; // (Src::kAllClasses; no indexed array: scratch)
     uint32_t cNodes = 0, cTris = 0, cHits = 0, cIter = 0, rSteps = 0;
     uint32_t cSeedHits = 0, seedTri = seed::kNone; // (COUNT) rays whose candidate was hit; the candidate of a ray's first step
 
@@ -1180,6 +1183,11 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
                 // the candidate is the ray's first pending triangle group: the step below tests
                 // it like any leaf triangle, and the root visit of that step sees its h.t
                 ts = TravState { static_cast<uint32_t>(sc.root_opaque), sc.root_opaque >= 0 ? rootGroupBits() : 0u, recC, recC != seed::kNone ? 1u : 0u };
+                if constexpr (Src::kAllClasses) {
+                    tmin = __uint_as_float(recA);
+                    while (pass < 3 && classRoot(pass) < 0) ++pass;
+                    ts = TravState { pass < 3 ? static_cast<uint32_t>(classRoot(pass)) : 0u, pass < 3 ? rootGroupBits() : 0u, 0u, 0u };
+                }
                 if (COUNT) seedTri = recC;
             }
             if (avail < n) {
@@ -1202,13 +1210,29 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
         // ---- one step: a pending leaf triangle and the next node -------------------
         // (an active lane is never done here: the check after the step retires or
         // restarts it, and a step of a done lane would change nothing anyway)
-        if (active) travStepDual<kTraceBlock, false, true>(sc, nc, ts, nBase, nBits, st, o, d, idir, oct, tmin, h, pass, cNodes, cTris);
+        if (active) travStepDual<kTraceBlock, false, true, Src::kAllClasses>(sc, nc, ts, nBase, nBits, st, o, d, idir, oct, tmin, h, pass, cNodes, cTris);
         if (COUNT && active && seedTri != seed::kNone) {
             cSeedHits += h.tri == seedTri ? 1u : 0u;
             seedTri = seed::kNone;
         }
         // ---- pass finished -------------------------------------------------------------
-        if (active && done() && (!Src::kMaskedPass || sc.root_masked < 0) && !exhausted) {
+        if constexpr (Src::kAllClasses) {
+            // the next class with geometry, the hit so far kept (h.t is the query's tmax)
+            if (active && done()) {
+                ++pass;
+                while (pass < 3 && classRoot(pass) < 0) ++pass;
+                if (pass < 3) {
+                    ts = TravState { static_cast<uint32_t>(classRoot(pass)), rootGroupBits(), 0u, 0u };
+                    st.depth = 0;
+                } else if (!exhausted) {
+                    active = false;
+                    pending = true;
+                } else {
+                    storeHit();
+                    active = false;
+                }
+            }
+        } else if (active && done() && (!Src::kMaskedPass || sc.root_masked < 0) && !exhausted) {
             active = false;
             pending = true;
         } else if (active && done()) {
@@ -1931,9 +1955,11 @@ __device__ __forceinline__ V3 shfl3(V3 v, uint32_t src)
 // kShadowOpaque - the list through the opaque class's world BVH only (cullMask
 // RT_HIT_MASK_OPAQUE: rt-shadow/raygen.rgen:64-65, ddgi_rt_shadows.inc); an instantiation
 // of its own, the other modes' code is what it was.
-constexpr int kShadowWorld = 0, kShadowSun = 1, kShadowSunWorld = 2, kShadowOpaque = 3;
+// kShadowPath - the path tracer's shadow rays (closesthit.rchit:31-49: cullMask opaque | masked,
+// RayFlags_Opaque): roots {opaque, masked, -1}, no alpha test; an empty list returns at once.
+constexpr int kShadowWorld = 0, kShadowSun = 1, kShadowSunWorld = 2, kShadowOpaque = 3, kShadowPath = 4;
 
-template<bool COUNT, bool SUN, bool OPAQUE_ONLY = false>
+template<bool COUNT, bool SUN, bool OPAQUE_ONLY = false, bool NO_BLEND = false>
 __device__ __forceinline__ void shadowPhase(const SceneArgs& sc, const FrameArgs& f, const NodeCache& nc, Stack<kTraceBlock>& st, const TailLds& tl,
                                             uint32_t& cNodes, uint32_t& cTris, uint32_t& cShadow)
 {
@@ -1943,7 +1969,7 @@ __device__ __forceinline__ void shadowPhase(const SceneArgs& sc, const FrameArgs
     const uint32_t total = SUN ? *f.sun_count : *f.shadow_count;
     uint32_t* const heads = SUN ? f.sun_heads : f.shadow_heads;
     const ShadowRay* const list = SUN ? f.sun_rays : f.shadow_rays;
-    const int32_t roots[3] = { SUN ? sc.sun_root : sc.root_opaque, SUN || OPAQUE_ONLY ? -1 : sc.root_masked, SUN || OPAQUE_ONLY ? -1 : sc.root_blend };
+    const int32_t roots[3] = { SUN ? sc.sun_root : sc.root_opaque, SUN || OPAQUE_ONLY ? -1 : sc.root_masked, SUN || OPAQUE_ONLY || NO_BLEND ? -1 : sc.root_blend };
 
     uint32_t poolNext = 0, poolEnd = 0;
     const uint32_t home = xccId();
@@ -2089,6 +2115,8 @@ template<bool COUNT, int WPE, int MODE = kShadowWorld>
 __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_eu(WPE))) k_trace_shadow(SceneArgs sc, FrameArgs f)
 {
     if (frameAborted(f.abort_word)) return;
+    if constexpr (MODE == kShadowPath)
+        if (*f.shadow_count == 0u) return;
     __shared__ uint32_t ldsStack[kStackLds * 2 * kTraceBlock];
     // 8 cached nodes fewer than k_trace: the tail tables then fit 6 workgroups per CU
     // (the light-space traversal caches none)
@@ -2105,6 +2133,8 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
     uint32_t cNodes = 0, cTris = 0, cShadow = 0;
     if constexpr (MODE == kShadowOpaque) {
         shadowPhase<COUNT, false, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
+    } else if constexpr (MODE == kShadowPath) {
+        shadowPhase<COUNT, false, false, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
     } else {
         if constexpr (MODE != kShadowWorld) shadowPhase<COUNT, true>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
         if constexpr (MODE != kShadowSun) shadowPhase<COUNT, false>(sc, f, nc, st, tl, cNodes, cTris, cShadow);
@@ -2599,6 +2629,7 @@ __global__ void __launch_bounds__(kTraceBlock) __attribute__((amdgpu_waves_per_e
 #include "ddgi_compose.inc"
 #include "ddgi_reflections.inc"
 #include "ddgi_rt_shadows.inc"
+#include "ddgi_path_tracer.inc"
 
 } // namespace dev
 
@@ -2798,6 +2829,48 @@ hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s)
     const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
     if (pixels == 0 || a.light_count == 0) return hipSuccess;
     hipLaunchKernelGGL(dev::k_rtshadow_resolve, dim3(static_cast<uint32_t>((pixels + 255u) / 256u)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+// One batch of the path tracer (global slots [a.slot0, a.slot1) of the 8 x 8 tile order): the
+// setup, then kMaxSegments times trace / hit / shadow trace / shade, each launch reading its
+// list's count on the device. counters: kPtCounterWords words, zeroed by the caller on `s`
+// before. The grids of the hit and shade stages cover the batch; a workgroup past the list
+// returns at once.
+hipError_t launch_path_trace_batch(const SceneArgs& sc, const FrameArgs& f0, const PtArgs& a, uint32_t* counters, uint32_t traceBlocks, uint32_t shadowBlocks,
+                                   hipStream_t s, uint32_t segments)
+{
+    const uint32_t slots = a.slot1 - a.slot0;
+    if (slots == 0 || (slots & 63u)) return hipErrorInvalidValue;
+    const uint32_t blocks = (slots + 255u) / 256u;
+    hipLaunchKernelGGL(dev::k_pt_setup, dim3(blocks), dim3(256), 0, s, a, a.lists[0], counters + kPtListCountWord);
+    for (uint32_t seg = 0; seg < pt::kMaxSegments && seg < segments; ++seg) {
+        FrameArgs f = f0;
+        uint32_t* const own = counters + seg * kPtSegmentWords;
+        f.ray_list = a.lists[seg & 1u];
+        f.list_count = own + kPtListCountWord;
+        f.ray_counter = own;
+        f.shadow_count = own + kPtShadowCountWord;
+        f.shadow_heads = own + kPtShadowHeadWord;
+        void* args[] = { const_cast<SceneArgs*>(&sc), &f };
+        hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace<false, kTraceWpe, dev::PathRays>), dim3(traceBlocks), dim3(kTraceBlock), args, 0, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(dev::k_pt_hit, dim3(blocks), dim3(256), 0, s, sc, f, a);
+        if (f.light_count > 0) {
+            e = hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace_shadow<false, kShadowWpe, dev::kShadowPath>), dim3(shadowBlocks), dim3(kTraceBlock), args, 0, s);
+            if (e != hipSuccess) return e;
+        }
+        // (the last segment's survivors are written, never listed: goesOn)
+        hipLaunchKernelGGL(dev::k_pt_shade, dim3(blocks), dim3(256), 0, s, sc, f, a, seg, a.lists[(seg + 1u) & 1u], own + kPtSegmentWords + kPtListCountWord);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_path_trace_accumulate(const PtArgs& a, hipStream_t s)
+{
+    const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
+    if (pixels == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_pt_accumulate, dim3(static_cast<uint32_t>((pixels + 255u) / 256u)), dim3(256), 0, s, a);
     return hipGetLastError();
 }
 

@@ -5,6 +5,7 @@
 #include <cstring>
 
 #include "ddgi_context.h"
+#include "path_tracer_host.h"
 #include "refl_denoise_host.h"
 #include "rt_shadows_host.h"
 
@@ -233,6 +234,92 @@ int ark_ddgi_rt_local_shadows(ArkDdgiCtx* ctx, const ArkRtShadowsDesc* desc, voi
         ARK_HIP(launch_rt_shadow_batch(ctx->scene, f, a, l0, l1, shadowBlocksFor(ctx, pixels * (l1 - l0)), s));
     }
     ARK_HIP(launch_rt_shadow_resolve(a, s));
+    ARK_HIP(orderEnd(ctx, s));
+    return ARK_DDGI_OK;
+}
+
+// The path tracer (include/ark_ddgi.h; PathTracerNode.cpp:81-103; ddgi_path_tracer.inc): the
+// frame in batches of whole 8 x 8 tiles whose lists and path state fit kPathTracerBudget,
+// each batch 16 segments enqueued without a wait, then the accumulate step or the reset copy.
+// The work set grows only when a call needs more than any before it (width, height and the
+// light count decide), so a steady sequence of frames allocates nothing.
+int ark_ddgi_path_trace(ArkDdgiCtx* ctx, const ArkPathTracerDesc* desc, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!desc || desc->struct_size != sizeof(ArkPathTracerDesc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkPathTracerDesc");
+    if (const char* why = pt::descProblem(*desc)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "path_trace: %s", why);
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "path_trace before ark_ddgi_set_scene");
+    const uint64_t pixels = static_cast<uint64_t>(desc->width) * desc->height;
+    if (pixels == 0) return ARK_DDGI_OK;
+    const hipStream_t s = streamOf(hipStream);
+    ARK_HIP(hipSetDevice(ctx->device));
+    int rc;
+    // the scene first, as ark_ddgi_rt_reflections: a deeper sun BVH may reallocate the spill area
+    if (ctx->sceneVersion != ctx->sceneStore->version) {
+        if ((rc = refreshScene(ctx)) != 0) return rc;
+    } else if ((rc = ensureSpill(ctx)) != 0) {
+        return rc;
+    }
+    PtArgs a {};
+    a.width = desc->width;
+    a.height = desc->height;
+    a.frame_index = desc->frame_index;
+    a.flags = desc->flags;
+    a.accumulated_frames = desc->accumulated_frames;
+    a.environment_multiplier = desc->environment_multiplier;
+    a.z_near = desc->z_near;
+    a.z_far = desc->z_far;
+    std::memcpy(a.world_from_view, desc->world_from_view, sizeof(a.world_from_view));
+    std::memcpy(a.view_from_projection, desc->view_from_projection, sizeof(a.view_from_projection));
+    a.image = desc->image;
+    a.accumulation = desc->accumulation;
+    // batches of whole tiles under the budget, or the caller's size
+    const uint64_t slots = static_cast<uint64_t>((desc->width + 7u) / 8u) * ((desc->height + 7u) / 8u) * 64u;
+    const uint64_t perSlot = ptBytesPerSlot(ctx->lightCount);
+    uint64_t batch = std::max<uint64_t>(64, kPathTracerBudget / perSlot / 64u * 64u);
+    if (desc->max_paths_per_batch) batch = std::max<uint64_t>(64, std::min<uint64_t>(batch, desc->max_paths_per_batch / 64u * 64u));
+    batch = std::min(batch, slots);
+    auto al = [](uint64_t b) { return (b + 255) & ~static_cast<uint64_t>(255); };
+    const uint64_t counterBytes = kPtCounterWords * 4u;
+    const uint64_t bytes = al(counterBytes) + al(batch * 32) + 2 * al(batch * 32) + al(batch * 64) + al(batch * sizeof(GpuHit)) + al(batch * 4) +
+                           al(batch * ctx->lightCount * sizeof(ShadowRay));
+    if (ctx->ptWork.bytes < bytes) {
+        if (ctx->ptWork.ptr) ARK_HIP(drainContext(ctx)); // an earlier frame may still use the smaller one
+        ARK_HIP(ctx->ptWork.alloc(bytes));
+    }
+    FrameArgs f = samplingSetArgs(ctx);
+    f.z_far = desc->z_far;
+    f.spill = ctx->spill.as<uint32_t>();
+    uint32_t* counters;
+    {
+        char* w = static_cast<char*>(ctx->ptWork.ptr);
+        auto take = [&](uint64_t b) {
+            char* q = w;
+            w += al(b);
+            return q;
+        };
+        counters = reinterpret_cast<uint32_t*>(take(counterBytes));
+        a.state = reinterpret_cast<float4*>(take(batch * 32));
+        a.lists[0] = reinterpret_cast<float4*>(take(batch * 32));
+        a.lists[1] = reinterpret_cast<float4*>(take(batch * 32));
+        a.surf = reinterpret_cast<float4*>(take(batch * 64));
+        f.hits = reinterpret_cast<GpuHit*>(take(batch * sizeof(GpuHit)));
+        f.shadow_bits = reinterpret_cast<uint32_t*>(take(batch * 4));
+        f.shadow_rays = reinterpret_cast<ShadowRay*>(take(batch * ctx->lightCount * sizeof(ShadowRay)));
+    }
+    f.light_count = ctx->lightCount;
+    f.refill_min = ctx->refillMin;
+    f.sun_refill_min = ctx->sunRefillMin;
+    f.grab_chunk = ctx->grabChunk;
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(flushLights(ctx, s));
+    for (uint64_t s0 = 0; s0 < slots; s0 += batch) {
+        a.slot0 = static_cast<uint32_t>(s0);
+        a.slot1 = static_cast<uint32_t>(std::min(slots, s0 + batch));
+        ARK_HIP(hipMemsetAsync(counters, 0, counterBytes, s));
+        ARK_HIP(launch_path_trace_batch(ctx->scene, f, a, counters, ctx->traceBlocks, shadowBlocksFor(ctx, a.slot1 - a.slot0), s, ctx->ptSegments));
+    }
+    if (desc->flags) ARK_HIP(launch_path_trace_accumulate(a, s));
     ARK_HIP(orderEnd(ctx, s));
     return ARK_DDGI_OK;
 }

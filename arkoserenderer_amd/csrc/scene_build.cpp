@@ -8,6 +8,7 @@
 
 #include "ark_fmath.h"
 #include "bvh8_check.h"
+#include "shading_math.h"
 #include "sun_bvh.h"
 
 namespace ark {
@@ -57,12 +58,6 @@ void parallelFor(size_t n, int threads, F f)
     for (int t = 1; t < T; ++t) pool.emplace_back([&, t] { f(n * t / T, n * (t + 1) / T); });
     f(0, n / T);
     for (std::thread& th : pool) th.join();
-}
-
-// sRGB EOTF applied per texel before filtering (Vulkan sRGB formats).
-float srgbToLinear(float c)
-{
-    return c <= 0.04045f ? c / 12.92f : powf_((c + 0.055f) / 1.055f, 2.4f);
 }
 
 int validateScene(ErrorSink* err,const ArkDdgiScene* s)
@@ -138,16 +133,7 @@ int decodeTextures(ErrorSink* err,const ArkDdgiScene* s, std::vector<GpuTextureI
             for (size_t p = 0; p < n; ++p)
                 for (int c = 0; c < 4; ++c) {
                     float v = 0.0f;
-                    switch (t.format) {
-                    case ARK_TEX_RGBA8_UNORM: v = static_cast<float>(static_cast<const uint8_t*>(t.data)[p * 4 + c]) / 255.0f; break;
-                    case ARK_TEX_RGBA8_SRGB:
-                        v = static_cast<float>(static_cast<const uint8_t*>(t.data)[p * 4 + c]) / 255.0f;
-                        if (c < 3) v = srgbToLinear(v);
-                        break;
-                    case ARK_TEX_R32F: v = c == 0 ? static_cast<const float*>(t.data)[p] : (c == 3 ? 1.0f : 0.0f); break;
-                    case ARK_TEX_RGBA32F: v = static_cast<const float*>(t.data)[p * 4 + c]; break;
-                    default: return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "texture %u: unknown format", i);
-                    }
+                    if (!dev::decodeTexel(t.format, t.data, p, c, &v)) return err->fail(ARK_DDGI_E_INVALID_ARGUMENT, "texture %u: unknown format", i);
                     texels.push_back(v);
                 }
         }

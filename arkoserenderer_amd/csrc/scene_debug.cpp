@@ -2,6 +2,7 @@
 // installed-BVH checks, the last refit's reach).
 #include "../../include/ark_ddgi_debug.h"
 #include "bvh8_check.h"
+#include "path_tracer_host.h"
 #include "scene_store_internal.h"
 
 namespace ark {
@@ -105,6 +106,27 @@ int sceneRecordsAndClasses(const SceneStore& st, ErrorSink* err, std::vector<uin
     if (!records.empty()) ARK_HIP(hipMemcpy(records.data(), st.args.tris, records.size() * 4u, hipMemcpyDeviceToHost));
     const std::vector<int> cls = instanceClasses(st);
     classOf.assign(cls.begin(), cls.end());
+    return ARK_DDGI_OK;
+}
+
+int sceneHostCopy(const SceneStore& st, ErrorSink* err, pt::HostScene& out)
+{
+    auto fetch = [&](auto& vec, const void* dev, size_t count) -> hipError_t {
+        vec.resize(count);
+        return count ? hipMemcpy(vec.data(), dev, count * sizeof(vec[0]), hipMemcpyDeviceToHost) : hipSuccess;
+    };
+    static_assert(sizeof(pt::F4) == 16, "a texel");
+    ARK_HIP(fetch(out.tris, st.args.tris, st.world.records));
+    ARK_HIP(fetch(out.indices, st.args.indices, st.indices.bytes / sizeof(uint32_t)));
+    ARK_HIP(fetch(out.vertices, st.args.vertices, st.vertices.bytes / sizeof(float)));
+    ARK_HIP(fetch(out.meshes, st.args.meshes, st.meshes.bytes / sizeof(ArkRTTriangleMesh)));
+    ARK_HIP(fetch(out.materials, st.args.materials, st.materials.bytes / sizeof(ArkShaderMaterial)));
+    ARK_HIP(fetch(out.instances, st.args.instances, st.instHost.size()));
+    ARK_HIP(fetch(out.texInfos, st.args.tex_infos, st.texInfos.bytes / sizeof(GpuTextureInfo)));
+    ARK_HIP(fetch(out.texels, st.args.texels, st.texels.bytes / sizeof(pt::F4)));
+    out.textureCount = st.args.texture_count;
+    out.whiteTexture = st.args.white_texture;
+    out.envTexture = st.args.env_texture;
     return ARK_DDGI_OK;
 }
 

@@ -321,6 +321,13 @@ int sceneRefitReach(const SceneStore& st, ErrorSink* err, uint64_t* out);
 // instances' hit-mask classes, downloaded (the device is idle)
 int sceneRecordsAndClasses(const SceneStore& st, ErrorSink* err, std::vector<uint32_t>& records, std::vector<int32_t>& classOf);
 
+// ark_ddgi_debug_path_tracer_host_ctx: the front copy's records and instance table and the
+// shading pools, downloaded (the device is idle); the lights are the calling context's
+namespace pt {
+struct HostScene;
+}
+int sceneHostCopy(const SceneStore& st, ErrorSink* err, pt::HostScene& out);
+
 // SpotLightData as the closest hit reads it
 GpuSpotLight gpuSpotLight(const ArkSpotLight& sl);
 

@@ -598,6 +598,11 @@ class DDGIContext:
         desc.struct_size = C.sizeof(abi.ArkRtShadowsDesc)
         self.check(self.lib.ark_ddgi_rt_local_shadows(self.h, C.byref(desc), C.c_void_p(stream) if stream else None), "ark_ddgi_rt_local_shadows")
 
+    def path_trace(self, desc: abi.ArkPathTracerDesc, stream: int | None = None):
+        """ark_ddgi_path_trace: `desc` holds device pointers (include/ark_ddgi.h; path_tracer_desc)."""
+        desc.struct_size = C.sizeof(abi.ArkPathTracerDesc)
+        self.check(self.lib.ark_ddgi_path_trace(self.h, C.byref(desc), C.c_void_p(stream) if stream else None), "ark_ddgi_path_trace")
+
     def rt_reflections_denoise(self, desc: abi.ArkReflDenoiseDesc, stream: int | None = None):
         """ark_ddgi_rt_reflections_denoise: `desc` holds device pointers (include/ark_ddgi.h; refl_denoise_desc)."""
         desc.struct_size = C.sizeof(abi.ArkReflDenoiseDesc)
@@ -1354,3 +1359,121 @@ class RTLocalShadowNode:
         """The same frame through rt_shadows_host (no GPU): (masks, counts)."""
         depth = np.asarray(depth)
         return rt_shadows_host(records, class_of, class_mask, int(depth.shape[1]), int(depth.shape[0]), camera, depth, lights, self.frame_parameter(frame_index))
+
+
+def path_tracer_desc(width: int, height: int, camera: dict, image, accumulation=None, flags: int = 0, frame_index: int = 0, accumulated_frames: int = 0,
+                     environment_multiplier: float = 1.0, max_paths_per_batch: int = 0) -> abi.ArkPathTracerDesc:
+    """ArkPathTracerDesc from a camera dict (world_from_view, view_from_projection: column-major
+    16 floats; z_near, z_far) and the planes' addresses (device addresses for
+    DDGIContext.path_trace, host addresses for path_tracer_host)."""
+    d = abi.ArkPathTracerDesc()
+    d.struct_size = C.sizeof(abi.ArkPathTracerDesc)
+    d.width, d.height, d.flags = int(width), int(height), int(flags)
+    d.frame_index, d.accumulated_frames, d.max_paths_per_batch = int(frame_index) & 0xFFFFFFFF, int(accumulated_frames), int(max_paths_per_batch)
+    d.environment_multiplier, d.z_near, d.z_far = float(environment_multiplier), float(camera["z_near"]), float(camera["z_far"])
+    for k in ("world_from_view", "view_from_projection"):
+        getattr(d, k)[:] = [float(v) for v in np.asarray(camera[k], np.float32).reshape(16)]
+    d.image = int(image) if image else None
+    d.accumulation = int(accumulation) if accumulation else None
+    return d
+
+
+def _path_tracer_host(call, width, height, camera, flags, frame_index, accumulated_frames, environment_multiplier, accumulation, vertices):
+    image = np.full((height, width, 4), 0x5555, np.uint16)
+    acc = None
+    if flags:
+        acc = np.ascontiguousarray(accumulation, dtype=np.float32).copy() if accumulation is not None else np.zeros((height, width, 4), np.float32)
+        if acc.shape != (height, width, 4):
+            raise ValueError(f"path_tracer_host: accumulation must be [{height}, {width}, 4], got {list(acc.shape)}")
+    d = path_tracer_desc(width, height, camera, image.ctypes.data if image.size else 8, acc.ctypes.data if acc is not None and acc.size else (16 if flags else None), flags,
+                         frame_index, accumulated_frames, environment_multiplier)
+    vtx = np.zeros((height, width, abi.PATH_TRACER_MAX_SEGMENTS), np.dtype(abi.PATH_TRACER_VERTEX)) if vertices else None
+    out = (C.c_uint64 * len(abi.PATH_TRACER_COUNTS))()
+    call(d, vtx.ctypes.data if vtx is not None and vtx.size else None, out)
+    return image, acc, vtx, dict(zip(abi.PATH_TRACER_COUNTS, (int(v) for v in out)))
+
+
+def path_tracer_host(scene: SceneData, width: int, height: int, camera: dict, flags: int = 0, frame_index: int = 0, accumulated_frames: int = 0,
+                     environment_multiplier: float = 1.0, accumulation=None, vertices: bool = False):
+    """ark_ddgi_debug_path_tracer_host: the frame of ark_ddgi_path_trace restated on the host
+    over `scene`, no GPU. Returns (image uint16 [h, w, 4], accumulation float32 [h, w, 4] or
+    None, vertices (a structured array [h, w, 16] of abi.PATH_TRACER_VERTEX) or None, counts)."""
+    lib = abi.load_library()
+    abi_scene = scene.to_abi()
+
+    def call(d, vtx, out):
+        rc = lib.ark_ddgi_debug_path_tracer_host(C.byref(abi_scene), C.byref(d), vtx, out)
+        if rc != 0:
+            raise abi.ArkDdgiError(rc, "ark_ddgi_debug_path_tracer_host: a scene or a descriptor the library refuses")
+
+    return _path_tracer_host(call, width, height, camera, flags, frame_index, accumulated_frames, environment_multiplier, accumulation, vertices)
+
+
+def path_tracer_host_ctx(ctx: DDGIContext, width: int, height: int, camera: dict, flags: int = 0, frame_index: int = 0, accumulated_frames: int = 0,
+                         environment_multiplier: float = 1.0, accumulation=None, vertices: bool = False):
+    """ark_ddgi_debug_path_tracer_host_ctx: path_tracer_host over the context's own scene,
+    downloaded (it follows refits and set_lights). Synchronous; needs the context's GPU."""
+
+    def call(d, vtx, out):
+        ctx.check(ctx.lib.ark_ddgi_debug_path_tracer_host_ctx(ctx.h, C.byref(d), vtx, out), "ark_ddgi_debug_path_tracer_host_ctx")
+
+    return _path_tracer_host(call, width, height, camera, flags, frame_index, accumulated_frames, environment_multiplier, accumulation, vertices)
+
+
+def path_tracer_last_counts(ctx: DDGIContext) -> tuple:
+    """ark_ddgi_debug_path_tracer_last_counts: (live paths per segment [16], shadow rays listed
+    per segment [16]) of the last batch of the context's last path_trace call. Synchronous."""
+    out = (C.c_uint32 * (2 * abi.PATH_TRACER_MAX_SEGMENTS))()
+    ctx.check(ctx.lib.ark_ddgi_debug_path_tracer_last_counts(ctx.h, out), "ark_ddgi_debug_path_tracer_last_counts")
+    v = [int(x) for x in out]
+    return v[:abi.PATH_TRACER_MAX_SEGMENTS], v[abi.PATH_TRACER_MAX_SEGMENTS:]
+
+
+class PathTracerNode:
+    """Mirror of PathTracerNode (name "Path tracer", PathTracerNode.cpp:81-103): one path per
+    pixel and frame into the RGBA16F image, accumulated into the caller's RGBA32F plane. The
+    node holds the reference's state; the library holds none."""
+
+    def __init__(self):
+        self.should_accumulate = True           # m_shouldAccumulate
+        self.current_accumulated_frames = 0     # m_currentAccumulatedFrames
+        self.max_accumulated_frames = 1000      # m_maxAccumulatedFrames
+
+    def name(self) -> str:
+        return "Path tracer"
+
+    def plan(self, is_relative_first_frame: bool, camera_changed: bool, pending_uploads: bool) -> int:
+        """The frame's flags by PathTracerNode.cpp:83-84: ARK_PATH_TRACER_RESET,
+        ARK_PATH_TRACER_ACCUMULATE, or -1 when nothing is traced (the maximum is reached)."""
+        should_reset = (not self.should_accumulate) or is_relative_first_frame or camera_changed or pending_uploads
+        should_accum = (not should_reset) and self.should_accumulate and self.current_accumulated_frames < self.max_accumulated_frames
+        if should_accum:
+            return abi.ARK_PATH_TRACER_ACCUMULATE
+        return abi.ARK_PATH_TRACER_RESET if should_reset else -1
+
+    def advance(self, flags: int):
+        """The frame count after a frame planned as `flags` (PathTracerNode.cpp:98, :101)."""
+        if flags == abi.ARK_PATH_TRACER_ACCUMULATE:
+            self.current_accumulated_frames += 1
+        elif flags == abi.ARK_PATH_TRACER_RESET:
+            self.current_accumulated_frames = 1
+
+    def execute(self, ctx: DDGIContext, app: AppState, camera: dict, image, accumulation, environment_multiplier: float = 1.0, camera_changed: bool = False,
+                pending_uploads: bool = False, stream: int | None = None, max_paths_per_batch: int = 0):
+        """image: float16 [h, w, 4] device tensor (pathTraceImage); accumulation: float32
+        [h, w, 4] device tensor (PathTracerAccumulation). camera_changed and pending_uploads
+        are the caller's (scene.camera().hasChangedSinceLastFrame(), scene.hasPendingUploads()).
+        Returns the accumulation plane."""
+        import torch
+
+        node = "PathTracerNode"
+        h, w = int(image.shape[0]), int(image.shape[1])
+        _check_plane(node, "image", image, h, w, 4, (torch.float16,))
+        _check_plane(node, "accumulation", accumulation, h, w, 4, (torch.float32,))
+        flags = self.plan(app.is_first_frame(), camera_changed, pending_uploads)
+        if flags >= 0:
+            d = path_tracer_desc(w, h, camera, image.data_ptr(), accumulation.data_ptr(), flags, app.frame_index, self.current_accumulated_frames, environment_multiplier,
+                                 max_paths_per_batch)
+            ctx.path_trace(d, _tensor_stream(image, stream))
+            self.advance(flags)
+        return accumulation

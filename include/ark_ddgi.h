@@ -944,6 +944,39 @@ typedef struct ArkRtShadowsDesc {
  * nothing is enqueued. */
 int ark_ddgi_rt_local_shadows(ArkDdgiCtx* ctx, const ArkRtShadowsDesc* desc, void* hip_stream);
 
+/* ---- Path tracer ---------------------------------------------------------------------
+ * Replaces the execute lambda of PathTracerNode (PathTracerNode.cpp:81-103): the traceRays
+ * of pathtracer/pathtracer.rgen with its hit groups (closesthit.rchit with the default BRDF
+ * for the opaque and masked classes, the glass BRDF for the blend class; anyhit.rahit) and
+ * then accumulate.comp or the reset copy. One path per pixel, at most 16 segments, against
+ * the context's scene and lights (ark_ddgi_set_scene, ark_ddgi_set_lights). `image` gets
+ * (radiance, 0) per pixel, rounded to fp16; every texel is written. The library keeps no
+ * accumulation state: the caller's node counts the frames (PathTracerNode.cpp:83-102).
+ * max_paths_per_batch: 0, or the number of paths traced at a time (rounded down to whole
+ * 8 x 8 tiles, at least one tile); the result does not depend on it. */
+#define ARK_PATH_TRACER_RESET      (1u << 0) /* copyTexture(pathTraceImage -> accumulation), PathTracerNode.cpp:99-101 */
+#define ARK_PATH_TRACER_ACCUMULATE (1u << 1) /* accumulate.comp with frameCount = accumulated_frames */
+typedef struct ArkPathTracerDesc {
+    uint32_t struct_size, width, height, flags;
+    uint32_t frame_index;          /* constants.frameIndex */
+    uint32_t accumulated_frames;   /* n of accumulate.comp */
+    uint32_t max_paths_per_batch;  /* 0: the library's own ray-list budget */
+    float environment_multiplier, z_near, z_far;
+    float world_from_view[16], view_from_projection[16];
+    uint16_t* image;               /* pathTraceImage RGBA16F: radiance, 0 */
+    float* accumulation;           /* PathTracerAccumulation RGBA32F; required when a flag is set */
+    int32_t reserved[4];
+} ArkPathTracerDesc;
+
+/* Enqueues the frame on `hip_stream` (NULL = the null stream) without a host wait, after
+ * every operation of this context called before it (refits, vertex updates and installs
+ * among them; it shares the update's traversal stack space). ARK_DDGI_E_INVALID_ARGUMENT,
+ * with nothing enqueued, for a wrong struct_size, an unknown flag, both flags, a flag without
+ * `accumulation`, a null `image`, a plane not aligned to its texel (8 and 16 bytes), planes
+ * whose byte ranges overlap, a non-finite matrix or scalar, width * height >= 2^28;
+ * ARK_DDGI_E_NO_SCENE before a scene is set. An empty image: OK, nothing is enqueued. */
+int ark_ddgi_path_trace(ArkDdgiCtx* ctx, const ArkPathTracerDesc* desc, void* hip_stream);
+
 /* ---- DDGI probe debug visualisation --------------------------
  * The fragment stage of DDGIProbeDebug (DDGIProbeDebug.cpp:34-71,
  * ddgi/probeDebug.frag): for each (probe index, sphere normal) sample, the colour the

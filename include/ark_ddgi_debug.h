@@ -367,6 +367,48 @@ int ark_ddgi_debug_refl_denoise_kat(int which, const float* in, int n_in, float*
  * 4 historyCopy. For timing the passes (tools/refl_denoise_cost.py). */
 int ark_ddgi_debug_refl_denoise_pass(struct ArkDdgiCtx* ctx, const ArkReflDenoiseDesc* desc, int pass, void* hip_stream);
 
+/* The path tracer (ark_ddgi_path_trace) restated serially on the host from the functions its
+ * kernels call (csrc/path_tracer.h): every path walked segment by segment, hits found by
+ * brute force over the triangle records with the kernels' Möller–Trumbore and tie rule, the
+ * image and (with a flag) the accumulation plane written. `desc` is the entry's, except that
+ * image and accumulation are HOST pointers.
+ * _host: no GPU; the scene preprocessed on the host as ark_ddgi_set_scene does it. _host_ctx:
+ * over the context's own scene downloaded (the front copy's records and instance table, the
+ * shading pools, the context's lights); it follows refits by construction. Synchronous.
+ * vertices: NULL, or width * height * 16 records of 33 words, pixel-major, one per segment:
+ *   [0] status (0 the path had ended, 1 scattered on, 2 missed, 3 killed (pdf <= 0), 4 hit and
+ *   ended by the loop's condition), [1] RNG state before, [2..4] origin, [5..7] direction,
+ *   [8] tmin, [9] record index of the hit (0xffffffff none), [10..12] t, u, v, [13] back face,
+ *   [14] shadow bits (bit l: light l cast a ray, bit 16 + l: occluded), [15..17] attenuation
+ *   and [18..20] radiance before, [21..23] and [24..26] after, [27..29] scattered direction,
+ *   [30] RNG state after, [31] candidates the alpha test refused, [32] the glass program ran.
+ * counts (may be NULL): 8 = {glass vertices, alpha-refused candidates, killed paths, paths
+ * with a segment 8, occluded shadow rays, lit shadow rays, missed segments, vertices}.
+ * _check_desc: the entry's argument checks alone (struct_size included), no context and no
+ * device; pointers are compared, never followed. _layout: out[0 .. n) of the offsets of
+ * ArkPathTracerDesc's fields from width on in declaration order (14 words), then
+ * sizeof(ArkPathTracerDesc) and the bytes of a vertex record; returns how many it wrote.
+ * _accumulate_host: the accumulate step or the reset copy alone over host planes (a flag is
+ * required). _sample: out_state[2] = {the pixel's seed, the state after the two jitter
+ * draws}, out_ray[6] = the camera ray's origin and direction. */
+int ark_ddgi_debug_path_tracer_host(const ArkDdgiScene* scene, const ArkPathTracerDesc* desc, void* vertices, uint64_t* counts);
+int ark_ddgi_debug_path_tracer_host_ctx(struct ArkDdgiCtx* ctx, const ArkPathTracerDesc* desc, void* vertices, uint64_t* counts);
+int ark_ddgi_debug_path_tracer_check_desc(const ArkPathTracerDesc* desc);
+int ark_ddgi_debug_path_tracer_layout(uint32_t* out, int n);
+int ark_ddgi_debug_path_tracer_accumulate_host(const ArkPathTracerDesc* desc);
+/* The list counts the last batch of the context's last ark_ddgi_path_trace call left on the
+ * device: out[0 .. 16) the live paths of each segment, out[16 .. 32) the shadow rays each
+ * segment listed. All zero before the first call. Synchronous. (A frame that fits one batch
+ * is counted whole: tools/path_tracer_cost.py.) */
+int ark_ddgi_debug_path_tracer_last_counts(struct ArkDdgiCtx* ctx, uint32_t* out);
+/* _set_segments: the segments (1..16, default 16) the context's next ark_ddgi_path_trace calls
+ * enqueue. For timing only (tools/path_tracer_cost.py): with fewer than 16 the pixels of paths
+ * that would have gone on are not written. _random: pt_randomFloat alone. */
+int ark_ddgi_debug_path_tracer_set_segments(struct ArkDdgiCtx* ctx, uint32_t segments);
+int ark_ddgi_debug_path_tracer_random(uint32_t state, float* out_value, uint32_t* out_next);
+int ark_ddgi_debug_path_tracer_sample(uint32_t px, uint32_t py, uint32_t width, uint32_t height, uint32_t frame_index, const float* world_from_view,
+                                      const float* view_from_projection, uint32_t* out_state, float* out_ray);
+
 #ifdef __cplusplus
 }
 #endif
