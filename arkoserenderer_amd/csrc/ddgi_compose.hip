@@ -1,7 +1,8 @@
-// Included inside namespace ark::dev by ddgi_kernels.hip (after sampleDDGI).
+// ddgi_compose.hip — the DDGI consumers that only read the atlases (ddgi_sampling.h):
+// lighting compose and the probe debug visualisation.
 //
-// DDGI consumer: lighting compose (lightingCompose.comp:22-135, WITH_DDGI = 1,
-// driven by LightingComposeNode.cpp:60-110).
+// Lighting compose (lightingCompose.comp:22-135, WITH_DDGI = 1, driven by
+// LightingComposeNode.cpp:60-110).
 //
 // One thread per pixel, 64 x 4 tiles: a wave reads one row of 64 pixels, so a 4-B plane
 // is two whole 128-B lines per wave and an 8-B plane four (16 x 16 tiles read half lines
@@ -12,6 +13,16 @@
 // beyond the plane bytes is atlas texels missing the XCDs' L2s. Matrix products are summed column by column,
 // left to right, without contraction (the same order as the oracle); GLSL leaves
 // that order to the driver.
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/ark_ddgi.h"
+#include "ddgi_device.h"
+#include "ddgi_kernels.h"
+#include "ddgi_sampling.h"
+
+namespace ark {
+namespace dev {
 
 __device__ __forceinline__ float4 ldHalf4(const uint16_t* p, uint32_t i)
 {
@@ -172,3 +183,23 @@ __global__ void __launch_bounds__(256) k_probe_debug(FrameArgs f, ArkProbeDebugD
     o.y = static_cast<uint32_t>(f32_to_f16(c.z)) | (0x3c00u << 16);
     reinterpret_cast<uint2*>(d.out)[i] = o;
 }
+
+} // namespace dev
+
+hipError_t launch_lighting_compose(const FrameArgs& f, const ArkComposeDesc& c, hipStream_t s)
+{
+    if (c.width == 0 || c.height == 0) return hipSuccess;
+    const uint64_t tiles = static_cast<uint64_t>((c.width + 63u) / 64u) * ((c.height + 3u) / 4u); // 64 x 4 tiles (k_lighting_compose)
+    if (tiles > (1ull << 31)) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_lighting_compose, dim3(static_cast<uint32_t>((tiles + 7u) / 8u * 8u)), dim3(256), 0, s, f, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_probe_debug(const FrameArgs& f, const ArkProbeDebugDesc& d, hipStream_t s)
+{
+    if (d.count == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_probe_debug, dim3((d.count + 255u) / 256u), dim3(256), 0, s, f, d);
+    return hipGetLastError();
+}
+
+} // namespace ark

@@ -4,6 +4,10 @@
 //   ddgi_frame.cpp          the update (frames in flight: frame_book.h), sequencing, exchanges
 //   ddgi_passes.cpp         AO bake, lighting compose, RT reflections, probe debug
 //   ddgi_debug_entries.cpp  the ark_ddgi_debug_* entries (include/ark_ddgi_debug.h)
+// Their kernels and launchers (ddgi_kernels.h), one unit per pass: ddgi_kernels.hip +
+// ddgi_update.hip (the update), ddgi_bake.hip, ddgi_compose.hip (compose, probe debug),
+// ddgi_reflections.hip, ddgi_rt_shadows.hip, ddgi_path_tracer.hip; the traversal they share
+// is ddgi_traversal.h and ddgi_trace_kernels.h.
 // A context owns the device memory of one DDGI node instance on one GPU: the persistent
 // atlases/offsets (the DDGISamplingSet, DDGINode.cpp:62-66), the per-update
 // working set (slot table, hit records, surfels) and its lights, and holds the scene

@@ -278,7 +278,7 @@ __device__ __forceinline__ bool frameAborted(const uint32_t* abortWord)
     return sAbort != 0u;
 }
 
-// AO / bent-normal bake of one mesh segment (ark_ddgi_bake_ao; ddgi_kernels.hip §5)
+// AO / bent-normal bake of one mesh segment (ark_ddgi_bake_ao; ddgi_bake.hip)
 struct BakeArgs {
     uint32_t W, H, samples, tri_count;
     int32_t bent;
@@ -503,7 +503,7 @@ hipError_t launch_lighting_compose(const FrameArgs& f, const ArkComposeDesc& c, 
 // 1 closest-hit traversal, 2 shadow-ray list, 3 shadow traversal, 4 shading
 hipError_t launch_rt_reflections(const SceneArgs& sc, const FrameArgs& f, const ArkReflectionsDesc& r, uint32_t traceBlocks, uint32_t shadowBlocks,
                                  hipStream_t s);
-// RT local shadows (ddgi_rt_shadows.inc): the call's lights travel as kernel arguments
+// RT local shadows (ddgi_rt_shadows.hip): the call's lights travel as kernel arguments
 constexpr uint64_t kRtShadowRayBudget = 512ull << 20; // bytes of one traversal launch's worst-case ray list
 struct RtShadowArgs {
     uint32_t width, height, frame_index, light_count;
@@ -516,7 +516,7 @@ struct RtShadowArgs {
 // the ray list of lights [l0, l1) into f.shadow_rays / f.shadow_count, and its opaque-only traversal
 hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s);
 hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s);
-// The path tracer (ddgi_path_tracer.inc). Its counters, per segment on lines of their own: the
+// The path tracer (ddgi_path_tracer.hip). Its counters, per segment on lines of their own: the
 // trace's partition heads, the shadow list's count and heads, the path list's count; one
 // block more for the count the last segment's shading is handed.
 constexpr uint32_t kPtShadowCountWord = kRayParts * kRayCounterStride;

@@ -1,8 +1,7 @@
-// The path tracer (PathTracerNode.cpp:81-103, pathtracer/pathtracer.rgen, closesthit.rchit,
-// material.glsl, accumulate.comp) as a wavefront pipeline over a compacted list of live
-// paths; included by ddgi_kernels.hip inside namespace ark::dev. The per-path arithmetic is
-// path_tracer.h's, shared with the host restatement (path_tracer_host.cpp), in the same
-// operation order.
+// ddgi_path_tracer.hip — the path tracer (PathTracerNode.cpp:81-103, pathtracer/pathtracer.rgen,
+// closesthit.rchit, material.glsl, accumulate.comp) as a wavefront pipeline over a compacted
+// list of live paths. The per-path arithmetic is path_tracer.h's, shared with the host
+// restatement (path_tracer_host.cpp), in the same operation order.
 //
 //   k_pt_setup            per pixel slot of the 8 x 8 tile order: RNG seed, camera ray, path
 //                         state; appends {origin, tmin}, {direction, slot} (one list atomic
@@ -22,6 +21,50 @@
 //
 // A path's state lives at its slot, not at its list position, and nothing is summed across
 // paths: a pixel does not depend on the order of a list.
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/ark_ddgi.h"
+#include "ddgi_device.h"
+#include "ddgi_kernels.h"
+#include "ddgi_shading.h"
+#include "ddgi_trace_kernels.h"
+#include "path_tracer.h"
+
+namespace ark {
+namespace dev {
+
+// k_trace's source (the Src contract: ddgi_trace_kernels.h).
+// PathRays: the path tracer's list (pathtracer.rgen:42-50: RayFlags_None, cullMask opaque |
+// masked | blend): {origin, tmin}, {direction, slot}, tmax zFar on every segment. One closest
+// hit over the three classes: the lane walks the roots in turn and keeps its hit, so tmax
+// shrinks from class to class and the tie rule holds across them; `pass` is the class, and
+// class 1's candidates take the path tracer's alpha test. An empty list returns at once.
+struct PathRays {
+    static constexpr bool kAllClasses = true;
+    static constexpr bool kMaskedPass = false;
+    static constexpr bool kSeeds = false;
+    static constexpr float kTmin = 0.0001f; // (each ray carries its own)
+    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
+    {
+        grabItemsWave(f.ray_counter, *f.list_count, home, lane, tried, b, e, chunk);
+    }
+    __device__ static PoolRec stage(const SceneArgs&, const FrameArgs& f, uint32_t r)
+    {
+        const float4 a = f.ray_list[2u * r], b = f.ray_list[2u * r + 1u];
+        PoolRec rec;
+        rec.o = { a.x, a.y, a.z };
+        rec.d = { b.x, b.y, b.z };
+        rec.a = __float_as_uint(a.w); // tmin
+        rec.c = seed::kNone;
+        return rec;
+    }
+    __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t, uint32_t& ray, float& tmax)
+    {
+        ray = r;
+        tmax = f.z_far;
+    }
+};
 
 __device__ __forceinline__ pt::SceneView<float4> ptView(const SceneArgs& sc)
 {
@@ -47,7 +90,7 @@ __device__ __forceinline__ pt::SceneView<float4> ptView(const SceneArgs& sc)
     return v;
 }
 
-// anyhit.rahit for k_trace<PathRays> (travStepDual's PT alpha test)
+// anyhit.rahit for k_trace<PathRays> (travStepDual's PATH alpha test; declared in ddgi_traversal.h)
 __device__ bool alphaAcceptPath(const SceneArgs& sc, uint32_t inst, uint32_t prim, float u, float v)
 {
     return pt::alphaAccept(ptView(sc), inst, prim, u, v);
@@ -225,3 +268,49 @@ __global__ void __launch_bounds__(256) k_pt_accumulate(PtArgs a)
         *acc = make_float4(pt::accumulate(c.x, r, n), pt::accumulate(c.y, g, n), pt::accumulate(c.z, b, n), 1.0f);
     }
 }
+
+} // namespace dev
+
+// One batch of the path tracer (global slots [a.slot0, a.slot1) of the 8 x 8 tile order): the
+// setup, then kMaxSegments times trace / hit / shadow trace / shade, each launch reading its
+// list's count on the device. counters: kPtCounterWords words, zeroed by the caller on `s`
+// before. The grids of the hit and shade stages cover the batch; a workgroup past the list
+// returns at once.
+hipError_t launch_path_trace_batch(const SceneArgs& sc, const FrameArgs& f0, const PtArgs& a, uint32_t* counters, uint32_t traceBlocks, uint32_t shadowBlocks,
+                                   hipStream_t s, uint32_t segments)
+{
+    const uint32_t slots = a.slot1 - a.slot0;
+    if (slots == 0 || (slots & 63u)) return hipErrorInvalidValue;
+    const uint32_t blocks = (slots + 255u) / 256u;
+    hipLaunchKernelGGL(dev::k_pt_setup, dim3(blocks), dim3(256), 0, s, a, a.lists[0], counters + kPtListCountWord);
+    for (uint32_t seg = 0; seg < pt::kMaxSegments && seg < segments; ++seg) {
+        FrameArgs f = f0;
+        uint32_t* const own = counters + seg * kPtSegmentWords;
+        f.ray_list = a.lists[seg & 1u];
+        f.list_count = own + kPtListCountWord;
+        f.ray_counter = own;
+        f.shadow_count = own + kPtShadowCountWord;
+        f.shadow_heads = own + kPtShadowHeadWord;
+        void* args[] = { const_cast<SceneArgs*>(&sc), &f };
+        hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace<false, dev::kTraceWpe, dev::PathRays>), dim3(traceBlocks), dim3(kTraceBlock), args, 0, s);
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(dev::k_pt_hit, dim3(blocks), dim3(256), 0, s, sc, f, a);
+        if (f.light_count > 0) {
+            e = hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace_shadow<false, dev::kShadowWpe, dev::kShadowPath>), dim3(shadowBlocks), dim3(kTraceBlock), args, 0, s);
+            if (e != hipSuccess) return e;
+        }
+        // (the last segment's survivors are written, never listed: goesOn)
+        hipLaunchKernelGGL(dev::k_pt_shade, dim3(blocks), dim3(256), 0, s, sc, f, a, seg, a.lists[(seg + 1u) & 1u], own + kPtSegmentWords + kPtListCountWord);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_path_trace_accumulate(const PtArgs& a, hipStream_t s)
+{
+    const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
+    if (pixels == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_pt_accumulate, dim3(static_cast<uint32_t>((pixels + 255u) / 256u)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+} // namespace ark

@@ -1,6 +1,6 @@
-// RT reflections ray generation (rt-reflections/raygen.rgen:54-166, WITH_DDGI) as a
-// ray-list pipeline; included by ddgi_kernels.hip inside namespace ark::dev. Every
-// step follows oracle/ddgi_oracle.cpp oracle_rt_reflections in the same operation order.
+// ddgi_reflections.hip — RT reflections ray generation (rt-reflections/raygen.rgen:54-166,
+// WITH_DDGI) as a ray-list pipeline. Every step follows oracle/ddgi_oracle.cpp
+// oracle_rt_reflections in the same operation order.
 //
 //   k_refl_setup      G-buffer decode + GGX VNDF sample per pixel (8 x 8 tiles):
 //                     pixels that trace no ray are written here; the others append
@@ -8,9 +8,51 @@
 //                     atomic per 1,024 pixels)
 //   k_trace<ListRays> persistent closest-hit traversal of the opaque class with the
 //                     probe rays' ballot refill and dual steps
-//   k_shadow_gen<true> + k_trace_shadow: the closest hit's shadow rays (both faces)
+//   k_shadow_gen<true> + k_trace_shadow: the closest hit's shadow rays (both faces;
+//                     the update's instances, launch_trace_shadow of ddgi_kernels.hip)
 //   k_refl_shade      closest-hit program with the occluded bits, DDGI lookup,
 //                     environment on a miss
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/ark_ddgi.h"
+#include "ddgi_device.h"
+#include "ddgi_kernels.h"
+#include "ddgi_sampling.h"
+#include "ddgi_shading.h"
+#include "ddgi_trace_kernels.h"
+
+namespace ark {
+namespace dev {
+
+// k_trace's source (the Src contract: ddgi_trace_kernels.h). ListRays: a ray list of
+// {origin, tmax}, {direction, id} (rt-reflections/raygen.rgen:111-119: RayFlags_Opaque,
+// cullMask 0x01, tmin 0.01), f.list_count entries, the hit record at the list index.
+struct ListRays {
+    static constexpr bool kAllClasses = false;
+    static constexpr bool kMaskedPass = false;
+    static constexpr bool kSeeds = false;
+    static constexpr float kTmin = 0.01f;
+    __device__ static void grab(const FrameArgs& f, uint32_t home, uint32_t lane, uint32_t& tried, uint32_t& b, uint32_t& e, uint32_t chunk)
+    {
+        grabItemsWave(f.ray_counter, *f.list_count, home, lane, tried, b, e, chunk);
+    }
+    __device__ static PoolRec stage(const SceneArgs&, const FrameArgs& f, uint32_t r)
+    {
+        const float4 a = f.ray_list[2u * r], b = f.ray_list[2u * r + 1u];
+        PoolRec rec;
+        rec.o = { a.x, a.y, a.z };
+        rec.d = { b.x, b.y, b.z };
+        rec.a = __float_as_uint(a.w); // tmax
+        rec.c = seed::kNone;
+        return rec;
+    }
+    __device__ static void take(const FrameArgs& f, uint32_t r, uint32_t recA, uint32_t& ray, float& tmax)
+    {
+        ray = r;
+        tmax = __uint_as_float(recA);
+    }
+};
 
 // raygen.rgen:34-50 createIsotropicTBN: rows T, B, N (returned transposed)
 struct ReflTBN {
@@ -287,3 +329,26 @@ __global__ void __launch_bounds__(256) k_refl_shade(SceneArgs sc, FrameArgs f, A
     reflStore(r.out_radiance, p, radiance, tmax);
     reflStore(r.out_direction, p, rayDirection, 0.0f);
 }
+
+} // namespace dev
+
+hipError_t launch_rt_reflections(const SceneArgs& sc, const FrameArgs& f, const ArkReflectionsDesc& r, uint32_t traceBlocks, uint32_t shadowBlocks,
+                                 hipStream_t s)
+{
+    const uint64_t pixels = static_cast<uint64_t>(r.width) * r.height;
+    const uint64_t slots = static_cast<uint64_t>((r.width + 7u) / 8u) * ((r.height + 7u) / 8u) * 64u;
+    hipLaunchKernelGGL(dev::k_refl_setup, dim3(static_cast<uint32_t>((slots + dev::kReflSetupSpan - 1) / dev::kReflSetupSpan)), dim3(256), 0, s, f, r,
+                       const_cast<float4*>(f.ray_list), const_cast<uint32_t*>(f.list_count));
+    void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
+    hipError_t e = hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace<false, 6, dev::ListRays>), dim3(traceBlocks), dim3(kTraceBlock), args, 0, s);
+    if (e != hipSuccess) return e;
+    if (f.light_count > 0) {
+        hipLaunchKernelGGL(dev::k_shadow_gen<true>, dim3(static_cast<uint32_t>((pixels + dev::kGenSpan - 1) / dev::kGenSpan)), dim3(256), 0, s, sc, f);
+        e = launch_trace_shadow(sc, f, shadowBlocks, false, s);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL(dev::k_refl_shade, dim3(static_cast<uint32_t>((pixels + 255) / 256)), dim3(256), 0, s, sc, f, r);
+    return hipGetLastError();
+}
+
+} // namespace ark

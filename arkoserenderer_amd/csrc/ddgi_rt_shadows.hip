@@ -1,7 +1,7 @@
-// Ray-traced local-light shadow masks (RTLocalShadowNode.cpp:47-90, rt-shadow/
-// raygen.rgen:33-80) as a ray-list pipeline; included by ddgi_kernels.hip inside namespace
-// ark::dev. The per-pixel arithmetic is rt_shadows.h's, shared with the host restatement
-// (rt_shadows_host.cpp), in the same operation order.
+// ddgi_rt_shadows.hip — ray-traced local-light shadow masks (RTLocalShadowNode.cpp:47-90,
+// rt-shadow/raygen.rgen:33-80) as a ray-list pipeline. The per-pixel arithmetic is
+// rt_shadows.h's, shared with the host restatement (rt_shadows_host.cpp), in the same
+// operation order.
 //
 //   k_rtshadow_gen      depth -> shading point -> disc sample -> per light of the batch the
 //                       cone test; a light that needs a ray appends {origin, tmax},
@@ -10,6 +10,7 @@
 //                       contiguous). The pixel's result word: bit l = light l's ray is listed.
 //   k_trace_shadow<kShadowOpaque>  persistent any-hit traversal of the opaque class only
 //                       (cullMask RT_HIT_MASK_OPAQUE): an occluded ray sets bit 16 + l
+//                       (the template of ddgi_trace_kernels.h, this mode instantiated here)
 //   k_rtshadow_resolve  listed and not occluded -> 255, else 0 (sky, outside the cone,
 //                       occluded), one byte per light and pixel
 //
@@ -17,6 +18,17 @@
 // consecutive lights whose worst-case ray lists (pixels x lights x 32 B) fit
 // kRtShadowRayBudget = 512 MiB: one traversal launch per batch. 1920 x 1080 pixels take
 // 63.3 MiB per light: up to 8 lights are one launch. A batch holds at least one light.
+
+#include <hip/hip_runtime.h>
+
+#include "../../include/ark_ddgi.h"
+#include "ddgi_device.h"
+#include "ddgi_kernels.h"
+#include "ddgi_trace_kernels.h"
+#include "rt_shadows.h"
+
+namespace ark {
+namespace dev {
 
 __global__ void __launch_bounds__(256) k_rtshadow_gen(RtShadowArgs a, uint32_t l0, uint32_t l1, ShadowRay* __restrict__ list, uint32_t* listCount)
 {
@@ -96,3 +108,27 @@ __global__ void __launch_bounds__(256) k_rtshadow_resolve(RtShadowArgs a)
         a.masks[l][p] = lit ? uint8_t(255) : uint8_t(0);
     }
 }
+
+} // namespace dev
+
+// One batch of lights [l0, l1) of ark_ddgi_rt_local_shadows: the ray list, then its
+// traversal through the opaque class (never the counting instantiation: the shadow
+// counters stay the DDGI path's).
+hipError_t launch_rt_shadow_batch(const SceneArgs& sc, const FrameArgs& f, const RtShadowArgs& a, uint32_t l0, uint32_t l1, uint32_t shadowBlocks, hipStream_t s)
+{
+    const uint64_t slots = static_cast<uint64_t>((a.width + 7u) / 8u) * ((a.height + 7u) / 8u) * 64u;
+    if (slots == 0 || l0 >= l1 || l1 > rtshadow::kMaxLights) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(dev::k_rtshadow_gen, dim3(static_cast<uint32_t>((slots + 255u) / 256u)), dim3(256), 0, s, a, l0, l1, f.shadow_rays, f.shadow_count);
+    void* args[] = { const_cast<SceneArgs*>(&sc), const_cast<FrameArgs*>(&f) };
+    return hipLaunchKernel(reinterpret_cast<const void*>(&dev::k_trace_shadow<false, dev::kShadowWpe, dev::kShadowOpaque>), dim3(shadowBlocks), dim3(kTraceBlock), args, 0, s);
+}
+
+hipError_t launch_rt_shadow_resolve(const RtShadowArgs& a, hipStream_t s)
+{
+    const uint64_t pixels = static_cast<uint64_t>(a.width) * a.height;
+    if (pixels == 0 || a.light_count == 0) return hipSuccess;
+    hipLaunchKernelGGL(dev::k_rtshadow_resolve, dim3(static_cast<uint32_t>((pixels + 255u) / 256u)), dim3(256), 0, s, a);
+    return hipGetLastError();
+}
+
+} // namespace ark

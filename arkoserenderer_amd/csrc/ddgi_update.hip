@@ -1,4 +1,4 @@
-// ddgi_update.hip — the probe update of the DDGI path (kernel 4 of ddgi_kernels.hip):
+// ddgi_update.hip — the probe update of the DDGI path (launch 5 of the update, ddgi_kernels.hip):
 // irradiance + visibility blend (probeUpdateIrradiance.comp, probeUpdateVisibility.comp),
 // tile border copy (probeBorderCopy*.comp) and probe offsets (probeUpdateOffset.comp).
 //

@@ -1,6 +1,6 @@
 // path_tracer.h — the arithmetic of the reference's path tracer (arkose/shaders/pathtracer/
 // pathtracer.rgen, closesthit.rchit, material.glsl, common.glsl, accumulate.comp), written
-// once: the kernels of ddgi_path_tracer.inc and the serial host restatement
+// once: the kernels of ddgi_path_tracer.hip and the serial host restatement
 // (path_tracer_host.cpp) call these functions in the same order, and both sides are compiled
 // with -ffp-contract=off, so a path is the same bits on both. Pure C++ without a HIP
 // dependency (the host side is also built on its own, tests/cpp). Vectors, the BRDF and the

@@ -1,6 +1,6 @@
 // rt_shadows.h — the arithmetic of the reference's local-light shadow raygen
 // (arkose/shaders/rt-shadow/raygen.rgen:33-80), written once: k_rtshadow_gen
-// (ddgi_rt_shadows.inc) and the serial host restatement (rt_shadows_host.cpp) call these
+// (ddgi_rt_shadows.hip) and the serial host restatement (rt_shadows_host.cpp) call these
 // functions in the same order, and both sides are compiled with -ffp-contract=off, so their
 // rays are the same bits. Pure C++ without a HIP dependency (the host side is also built on
 // its own, tests/cpp).

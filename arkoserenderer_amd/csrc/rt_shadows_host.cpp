@@ -41,7 +41,7 @@ struct Tri {
     float v0[3], e1[3], e2[3];
 };
 
-// the kernels' Möller–Trumbore (ddgi_kernels.hip intersectTri), any hit in [tmin, tmax]
+// the kernels' Möller–Trumbore (shading_math.h intersectTri, ddgi_traversal.h), any hit in [tmin, tmax]
 bool hits(const float o[3], const float d[3], float tmin, float tmax, const Tri& g)
 {
     auto cr = [](const float* a, const float* b, float* c) {

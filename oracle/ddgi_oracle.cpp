@@ -583,8 +583,8 @@ struct Ray {
     float tmin, tmax;
 };
 
-// Möller–Trumbore (shared exact op order with the HIP kernel, ddgi_kernels.hip
-// intersectTri): cross and dot products fused explicitly, one fma per cross
+// Möller–Trumbore (shared exact op order with the HIP kernels' intersectTri,
+// shading_math.h, called from ddgi_traversal.h): cross and dot products fused explicitly, one fma per cross
 // component (a.y b.z - a.z b.y = fma(a.y, b.z, -(a.z b.y))) and two per dot
 // product (fma(a.x, b.x, fma(a.y, b.y, a.z b.z))). The Vulkan driver's intersection
 // arithmetic is unspecified, so the restatement fixes one.
@@ -1786,7 +1786,7 @@ int oracle_lighting_compose(void* ctx, const ArkComposeDesc* c, int threads)
 // RT reflections ray generation (rt-reflections/raygen.rgen:54-166, WITH_DDGI;
 // include/ark_ddgi.h ark_ddgi_rt_reflections) on host arrays, against the oracle's
 // scene and current atlases. Matrix products sum in index order (the HIP kernel's
-// ddgi_reflections.inc does the same).
+// ddgi_reflections.hip does the same).
 int oracle_rt_reflections(void* ctx, const ArkReflectionsDesc* r, int threads)
 {
     const Oracle& o = *static_cast<Oracle*>(ctx);

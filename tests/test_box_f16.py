@@ -1,6 +1,6 @@
 """The reduced-precision BVH8 child tests are conservative (host restatement, no GPU).
 
-visitNode8 (ddgi_kernels.hip) tests children with fp32 slabs. Round 4 also built two
+visitNode8 (ddgi_traversal.h) tests children with fp32 slabs. Round 4 also built two
 packed-fp16 forms (per-axis error bounds, and directed rounding: near planes toward
 -inf, far planes toward +inf); they were measured 10x slower and removed from the
 kernels in round 5, and their host restatements stay as the record that

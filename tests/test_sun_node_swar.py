@@ -1,4 +1,4 @@
-"""The bytewise arithmetic of the sun's light-space node test (ddgi_kernels.hip
+"""The bytewise arithmetic of the sun's light-space node test (ddgi_traversal.h
 geBytes / visitNodeSun), restated in numpy and checked exhaustively on the CPU: the
 unsigned compare of four packed bytes with one subtraction and one three-input boolean
 function, and the gather of the eight per-child results into the 8-bit slot mask by the

@@ -4,18 +4,30 @@ kernel's register use and spills, and the loop blocks of the traversal step.
 
     python tools/isa_budget.py <file.s> [kernel-substring] [--blocks] [--json]
 
-Build the assembly with the library's own flags (tools/isa_budget.py --build OUT.s
-[EXTRA...] runs hipcc on ddgi_kernels.hip with the Makefile's kernel flags plus EXTRA).
+Build the assembly with the library's own flags: tools/isa_budget.py --build UNIT [EXTRA...]
+runs the Makefile's asm rule for the device unit UNIT (ddgi_kernels, ddgi_update, ...; `all`:
+every unit) with EXTRA added to its flags, and prints the path of each .s written.
+
+    python tools/isa_budget.py --inventory <file.s> [<file.s> ...]
+
+One line per kernel of the files, sorted by demangled name: SGPRs, VGPRs, VGPR and SGPR
+spills, LDS and scratch bytes, the instruction count and the SHA-256 of the normalised
+instruction stream (instructions and local labels only; the function index of .LBB<i>_<n>,
+.Ltmp<n> and .Lfunc_* becomes a placeholder, since it changes with a function's position in
+its unit). Two builds generate the same code for a kernel iff its lines are equal: a pull
+request proves "before = after" by diffing two inventories.
 """
+import hashlib
 import json
+import os
 import re
+import shutil
 import subprocess
 import sys
 from collections import Counter, OrderedDict
 
-ROOT = __import__("os").path.dirname(__import__("os").path.dirname(__import__("os").path.abspath(__file__)))
-FLAGS = ["-x", "hip", "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-Wno-unused-function",
-         "-munsafe-fp-atomics", "-fno-slp-vectorize", "-mllvm", "-amdgpu-set-wave-priority", "--cuda-device-only", "-S"]
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = f"{ROOT}/arkoserenderer_amd/csrc"
 
 
 def kind(op):
@@ -64,11 +76,60 @@ def parse(path, key):
     return name, blocks, meta
 
 
+META = ("sgpr_count", "vgpr_count", "vgpr_spill_count", "sgpr_spill_count", "group_segment_fixed_size", "private_segment_fixed_size")
+
+
+def inventory(paths):
+    """[(mangled name, {META...}, instruction count, digest)] of every kernel of the files."""
+    rows = []
+    for path in paths:
+        lines = open(path).read().split("\n")
+        # the kernels' metadata: the entries of amdhsa.kernels, each a run of "    .key: value"
+        meta = {}
+        k0 = lines.index("amdhsa.kernels:")
+        for entry in re.split(r"\n  - ", "\n".join(lines[k0 + 1:lines.index("amdhsa.target:", k0) if "amdhsa.target:" in lines[k0:] else len(lines)])):
+            fields = dict(re.findall(r"^\s*\.(\w+):\s+(\S+)\s*$", entry, re.M))
+            if "name" in fields:
+                meta[fields["name"]] = {k: int(fields[k]) for k in META}
+        for name in meta:
+            i0 = lines.index(next(l for l in lines if l.startswith(name + ":")))
+            i1 = next(i for i in range(i0, len(lines)) if lines[i].startswith(".Lfunc_end"))
+            stream, count = [], 0
+            for l in lines[i0 + 1:i1]:
+                t = l.split(";")[0].strip()
+                label = re.match(r"^\.L\w+:$", t)
+                if not t or (t.startswith(".") and not label):
+                    continue
+                count += 0 if label else 1
+                t = re.sub(r"\.LBB\d+_", ".LBB#_", t)
+                t = re.sub(r"\.L(tmp|func_begin|func_end)\d+", r".L\1#", t)
+                stream.append(" ".join(t.split()))
+            rows.append((name, meta[name], count, hashlib.sha256("\n".join(stream).encode()).hexdigest()))
+    names = [r[0] for r in rows]
+    dup = {n for n in names if names.count(n) > 1}
+    if dup:
+        raise SystemExit(f"kernels emitted by more than one unit: {sorted(dup)}")
+    filt = shutil.which("llvm-cxxfilt") or shutil.which("llvm-cxxfilt", path="/opt/rocm/llvm/bin") or shutil.which("c++filt")
+    plain = subprocess.run([filt], input="\n".join(names), capture_output=True, text=True, check=True).stdout.split("\n") if filt else names
+    return sorted((plain[i],) + rows[i] for i in range(len(rows)))
+
+
 def main():
     if sys.argv[1] == "--build":
-        out, extra = sys.argv[2], sys.argv[3:]
-        subprocess.run(["/opt/rocm/bin/hipcc", *FLAGS, *extra, "-o", out, "ddgi_kernels.hip"], cwd=f"{ROOT}/arkoserenderer_amd/csrc", check=True,
-                       stderr=subprocess.DEVNULL)
+        unit, extra = sys.argv[2], sys.argv[3:]
+        goal = "asm" if unit == "all" else f"build/{unit}.s"
+        # (-B: a changed EXTRA is not a changed prerequisite)
+        subprocess.run(["make", "-B" if extra else "-s", goal, "EXTRA=" + " ".join(extra)], cwd=CSRC, check=True, stderr=subprocess.DEVNULL)
+        for s in sorted(os.listdir(f"{CSRC}/build")):
+            if s.endswith(".s") and unit in ("all", s[:-2]):
+                print(f"{CSRC}/build/{s}")
+        return
+    if sys.argv[1] == "--inventory":
+        rows = inventory(sys.argv[2:])
+        print("# sgpr vgpr vgpr_spill sgpr_spill lds_bytes scratch_bytes instructions sha256(normalised stream) kernel")
+        for plain, _, m, count, digest in rows:
+            print(" ".join(str(m[k]) for k in META), count, digest, plain)
+        print(f"# {len(rows)} kernels")
         return
     path = sys.argv[1]
     key = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("--") else "k_traceILb0ELi6ENS0_9ProbeRays"
