@@ -622,6 +622,13 @@ class ArkSoupParams(C.Structure):
     ]
 
 
+class ArkDdgiDebugHit(C.Structure):
+    """One planted hit record of ark_ddgi_debug_probe_update. Not in ABI_STRUCTS
+    (ark_ddgi_debug_struct_sizes' list is closed): ark_ddgi_debug_probe_update_layout gives
+    its size and offsets."""
+    _fields_ = [("t", C.c_float), ("tri", C.c_uint32)]
+
+
 ABI_STRUCTS = [
     ArkDdgiDesc, ArkRTVertex, ArkRTTriangleMesh, ArkShaderMaterial, ArkTexture, ArkRTInstance,
     ArkDirectionalLight, ArkSpotLight, ArkDdgiScene, ArkDdgiFrameParams, ArkDdgiCounters,
@@ -752,6 +759,8 @@ EXPORTS = {
     "ark_ddgi_debug_seed_candidate_ok": (C.c_int, [C.c_uint32, C.c_uint32, C.c_uint32]),
     "ark_ddgi_debug_seed_info": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "ark_ddgi_debug_seed_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
+    "ark_ddgi_debug_probe_update": (C.c_int, [C.c_void_p, C.POINTER(ArkDdgiFrameParams), C.c_void_p, C.c_void_p]),
+    "ark_ddgi_debug_probe_update_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
 }
 
 _lib = None

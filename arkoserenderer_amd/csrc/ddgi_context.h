@@ -233,5 +233,6 @@ hipError_t drainContext(ArkDdgiCtx* ctx);                // waits for every oper
 SceneCall sceneCall(ArkDdgiCtx* ctx);                    // what the scene's calls take from the calling context
 // ddgi_frame.cpp
 int checkSequencing(ArkDdgiCtx* ctx); // reports a sequence-word wait that gave up (fail closed), once
+int debugProbeUpdate(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugHit* hits, void* hipStream); // ark_ddgi_debug_probe_update
 
 } // namespace ark

@@ -1,6 +1,7 @@
 // ddgi_debug_entries.cpp — the ark_ddgi_debug_* entries of a context
 // (include/ark_ddgi_debug.h): what the tests read back or force, none of it on an update's path.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 
 #include "ddgi_context.h"
@@ -242,6 +243,22 @@ int ark_ddgi_debug_shade_schedule(ArkDdgiCtx* ctx, uint64_t* out)
     out[0] = 1;
     out[1] = n;
     return ARK_DDGI_OK;
+}
+
+// The probe update's launches alone over planted surfels and hit records (ddgi_frame.cpp: it
+// shares the update's arguments and its book of the frames in flight).
+int ark_ddgi_debug_probe_update(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* params, const ArkDdgiDebugHit* hits, void* hipStream)
+{
+    return debugProbeUpdate(ctx, params, hits, hipStream);
+}
+
+int ark_ddgi_debug_probe_update_layout(uint32_t* out, int n)
+{
+    const uint32_t words[] = { sizeof(ArkDdgiDebugHit), offsetof(ArkDdgiDebugHit, t), offsetof(ArkDdgiDebugHit, tri) };
+    const int m = static_cast<int>(sizeof(words) / sizeof(words[0]));
+    if (!out) return 0;
+    for (int i = 0; i < n && i < m; ++i) out[i] = words[i];
+    return m < n ? m : n;
 }
 
 uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z) { return seed::texelOf(x, y, z); }

@@ -325,6 +325,49 @@ int updateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, void* hipStream, vo
     return ARK_DDGI_OK;
 }
 
+// ark_ddgi_debug_probe_update: the probe update's launches alone as one serial frame, through
+// the update's own arguments and the book of the frames in flight, over the surfels the context
+// holds and the caller's hit records (no traversal, no shading; the window does not advance).
+int probeUpdateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugHit* hits, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!p || p->struct_size != sizeof(ArkDdgiFrameParams)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiFrameParams");
+    const uint32_t N = static_cast<uint32_t>(ctx->N);
+    const uint32_t K = std::min(p->probe_updates, N);
+    const uint32_t R = p->rays_per_probe;
+    if (K == 0 || R == 0 || K > static_cast<uint32_t>(ctx->Kmax) || R > static_cast<uint32_t>(ctx->Rmax))
+        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "probe_updates %u / rays_per_probe %u outside [1,%d] / [1,%d]", K, R, ctx->Kmax, ctx->Rmax);
+    if (p->update_offsets && !hits) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "debug_probe_update: update_offsets needs the hit records");
+    const hipStream_t s = streamOf(hipStream);
+    if (const int r = checkSequencing(ctx)) return r;
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(orderBegin(ctx, s));
+    if (ctx->orderR != R) { // (the slot table's pass stores the samples in traversal order too)
+        sampleTraversalOrder(R, ctx->orderHost);
+        ARK_HIP(hipMemcpyAsync(ctx->order.ptr, ctx->orderHost.data(), R * 4, hipMemcpyHostToDevice, s));
+        ctx->orderR = R;
+    }
+    const FramePlan plan = ctx->frames.begin(R, true); // serial: every launch in line on s
+    FrameArgs f = frameArgs(ctx, p, K, R, plan);
+    f.seed_offsets_write = 0u; // planted records name no triangles of a scene
+    if (hits && f.window_probes > 0) {
+        std::vector<GpuHit> rec(static_cast<size_t>(f.window_probes) * R);
+        for (size_t i = 0; i < rec.size(); ++i) rec[i] = GpuHit { hits[i].t, 0.0f, 0.0f, hits[i].tri };
+        ARK_HIP(hipMemcpyAsync(f.hits, rec.data(), rec.size() * sizeof(GpuHit), hipMemcpyHostToDevice, s));
+        ARK_HIP(hipStreamSynchronize(s)); // rec leaves scope
+    }
+    ARK_HIP(launch_probe_slots(f, s));
+    if (f.window_probes > 0) {
+        ARK_HIP(launch_probe_offsets(f, s));
+        ARK_HIP(launch_probe_update(f, s));
+    }
+    ARK_HIP(hipEventRecord(ctx->evFrameDone[plan.b], s));
+    ctx->lastStream = s;
+    ARK_HIP(orderEnd(ctx, s));
+    ctx->frames.finished(plan, R);
+    return ARK_DDGI_OK;
+}
+
 // The last window as Z-slab ranks exchange it (ark_ddgi_window_exchange_info)
 ArkDdgiWindowExchange windowExchangeInfo(const ArkDdgiCtx* ctx)
 {
@@ -378,6 +421,11 @@ int windowPack(ArkDdgiCtx* ctx, void* buf, uint64_t bytes, void* hipStream, bool
 // call that sees the host-mapped flag drains the device (the late producer ends by
 // itself), clears both words, switches the context to event sequencing (which no
 // queue order can stall; FrameBook::timedOut) and reports ARK_DDGI_E_DEVICE; the calls after it run.
+int ark::debugProbeUpdate(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugHit* hits, void* hipStream)
+{
+    return probeUpdateImpl(ctx, p, hits, hipStream);
+}
+
 int ark::checkSequencing(ArkDdgiCtx* ctx)
 {
     if (!ctx->hostAbort || __atomic_load_n(ctx->hostAbort, __ATOMIC_ACQUIRE) == 0u) return ARK_DDGI_OK;

@@ -448,6 +448,19 @@ class DDGIContext:
     def update(self, params: abi.ArkDdgiFrameParams, stream: int | None = None):
         self.check(self.lib.ark_ddgi_update(self.h, C.byref(params), C.c_void_p(stream) if stream else None), "ark_ddgi_update")
 
+    def debug_probe_update(self, params: abi.ArkDdgiFrameParams, hits=None, stream: int | None = None):
+        """ark_ddgi_debug_probe_update: the probe update's launches alone (slot table, offsets,
+        blend and borders) over the surfels the context holds (write(ARK_DDGI_SURFELS) plants
+        them). `hits`: [window probes, rays_per_probe] records with fields t (float32) and tri
+        (uint32, 0xffffffff a miss) in slot order, required when params.update_offsets."""
+        a = None
+        if hits is not None:
+            a = np.zeros(np.asarray(hits).shape, np.dtype([("t", np.float32), ("tri", np.uint32)]))
+            a["t"], a["tri"] = hits["t"], hits["tri"]
+            a = np.ascontiguousarray(a)
+        self.check(self.lib.ark_ddgi_debug_probe_update(self.h, C.byref(params), C.c_void_p(a.ctypes.data) if a is not None else None,
+                                                        C.c_void_p(stream) if stream else None), "ark_ddgi_debug_probe_update")
+
     def update_overlapped(self, params: abi.ArkDdgiFrameParams, stream: int | None, shade_wait_event: int | None,
                           done_event: int | None):
         """ark_ddgi_update_overlapped: raw hipStream_t / hipEvent_t handles (ints)."""

@@ -409,6 +409,27 @@ int ark_ddgi_debug_path_tracer_random(uint32_t state, float* out_value, uint32_t
 int ark_ddgi_debug_path_tracer_sample(uint32_t px, uint32_t py, uint32_t width, uint32_t height, uint32_t frame_index, const float* world_from_view,
                                       const float* view_from_projection, uint32_t* out_state, float* out_ray);
 
+/* The probe update's launches alone, over planted inputs (tests/test_gpu_probe_update_model.py):
+ * the slot table, then the probe offsets when params->update_offsets, then the irradiance and
+ * visibility blend with its border copy - the update's own launches with the update's own
+ * arguments, as one serial frame ordered like ark_ddgi_update after whatever the context did
+ * before. No traversal, no shading, no lights, and no scene is needed. The blend reads the
+ * surfels the context holds (ark_ddgi_write of ARK_DDGI_SURFELS plants them); the offsets read
+ * hit records: `hits` is a host array of [window probes][rays_per_probe] records in slot order
+ * (on a Z-slab rank the rank's probes of the window, compacted), tri = 0xffffffff for a miss,
+ * t negative for a back face; required when update_offsets is set, else it may be NULL. The
+ * records are uploaded before the launches (the call waits for that copy, not for the kernels).
+ * The planted records name no triangles of a scene, so the probe rays' hit candidates are not
+ * written. The rolling window does not advance. Refuses what ark_ddgi_update refuses of
+ * `params`. _layout: out[0 .. n) of {sizeof(ArkDdgiDebugHit), offsetof t, offsetof tri};
+ * returns how many it wrote. */
+typedef struct ArkDdgiDebugHit {
+    float t;
+    uint32_t tri;
+} ArkDdgiDebugHit;
+int ark_ddgi_debug_probe_update(struct ArkDdgiCtx* ctx, const ArkDdgiFrameParams* params, const ArkDdgiDebugHit* hits, void* hip_stream);
+int ark_ddgi_debug_probe_update_layout(uint32_t* out, int n);
+
 #ifdef __cplusplus
 }
 #endif

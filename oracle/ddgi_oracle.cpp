@@ -1306,141 +1306,35 @@ static void buildWorld(Oracle& o, int threads)
     o.bvhBlend = buildBvh(o.tris, blend, threads);
 }
 
-extern "C" {
-
-struct OracleCtx;
-
-void* oracle_create(const ArkDdgiDesc* desc)
+// The window's probes by slot (raygen.rgen:113: slot s <-> probe (first + s) % N).
+// A Z-slab shard (desc.shard_rank of desc.shard_count) updates only the
+// window probes whose z lies in its slab [r Z/P, (r+1) Z/P), in window order, at
+// compacted slots - the slot assignment of k_probe_slots, restated plainly.
+static std::vector<uint32_t> windowProbes(const Oracle& o, uint32_t first, uint32_t K)
 {
-    if (!desc) return nullptr;
-    auto* o = new Oracle();
-    o->desc = *desc;
-    o->g.X = desc->grid_dims[0];
-    o->g.Y = desc->grid_dims[1];
-    o->g.Z = desc->grid_dims[2];
-    if (o->g.X <= 0 || o->g.Y <= 0 || o->g.Z <= 0) { delete o; return nullptr; }
-    o->g.spacing = v3(desc->probe_spacing[0], desc->probe_spacing[1], desc->probe_spacing[2]);
-    o->g.origin = v3(desc->offset_to_first[0], desc->offset_to_first[1], desc->offset_to_first[2]);
-    // DDGINode.cpp:262-281
-    const int si = ARK_DDGI_IRRADIANCE_RES + 2 * ARK_DDGI_ATLAS_PADDING;
-    const int sv = ARK_DDGI_VISIBILITY_RES + 2 * ARK_DDGI_ATLAS_PADDING;
-    o->Wi = o->g.X * si * o->g.Y;
-    o->Hi = o->g.Z * si;
-    o->Wv = o->g.X * sv * o->g.Y;
-    o->Hv = o->g.Z * sv;
-    o->irr.resize(static_cast<size_t>(o->Wi) * o->Hi * 4);
-    o->vis.resize(static_cast<size_t>(o->Wv) * o->Hv * 2);
-    o->offsets.resize(static_cast<size_t>(o->g.N()) * 4);
-    o->Rmax = desc->max_rays_per_probe > 0 ? desc->max_rays_per_probe : ARK_DDGI_MAX_RAYS_PER_PROBE;
-    o->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
-    o->surfels.resize(static_cast<size_t>(o->Kmax) * o->Rmax * 4);
-    o->envWhite = whiteSrgbPixel();
-    resetHistory(*o);
-    return o;
-}
-
-void oracle_destroy(void* ctx) { delete static_cast<Oracle*>(ctx); }
-
-int oracle_reset_history(void* ctx)
-{
-    resetHistory(*static_cast<Oracle*>(ctx));
-    return 0;
-}
-
-int oracle_set_scene(void* ctx, const ArkDdgiScene* s, int threads)
-{
-    Oracle& o = *static_cast<Oracle*>(ctx);
-    if (!s) return ARK_DDGI_E_INVALID_ARGUMENT;
-    o.indices.assign(s->indices, s->indices + s->index_count);
-    o.positions.assign(s->positions, s->positions + 3 * static_cast<size_t>(s->vertex_count));
-    o.vertices.assign(s->vertices, s->vertices + s->vertex_count);
-    o.meshes.assign(s->meshes, s->meshes + s->mesh_count);
-    o.materials.assign(s->materials, s->materials + s->material_count);
-    o.instances.assign(s->instances, s->instances + s->instance_count);
-    o.textures.clear();
-    for (uint32_t i = 0; i < s->texture_count; ++i) o.textures.push_back(makeTex(s->textures[i]));
-    o.envTex = s->environment_texture;
-    o.hasSun = s->has_directional_light != 0;
-    o.sun = s->directional_light;
-    o.spots.assign(s->spot_lights, s->spot_lights + s->spot_light_count);
-    buildWorld(o, threads);
-    o.hasScene = true;
-    return 0;
-}
-
-// The per-frame light set (ark_ddgi_set_lights; GpuScene.cpp:790-858): the lights the
-// closest hit and the shadow rays of the next updates read.
-int oracle_set_lights(void* ctx, const ArkDdgiLights* L)
-{
-    Oracle& o = *static_cast<Oracle*>(ctx);
-    if (!L || !o.hasScene || L->spot_light_count > ARK_DDGI_MAX_SPOT_LIGHTS) return ARK_DDGI_E_INVALID_ARGUMENT;
-    o.hasSun = L->has_directional_light != 0;
-    o.sun = L->directional_light;
-    o.spots.assign(L->spot_lights, L->spot_lights + L->spot_light_count);
-    return 0;
-}
-
-// The per-frame instance transforms (ark_ddgi_set_instances; GpuScene.cpp:872-1009): the
-// world-space triangles recomputed and the BVHs rebuilt (the oracle has no refit: its
-// own BVH is rebuilt from scratch, which hits do not depend on).
-int oracle_set_instances(void* ctx, const ArkRTInstance* inst, uint32_t count, int threads)
-{
-    Oracle& o = *static_cast<Oracle*>(ctx);
-    if (!o.hasScene || count != o.instances.size() || (count && !inst)) return ARK_DDGI_E_INVALID_ARGUMENT;
-    for (uint32_t i = 0; i < count; ++i)
-        if (inst[i].rt_mesh_index != o.instances[i].rt_mesh_index || inst[i].triangle_count != o.instances[i].triangle_count ||
-            inst[i].hit_mask != o.instances[i].hit_mask)
-            return ARK_DDGI_E_INVALID_ARGUMENT;
-    o.instances.assign(inst, inst + count);
-    buildWorld(o, threads);
-    return 0;
-}
-
-// One DDGI update: DDGINode.cpp:132-259. `threads` host threads, parallel over probes.
-int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads)
-{
-    Oracle& o = *static_cast<Oracle*>(ctx);
-    if (!p || !o.hasScene) return ARK_DDGI_E_INVALID_ARGUMENT;
     const Grid& g = o.g;
     const uint32_t N = static_cast<uint32_t>(g.N());
-    const uint32_t K = std::min(p->probe_updates, N);
-    const uint32_t R = p->rays_per_probe;
-    if (K > static_cast<uint32_t>(o.Kmax) || R > static_cast<uint32_t>(o.Rmax) || R == 0) return ARK_DDGI_E_INVALID_ARGUMENT;
-    const uint32_t first = p->first_probe_index % N;
-    const uint32_t frameIdx = p->frame_index;
-    std::vector<Stats> tstats(std::max(threads, 1));
-    // The window's probes by slot (raygen.rgen:113: slot s <-> probe (first + s) % N).
-    // A Z-slab shard (desc.shard_rank of desc.shard_count) updates only the
-    // window probes whose z lies in its slab [r Z/P, (r+1) Z/P), in window order, at
-    // compacted slots - the slot assignment of k_probe_slots, restated plainly.
     std::vector<uint32_t> window;
     window.reserve(K);
-    {
-        const int P = std::max(1, static_cast<int>(o.desc.shard_count));
-        const int z0 = o.desc.shard_rank * (g.Z / P), z1 = z0 + g.Z / P;
-        for (uint32_t s = 0; s < K; ++s) {
-            const uint32_t probeIdx = (s + first) % N;
-            int x, y, z;
-            probeCoord(g, probeIdx, &x, &y, &z);
-            if (P == 1 || (z >= z0 && z < z1)) window.push_back(probeIdx);
-        }
+    const int P = std::max(1, static_cast<int>(o.desc.shard_count));
+    const int z0 = o.desc.shard_rank * (g.Z / P), z1 = z0 + g.Z / P;
+    for (uint32_t s = 0; s < K; ++s) {
+        const uint32_t probeIdx = (s + first) % N;
+        int x, y, z;
+        probeCoord(g, probeIdx, &x, &y, &z);
+        if (P == 1 || (z >= z0 && z < z1)) window.push_back(probeIdx);
     }
-    const int W = static_cast<int>(window.size());
+    return window;
+}
 
-    // 1. trace rays (raygen.rgen main, launch (K, R))
-    parallelFor(W, threads, [&](int slot, int tid) {
-        uint32_t probeIdx = window[slot];
-        V3 pos = probePosition(g, probeIdx);
-        const float* off = &o.offsets[static_cast<size_t>(probeIdx) * 4];
-        pos = pos + v3(off[0], off[1], off[2]);
-        for (uint32_t s = 0; s < R; ++s) {
-            V3 dir = calculateRotatedSphericalFibonacciSample(probeIdx, s, R, frameIdx);
-            float out[4];
-            traceProbeRay(o, probeIdx, pos, dir, *p, out, tstats[tid]);
-            uint16_t* dst = &o.surfels[(static_cast<size_t>(slot) * o.Rmax + s) * 4];
-            for (int c = 0; c < 4; ++c) dst[c] = f32_to_f16(out[c]);
-        }
-    });
+// Steps 2 to 6 of an update (DDGINode.cpp:165-256) over the surfels the oracle holds:
+// what consumes surfels, without the trace that writes them.
+static void blendWindow(Oracle& o, const ArkDdgiFrameParams* p, const std::vector<uint32_t>& window, int threads)
+{
+    const Grid& g = o.g;
+    const uint32_t R = p->rays_per_probe;
+    const uint32_t frameIdx = p->frame_index;
+    const int W = static_cast<int>(window.size());
 
     // 2+3. irradiance & visibility update (probeUpdateIrradiance.comp / probeUpdateVisibility.comp)
     const float gridMaxSpacing = fmaxf_(g.spacing.x, fmaxf_(g.spacing.y, g.spacing.z)); // DDGINode.cpp:148
@@ -1580,9 +1474,147 @@ int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads)
             cur[2] = newOffset.z;
         });
     }
+}
+
+extern "C" {
+
+struct OracleCtx;
+
+void* oracle_create(const ArkDdgiDesc* desc)
+{
+    if (!desc) return nullptr;
+    auto* o = new Oracle();
+    o->desc = *desc;
+    o->g.X = desc->grid_dims[0];
+    o->g.Y = desc->grid_dims[1];
+    o->g.Z = desc->grid_dims[2];
+    if (o->g.X <= 0 || o->g.Y <= 0 || o->g.Z <= 0) { delete o; return nullptr; }
+    o->g.spacing = v3(desc->probe_spacing[0], desc->probe_spacing[1], desc->probe_spacing[2]);
+    o->g.origin = v3(desc->offset_to_first[0], desc->offset_to_first[1], desc->offset_to_first[2]);
+    // DDGINode.cpp:262-281
+    const int si = ARK_DDGI_IRRADIANCE_RES + 2 * ARK_DDGI_ATLAS_PADDING;
+    const int sv = ARK_DDGI_VISIBILITY_RES + 2 * ARK_DDGI_ATLAS_PADDING;
+    o->Wi = o->g.X * si * o->g.Y;
+    o->Hi = o->g.Z * si;
+    o->Wv = o->g.X * sv * o->g.Y;
+    o->Hv = o->g.Z * sv;
+    o->irr.resize(static_cast<size_t>(o->Wi) * o->Hi * 4);
+    o->vis.resize(static_cast<size_t>(o->Wv) * o->Hv * 2);
+    o->offsets.resize(static_cast<size_t>(o->g.N()) * 4);
+    o->Rmax = desc->max_rays_per_probe > 0 ? desc->max_rays_per_probe : ARK_DDGI_MAX_RAYS_PER_PROBE;
+    o->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
+    o->surfels.resize(static_cast<size_t>(o->Kmax) * o->Rmax * 4);
+    o->envWhite = whiteSrgbPixel();
+    resetHistory(*o);
+    return o;
+}
+
+void oracle_destroy(void* ctx) { delete static_cast<Oracle*>(ctx); }
+
+int oracle_reset_history(void* ctx)
+{
+    resetHistory(*static_cast<Oracle*>(ctx));
+    return 0;
+}
+
+int oracle_set_scene(void* ctx, const ArkDdgiScene* s, int threads)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!s) return ARK_DDGI_E_INVALID_ARGUMENT;
+    o.indices.assign(s->indices, s->indices + s->index_count);
+    o.positions.assign(s->positions, s->positions + 3 * static_cast<size_t>(s->vertex_count));
+    o.vertices.assign(s->vertices, s->vertices + s->vertex_count);
+    o.meshes.assign(s->meshes, s->meshes + s->mesh_count);
+    o.materials.assign(s->materials, s->materials + s->material_count);
+    o.instances.assign(s->instances, s->instances + s->instance_count);
+    o.textures.clear();
+    for (uint32_t i = 0; i < s->texture_count; ++i) o.textures.push_back(makeTex(s->textures[i]));
+    o.envTex = s->environment_texture;
+    o.hasSun = s->has_directional_light != 0;
+    o.sun = s->directional_light;
+    o.spots.assign(s->spot_lights, s->spot_lights + s->spot_light_count);
+    buildWorld(o, threads);
+    o.hasScene = true;
+    return 0;
+}
+
+// The per-frame light set (ark_ddgi_set_lights; GpuScene.cpp:790-858): the lights the
+// closest hit and the shadow rays of the next updates read.
+int oracle_set_lights(void* ctx, const ArkDdgiLights* L)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!L || !o.hasScene || L->spot_light_count > ARK_DDGI_MAX_SPOT_LIGHTS) return ARK_DDGI_E_INVALID_ARGUMENT;
+    o.hasSun = L->has_directional_light != 0;
+    o.sun = L->directional_light;
+    o.spots.assign(L->spot_lights, L->spot_lights + L->spot_light_count);
+    return 0;
+}
+
+// The per-frame instance transforms (ark_ddgi_set_instances; GpuScene.cpp:872-1009): the
+// world-space triangles recomputed and the BVHs rebuilt (the oracle has no refit: its
+// own BVH is rebuilt from scratch, which hits do not depend on).
+int oracle_set_instances(void* ctx, const ArkRTInstance* inst, uint32_t count, int threads)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!o.hasScene || count != o.instances.size() || (count && !inst)) return ARK_DDGI_E_INVALID_ARGUMENT;
+    for (uint32_t i = 0; i < count; ++i)
+        if (inst[i].rt_mesh_index != o.instances[i].rt_mesh_index || inst[i].triangle_count != o.instances[i].triangle_count ||
+            inst[i].hit_mask != o.instances[i].hit_mask)
+            return ARK_DDGI_E_INVALID_ARGUMENT;
+    o.instances.assign(inst, inst + count);
+    buildWorld(o, threads);
+    return 0;
+}
+
+// One DDGI update: DDGINode.cpp:132-259. `threads` host threads, parallel over probes.
+int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!p || !o.hasScene) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const Grid& g = o.g;
+    const uint32_t N = static_cast<uint32_t>(g.N());
+    const uint32_t K = std::min(p->probe_updates, N);
+    const uint32_t R = p->rays_per_probe;
+    if (K > static_cast<uint32_t>(o.Kmax) || R > static_cast<uint32_t>(o.Rmax) || R == 0) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const uint32_t first = p->first_probe_index % N;
+    const uint32_t frameIdx = p->frame_index;
+    std::vector<Stats> tstats(std::max(threads, 1));
+    const std::vector<uint32_t> window = windowProbes(o, first, K);
+    const int W = static_cast<int>(window.size());
+
+    // 1. trace rays (raygen.rgen main, launch (K, R))
+    parallelFor(W, threads, [&](int slot, int tid) {
+        uint32_t probeIdx = window[slot];
+        V3 pos = probePosition(g, probeIdx);
+        const float* off = &o.offsets[static_cast<size_t>(probeIdx) * 4];
+        pos = pos + v3(off[0], off[1], off[2]);
+        for (uint32_t s = 0; s < R; ++s) {
+            V3 dir = calculateRotatedSphericalFibonacciSample(probeIdx, s, R, frameIdx);
+            float out[4];
+            traceProbeRay(o, probeIdx, pos, dir, *p, out, tstats[tid]);
+            uint16_t* dst = &o.surfels[(static_cast<size_t>(slot) * o.Rmax + s) * 4];
+            for (int c = 0; c < 4; ++c) dst[c] = f32_to_f16(out[c]);
+        }
+    });
+
+    blendWindow(o, p, window, threads);
     Stats tot;
     for (auto& s : tstats) { tot.nodes += s.nodes; tot.tris += s.tris; }
     o.stats = tot;
+    return 0;
+}
+
+// Steps 2 to 6 alone, over the surfels the oracle currently holds (oracle_write of
+// ARK_DDGI_SURFELS plants them): the blend on planted inputs. Needs no scene.
+int oracle_blend(void* ctx, const ArkDdgiFrameParams* p, int threads)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!p) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const uint32_t N = static_cast<uint32_t>(o.g.N());
+    const uint32_t K = std::min(p->probe_updates, N);
+    const uint32_t R = p->rays_per_probe;
+    if (K > static_cast<uint32_t>(o.Kmax) || R > static_cast<uint32_t>(o.Rmax) || R == 0) return ARK_DDGI_E_INVALID_ARGUMENT;
+    blendWindow(o, p, windowProbes(o, p->first_probe_index % N, K), threads);
     return 0;
 }
 

@@ -1,5 +1,6 @@
 // ASan + UBSan run of the host-side code on the path (SURVEY §5 "race detection /
-// sanitizers"): the CPU oracle (frames with offsets, the AO bake, lighting compose),
+// sanitizers"): the CPU oracle (frames with offsets, the blend alone on planted surfels, the
+// AO bake, lighting compose),
 // the synthetic soup generator and the BVH2 -> BVH8 builder with its structural check,
 // the three hit-mask classes' build (build_world_bvh8) and the refit's level order, the
 // LBVH restatement with the canonical tree comparison (compare_bvh8_canonical), and
@@ -24,6 +25,8 @@ void* oracle_create(const ArkDdgiDesc* desc);
 void oracle_destroy(void* ctx);
 int oracle_set_scene(void* ctx, const ArkDdgiScene* s, int threads);
 int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads);
+int oracle_blend(void* ctx, const ArkDdgiFrameParams* p, int threads);
+int oracle_write(void* ctx, int which, const void* src, uint64_t bytes);
 int oracle_read(void* ctx, int which, void* dst, uint64_t bytes);
 int oracle_bake_ao(void* ctx, uint32_t instance, uint32_t W, uint32_t H, uint32_t samples, int bent, uint32_t row0, uint32_t row1,
                    uint32_t* triOut, uint16_t* baryOut, uint8_t* out, int threads);
@@ -354,6 +357,27 @@ int main()
         p.delta_time = 1.0f / 60.0f;
         p.update_offsets = 1;
         CHECK(oracle_update(o, &p, 2) == 0);
+    }
+    {
+        // the blend alone on planted surfels: a ragged window that wraps past N = 64, 37 of 64 rays
+        std::vector<uint16_t> surfels(64 * 64 * 4);
+        for (size_t i = 0; i < surfels.size(); ++i) surfels[i] = static_cast<uint16_t>((i * 2654435761u) >> 17); // finite fp16 codes
+        CHECK(oracle_write(o, ARK_DDGI_SURFELS, surfels.data(), surfels.size() * 2) == 0);
+        ArkDdgiFrameParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.struct_size = sizeof(p);
+        p.rays_per_probe = 37;
+        p.probe_updates = 7;
+        p.first_probe_index = 60;
+        p.frame_index = 700;
+        p.hysteresis_irradiance = 0.98f;
+        p.hysteresis_visibility = 0.98f;
+        p.visibility_sharpness = 7.3f;
+        p.delta_time = 1.0f / 60.0f;
+        p.update_offsets = 1;
+        CHECK(oracle_blend(o, &p, 2) == 0);
+        p.rays_per_probe = 65; // more than max_rays_per_probe: refused
+        CHECK(oracle_blend(o, &p, 2) != 0);
     }
     std::vector<uint16_t> irr(4 * 10 * 4 * 4 * 10 * 4);
     CHECK(oracle_read(o, ARK_DDGI_ATLAS_IRRADIANCE, irr.data(), irr.size() * 2) == 0);

@@ -46,6 +46,7 @@ def load(libm: bool = False, variant: str | None = None):
         lib.oracle_set_lights.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiLights)]
         lib.oracle_set_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
         lib.oracle_update.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiFrameParams), C.c_int]
+        lib.oracle_blend.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiFrameParams), C.c_int]
         lib.oracle_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         lib.oracle_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         lib.oracle_get_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -121,6 +122,12 @@ class Oracle:
 
     def update(self, params, threads: int = 8):
         rc = self.lib.oracle_update(self.h, C.byref(params), threads)
+        assert rc == 0, rc
+
+    def blend(self, params, threads: int = 8):
+        """oracle_blend: steps 2 to 6 of an update over the surfels the oracle holds
+        (write(ARK_DDGI_SURFELS) plants them); needs no scene."""
+        rc = self.lib.oracle_blend(self.h, C.byref(params), threads)
         assert rc == 0, rc
 
     def _size(self, which):

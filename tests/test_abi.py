@@ -47,6 +47,17 @@ def test_struct_layouts_match_c():
     assert C.sizeof(abi.ArkRTTriangleMesh) == 12
 
 
+def test_debug_hit_layout_matches_c():
+    """ArkDdgiDebugHit (ark_ddgi_debug_probe_update's planted hit records) and its numpy form."""
+    lib = abi.load_library()
+    out = (C.c_uint32 * 3)()
+    assert lib.ark_ddgi_debug_probe_update_layout(out, 3) == 3
+    assert list(out) == [C.sizeof(abi.ArkDdgiDebugHit), abi.ArkDdgiDebugHit.t.offset, abi.ArkDdgiDebugHit.tri.offset] == [8, 0, 4]
+    dt = np.dtype([("t", np.float32), ("tri", np.uint32)])
+    assert (dt.itemsize, dt.fields["t"][1], dt.fields["tri"][1]) == (8, 0, 4)
+    assert lib.ark_ddgi_debug_probe_update(None, None, None, None) == -1
+
+
 def test_invalid_arguments_fail_cleanly():
     lib = abi.load_library()
     h = C.c_void_p()
