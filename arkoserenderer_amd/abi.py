@@ -46,6 +46,7 @@ ARK_DDGI_SURFELS = 2
 ARK_DDGI_PROBE_OFFSETS = 3
 ARK_DDGI_DEBUG_HITS = 100
 ARK_DDGI_DEBUG_RAY_STEPS = 101
+ARK_DDGI_DEBUG_SHADOW_BITS = 102
 
 ARK_DDGI_CLEAR_OVERFLOW_INF = 0
 ARK_DDGI_CLEAR_OVERFLOW_MAX_FINITE = 1
@@ -629,6 +630,12 @@ class ArkDdgiDebugHit(C.Structure):
     _fields_ = [("t", C.c_float), ("tri", C.c_uint32)]
 
 
+class ArkDdgiDebugShadeHit(C.Structure):
+    """One planted hit of ark_ddgi_debug_shade (instance 0xffffffff: a miss; t negative: a back
+    face). Not in ABI_STRUCTS: ark_ddgi_debug_shade_layout gives its size and offsets."""
+    _fields_ = [("instance", C.c_uint32), ("primitive", C.c_uint32), ("u", C.c_float), ("v", C.c_float), ("t", C.c_float)]
+
+
 ABI_STRUCTS = [
     ArkDdgiDesc, ArkRTVertex, ArkRTTriangleMesh, ArkShaderMaterial, ArkTexture, ArkRTInstance,
     ArkDirectionalLight, ArkSpotLight, ArkDdgiScene, ArkDdgiFrameParams, ArkDdgiCounters,
@@ -761,6 +768,10 @@ EXPORTS = {
     "ark_ddgi_debug_seed_fill": (C.c_int, [C.c_void_p, C.c_int, C.c_uint64]),
     "ark_ddgi_debug_probe_update": (C.c_int, [C.c_void_p, C.POINTER(ArkDdgiFrameParams), C.c_void_p, C.c_void_p]),
     "ark_ddgi_debug_probe_update_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_debug_shade": (C.c_int, [C.c_void_p, C.POINTER(ArkDdgiFrameParams), C.c_void_p, C.c_void_p]),
+    "ark_ddgi_debug_shade_layout": (C.c_int, [C.POINTER(C.c_uint32), C.c_int]),
+    "ark_ddgi_debug_world_records": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.POINTER(C.c_uint64)]),
+    "ark_ddgi_debug_shade_map": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint32, C.c_float, C.c_void_p, C.c_uint64, C.c_void_p]),
 }
 
 _lib = None

@@ -527,6 +527,8 @@ static int resourceInfo(const ArkDdgiCtx* ctx, int which, void** ptr, uint64_t* 
     case ARK_DDGI_SURFELS: *ptr = ctx->surfels.ptr; *bytes = ctx->surfels.bytes; return 0;
     case ARK_DDGI_PROBE_OFFSETS: *ptr = ctx->offsets.ptr; *bytes = ctx->offsets.bytes; return 0;
     case ARK_DDGI_DEBUG_HITS: *ptr = ctx->hits.as<GpuHit>() + static_cast<uint64_t>(ctx->frames.lastSet()) * ctx->Kmax * ctx->Rmax; *bytes = ctx->hits.bytes / 2; return 0;
+    case ARK_DDGI_DEBUG_SHADOW_BITS: // the head of the shading work set (shadeWorkLayout)
+        *ptr = ctx->shadeWork.ptr; *bytes = static_cast<uint64_t>(ctx->Kmax) * ctx->Rmax * 4u; return ctx->shadeWork.ptr ? 0 : ARK_DDGI_E_INVALID_ARGUMENT;
     case ARK_DDGI_DEBUG_RAY_STEPS: *ptr = ctx->raySteps.ptr; *bytes = ctx->raySteps.bytes; return ctx->raySteps.ptr ? 0 : ARK_DDGI_E_INVALID_ARGUMENT;
     default: return ARK_DDGI_E_INVALID_ARGUMENT;
     }

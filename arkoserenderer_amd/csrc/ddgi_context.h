@@ -234,5 +234,7 @@ SceneCall sceneCall(ArkDdgiCtx* ctx);                    // what the scene's cal
 // ddgi_frame.cpp
 int checkSequencing(ArkDdgiCtx* ctx); // reports a sequence-word wait that gave up (fail closed), once
 int debugProbeUpdate(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugHit* hits, void* hipStream); // ark_ddgi_debug_probe_update
+int debugShade(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugShadeHit* hits, void* hipStream);     // ark_ddgi_debug_shade
+int debugShadeMap(const uint32_t* words, uint64_t n, uint32_t instances, float zFar, const ArkDdgiDebugShadeHit* hits, uint64_t count, uint32_t* outTri); // ark_ddgi_debug_shade_map
 
 } // namespace ark

@@ -261,6 +261,45 @@ int ark_ddgi_debug_probe_update_layout(uint32_t* out, int n)
     return m < n ? m : n;
 }
 
+// Hit shading alone over planted hit records (ddgi_frame.cpp, beside the update it shares its
+// launches with).
+int ark_ddgi_debug_shade(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* params, const ArkDdgiDebugShadeHit* hits, void* hipStream)
+{
+    return debugShade(ctx, params, hits, hipStream);
+}
+
+int ark_ddgi_debug_world_records(ArkDdgiCtx* ctx, uint32_t* out_words, uint64_t capacity, uint64_t* out_records)
+{
+    if (!ctx || !out_records) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "world_records before ark_ddgi_set_scene");
+    ARK_HIP(hipSetDevice(ctx->device));
+    ARK_HIP(hipDeviceSynchronize());
+    if (ctx->sceneVersion != ctx->sceneStore->version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    std::vector<uint32_t> rec;
+    std::vector<int32_t> cls;
+    if (const int rc = sceneRecordsAndClasses(*ctx->sceneStore, ctx, rec, cls)) return rc;
+    *out_records = rec.size() / 12u;
+    if (out_words && capacity >= *out_records) std::memcpy(out_words, rec.data(), rec.size() * 4u);
+    return ARK_DDGI_OK;
+}
+
+int ark_ddgi_debug_shade_map(const uint32_t* record_words, uint64_t records, uint32_t instances, float z_far, const ArkDdgiDebugShadeHit* hits, uint64_t n,
+                             uint32_t* out_tri)
+{
+    return debugShadeMap(record_words, records, instances, z_far, hits, n, out_tri);
+}
+
+int ark_ddgi_debug_shade_layout(uint32_t* out, int n)
+{
+    const uint32_t words[] = { sizeof(ArkDdgiDebugShadeHit), offsetof(ArkDdgiDebugShadeHit, instance), offsetof(ArkDdgiDebugShadeHit, primitive),
+                               offsetof(ArkDdgiDebugShadeHit, u), offsetof(ArkDdgiDebugShadeHit, v), offsetof(ArkDdgiDebugShadeHit, t) };
+    const int m = static_cast<int>(sizeof(words) / sizeof(words[0]));
+    if (!out) return 0;
+    for (int i = 0; i < n && i < m; ++i) out[i] = words[i];
+    return m < n ? m : n;
+}
+
 uint32_t ark_ddgi_debug_seed_texel(float x, float y, float z) { return seed::texelOf(x, y, z); }
 int ark_ddgi_debug_seed_candidate_ok(uint32_t word, uint32_t first, uint32_t end) { return seed::candidateOk(word, first, end) ? 1 : 0; }
 

@@ -6,6 +6,8 @@
 #include <rocprofiler-sdk-roctx/roctx.h>
 
 #include <cmath>
+#include <cstdio>
+#include <string>
 
 #include "ddgi_context.h"
 #include "shade_schedule.h"
@@ -219,46 +221,60 @@ int traversalPart(ArkDdgiCtx* ctx, const FramePlan& plan, const FrameArgs& f, hi
     return ARK_DDGI_OK;
 }
 
+// Shadow rays and shading of the frame's window on s, in the schedule shadeScheduleOf picks:
+// the shadow-ray generator, their traversal and k_shade, or for the sun alone with its cover
+// map k_shade first and its deferred pass behind the traversal. `shadeWaits` runs before the
+// first kernel that reads the atlases. The update's caller part and ark_ddgi_debug_shade.
+template<class Waits>
+int shadeWindow(ArkDdgiCtx* ctx, const FramePlan& plan, const FrameArgs& f, hipStream_t s, bool timing, Waits&& shadeWaits, FrameArgs* shadeArgs)
+{
+    const bool count = ctx->counting;
+    FrameArgs fs = f;
+    fs.spill = ctx->spill.as<uint32_t>(); // region 0
+    if (count) ctx->coverFrame = fs;
+    // the sun alone, with its cover map: shading resolves the sun's rays itself, and
+    // only what the map leaves undecided is listed, traced and shaded in a second pass
+    // (not beside a half-occupancy traversal: shade_schedule.h)
+    const bool sunOnly = shadeScheduleOf({ f.light_count, ctx->scene.has_sun != 0, ctx->scene.sun_map != nullptr, ctx->desc.flags, halfWindow(plan, f),
+                                           ctx->sunOnlySmallWindows }) == ShadeSchedule::SunOnly;
+    ctx->lastSunOnly = sunOnly;
+    ctx->lastDeferredCount = fs.sun_rays ? fs.sun_count : fs.shadow_count;
+    // (the grid stays sized by the window although the cover map leaves a few percent of
+    // the sun's rays on the list: an eighth of it measured the same, EXPERIMENTS.md)
+    const uint32_t shadowBlocks = count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays);
+    if (f.light_count > 0 && !sunOnly) {
+        ARK_HIP(launch_shadow_gen(ctx->scene, fs, s));
+        ARK_HIP(launch_trace_shadow(ctx->scene, fs, shadowBlocks, count, s));
+    }
+    if (timing) ARK_HIP(hipEventRecord(ctx->ev[5], s));
+    ARK_HIP(shadeWaits());
+    ARK_HIP(launch_shade(ctx->scene, fs, ctx->shadeBlocks, count, s, sunOnly));
+    if (timing) ARK_HIP(hipEventRecord(ctx->ev[2], s));
+    if (sunOnly) {
+        // (timings: "shade" is pass 1, "shadow" the traversal and the deferred pass)
+        ARK_HIP(launch_trace_shadow(ctx->scene, fs, shadowBlocks, count, s));
+        ARK_HIP(launch_shade_deferred(ctx->scene, fs, s));
+    }
+    if (timing) ARK_HIP(hipEventRecord(ctx->ev[4], s));
+    *shadeArgs = fs;
+    return ARK_DDGI_OK;
+}
+
 // The caller's part of the frame on s: shadow rays, shading, the probe update (behind the
 // offsets when the frame is serial), then the frame's done signal: word main, or
 // evFrameDone[b]. Shading reads the previous frame's atlases at arbitrary probes: on a
 // Z-slab rank it waits for the previous exchange first (the traversal did not).
 int callerPart(ArkDdgiCtx* ctx, const FramePlan& plan, const FrameArgs& f, hipStream_t s, void* shadeWaitEvent, uint32_t shadeWaitSeq, RoctxRange& traceZone)
 {
-    const bool timing = ctx->timing, count = ctx->counting;
+    const bool timing = ctx->timing;
     auto shadeWaits = [&]() -> hipError_t {
         hipError_t e = shadeWaitEvent ? hipStreamWaitEvent(s, static_cast<hipEvent_t>(shadeWaitEvent), 0) : hipSuccess;
         return e != hipSuccess || !shadeWaitSeq ? e : seqWait(ctx, kSeqExchange, shadeWaitSeq, s);
     };
     if (f.window_probes > 0) {
         if (timing) ARK_HIP(hipEventRecord(ctx->ev[1], s));
-        FrameArgs fs = f;
-        fs.spill = ctx->spill.as<uint32_t>(); // region 0
-        if (count) ctx->coverFrame = fs;
-        // the sun alone, with its cover map: shading resolves the sun's rays itself, and
-        // only what the map leaves undecided is listed, traced and shaded in a second pass
-        // (not beside a half-occupancy traversal: shade_schedule.h)
-        const bool sunOnly = shadeScheduleOf({ f.light_count, ctx->scene.has_sun != 0, ctx->scene.sun_map != nullptr, ctx->desc.flags, halfWindow(plan, f),
-                                               ctx->sunOnlySmallWindows }) == ShadeSchedule::SunOnly;
-        ctx->lastSunOnly = sunOnly;
-        ctx->lastDeferredCount = fs.sun_rays ? fs.sun_count : fs.shadow_count;
-        // (the grid stays sized by the window although the cover map leaves a few percent of
-        // the sun's rays on the list: an eighth of it measured the same, EXPERIMENTS.md)
-        const uint32_t shadowBlocks = count ? ctx->shadowBlocks : shadowBlocksFor(ctx, f.window_rays);
-        if (f.light_count > 0 && !sunOnly) {
-            ARK_HIP(launch_shadow_gen(ctx->scene, fs, s));
-            ARK_HIP(launch_trace_shadow(ctx->scene, fs, shadowBlocks, count, s));
-        }
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[5], s));
-        ARK_HIP(shadeWaits());
-        ARK_HIP(launch_shade(ctx->scene, fs, ctx->shadeBlocks, count, s, sunOnly));
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[2], s));
-        if (sunOnly) {
-            // (timings: "shade" is pass 1, "shadow" the traversal and the deferred pass)
-            ARK_HIP(launch_trace_shadow(ctx->scene, fs, shadowBlocks, count, s));
-            ARK_HIP(launch_shade_deferred(ctx->scene, fs, s));
-        }
-        if (timing) ARK_HIP(hipEventRecord(ctx->ev[4], s));
+        FrameArgs fs;
+        if (const int rc = shadeWindow(ctx, plan, f, s, timing, shadeWaits, &fs)) return rc;
         traceZone.end();
         // probeUpdateOffset (serial frames), probeUpdateIrradiance/Visibility + border
         // corners/edges, fused
@@ -368,6 +384,107 @@ int probeUpdateImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiD
     return ARK_DDGI_OK;
 }
 
+// The hit records k_shade takes for planted hits, or false with the reason: `words` are the
+// front copy's n triangle records (12 words each: the instance in word 9, the primitive in
+// word 10, kHoleInstance for a hole), out[i] the record of hits[i]. A miss is {+inf, kNoHit}.
+bool shadeHitRecords(const uint32_t* words, uint64_t n, uint32_t instances, float zFar, const ArkDdgiDebugShadeHit* hits, uint64_t count, GpuHit* out,
+                     std::string* why)
+{
+    std::vector<std::vector<uint32_t>> recordOf(instances); // [instance][primitive] -> leaf-order record
+    for (uint64_t i = 0; i < n; ++i) {
+        const uint32_t inst = words[12u * i + 9u], prim = words[12u * i + 10u];
+        if (inst == kHoleInstance || inst >= recordOf.size()) continue;
+        if (recordOf[inst].size() <= prim) recordOf[inst].resize(static_cast<size_t>(prim) + 1u, kNoHit);
+        if (recordOf[inst][prim] == kNoHit) recordOf[inst][prim] = static_cast<uint32_t>(i);
+    }
+    char msg[160];
+    for (uint64_t i = 0; i < count; ++i) {
+        const ArkDdgiDebugShadeHit& h = hits[i];
+        if (h.instance == 0xffffffffu) {
+            out[i] = GpuHit { __builtin_bit_cast(float, 0x7f800000u), 0.0f, 0.0f, kNoHit };
+            continue;
+        }
+        msg[0] = 0;
+        if (h.instance >= recordOf.size() || h.primitive >= recordOf[h.instance].size() || recordOf[h.instance][h.primitive] == kNoHit)
+            std::snprintf(msg, sizeof(msg), "record %llu names no triangle of the scene (instance %u, primitive %u)", (unsigned long long)i, h.instance, h.primitive);
+        else if (!std::isfinite(h.t) || !(std::fabs(h.t) >= 0.0001f && std::fabs(h.t) <= zFar))
+            std::snprintf(msg, sizeof(msg), "record %llu has t = %g, |t| must be in [1e-4, %g]", (unsigned long long)i, static_cast<double>(h.t), static_cast<double>(zFar));
+        else if (!std::isfinite(h.u) || !std::isfinite(h.v) || h.u < 0.0f || h.v < 0.0f || h.u + h.v > 1.0f)
+            std::snprintf(msg, sizeof(msg), "record %llu has barycentrics (%g, %g) outside the triangle", (unsigned long long)i, static_cast<double>(h.u), static_cast<double>(h.v));
+        if (msg[0]) {
+            if (why) *why = msg;
+            return false;
+        }
+        out[i] = GpuHit { h.t, h.u, h.v, recordOf[h.instance][h.primitive] };
+    }
+    return true;
+}
+
+// ark_ddgi_debug_shade: hit shading alone as one serial frame, through the update's own
+// arguments and the book of the frames in flight: the slot table, the caller's hit records in
+// place of the primary traversal, then shadeWindow - the shadow rays really traced from the
+// planted hit points. No offsets, no blend; the window does not advance.
+// A record reaches the kernels only as the leaf-order index of a triangle record the front copy
+// holds, with barycentrics inside the triangle and a finite t in [1e-4, zFar]: everything the
+// kernels index by it (the shading record, its instance, material and textures) is then the
+// scene's own, sampleTexture wraps every texel coordinate into its texture and sampleDDGI
+// clamps every probe coordinate into the grid, so no planted record can make them read out
+// of bounds. Everything else is refused before the first launch.
+int shadeImpl(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugShadeHit* hits, void* hipStream)
+{
+    if (!ctx) return ARK_DDGI_E_INVALID_ARGUMENT;
+    if (!p || p->struct_size != sizeof(ArkDdgiFrameParams)) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "bad ArkDdgiFrameParams");
+    if (!ctx->hasScene) return ctx->fail(ARK_DDGI_E_NO_SCENE, "ark_ddgi_debug_shade before ark_ddgi_set_scene");
+    if (!hits) return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "debug_shade: no hit records");
+    const uint32_t N = static_cast<uint32_t>(ctx->N);
+    const uint32_t K = std::min(p->probe_updates, N);
+    const uint32_t R = p->rays_per_probe;
+    if (K == 0 || R == 0 || K > static_cast<uint32_t>(ctx->Kmax) || R > static_cast<uint32_t>(ctx->Rmax))
+        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "probe_updates %u / rays_per_probe %u outside [1,%d] / [1,%d]", K, R, ctx->Kmax, ctx->Rmax);
+    const hipStream_t s = streamOf(hipStream);
+    if (const int r = checkSequencing(ctx)) return r;
+    ARK_HIP(hipSetDevice(ctx->device));
+    // the front copy's records, downloaded from an idle device (as the host restatements' entries do)
+    ARK_HIP(hipDeviceSynchronize());
+    if (ctx->sceneVersion != ctx->sceneStore->version)
+        if (const int rc = refreshScene(ctx)) return rc;
+    std::vector<uint32_t> words;
+    std::vector<int32_t> classOf;
+    if (const int rc = sceneRecordsAndClasses(*ctx->sceneStore, ctx, words, classOf)) return rc;
+    const uint32_t first = p->first_probe_index % N;
+    const size_t rays = static_cast<size_t>(countSlabProbes(ctx, first, K)) * R;
+    std::vector<GpuHit> rec(rays);
+    std::string why;
+    if (!shadeHitRecords(words.data(), words.size() / 12u, static_cast<uint32_t>(classOf.size()), ctx->desc.z_far, hits, rays, rec.data(), &why))
+        return ctx->fail(ARK_DDGI_E_INVALID_ARGUMENT, "debug_shade: %s", why.c_str());
+    ARK_HIP(orderBegin(ctx, s));
+    ARK_HIP(flushLights(ctx, s));
+    if (ctx->orderR != R) {
+        sampleTraversalOrder(R, ctx->orderHost);
+        ARK_HIP(hipMemcpyAsync(ctx->order.ptr, ctx->orderHost.data(), R * 4, hipMemcpyHostToDevice, s));
+        ctx->orderR = R;
+    }
+    const FramePlan plan = ctx->frames.begin(R, true); // serial: every launch in line on s
+    FrameArgs f = frameArgs(ctx, p, K, R, plan);
+    f.seed_offsets_write = 0u; // no traversal: the hit candidates are not written
+    ctx->coverCountsValid = ctx->counting;
+    if (ctx->counting) ARK_HIP(hipMemsetAsync(ctx->counters.ptr, 0, ctx->counters.bytes, s));
+    ARK_HIP(launch_probe_slots(f, s));
+    if (f.window_probes > 0) {
+        ARK_HIP(hipMemcpyAsync(f.hits, rec.data(), rec.size() * sizeof(GpuHit), hipMemcpyHostToDevice, s));
+        ARK_HIP(hipStreamSynchronize(s)); // rec leaves scope
+        FrameArgs fs;
+        if (const int rc = shadeWindow(ctx, plan, f, s, false, [] { return hipSuccess; }, &fs)) return rc;
+    } else {
+        ctx->lastSunOnly = false;
+    }
+    ARK_HIP(hipEventRecord(ctx->evFrameDone[plan.b], s));
+    ctx->lastStream = s;
+    ARK_HIP(orderEnd(ctx, s));
+    ctx->frames.finished(plan, R);
+    return ARK_DDGI_OK;
+}
+
 // The last window as Z-slab ranks exchange it (ark_ddgi_window_exchange_info)
 ArkDdgiWindowExchange windowExchangeInfo(const ArkDdgiCtx* ctx)
 {
@@ -424,6 +541,20 @@ int windowPack(ArkDdgiCtx* ctx, void* buf, uint64_t bytes, void* hipStream, bool
 int ark::debugProbeUpdate(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugHit* hits, void* hipStream)
 {
     return probeUpdateImpl(ctx, p, hits, hipStream);
+}
+
+int ark::debugShadeMap(const uint32_t* words, uint64_t n, uint32_t instances, float zFar, const ArkDdgiDebugShadeHit* hits, uint64_t count, uint32_t* outTri)
+{
+    if ((n && !words) || (count && (!hits || !outTri))) return ARK_DDGI_E_INVALID_ARGUMENT;
+    std::vector<GpuHit> rec(count);
+    if (!shadeHitRecords(words, n, instances, zFar, hits, count, rec.data(), nullptr)) return ARK_DDGI_E_INVALID_ARGUMENT;
+    for (uint64_t i = 0; i < count; ++i) outTri[i] = rec[i].tri;
+    return ARK_DDGI_OK;
+}
+
+int ark::debugShade(ArkDdgiCtx* ctx, const ArkDdgiFrameParams* p, const ArkDdgiDebugShadeHit* hits, void* hipStream)
+{
+    return shadeImpl(ctx, p, hits, hipStream);
 }
 
 int ark::checkSequencing(ArkDdgiCtx* ctx)

@@ -21,6 +21,9 @@ import numpy as np
 from . import abi
 from .scene import SceneData
 
+# ArkDdgiDebugShadeHit as a numpy record (debug_shade)
+SHADE_HIT_DTYPE = np.dtype([("instance", np.uint32), ("primitive", np.uint32), ("u", np.float32), ("v", np.float32), ("t", np.float32)])
+
 
 @dataclass
 class ProbeGrid:
@@ -461,6 +464,28 @@ class DDGIContext:
         self.check(self.lib.ark_ddgi_debug_probe_update(self.h, C.byref(params), C.c_void_p(a.ctypes.data) if a is not None else None,
                                                         C.c_void_p(stream) if stream else None), "ark_ddgi_debug_probe_update")
 
+    def debug_shade(self, params: abi.ArkDdgiFrameParams, hits, stream: int | None = None) -> int:
+        """ark_ddgi_debug_shade: hit shading alone (slot table, shadow rays, k_shade in the
+        update's schedule) over planted hits: [window probes * rays_per_probe] records with
+        fields instance (0xffffffff a miss), primitive, u, v, t in slot order. Returns the
+        return code: 0, or ARK_DDGI_E_INVALID_ARGUMENT for a refused record (nothing launched)."""
+        a = np.zeros(np.asarray(hits).size, SHADE_HIT_DTYPE)
+        for k in SHADE_HIT_DTYPE.names:
+            a[k] = np.asarray(hits)[k].reshape(-1)
+        rc = self.lib.ark_ddgi_debug_shade(self.h, C.byref(params), C.c_void_p(a.ctypes.data), C.c_void_p(stream) if stream else None)
+        if rc != abi.ARK_DDGI_E_INVALID_ARGUMENT:
+            self.check(rc, "ark_ddgi_debug_shade")
+        return rc
+
+    def world_records(self) -> np.ndarray:
+        """ark_ddgi_debug_world_records: the front copy's triangle records in leaf order,
+        uint32 [records, 12] (word 9 the instance, word 10 the primitive; 0xffffffff: a hole)."""
+        n = C.c_uint64()
+        self.check(self.lib.ark_ddgi_debug_world_records(self.h, None, 0, C.byref(n)), "ark_ddgi_debug_world_records")
+        out = np.zeros((int(n.value), 12), np.uint32)
+        self.check(self.lib.ark_ddgi_debug_world_records(self.h, C.c_void_p(out.ctypes.data), int(n.value), C.byref(n)), "ark_ddgi_debug_world_records")
+        return out
+
     def update_overlapped(self, params: abi.ArkDdgiFrameParams, stream: int | None, shade_wait_event: int | None,
                           done_event: int | None):
         """ark_ddgi_update_overlapped: raw hipStream_t / hipEvent_t handles (ints)."""
@@ -518,7 +543,7 @@ class DDGIContext:
 
     def read(self, which: int) -> np.ndarray:
         n = self.size(which)
-        dt = np.float32 if which in (abi.ARK_DDGI_PROBE_OFFSETS, abi.ARK_DDGI_DEBUG_HITS) else np.uint16
+        dt = {abi.ARK_DDGI_PROBE_OFFSETS: np.float32, abi.ARK_DDGI_DEBUG_HITS: np.float32, abi.ARK_DDGI_DEBUG_SHADOW_BITS: np.uint32}.get(which, np.uint16)
         out = np.empty(n // np.dtype(dt).itemsize, dtype=dt)
         self.check(self.lib.ark_ddgi_read(self.h, which, out.ctypes.data, n), "ark_ddgi_read")
         return out

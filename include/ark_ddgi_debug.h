@@ -27,6 +27,17 @@ extern "C" {
  * (tools/ray_cost.py); counting is enabled first. */
 #define ARK_DDGI_DEBUG_RAY_STEPS 101
 
+/* Extra resource id for ark_ddgi_read: the light words of the last update or debug shade, one
+ * uint32 per window ray indexed like ARK_DDGI_DEBUG_HITS (slot * rays_per_probe + sample),
+ * sized max_probe_updates x max_rays_per_probe: the front hit's lit lights (LdotN > 0) in bits
+ * 0-15 - the sun first, then the spots in order - and the lights whose shadow ray was occluded
+ * in bits 16-31. Written for front hits only (a miss's or a back face's word keeps what an
+ * earlier frame left), and only when the context has lights. The schedule with the shadow-ray
+ * generator writes every front hit's word. The sun-only schedule writes every front hit's word
+ * only in its counting variant (ark_ddgi_set_counting); without counting it writes the words of
+ * the rays its cover map left undecided and no others. Before a scene is set: an error. */
+#define ARK_DDGI_DEBUG_SHADOW_BITS 102
+
 /* Evaluates op (0 sin, 1 cos, 2 acos, 3 atan2(x,y), 4 log2, 5 exp2, 6 pow(x,y),
  * 7 fp32->fp16->fp32 round trip, 8 powf_pos_(x,y)) on `device` for n inputs (host arrays). */
 int ark_ddgi_debug_fmath(int device, int op, const float* x, const float* y, float* out, uint64_t n);
@@ -429,6 +440,45 @@ typedef struct ArkDdgiDebugHit {
 } ArkDdgiDebugHit;
 int ark_ddgi_debug_probe_update(struct ArkDdgiCtx* ctx, const ArkDdgiFrameParams* params, const ArkDdgiDebugHit* hits, void* hip_stream);
 int ark_ddgi_debug_probe_update_layout(uint32_t* out, int n);
+
+/* Hit shading alone, over planted hits (tests/test_gpu_hit_shading.py): one serial frame ordered
+ * like ark_ddgi_update after whatever the context did before - the slot table, then `hits`
+ * uploaded in place of the primary traversal, then exactly the shadow-ray and shading launches
+ * of an update with the update's own arguments, in the schedule the update would pick (the
+ * shadow-ray generator, the shadow traversal and k_shade; or, for the sun alone with its cover
+ * map, k_shade, the traversal of what it left undecided and the deferred pass). The shadow rays
+ * are really traced through the scene's BVH from the planted hit points. No probe offsets and no
+ * blend run: surfels and ARK_DDGI_DEBUG_SHADOW_BITS are the outputs, ARK_DDGI_DEBUG_HITS reads
+ * the planted records back. The rolling window does not advance and the probe rays' hit
+ * candidates are not written.
+ * `hits`: a host array of [window probes][rays_per_probe] records in slot order (on a Z-slab
+ * rank the rank's probes of the window, compacted): instance 0xffffffff for a miss, else the
+ * instance and the primitive within it, the hit attributes (u, v) and t, negative for a back
+ * face. A hit need not lie where its ray meets the triangle: the hit point is origin + t dir.
+ * The call maps them to the front copy's leaf-order records on the host (it waits for the device
+ * first) and refuses, with ARK_DDGI_E_INVALID_ARGUMENT and before any launch: an instance or
+ * primitive the scene does not hold (a hole names none), a non-finite t or |t| outside
+ * [1e-4, z_far], a non-finite u or v, u < 0, v < 0 or u + v > 1. Refuses what ark_ddgi_update
+ * refuses of `params`. _layout: out[0 .. n) of {sizeof(ArkDdgiDebugShadeHit), offsetof instance,
+ * primitive, u, v, t}; returns how many it wrote.
+ * _map: the entry's own mapping and refusals alone, on the host (no context, no GPU):
+ * `record_words` are `records` triangle records of 12 words each as the world BVH holds them
+ * (word 9 the instance, word 10 the primitive, instance 0xffffffff a hole), `instances` the
+ * instance count; out_tri[i] receives the leaf-order record of hits[i] (0xffffffff for a
+ * miss). Returns ARK_DDGI_E_INVALID_ARGUMENT for exactly what ark_ddgi_debug_shade refuses. */
+/* _world_records: the triangle records the context's kernels read now (the front copy), in leaf
+ * order, 12 words each, downloaded: *out_records receives their count, out_words the records
+ * when it is not NULL and `capacity` (in records) holds them. What ARK_DDGI_DEBUG_HITS' triangle
+ * indices point into. Synchronous. */
+int ark_ddgi_debug_world_records(struct ArkDdgiCtx* ctx, uint32_t* out_words, uint64_t capacity, uint64_t* out_records);
+typedef struct ArkDdgiDebugShadeHit {
+    uint32_t instance, primitive;
+    float u, v, t;
+} ArkDdgiDebugShadeHit;
+int ark_ddgi_debug_shade(struct ArkDdgiCtx* ctx, const ArkDdgiFrameParams* params, const ArkDdgiDebugShadeHit* hits, void* hip_stream);
+int ark_ddgi_debug_shade_layout(uint32_t* out, int n);
+int ark_ddgi_debug_shade_map(const uint32_t* record_words, uint64_t records, uint32_t instances, float z_far, const ArkDdgiDebugShadeHit* hits, uint64_t n,
+                             uint32_t* out_tri);
 
 #ifdef __cplusplus
 }

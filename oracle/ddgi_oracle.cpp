@@ -644,6 +644,16 @@ struct Stats {
     uint64_t nodes = 0, tris = 0;
 };
 
+// A probe ray's accepted hit without the traversal that found it (oracle_shade,
+// oracle_read of ORACLE_SHADE_HITS): instance kOracleMiss for a miss, t negative for a
+// back face (payload.hitT), (u, v) the hit attributes.
+struct OracleShadeHit {
+    uint32_t instance, primitive;
+    float u, v, t;
+};
+const uint32_t kOracleMiss = 0xffffffffu;
+const int ORACLE_SHADE_HITS = 200, ORACLE_SHADOW_BITS = 201; // oracle_read ids
+
 // ---------------------------------------------------------------------------
 // Oracle context
 // ---------------------------------------------------------------------------
@@ -672,6 +682,12 @@ struct Oracle {
     ArkDirectionalLight sun {};
     std::vector<ArkSpotLight> spots;
     Stats stats;
+    // first index into `tris` of every instance (buildWorld pushes them in instance order)
+    std::vector<uint32_t> instFirstTri;
+    // the last update's or shade's per-ray records at slot * rays_per_probe + sample:
+    // the accepted hit in neutral form and the light word (lit bits 0-15, occluded 16-31)
+    std::vector<OracleShadeHit> lastHits;
+    std::vector<uint32_t> lastBits;
 };
 
 // Closest-hit traversal within one BVH (mask class), masked pass applies the
@@ -871,8 +887,9 @@ struct Surface {
 };
 
 // opaque.rchit:105-176 (RT_EVALUATE_DIRECT_LIGHT=1, RT_USE_EXTENDED_RAY_PAYLOAD=1)
-Surface closestHit(const Oracle& o, const Ray& ray, const Hit& h, float ambientAmount, Stats& st, bool shade)
+Surface closestHit(const Oracle& o, const Ray& ray, const Hit& h, float ambientAmount, Stats& st, bool shade, uint32_t* lightWord = nullptr)
 {
+    uint32_t word = 0, l = 0; // bit l: the sun first, then the spots in order
     Surface s {};
     const WTri& t = o.tris[h.tri];
     s.hitT = h.backface ? -h.t : h.t;
@@ -908,12 +925,15 @@ Surface closestHit(const Oracle& o, const Ray& ray, const Hit& h, float ambientA
         float LdotN = dot(L, N);
         if (LdotN > 0.0f) {
             float shadowFactor = traceShadowRay(o, hitPoint, L, 2.0f * zFar, st);
+            word |= 1u | (shadowFactor == 0.0f ? 1u << 16 : 0u);
             V3 brdf = evaluateDefaultBRDF(L, V, N, baseColor, roughness, metallic, clearcoat, ccRough);
             V3 directLight = v3(o.sun.color[0], o.sun.color[1], o.sun.color[2]) * shadowFactor;
             color = color + brdf * LdotN * directLight;
         }
+        l++;
     }
     for (const ArkSpotLight& sl : o.spots) { // opaque.rchit:75-103
+        const uint32_t bit = l++;
         V3 dir = v3(sl.world_space_direction[0], sl.world_space_direction[1], sl.world_space_direction[2]);
         V3 L = -normalize(dir);
         float LdotN = dot(L, N);
@@ -922,6 +942,7 @@ Surface closestHit(const Oracle& o, const Ray& ray, const Hit& h, float ambientA
             float distanceToLight = length(toLight);
             V3 normalizedToLight = toLight / distanceToLight;
             float shadowFactor = traceShadowRay(o, hitPoint, normalizedToLight, distanceToLight - 0.001f, st);
+            if (bit < 16u) word |= (1u << bit) | (shadowFactor == 0.0f ? 1u << (16u + bit) : 0u);
             float distanceAttenuation = 1.0f / square(distanceToLight);
             V3 right = v3(sl.world_space_right[0], sl.world_space_right[1], sl.world_space_right[2]);
             V3 up = v3(sl.world_space_up[0], sl.world_space_up[1], sl.world_space_up[2]);
@@ -931,6 +952,7 @@ Surface closestHit(const Oracle& o, const Ray& ray, const Hit& h, float ambientA
             color = color + brdf * LdotN * directLight;
         }
     }
+    if (lightWord) *lightWord = word;
     s.color = color;
     s.baseColor = baseColor;
     s.normal = N;
@@ -1033,13 +1055,52 @@ V3 evaluateIndirectLightFromPreviousFrame(const Oracle& o, V3 P, V3 V, V3 N, V3 
     return splat(1.0f - metallic) * (splat(1.0f) - F) * irradiance;
 }
 
+// What follows the two traversals of tracePrimaryRay (raygen.rgen:70-92) and main's
+// :123-138 for one ray: the environment on a miss, else the accepted hit's closest-hit
+// shader (its shadow rays traced from the hit point), the indirect term and the back-face
+// rule. `lightWord`: the hit's lit and occluded light bits (0 for a miss or a back face).
+void shadeProbeRay(const Oracle& o, V3 origin, V3 dir, const ArkDdgiFrameParams& p, bool didHit, const Hit& accepted, float out[4], Stats& st,
+                   uint32_t* lightWord)
+{
+    const float zFar = o.desc.z_far;
+    V3 color = splat(0.0f);
+    Ray ray { origin, dir, 0.0001f, zFar };
+    *lightWord = 0;
+    float dist;
+    if (!didHit) { // raygen.rgen:70-79
+        dist = zFar;
+        float u, v;
+        sphericalUvFromDirection(dir, &u, &v);
+        float c[4];
+        const Tex& env = (o.envTex >= 0) ? o.textures[o.envTex] : o.envWhite;
+        sampleBilinear(env, u, v, c);
+        color = p.environment_multiplier * v3(c[0], c[1], c[2]);
+    } else {
+        Surface s = closestHit(o, ray, accepted, p.ambient_amount, st, !accepted.backface, lightWord);
+        dist = accepted.backface ? -accepted.t : accepted.t;
+        if (!accepted.backface) {
+            color = s.color;
+            V3 hitPos = origin + dist * dir;
+            V3 indirect = evaluateIndirectLightFromPreviousFrame(o, hitPos, -dir, s.normal, s.baseColor, s.metallic);
+            color = color + s.baseColor * indirect;
+        } else {
+            color = splat(0.0f); // raygen.rgen:129-134
+            dist = dist * 0.2f;
+        }
+    }
+    out[0] = color.x;
+    out[1] = color.y;
+    out[2] = color.z;
+    out[3] = dist;
+}
+
 // raygen.rgen:35-92 (tracePrimaryRay) + :108-139 (main) for one (probe, sample).
-void traceProbeRay(const Oracle& o, uint32_t probeIdx, V3 origin, V3 dir, const ArkDdgiFrameParams& p, float out[4], Stats& st)
+void traceProbeRay(const Oracle& o, uint32_t probeIdx, V3 origin, V3 dir, const ArkDdgiFrameParams& p, float out[4], Stats& st,
+                   OracleShadeHit* hitOut = nullptr, uint32_t* lightWord = nullptr)
 {
     const float zFar = o.desc.z_far;
     float tmin = 0.0001f, tmax = zFar;
     int numHits = 0;
-    V3 color = splat(0.0f);
     Ray ray { origin, dir, tmin, tmax };
     // Opaque pass: RayFlags_Opaque, cullMask RT_HIT_MASK_OPAQUE (raygen.rgen:43-55)
     Hit hit;
@@ -1062,32 +1123,17 @@ void traceProbeRay(const Oracle& o, uint32_t probeIdx, V3 origin, V3 dir, const 
             numHits += 1;
         }
     }
-    float dist;
-    if (numHits == 0) { // raygen.rgen:70-79
-        dist = zFar;
-        float u, v;
-        sphericalUvFromDirection(dir, &u, &v);
-        float c[4];
-        const Tex& env = (o.envTex >= 0) ? o.textures[o.envTex] : o.envWhite;
-        sampleBilinear(env, u, v, c);
-        color = p.environment_multiplier * v3(c[0], c[1], c[2]);
-    } else {
-        Surface s = closestHit(o, ray, accepted, p.ambient_amount, st, !accepted.backface);
-        dist = tmax;
-        if (!accepted.backface) {
-            color = s.color;
-            V3 hitPos = origin + dist * dir;
-            V3 indirect = evaluateIndirectLightFromPreviousFrame(o, hitPos, -dir, s.normal, s.baseColor, s.metallic);
-            color = color + s.baseColor * indirect;
+    uint32_t word = 0;
+    shadeProbeRay(o, origin, dir, p, numHits > 0, accepted, out, st, &word);
+    if (lightWord) *lightWord = word;
+    if (hitOut) {
+        if (numHits > 0) {
+            const WTri& t = o.tris[accepted.tri];
+            *hitOut = { t.inst, t.prim, accepted.u, accepted.v, tmax };
         } else {
-            color = splat(0.0f); // raygen.rgen:129-134
-            dist = dist * 0.2f;
+            *hitOut = { kOracleMiss, 0u, 0.0f, 0.0f, zFar };
         }
     }
-    out[0] = color.x;
-    out[1] = color.y;
-    out[2] = color.z;
-    out[3] = dist;
 }
 
 template<typename F>
@@ -1277,10 +1323,12 @@ void bakeTexel(const Oracle& o, const ArkRTTriangleMesh& m, uint32_t p, uint32_t
 static void buildWorld(Oracle& o, int threads)
 {
     o.tris.clear();
+    o.instFirstTri.clear();
     std::vector<uint32_t> opaque, masked, blend;
     uint32_t gid = 0;
     for (uint32_t ii = 0; ii < o.instances.size(); ++ii) {
         const ArkRTInstance& inst = o.instances[ii];
+        o.instFirstTri.push_back(static_cast<uint32_t>(o.tris.size()));
         const ArkRTTriangleMesh& m = o.meshes[inst.rt_mesh_index];
         const float* M = inst.object_to_world;
         float det = M[0] * (M[5] * M[10] - M[6] * M[9]) - M[1] * (M[4] * M[10] - M[6] * M[8]) + M[2] * (M[4] * M[9] - M[5] * M[8]);
@@ -1504,6 +1552,8 @@ void* oracle_create(const ArkDdgiDesc* desc)
     o->Rmax = desc->max_rays_per_probe > 0 ? desc->max_rays_per_probe : ARK_DDGI_MAX_RAYS_PER_PROBE;
     o->Kmax = desc->max_probe_updates > 0 ? desc->max_probe_updates : ARK_DDGI_REFERENCE_MAX_PROBE_UPDATES;
     o->surfels.resize(static_cast<size_t>(o->Kmax) * o->Rmax * 4);
+    o->lastHits.assign(static_cast<size_t>(o->Kmax) * o->Rmax, OracleShadeHit { kOracleMiss, 0u, 0.0f, 0.0f, 0.0f });
+    o->lastBits.assign(static_cast<size_t>(o->Kmax) * o->Rmax, 0u);
     o->envWhite = whiteSrgbPixel();
     resetHistory(*o);
     return o;
@@ -1591,7 +1641,8 @@ int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads)
         for (uint32_t s = 0; s < R; ++s) {
             V3 dir = calculateRotatedSphericalFibonacciSample(probeIdx, s, R, frameIdx);
             float out[4];
-            traceProbeRay(o, probeIdx, pos, dir, *p, out, tstats[tid]);
+            const size_t rec = static_cast<size_t>(slot) * R + s;
+            traceProbeRay(o, probeIdx, pos, dir, *p, out, tstats[tid], &o.lastHits[rec], &o.lastBits[rec]);
             uint16_t* dst = &o.surfels[(static_cast<size_t>(slot) * o.Rmax + s) * 4];
             for (int c = 0; c < 4; ++c) dst[c] = f32_to_f16(out[c]);
         }
@@ -1618,6 +1669,62 @@ int oracle_blend(void* ctx, const ArkDdgiFrameParams* p, int threads)
     return 0;
 }
 
+// Step 1 of an update without its two traversals (what traceProbeRay does after them): the
+// window's rays take their accepted hits from `hits` ([window probes][rays_per_probe] in
+// slot order, on a Z-slab rank the rank's probes compacted), the closest-hit shader traces
+// its own shadow rays from the hit point, and the surfels are written. The hits and the
+// light words stay readable (ORACLE_SHADE_HITS, ORACLE_SHADOW_BITS). No blend, no offsets.
+// Refuses a record that names no triangle of the scene, a non-finite or out-of-range t,
+// and barycentrics outside the triangle.
+int oracle_shade(void* ctx, const ArkDdgiFrameParams* p, const OracleShadeHit* hits, int threads)
+{
+    Oracle& o = *static_cast<Oracle*>(ctx);
+    if (!p || !hits || !o.hasScene) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const Grid& g = o.g;
+    const uint32_t N = static_cast<uint32_t>(g.N());
+    const uint32_t K = std::min(p->probe_updates, N);
+    const uint32_t R = p->rays_per_probe;
+    if (K > static_cast<uint32_t>(o.Kmax) || R > static_cast<uint32_t>(o.Rmax) || R == 0) return ARK_DDGI_E_INVALID_ARGUMENT;
+    const std::vector<uint32_t> window = windowProbes(o, p->first_probe_index % N, K);
+    const int W = static_cast<int>(window.size());
+    const float zFar = o.desc.z_far;
+    for (size_t i = 0; i < static_cast<size_t>(W) * R; ++i) {
+        const OracleShadeHit& h = hits[i];
+        if (h.instance == kOracleMiss) continue;
+        if (h.instance >= o.instances.size() || h.primitive >= o.instances[h.instance].triangle_count) return ARK_DDGI_E_INVALID_ARGUMENT;
+        if (!std::isfinite(h.t) || !(fabsf(h.t) >= 0.0001f && fabsf(h.t) <= zFar)) return ARK_DDGI_E_INVALID_ARGUMENT;
+        if (!std::isfinite(h.u) || !std::isfinite(h.v) || h.u < 0.0f || h.v < 0.0f || h.u + h.v > 1.0f) return ARK_DDGI_E_INVALID_ARGUMENT;
+    }
+    std::vector<Stats> tstats(std::max(threads, 1));
+    parallelFor(W, threads, [&](int slot, int tid) {
+        uint32_t probeIdx = window[slot];
+        V3 pos = probePosition(g, probeIdx);
+        const float* off = &o.offsets[static_cast<size_t>(probeIdx) * 4];
+        pos = pos + v3(off[0], off[1], off[2]);
+        for (uint32_t s = 0; s < R; ++s) {
+            V3 dir = calculateRotatedSphericalFibonacciSample(probeIdx, s, R, p->frame_index);
+            const size_t rec = static_cast<size_t>(slot) * R + s;
+            const OracleShadeHit& h = hits[rec];
+            Hit accepted;
+            const bool didHit = h.instance != kOracleMiss;
+            if (didHit) {
+                accepted.hit = true;
+                accepted.backface = h.t < 0.0f;
+                accepted.t = fabsf(h.t);
+                accepted.u = h.u;
+                accepted.v = h.v;
+                accepted.tri = o.instFirstTri[h.instance] + h.primitive;
+            }
+            float out[4];
+            shadeProbeRay(o, pos, dir, *p, didHit, accepted, out, tstats[tid], &o.lastBits[rec]);
+            o.lastHits[rec] = h;
+            uint16_t* dst = &o.surfels[(static_cast<size_t>(slot) * o.Rmax + s) * 4];
+            for (int c = 0; c < 4; ++c) dst[c] = f32_to_f16(out[c]);
+        }
+    });
+    return 0;
+}
+
 int oracle_read(void* ctx, int which, void* dst, uint64_t bytes)
 {
     Oracle& o = *static_cast<Oracle*>(ctx);
@@ -1628,6 +1735,8 @@ int oracle_read(void* ctx, int which, void* dst, uint64_t bytes)
     case ARK_DDGI_ATLAS_VISIBILITY: src = o.vis.data(); n = o.vis.size() * 2; break;
     case ARK_DDGI_SURFELS: src = o.surfels.data(); n = o.surfels.size() * 2; break;
     case ARK_DDGI_PROBE_OFFSETS: src = o.offsets.data(); n = o.offsets.size() * 4; break;
+    case ORACLE_SHADE_HITS: src = o.lastHits.data(); n = o.lastHits.size() * sizeof(OracleShadeHit); break;
+    case ORACLE_SHADOW_BITS: src = o.lastBits.data(); n = o.lastBits.size() * 4; break;
     default: return ARK_DDGI_E_INVALID_ARGUMENT;
     }
     if (bytes != n) return ARK_DDGI_E_SIZE_MISMATCH;

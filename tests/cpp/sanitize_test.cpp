@@ -26,6 +26,11 @@ void oracle_destroy(void* ctx);
 int oracle_set_scene(void* ctx, const ArkDdgiScene* s, int threads);
 int oracle_update(void* ctx, const ArkDdgiFrameParams* p, int threads);
 int oracle_blend(void* ctx, const ArkDdgiFrameParams* p, int threads);
+struct OracleShadeHit {
+    uint32_t instance, primitive;
+    float u, v, t;
+};
+int oracle_shade(void* ctx, const ArkDdgiFrameParams* p, const OracleShadeHit* hits, int threads);
 int oracle_write(void* ctx, int which, const void* src, uint64_t bytes);
 int oracle_read(void* ctx, int which, void* dst, uint64_t bytes);
 int oracle_bake_ao(void* ctx, uint32_t instance, uint32_t W, uint32_t H, uint32_t samples, int bent, uint32_t row0, uint32_t row1,
@@ -378,6 +383,33 @@ int main()
         CHECK(oracle_blend(o, &p, 2) == 0);
         p.rays_per_probe = 65; // more than max_rays_per_probe: refused
         CHECK(oracle_blend(o, &p, 2) != 0);
+    }
+    {
+        // shading alone on planted hits: the same ragged window; front hits, back faces and
+        // misses over the soup's first instances, shadow rays traced from the hit points
+        ArkDdgiFrameParams p;
+        std::memset(&p, 0, sizeof(p));
+        p.struct_size = sizeof(p);
+        p.rays_per_probe = 37;
+        p.probe_updates = 7;
+        p.first_probe_index = 60;
+        p.frame_index = 700;
+        p.environment_multiplier = 1.0f;
+        p.ambient_amount = 0.1f;
+        std::vector<OracleShadeHit> hits(7 * 37);
+        for (size_t i = 0; i < hits.size(); ++i) {
+            const uint32_t inst = static_cast<uint32_t>(i % scene->instance_count);
+            hits[i] = { inst, static_cast<uint32_t>(i % scene->instances[inst].triangle_count), 0.25f, 0.5f, i % 3 == 1 ? -1.5f : 0.75f };
+            if (i % 5 == 4) hits[i].instance = 0xffffffffu; // a miss
+        }
+        CHECK(oracle_shade(o, &p, hits.data(), 2) == 0);
+        std::vector<uint32_t> bits(64 * 64);
+        CHECK(oracle_read(o, 201, bits.data(), bits.size() * 4) == 0);
+        hits[3].primitive = scene->instances[hits[3].instance].triangle_count; // past the instance: refused
+        CHECK(oracle_shade(o, &p, hits.data(), 2) != 0);
+        hits[3].primitive = 0;
+        hits[3].u = 0.75f; // u + v > 1: refused
+        CHECK(oracle_shade(o, &p, hits.data(), 2) != 0);
     }
     std::vector<uint16_t> irr(4 * 10 * 4 * 4 * 10 * 4);
     CHECK(oracle_read(o, ARK_DDGI_ATLAS_IRRADIANCE, irr.data(), irr.size() * 2) == 0);

@@ -26,6 +26,14 @@ VARIANTS = {
     "witness": (os.path.join(ROOT, "oracle", "build", "libddgi_oracle_witness.so"), 1, 1),
 }
 
+# oracle_read ids of the last update's or shade's per-ray records (oracle/ddgi_oracle.cpp), at
+# slot * rays_per_probe + sample: the accepted hits in neutral form and the light words
+ORACLE_SHADE_HITS = 200
+ORACLE_SHADOW_BITS = 201
+# OracleShadeHit: instance MISS for a miss, t negative for a back face
+SHADE_HIT_DTYPE = np.dtype([("instance", np.uint32), ("primitive", np.uint32), ("u", np.float32), ("v", np.float32), ("t", np.float32)])
+MISS = 0xFFFFFFFF
+
 _libs = {}
 
 
@@ -47,6 +55,7 @@ def load(libm: bool = False, variant: str | None = None):
         lib.oracle_set_instances.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int]
         lib.oracle_update.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiFrameParams), C.c_int]
         lib.oracle_blend.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiFrameParams), C.c_int]
+        lib.oracle_shade.argtypes = [C.c_void_p, C.POINTER(abi.ArkDdgiFrameParams), C.c_void_p, C.c_int]
         lib.oracle_read.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         lib.oracle_write.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_uint64]
         lib.oracle_get_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
@@ -130,8 +139,17 @@ class Oracle:
         rc = self.lib.oracle_blend(self.h, C.byref(params), threads)
         assert rc == 0, rc
 
+    def shade(self, params, hits, threads: int = 8):
+        """oracle_shade: the window's surfels from planted hits (SHADE_HIT_DTYPE, [window
+        probes * rays_per_probe] in slot order), shadow rays traced from the hit points;
+        returns the return code (0, or ARK_DDGI_E_INVALID_ARGUMENT for a refused record)."""
+        hits = np.ascontiguousarray(hits, SHADE_HIT_DTYPE)
+        return self.lib.oracle_shade(self.h, C.byref(params), hits.ctypes.data, threads)
+
     def _size(self, which):
         X, Y, Z = self.desc.grid_dims
+        if which == ORACLE_SHADE_HITS or which == ORACLE_SHADOW_BITS:
+            return self.desc.max_probe_updates * self.desc.max_rays_per_probe
         if which == abi.ARK_DDGI_ATLAS_IRRADIANCE:
             return X * 10 * Y * Z * 10 * 4
         if which == abi.ARK_DDGI_ATLAS_VISIBILITY:
@@ -142,7 +160,7 @@ class Oracle:
 
     def read(self, which):
         n = self._size(which)
-        dt = np.float32 if which == abi.ARK_DDGI_PROBE_OFFSETS else np.uint16
+        dt = {abi.ARK_DDGI_PROBE_OFFSETS: np.float32, ORACLE_SHADE_HITS: SHADE_HIT_DTYPE, ORACLE_SHADOW_BITS: np.uint32}.get(which, np.uint16)
         out = np.empty(n, dtype=dt)
         rc = self.lib.oracle_read(self.h, which, out.ctypes.data, out.nbytes)
         assert rc == 0, rc

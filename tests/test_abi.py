@@ -58,6 +58,43 @@ def test_debug_hit_layout_matches_c():
     assert lib.ark_ddgi_debug_probe_update(None, None, None, None) == -1
 
 
+def test_debug_shade_hit_layout_and_refusals():
+    """ArkDdgiDebugShadeHit (ark_ddgi_debug_shade's planted hits), its numpy form, and the
+    entry's host side - the mapping to leaf-order records and every refusal - without a GPU:
+    ark_ddgi_debug_shade_map is what the entry runs before its first launch."""
+    from arkoserenderer_amd import ddgi as D
+
+    lib = abi.load_library()
+    out = (C.c_uint32 * 6)()
+    assert lib.ark_ddgi_debug_shade_layout(out, 6) == 6
+    H = abi.ArkDdgiDebugShadeHit
+    assert list(out) == [C.sizeof(H), H.instance.offset, H.primitive.offset, H.u.offset, H.v.offset, H.t.offset] == [20, 0, 4, 8, 12, 16]
+    dt = D.SHADE_HIT_DTYPE
+    assert [dt.itemsize] + [dt.fields[k][1] for k in dt.names] == [20, 0, 4, 8, 12, 16]
+    assert lib.ark_ddgi_debug_shade(None, None, None, None) == -1
+    # five records in leaf order: (instance, primitive) = (1, 0), a hole, (0, 1), (0, 0), (1, 2); instance 1 has no primitive 1
+    words = np.zeros((5, 12), np.uint32)
+    words[:, 9], words[:, 10] = [1, 0xFFFFFFFF, 0, 0, 1], [0, 0, 1, 0, 2]
+
+    def run(rows, z_far=100.0):
+        hits = np.array(rows, dt)
+        tri = np.full(len(hits), 77, np.uint32)
+        return lib.ark_ddgi_debug_shade_map(words.ctypes.data, 5, 2, z_far, hits.ctypes.data, len(hits), tri.ctypes.data), tri.tolist()
+
+    good = [(0, 0, 0.25, 0.5, 1.0), (0, 1, 0.0, 0.0, -2.0), (1, 0, 1.0, 0.0, 1e-4), (1, 2, 0.0, 1.0, 100.0), (0xFFFFFFFF, 9, np.nan, np.nan, np.nan)]
+    assert run(good) == (0, [3, 2, 0, 4, 0xFFFFFFFF])
+    nan, inf = float("nan"), float("inf")
+    for bad in [(2, 0, 0.2, 0.2, 1.0), (1, 1, 0.2, 0.2, 1.0), (1, 3, 0.2, 0.2, 1.0), (0xFFFFFFFE, 0, 0.2, 0.2, 1.0),  # unknown instance, primitive; a hole names none
+                (0, 0, 0.2, 0.2, nan), (0, 0, 0.2, 0.2, inf), (0, 0, 0.2, 0.2, -inf), (0, 0, 0.2, 0.2, 0.0), (0, 0, 0.2, 0.2, 9e-5), (0, 0, 0.2, 0.2, -9e-5),
+                (0, 0, 0.2, 0.2, 100.01), (0, 0, 0.2, 0.2, -100.01),
+                (0, 0, nan, 0.2, 1.0), (0, 0, 0.2, nan, 1.0), (0, 0, inf, 0.2, 1.0), (0, 0, 0.2, -inf, 1.0),
+                (0, 0, -1e-7, 0.2, 1.0), (0, 0, 0.2, -1e-7, 1.0), (0, 0, 0.75, 0.2500001, 1.0)]:
+        rc, tri = run(good[:2] + [bad] + good[2:])
+        assert rc == abi.ARK_DDGI_E_INVALID_ARGUMENT, bad
+    assert lib.ark_ddgi_debug_shade_map(None, 0, 0, 100.0, None, 0, None) == 0
+    assert lib.ark_ddgi_debug_shade_map(None, 5, 2, 100.0, None, 0, None) == -1
+
+
 def test_invalid_arguments_fail_cleanly():
     lib = abi.load_library()
     h = C.c_void_p()
